@@ -6,7 +6,13 @@ GPs (means + variances) + risk-sensitive cost + gradient w.r.t. U, i.e. one obje
 callback pair of the reference (src/mpc.py:202-255).  One bench *step* = one batched call of the hot
 path over B trajectories per GPU, inputs already resident in HBM.
 
-    python bench.py [--gpus N --steps K --warmup W] [--config C3]
+    python bench.py [--gpus N --steps K --warmup W] [--config C3] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the headline line (rollouts/s and ms_per_step).  Everything
+else it can measure -- the roofline block with per-kernel timing, the PCIe-inclusive, sustained and objective-only
+rates, the secondary workloads (`extras`), the CPU baselines and the multi-GPU collective instrumentation -- runs only
+with ``--full``.  ``--dump-outputs DIR`` writes what the last timed step returned (cost, and grad unless
+``--forward-only``) as float64 ``DIR/<name>.npy``; the inputs are seeded, so two builds can be compared array by array.
 
 ``--gpus N`` with N > 1 and no WORLD_SIZE in the environment spawns N rank processes itself (one per
 GPU, RCCL over xGMI) BEFORE anything touches a GPU in this process, relays rank 0's JSON line and
@@ -40,6 +46,12 @@ def parse_args():
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--config", default="C3")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every side measurement (roofline with per-kernel timing, PCIe-inclusive / sustained / "
+                         "objective-only rates, the secondary workloads, the CPU baselines, multi-GPU instrumentation); a plain "
+                         "run only times the headline")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write the outputs of the last timed step (cost, grad) as float64 DIR/<name>.npy")
     ap.add_argument("--batch", type=int, default=0, help="trajectories per GPU (default: the config's B)")
     ap.add_argument("--n-train", type=int, default=0,
                     help="training-set size instead of the config's N (side measurements, e.g. the mid-size case N = 1024, B = 16; "
@@ -50,13 +62,13 @@ def parse_args():
     ap.add_argument("--graph", action="store_true", help="replay each rollout as one hipGraph (small batches)")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend for --gpus > 1 (nccl = RCCL; gloo for rehearsals)")
     ap.add_argument("--no-legs", action="store_true",
-                    help="skip the secondary workloads the default run times after the headline (C4, C5, C3 with one lambda, C3 at B = 1 "
+                    help="skip the secondary workloads a --full run times after the headline (C4, C5, C3 with one lambda, C3 at B = 1 "
                          "as one graph, the closed loop): each is a short bench.py child process, reported under `extras`")
     ap.add_argument("--full-json", action="store_true",
                     help="print the FULL record on stdout (every note and definition: ~4 KB per line, 14 KB with the legs) instead of "
-                         "the compact one; the default run prints the compact record and writes the full one to stderr")
+                         "the compact one; a --full run prints the compact record and writes the full one to stderr")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the PCIe-inclusive and objective-only side measurements (profiling passes: only the timed workload runs)")
+                    help="with --full: skip the PCIe-inclusive and objective-only side measurements (profiling passes: only the timed workload runs)")
     ap.add_argument("--kinv-cache", default="",
                     help="file to load the inverse kernel matrices from / save them to (profiling passes: rocprofv3 --pmc crashes "
                          "inside rocSOLVER's 4096^2 LU, so an unprofiled run writes the file and the profiled runs read it)")
@@ -327,7 +339,7 @@ def measured_traffic(config, B, want_grad, kernel_hint):
 
 
 # ----------------------------------------------------------------------------------------------------------------------
-# secondary workloads of the default run
+# secondary workloads of a --full run
 # ----------------------------------------------------------------------------------------------------------------------
 LEGS = [
     # name, bench.py arguments (each leg: its own process, its own barrier + synchronize bracket, its own roofline block)
@@ -359,7 +371,7 @@ def run_legs(timeout_s=240):
     roofline key) go to stderr and gpurun_out/.  A leg that fails or times out is recorded as such, never dropped silently."""
     out, full = {}, {}
     for name, argv in LEGS:
-        cmd = [sys.executable, os.path.abspath(__file__)] + argv + ["--no-cpu-baseline", "--no-extras", "--no-legs", "--full-json"]
+        cmd = [sys.executable, os.path.abspath(__file__)] + argv + ["--full", "--no-cpu-baseline", "--no-extras", "--no-legs", "--full-json"]
         t0 = time.perf_counter()
         try:
             p = subprocess.run(cmd, capture_output=True, text=True, timeout=timeout_s)
@@ -429,6 +441,28 @@ def compact_record(full):
         else:
             out[k] = v
     return out
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+NPY_HEADER_SLACK = 4096          # room for the .npy headers of the (at most three) files inside the limit
+
+
+def dump_outputs(outdir, arrays, seed=0):
+    """What the timed path returned in its last step, as float64 <outdir>/<name>.npy.  Past 64 MB in all, every array keeps
+    the same seeded sample of batch rows (their leading axis) and the row indices go to sample_rows.npy."""
+    import numpy as np
+    os.makedirs(outdir, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float64) for k, v in arrays.items() if v is not None}
+    total = sum(a.nbytes for a in arrays.values())
+    budget = DUMP_LIMIT_BYTES - NPY_HEADER_SLACK
+    if total > budget:
+        rows = arrays["cost"].shape[0]
+        keep = max(1, budget // (total // rows + 8))            # + 8: the row's entry in sample_rows
+        idx = np.sort(np.random.default_rng(seed).choice(rows, keep, replace=False))
+        arrays = {k: a[idx] for k, a in arrays.items()}
+        arrays["sample_rows"] = idx.astype(np.float64)
+    for k, a in arrays.items():
+        np.save(os.path.join(outdir, k + ".npy"), a)
 
 
 # ----------------------------------------------------------------------------------------------------------------------
@@ -522,41 +556,57 @@ def run_rank(args):
             return gather_results(r["cost"], r.get("grad"), dist)
         return r["cost"], r.get("grad")
 
+    def check_finite(c, gr):
+        if (not torch.isfinite(c).all() or (gr is not None and not torch.isfinite(gr).all())) and \
+                not os.environ.get("GPMPC_BENCH_TIMING_EXPERIMENT"):  # (timing-only experimental kernel builds compute wrong numbers)
+            raise SystemExit("non-finite rollout outputs")
+
+    warm = None
     for _ in range(args.warmup):
-        c, gr = step()
+        warm = step()
     torch.cuda.synchronize()
-    if (not torch.isfinite(c).all() or (gr is not None and not torch.isfinite(gr).all())) and \
-            not os.environ.get("GPMPC_BENCH_TIMING_EXPERIMENT"):      # (timing-only experimental kernel builds compute wrong numbers)
-        raise SystemExit("non-finite rollout outputs")
+    if warm is not None:
+        check_finite(*warm)
 
     L = lib()
-    L.gpmpc_timing_enable(0 if args.graph else 1)         # per-kernel events and graph replay exclude each other
     ms, nl = ctypes.c_double(), ctypes.c_longlong()
-    L.gpmpc_pair_kernel_time(ctypes.byref(ms), ctypes.byref(nl), 1)
+    if args.full:
+        L.gpmpc_timing_enable(0 if args.graph else 1)     # per-kernel events and graph replay exclude each other
+        L.gpmpc_pair_kernel_time(ctypes.byref(ms), ctypes.byref(nl), 1)
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step()
+        last = step()
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
     elapsed = time.perf_counter() - t0
+    if warm is None:                                       # --warmup 0: the outputs of the last timed step are checked instead
+        check_finite(*last)
+    # host copies of what the last timed step returned, taken before anything else can reuse its buffers (graph replay)
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = {"cost": last[0].cpu().numpy(), "grad": None if last[1] is None else last[1].cpu().numpy()}
     tcls = []
-    for cls in (0, 1, 2):                                  # 0: the full pair kernel, 1: its horizon-step-1 variant, 2: fused step kernel
-        L.gpmpc_pair_kernel_time_class(cls, ctypes.byref(ms), ctypes.byref(nl))
-        tcls.append((ms.value, nl.value))
-    L.gpmpc_timing_enable(0)
+    if args.full:
+        for cls in (0, 1, 2):                              # 0: the full pair kernel, 1: its horizon-step-1 variant, 2: fused step kernel
+            L.gpmpc_pair_kernel_time_class(cls, ctypes.byref(ms), ctypes.byref(nl))
+            tcls.append((ms.value, nl.value))
+        L.gpmpc_timing_enable(0)
     multi = None
+    elapsed_rank = elapsed
     if world > 1:
         tmax = torch.tensor([elapsed], dtype=torch.float64, device=device)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
+        elapsed = float(tmax.item())
+    if world > 1 and args.full:
         # instrumentation of the first real multi-GPU run (outside the timed region): were it to scale below expectation, these
         # say whether the ranks differ (per-rank elapsed of the timed region, rollout-only rate without the collective) or the
         # collective costs (latency of the fused all_gather of [cost | grad] alone, 100 repetitions)
         el_all = [torch.zeros(1, dtype=torch.float64, device=device) for _ in range(world)]
-        dist.all_gather(el_all, torch.tensor([elapsed], dtype=torch.float64, device=device))
+        dist.all_gather(el_all, torch.tensor([elapsed_rank], dtype=torch.float64, device=device))
         torch.cuda.synchronize()
         tq = time.perf_counter()
         for _ in range(max(2, min(args.steps, 5))):
@@ -583,90 +633,94 @@ def run_rank(args):
                  "rollouts_per_s_min_max_over_ranks": [min(float(t.item()) for t in lr_all), max(float(t.item()) for t in lr_all)],
                  "all_gather_cost_grad_latency_us": ag_us, "all_gather_bytes_per_rank": 8 * (hi - lo) * (1 + (H * da if want_grad else 0)),
                  "kinv_broadcast_ms": bcast_ms, "kinv_bytes": 8 * ds * N * N}
-        elapsed = float(tmax.item())
 
     if rank == 0:
+        if dumped is not None:
+            dump_outputs(args.dump_outputs, dumped)
         rollouts = B * world * args.steps
         value = rollouts / elapsed
-        pairs_per_launch = B * ds * N * (N + 1) / 2                 # one horizon step, all trajectories and GPs
-        # (one lambda, 2 <= ds <= 4: the cross units run in their own kernel, pair_kernel_sbfx.h -- beside the timed launch at small batches --;
-        # the timed launch then covers the variance units only, and so do its pair count and weight bytes)
-        fc_plan = pack.plan_fullcov(B, H, want_grad=want_grad) if fullcov else {}
-        cross_elsewhere = bool(fc_plan.get("shared_cross_units"))
-        if fullcov and not cross_elsewhere:                         # + ds(ds-1)/2 cross units over all N^2 ordered pairs
-            pairs_per_launch += B * (ds * (ds - 1) / 2) * N * N
-        shared = bool(pack.shared_lambda) and not fullcov and os.environ.get("GPMPC_SHARED", "") != "0"
-        fl, slots = pair_work(D, ds, want_grad, fullcov, shared)
-        full_ms, full_n = tcls[0]
-        fused_path = full_n == 0 and tcls[2][1] > 0            # small batches: one fused launch per horizon step
-        if fused_path:
-            full_ms, full_n = tcls[2]
-        if not full_n and args.graph and world == 1:
-            # graph replay carries no per-kernel events: time the dominant kernel in a short UNCAPTURED pass outside the timed region
-            # (same launches, same inputs; HIP events on the launch stream)
-            L.gpmpc_timing_enable(1)
-            L.gpmpc_pair_kernel_time(ctypes.byref(ms), ctypes.byref(nl), 1)
-            for _ in range(max(3, min(args.steps, 20))):
-                g.rollout(pack, x0, U, cost, want_grad=want_grad, want_traj=False, graph=False)
-            torch.cuda.synchronize()
-            tc2 = []
-            for cls in (0, 1, 2):
-                L.gpmpc_pair_kernel_time_class(cls, ctypes.byref(ms), ctypes.byref(nl))
-                tc2.append((ms.value, nl.value))
-            L.gpmpc_timing_enable(0)
-            tcls = tc2
+        if args.full:                                          # roofline of the dominant kernel (per-kernel HIP events)
+            pairs_per_launch = B * ds * N * (N + 1) / 2                 # one horizon step, all trajectories and GPs
+            # (one lambda, 2 <= ds <= 4: the cross units run in their own kernel, pair_kernel_sbfx.h -- beside the timed launch at small batches --;
+            # the timed launch then covers the variance units only, and so do its pair count and weight bytes)
+            fc_plan = pack.plan_fullcov(B, H, want_grad=want_grad) if fullcov else {}
+            cross_elsewhere = bool(fc_plan.get("shared_cross_units"))
+            if fullcov and not cross_elsewhere:                         # + ds(ds-1)/2 cross units over all N^2 ordered pairs
+                pairs_per_launch += B * (ds * (ds - 1) / 2) * N * N
+            shared = bool(pack.shared_lambda) and not fullcov and os.environ.get("GPMPC_SHARED", "") != "0"
+            fl, slots = pair_work(D, ds, want_grad, fullcov, shared)
             full_ms, full_n = tcls[0]
-            fused_path = full_n == 0 and tcls[2][1] > 0
+            fused_path = full_n == 0 and tcls[2][1] > 0            # small batches: one fused launch per horizon step
             if fused_path:
                 full_ms, full_n = tcls[2]
-            kernel_timed_in = "a separate uncaptured pass after the timed region (graph replay has no per-kernel events)"
-        else:
-            kernel_timed_in = "the timed region"
-        launch_s = (full_ms / full_n) * 1e-3 if full_n else float("nan")
-        # mid-size batches run as concurrent sub-batches (step.hip split_count): one timed launch then covers B / S trajectories
-        plan = pack.plan(B, H, want_grad=want_grad, graph=args.graph) if not fullcov else pack.plan_fullcov(B, H, want_grad=want_grad)
-        persist = plan.get("form") == "persist"                # whole-horizon kernel: ONE launch per rollout call
-        per_rollout = 1 if persist else (H if fused_path else max(H - 1, 1))
-        n_timed_calls = args.steps if kernel_timed_in == "the timed region" else max(3, min(args.steps, 20))
-        n_sub = max(1, int(round(full_n / float(n_timed_calls * per_rollout)))) if full_n else 1
-        if persist:
-            pairs_per_launch *= H
-        pairs_per_launch /= n_sub
-        achieved = pairs_per_launch * fl / launch_s / 1e12
-        m_bytes = 8 * (ds * N * (N + 1) / 2 + (ds * (ds - 1) / 2 * N * N if (fullcov and not cross_elsewhere) else 0))     # M read once per launch
-        sm = "sbf" if fullcov else ("sbs" if shared else "sb")
-        # (no sidecar for the launch that covers the variance units only: the recorded counters belong to the per-unit launch)
-        traffic, traffic_src = (None, None) if (args.n_train or cross_elsewhere) else measured_traffic(args.config, B, want_grad, sm)
-        ng = 0
-        if shared:                                             # GPs per workgroup: gpmpc_sbs_group (gpmpc_internal.h)
-            cap = max(2, min(4, 48 // (1 + D + ds)))
-            groups = (ds + cap - 1) // cap
-            ng = (ds + groups - 1) // groups
-        i_f64, i_int, i_fl = pair_instr(D, ds, want_grad, fullcov, ng)
-        # every VALU instruction (fp64-rate or integer) occupies its SIMD for 4 cycles per wave64 at the spec clock
-        issue_util = (i_f64 + i_int) * 4.0 * pairs_per_launch / 64.0 / (1024 * launch_s * 2.4e9)
-        executed_frac = pairs_per_launch * i_fl / launch_s / 1e12 / FP64_PEAK_TFLOPS
-        kname = plan.get("kernel") or f"gpmpc_pair_kernel_{sm}"
-        if fullcov and plan.get("form") == "four_launch":
-            kname = f"gpmpc_pair_kernel_{sm}"
-        kname += (" (whole horizon of one trajectory per workgroup: every step's mean sums, pair sums and finish work)" if persist else
-                  " (one launch per horizon step: mean sums + finish work + pair tiles; NOT a pair-only time)" if fused_path
-                  else " (full variant; the cheaper horizon-step-1 variant is reported under first_step_variant)")
-        # Which roofline binds the dominant kernel: per launch it must move the upper triangles of the weight
-        # matrices once (8 bytes per pair when ONE trajectory streams them, 8 / B with B trajectories sharing a launch) and issue the
-        # column loop's VALU instructions; whichever takes longer at the machine's peaks is the bound.
-        m_launch = m_bytes                                      # every timed launch (a sub-batch's too) streams the matrices itself
-        t_hbm = m_launch / (HBM_PEAK_GBS * 1e9)
-        t_valu = (i_f64 + i_int) * 4.0 * pairs_per_launch / 64.0 / (1024 * 2.4e9)
-        hbm_bound = t_hbm > t_valu
-        # bytes of the weight stream that one step re-reads fit the 256 MiB Infinity Cache (guide: a table stays resident while
-        # table + everything else touched between two uses fits): they are then served on-die, at the IC's ~8.6 TB/s, not by HBM
-        ic_resident = m_bytes <= 200e6
+            if not full_n and args.graph and world == 1:
+                # graph replay carries no per-kernel events: time the dominant kernel in a short UNCAPTURED pass outside the timed region
+                # (same launches, same inputs; HIP events on the launch stream)
+                L.gpmpc_timing_enable(1)
+                L.gpmpc_pair_kernel_time(ctypes.byref(ms), ctypes.byref(nl), 1)
+                for _ in range(max(3, min(args.steps, 20))):
+                    g.rollout(pack, x0, U, cost, want_grad=want_grad, want_traj=False, graph=False)
+                torch.cuda.synchronize()
+                tc2 = []
+                for cls in (0, 1, 2):
+                    L.gpmpc_pair_kernel_time_class(cls, ctypes.byref(ms), ctypes.byref(nl))
+                    tc2.append((ms.value, nl.value))
+                L.gpmpc_timing_enable(0)
+                tcls = tc2
+                full_ms, full_n = tcls[0]
+                fused_path = full_n == 0 and tcls[2][1] > 0
+                if fused_path:
+                    full_ms, full_n = tcls[2]
+                kernel_timed_in = "a separate uncaptured pass after the timed region (graph replay has no per-kernel events)"
+            else:
+                kernel_timed_in = "the timed region"
+            launch_s = (full_ms / full_n) * 1e-3 if full_n else float("nan")
+            # mid-size batches run as concurrent sub-batches (step.hip split_count): one timed launch then covers B / S trajectories
+            plan = pack.plan(B, H, want_grad=want_grad, graph=args.graph) if not fullcov else pack.plan_fullcov(B, H, want_grad=want_grad)
+            persist = plan.get("form") == "persist"                # whole-horizon kernel: ONE launch per rollout call
+            per_rollout = 1 if persist else (H if fused_path else max(H - 1, 1))
+            n_timed_calls = args.steps if kernel_timed_in == "the timed region" else max(3, min(args.steps, 20))
+            n_sub = max(1, int(round(full_n / float(n_timed_calls * per_rollout)))) if full_n else 1
+            if persist:
+                pairs_per_launch *= H
+            pairs_per_launch /= n_sub
+            achieved = pairs_per_launch * fl / launch_s / 1e12
+            m_bytes = 8 * (ds * N * (N + 1) / 2 + (ds * (ds - 1) / 2 * N * N if (fullcov and not cross_elsewhere) else 0))     # M read once per launch
+            sm = "sbf" if fullcov else ("sbs" if shared else "sb")
+            # (no sidecar for the launch that covers the variance units only: the recorded counters belong to the per-unit launch)
+            traffic, traffic_src = (None, None) if (args.n_train or cross_elsewhere) else measured_traffic(args.config, B, want_grad, sm)
+            ng = 0
+            if shared:                                             # GPs per workgroup: gpmpc_sbs_group (gpmpc_internal.h)
+                cap = max(2, min(4, 48 // (1 + D + ds)))
+                groups = (ds + cap - 1) // cap
+                ng = (ds + groups - 1) // groups
+            i_f64, i_int, i_fl = pair_instr(D, ds, want_grad, fullcov, ng)
+            # every VALU instruction (fp64-rate or integer) occupies its SIMD for 4 cycles per wave64 at the spec clock
+            issue_util = (i_f64 + i_int) * 4.0 * pairs_per_launch / 64.0 / (1024 * launch_s * 2.4e9)
+            executed_frac = pairs_per_launch * i_fl / launch_s / 1e12 / FP64_PEAK_TFLOPS
+            kname = plan.get("kernel") or f"gpmpc_pair_kernel_{sm}"
+            if fullcov and plan.get("form") == "four_launch":
+                kname = f"gpmpc_pair_kernel_{sm}"
+            kname += (" (whole horizon of one trajectory per workgroup: every step's mean sums, pair sums and finish work)" if persist else
+                      " (one launch per horizon step: mean sums + finish work + pair tiles; NOT a pair-only time)" if fused_path
+                      else " (full variant; the cheaper horizon-step-1 variant is reported under first_step_variant)")
+            # Which roofline binds the dominant kernel: per launch it must move the upper triangles of the weight
+            # matrices once (8 bytes per pair when ONE trajectory streams them, 8 / B with B trajectories sharing a launch) and issue the
+            # column loop's VALU instructions; whichever takes longer at the machine's peaks is the bound.
+            m_launch = m_bytes                                      # every timed launch (a sub-batch's too) streams the matrices itself
+            t_hbm = m_launch / (HBM_PEAK_GBS * 1e9)
+            t_valu = (i_f64 + i_int) * 4.0 * pairs_per_launch / 64.0 / (1024 * 2.4e9)
+            hbm_bound = t_hbm > t_valu
+            # bytes of the weight stream that one step re-reads fit the 256 MiB Infinity Cache (a table stays resident while
+            # table + everything else touched between two uses fits): they are then served on-die, at the IC's ~8.6 TB/s, not by HBM
+            ic_resident = m_bytes <= 200e6
         out = {
             "metric": "GP-MPC rollouts/sec (N train pts x H horizon x d dims)",
             "value": value, "unit": "rollouts/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True, "scaling": "weak",
             "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+            # HIP events around every timed launch of the dominant kernel (--full, roofline) cost a little host time per step
+            "per_kernel_events": bool(args.full and not args.graph),
             "config": {"workload": f"{args.config}{' with N changed' if args.n_train else ''}: N={N}, d(state_dim)={ds}, action_dim={da}, H={H}, "
                                    f"B={B} trajectories per GPU, gamma={cfg['gamma']}, "
                                    + ("full covariance, " if fullcov else "")
@@ -679,7 +733,9 @@ def run_rank(args):
                      "backend": dist.get_backend() if world > 1 else None,
                      "visible_devices": ndev, "launcher": "torch.distributed.run / external" if "TORCHELASTIC_RUN_ID" in os.environ
                      else ("bench.py spawn" if world > 1 else "single process")},
-            "roofline": ({
+        }
+        if args.full:
+            out["roofline"] = ({
                 "kernel": kname,
                 "bound": "hbm", "served_from": "infinity_cache" if ic_resident else "hbm",
                 "bound_note": f"weight stream: one launch must read the upper triangles of the {ds} weight matrices ({m_launch / 1e6:.1f} MB "
@@ -722,12 +778,11 @@ def run_rank(args):
                 "hbm_algorithmic_GBs": m_launch / launch_s / 1e9, "hbm_frac": m_launch / launch_s / 1e9 / HBM_PEAK_GBS,
                 "hbm_note": "weight-matrix bytes one launch must read at least once (upper triangles, 8 bytes per pair; sub-batches of a "
                             "split call each read them) / avg_launch_ms / 8 TB/s",
-            },
-            "pack_build_ms": pack_ms,
-        }
+            }
+        out["pack_build_ms"] = pack_ms
         if multi is not None:
             out["multi_gpu"] = multi
-        if world == 1 and not args.graph and not args.no_extras:
+        if args.full and world == 1 and not args.graph and not args.no_extras:
             # PCIe-inclusive rate, outside the timed region: U from pinned host memory in, [cost | grad] back out, per step
             Uh = torch.as_tensor(pb["U"][lo:hi]).pin_memory()
             Ud = torch.empty_like(U)
@@ -741,7 +796,7 @@ def run_rank(args):
                     gr.cpu()
             torch.cuda.synchronize()
             out["pcie_inclusive_rollouts_per_s"] = max(2, min(args.steps, 5)) * B / (time.perf_counter() - tp)
-        if world == 1 and not args.graph and not args.no_extras:
+        if args.full and world == 1 and not args.graph and not args.no_extras:
             # sustained rate: the same step repeated for ~5 s, outside the timed region (the timed K steps are a sub-second
             # burst; the kernel runs the chip on its power cap, so this is the number a long job sees)
             torch.cuda.synchronize()
@@ -752,7 +807,7 @@ def run_rank(args):
                 ns += 4
                 torch.cuda.synchronize()
             out["sustained"] = {"seconds": time.perf_counter() - ts, "steps": ns, "rollouts_per_s": ns * B / (time.perf_counter() - ts)}
-        if world == 1 and want_grad and not fullcov and not args.no_extras:
+        if args.full and world == 1 and want_grad and not fullcov and not args.no_extras:
             # objective-only rate beside the headline, outside the timed region
             for _ in range(2):
                 g.rollout(pack, x0, U, cost, want_grad=False, want_traj=False)
@@ -764,9 +819,9 @@ def run_rank(args):
             out["forward_only_rollouts_per_s"] = 3 * B / (time.perf_counter() - tf)
         default_run = (args.config == "C3" and not args.batch and not args.n_train and not args.shared_lambda and not args.graph
                        and not args.forward_only)
-        if world == 1 and default_run and not args.no_legs and not args.no_extras:
+        if args.full and world == 1 and default_run and not args.no_legs and not args.no_extras:
             out["extras"], out["extras_full"] = run_legs()
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             res = cpu_baseline(pb, cfg, fullcov, args.cpu_reps)
             H_s = res["H_sample"]
             out["cpu_baseline"] = {
@@ -797,7 +852,7 @@ def run_rank(args):
                 return None
             return v
         full = _clean(out)
-        if args.full_json:
+        if args.full_json or not args.full:
             full.pop("extras_full", None)
             print(json.dumps(full, allow_nan=False), flush=True)
         else:
@@ -912,7 +967,11 @@ def run_closed_loop(args):
 
 def main():
     args = parse_args()
+    if args.steps < 1:
+        raise SystemExit("bench.py: --steps must be >= 1")
     if args.closed_loop:
+        if args.dump_outputs:
+            raise SystemExit("bench.py: --dump-outputs covers the rollout benchmark, not --closed-loop")
         return run_closed_loop(args)
     if args.gpus < 1:
         raise SystemExit("bench.py: --gpus must be >= 1")

@@ -17,6 +17,9 @@ def pytest_configure(config):
 
 @pytest.fixture(scope="session")
 def golden():
+    # (split fixtures -- parts, triangle-stored matrices -- come back merged: oracle/golden.py)
+    from oracle.golden import load as load_golden
+
     def load(name):
-        return np.load(os.path.join(GOLDEN, name))
+        return load_golden(name, GOLDEN)
     return load

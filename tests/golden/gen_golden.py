@@ -27,6 +27,7 @@ Fixtures:
 
   g10_readme_regime.npz  the reference's own regime: README experiment data, lambda = 0.5 for every GP, H = 6,
                        sigma_n in {1e-3, 1e-5}: means / variances / cost / gradient of four candidate plans
+                       (sigma_n = 1e-5 in g10_readme_regime_part2.npz, to keep each file under 1 MiB)
   g11_fullsize_pin.npz reference-produced mean / variance of every GP at N = 2048 (C3 training set re-derived from the
                        seed) for two single-step queries
 
@@ -56,6 +57,8 @@ from src.tools.uncertainty_prop import (                           # noqa: E402
     mean_prop_torch, variance_prop_torch, covariance_prop_torch)
 
 OUT = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, os.path.dirname(os.path.dirname(OUT)))
+from oracle.golden import save_split                              # noqa: E402
 T = lambda a: torch.tensor(np.asarray(a), dtype=torch.float64)     # noqa: E731
 
 
@@ -457,7 +460,10 @@ def g10():
             means[b] = torch.stack(sm).detach().numpy()
             vars_[b] = torch.stack([torch.diag(s) for s in sc]).detach().numpy()
         out.update({f"s{si}_means": means, f"s{si}_vars": vars_, f"s{si}_costs": costs, f"s{si}_grads": grads})
-    np.savez(os.path.join(OUT, "g10_readme_regime.npz"), **out)
+    # 2.6 MB in one file: split per sigma_n and each Ky_inv stored as its upper triangle plus the exact residual of the lower
+    # one (the LU inverse is symmetric only up to round-off); oracle/golden.py reads it back
+    parts = [{k: v for k, v in out.items() if not k.startswith("s1_")}, {k: v for k, v in out.items() if k.startswith("s1_")}]
+    save_split(os.path.join(OUT, "g10_readme_regime.npz"), parts, nearly_symmetric=("s0_Ky_inv", "s1_Ky_inv"))
 
 
 def g11():

@@ -487,3 +487,56 @@ def test_bench_stdout_record_is_compact():
     for k in ("value", "unit", "cores", "kind", "sample"):
         assert k in d["cpu_baseline"]
     assert bench.short_kernel("k_step_fused<5,4,true,32,1> (one launch per horizon step: ...)") == "k_step_fused<5,4,true,32,1>"
+
+
+def test_bench_dump_outputs_keeps_small_outputs_and_samples_large_ones(tmp_path, monkeypatch):
+    """--dump-outputs: under the limit every array is written as float64, unchanged; over it, the files stay within the
+    limit, cost and grad keep the SAME seeded rows, sample_rows.npy names them, and a second call writes identical files."""
+    sys.path.insert(0, ROOT)
+    import bench
+    rng = np.random.default_rng(5)
+    cost = rng.standard_normal(300)
+    grad = cost[:, None, None] * np.arange(1, 7)[None, :, None]          # row i of grad is a function of cost[i]
+    bench.dump_outputs(str(tmp_path / "small"), {"cost": cost, "grad": grad})
+    assert sorted(os.listdir(tmp_path / "small")) == ["cost.npy", "grad.npy"]
+    for name, a in (("cost", cost), ("grad", grad)):
+        b = np.load(tmp_path / "small" / f"{name}.npy")
+        assert b.dtype == np.float64 and np.array_equal(a, b)
+    assert bench.dump_outputs(str(tmp_path / "none"), {"cost": cost, "grad": None}) is None
+    assert sorted(os.listdir(tmp_path / "none")) == ["cost.npy"]
+    limit = bench.NPY_HEADER_SLACK + 4000                               # ~70 of the 300 rows (8 + 48 + 8 bytes each) fit
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", limit)
+    files = []
+    for run in ("big1", "big2"):
+        bench.dump_outputs(str(tmp_path / run), {"cost": cost.astype(np.float32), "grad": grad})
+        names = sorted(os.listdir(tmp_path / run))
+        assert names == ["cost.npy", "grad.npy", "sample_rows.npy"]
+        assert sum(os.path.getsize(tmp_path / run / n) for n in names) <= limit
+        files.append({n: open(tmp_path / run / n, "rb").read() for n in names})
+    assert files[0] == files[1]
+    c, g, rows = (np.load(tmp_path / "big1" / n) for n in ("cost.npy", "grad.npy", "sample_rows.npy"))
+    assert c.dtype == g.dtype == rows.dtype == np.float64
+    idx = rows.astype(np.int64)
+    assert 1 < len(idx) < len(cost) and np.all(np.diff(idx) > 0) and np.array_equal(rows, idx)
+    assert np.array_equal(c, cost.astype(np.float32).astype(np.float64)[idx]) and np.array_equal(g, grad[idx])
+
+
+def test_split_golden_fixture_round_trip(tmp_path):
+    """oracle/golden.py: a fixture written in parts with a nearly symmetric matrix stored as triangle + residual comes back
+    bit for bit under its own names; the split g10 fixture has both noise levels' inverses; a whole fixture loads as np.load."""
+    sys.path.insert(0, ROOT)
+    from oracle import golden
+    rng = np.random.default_rng(11)
+    a = rng.standard_normal((37, 37))
+    m = np.linalg.inv(a @ a.T + 37 * np.eye(37))                        # an LU inverse: symmetric up to round-off
+    parts = [{"m": m, "v": np.arange(5.0)}, {"w": rng.standard_normal((2, 3))}]
+    golden.save_split(str(tmp_path / "f.npz"), parts, nearly_symmetric=("m",))
+    assert sorted(os.listdir(tmp_path)) == ["f.npz", "f_part2.npz"] and "m" not in np.load(tmp_path / "f.npz").files
+    d = golden.load("f.npz", str(tmp_path))
+    assert set(d) == {"m", "v", "w"}
+    for k, v in (("m", m), ("v", parts[0]["v"]), ("w", parts[1]["w"])):
+        assert d[k].dtype == v.dtype and d[k].shape == v.shape and d[k].tobytes() == v.tobytes()
+    z = golden.load("g10_readme_regime.npz")
+    N = int(z["dims"][0])
+    assert z["s0_Ky_inv"].shape == z["s1_Ky_inv"].shape == (N, N) and z["s1_vars"].shape == z["s0_vars"].shape
+    assert isinstance(golden.load("g3_rollout_c1.npz"), type(np.load(os.path.join(golden.GOLDEN, "g3_rollout_c1.npz"))))

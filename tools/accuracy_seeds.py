@@ -11,7 +11,7 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 import gaussian_process_mpc_amd as G
-from oracle import cport, gpmpc_oracle as O
+from oracle import cport, golden, gpmpc_oracle as O
 from gaussian_process_mpc_amd.synth import synth_problem
 torch.set_num_threads(16)
 seeds = int(sys.argv[1]) if len(sys.argv) > 1 else 9
@@ -35,7 +35,7 @@ for sn in (1e-2, 1e-3, 1e-4, 1e-5):
     print(f"sigma_n={sn:<6g} HIP median {np.median(hip):.1e} [{hip.min():.1e} .. {hip.max():.1e}] | reference op order median {np.median(ref):.1e} "
           f"[{ref.min():.1e} .. {ref.max():.1e}] | HIP / reference: median {np.median(ratio):.2f} [{ratio.min():.2f} .. {ratio.max():.2f}], "
           f"HIP closer in {int((ratio < 1).sum())} of {seeds}")
-z = np.load(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden", "g10_readme_regime.npz"))
+z = golden.load("g10_readme_regime.npz")          # (two files, triangle-stored inverses: merged by oracle/golden.py)
 Ng, dsg, dag, Hg = (int(v) for v in z["dims"])
 for si, sn in enumerate(z["sigma_ns"]):
     kinv = np.stack([z[f"s{si}_Ky_inv"]] * dsg)

@@ -27,21 +27,21 @@ PMC_BATCH=1 PMC_STEPS=2 bash tools/prof_pmc.sh C4 --batch 1 > $O/pmc_C4_B1.log 2
 PMC_BATCH=1 PMC_STEPS=3 bash tools/prof_pmc.sh C5 --batch 1 > $O/pmc_C5_B1.log 2>&1; cp gpurun_out/pmc_C5/pmc_C5.txt $O/pmc_C5_B1.txt; cp gpurun_out/pmc_C5/pmc_C5.json $O/pmc_C5_B1.json
 fi
 if [ $STEP = all ] || [ $STEP = bench ]; then
-python bench.py > $O/bench_C3.json 2> $O/bench_C3.err || echo "bench C3 failed"
-python bench.py --config C3 --shared-lambda --no-cpu-baseline --no-legs > $O/bench_C3_shared.json 2>/dev/null || echo "bench C3 shared failed"
-for c in C4 C5; do python bench.py --config $c --steps 5 --warmup 2 --no-cpu-baseline > $O/bench_$c.json 2>/dev/null || echo "bench $c failed"; done
+python bench.py --full > $O/bench_C3.json 2> $O/bench_C3.err || echo "bench C3 failed"
+python bench.py --full --config C3 --shared-lambda --no-cpu-baseline --no-legs > $O/bench_C3_shared.json 2>/dev/null || echo "bench C3 shared failed"
+for c in C4 C5; do python bench.py --full --config $c --steps 5 --warmup 2 --no-cpu-baseline > $O/bench_$c.json 2>/dev/null || echo "bench $c failed"; done
 for c in C1 C2; do
-  python bench.py --config $c --steps 200 --warmup 20 --no-cpu-baseline > $O/bench_$c.json 2>/dev/null
-  python bench.py --config $c --steps 200 --warmup 20 --no-cpu-baseline --graph > $O/bench_${c}_graph.json 2>/dev/null
+  python bench.py --full --config $c --steps 200 --warmup 20 --no-cpu-baseline > $O/bench_$c.json 2>/dev/null
+  python bench.py --full --config $c --steps 200 --warmup 20 --no-cpu-baseline --graph > $O/bench_${c}_graph.json 2>/dev/null
 done
-python bench.py --config C3 --steps 5 --warmup 2 --no-cpu-baseline --forward-only > $O/bench_C3_fwd.json 2>/dev/null
-for b in 1 4 16 32; do python bench.py --config C3 --batch $b --steps 20 --warmup 5 --no-cpu-baseline --graph > $O/bench_C3_B$b.json 2>/dev/null; done
-python bench.py --config C4 --batch 1 --steps 10 --warmup 3 --no-cpu-baseline --graph > $O/bench_C4_B1.json 2>/dev/null
-for b in 1 2 4 8; do python bench.py --config C5 --batch $b --steps 20 --warmup 5 --no-cpu-baseline --no-extras > $O/bench_C5_B$b.json 2>/dev/null; done
-python bench.py --config C3 --n-train 300 --batch 256 --shared-lambda --steps 20 --warmup 5 --no-cpu-baseline --no-extras > $O/bench_N300_B256_shared.json 2>/dev/null
-for n in 300 512; do python bench.py --config C3 --n-train $n --batch 256 --steps 20 --warmup 5 --no-cpu-baseline --no-extras > $O/bench_N${n}_B256.json 2>/dev/null; done
-for b in 8 16 32; do python bench.py --config C3 --n-train 1024 --batch $b --steps 50 --warmup 10 --no-cpu-baseline --no-extras --graph > $O/bench_N1024_B$b.json 2>/dev/null; done
-python bench.py --gpus 2 --oversubscribe --backend gloo --steps 3 --warmup 1 --no-cpu-baseline > $O/bench_2rank_gloo_one_card.json 2>$O/bench_2rank.err
+python bench.py --full --config C3 --steps 5 --warmup 2 --no-cpu-baseline --forward-only > $O/bench_C3_fwd.json 2>/dev/null
+for b in 1 4 16 32; do python bench.py --full --config C3 --batch $b --steps 20 --warmup 5 --no-cpu-baseline --graph > $O/bench_C3_B$b.json 2>/dev/null; done
+python bench.py --full --config C4 --batch 1 --steps 10 --warmup 3 --no-cpu-baseline --graph > $O/bench_C4_B1.json 2>/dev/null
+for b in 1 2 4 8; do python bench.py --full --config C5 --batch $b --steps 20 --warmup 5 --no-cpu-baseline --no-extras > $O/bench_C5_B$b.json 2>/dev/null; done
+python bench.py --full --config C3 --n-train 300 --batch 256 --shared-lambda --steps 20 --warmup 5 --no-cpu-baseline --no-extras > $O/bench_N300_B256_shared.json 2>/dev/null
+for n in 300 512; do python bench.py --full --config C3 --n-train $n --batch 256 --steps 20 --warmup 5 --no-cpu-baseline --no-extras > $O/bench_N${n}_B256.json 2>/dev/null; done
+for b in 8 16 32; do python bench.py --full --config C3 --n-train 1024 --batch $b --steps 50 --warmup 10 --no-cpu-baseline --no-extras --graph > $O/bench_N1024_B$b.json 2>/dev/null; done
+python bench.py --full --gpus 2 --oversubscribe --backend gloo --steps 3 --warmup 1 --no-cpu-baseline > $O/bench_2rank_gloo_one_card.json 2>$O/bench_2rank.err
 for v in "" "--cl-distinct" "--cl-rebuild" "--cl-newton"; do python bench.py --closed-loop $v > "$O/closed_loop$(echo $v | tr -d ' ').json" 2>/dev/null; done
 python tools/callback_latency.py 2>/dev/null | tail -2 > $O/callback_latency.txt
 fi
