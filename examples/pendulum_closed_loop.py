@@ -3,7 +3,11 @@
 src/experiments/pretrain_uncertainty.py: pre-train the GP on random transitions, then run the MPC loop
 (Simulator.run, src/simulator.py:37-60) with the model growing by one observation per step.
 
-    python examples/pendulum_closed_loop.py [--pretrain 200] [--steps 25] [--horizon 10]
+    python examples/pendulum_closed_loop.py [--pretrain 200] [--steps 25] [--horizon 10] [--window N]
+
+--window N: fixed-size training window -- once the model holds N points every new observation replaces the oldest one (first-in
+first-out), so the cost of the data update and the memory stay constant however long the loop runs (what the solver makes of a model
+that has forgotten its pre-training points is another matter: BASELINE.md section 4w).
 
 Needs an MI355X and the built library; no gym, no cyipopt (the stand-in solver is scipy's L-BFGS-B on the same
 objective / gradient callbacks, so the trajectories are NOT the reference's Ipopt trajectories)."""
@@ -25,6 +29,8 @@ def main():
     ap.add_argument("--horizon", type=int, default=10)
     ap.add_argument("--gamma", type=float, default=1e-5)
     ap.add_argument("--starts", type=int, default=1, help="K > 1: lock-step multi-start solve, one batched rollout per tick (mpc.n_starts)")
+    ap.add_argument("--window", type=int, default=None, help="fixed-size training window of N points (Simulator max_train); default: the set grows")
+    ap.add_argument("--refresh", choices=("rebuild", "newton"), default=None, help="how the incremental path bounds its round-off")
     args = ap.parse_args()
 
     rng = np.random.default_rng(0)
@@ -45,13 +51,14 @@ def main():
     mpc.set_xref(np.zeros(2))
     mpc.n_starts = args.starts
 
-    sim = Simulator(mpc, plant, num_iters=args.steps, incremental=True)
+    sim = Simulator(mpc, plant, num_iters=args.steps, incremental=True, refresh=args.refresh, max_train=args.window)
     t0 = time.perf_counter()
     hist = sim.run()
     dt = time.perf_counter() - t0
     th = np.array([h[0][0] for h in hist])
     print(f"{len(hist)} MPC steps in {dt:.2f} s ({dt / len(hist) * 1e3:.1f} ms per step, solver: {mpc.solver_used}); "
-          f"training set {args.pretrain} -> {mpc.dynamics.gpr_err[0].num_train} points")
+          f"training set {args.pretrain} -> {mpc.dynamics.gpr_err[0].num_train} points"
+          + (f" (window of {args.window}, next slot {mpc.dynamics.window_slot})" if args.window else ""))
     print("theta:", np.array2string(th[:: max(1, len(th) // 10)], precision=2))
 
 

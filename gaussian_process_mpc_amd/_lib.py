@@ -59,6 +59,7 @@ SIGNATURES = {
     "gpmpc_pack_resize": (_i, [_vp, _i]),
     "gpmpc_pack_reload_tuning": (_i, [_vp]),
     "gpmpc_pack_graph_captures": (ctypes.c_longlong, [_vp]),
+    "gpmpc_pack_callback_captures": (ctypes.c_longlong, [_vp]),
     "gpmpc_store_host": (_i, [_vp, _vp, _sz, _vp]),
     "gpmpc_build_ky": (_i, [_i, _i, _vp, _dp, _d, _d, _vp, _vp, _vp]),
     "gpmpc_pack_build": (_i, [_vp, _vp, _vp, _vp, _dp, _dp, _vp]),
@@ -94,6 +95,9 @@ SIGNATURES = {
     "gpmpc_kinv_append": (_i, [_i, _vp, _vp, _d, _vp, _vp, _sz, _vp]),
     "gpmpc_gp_append_workspace_bytes": (_sz, [_i, _i]),
     "gpmpc_gp_append": (_i, [_i, _i, _vp, _vp, _dp, _d, _d, _vp, _vp, _sz, _vp, _sz, _vp, _vp, _vp, _sz, _vp, _sz, _vp]),
+    "gpmpc_kinv_remove": (_i, [_i, _vp, _sz, _i, _vp, _sz, _vp]),
+    "gpmpc_gp_replace_workspace_bytes": (_sz, [_i, _i]),
+    "gpmpc_gp_replace": (_i, [_i, _i, _i, _vp, _vp, _dp, _d, _d, _vp, _vp, _sz, _vp, _sz, _vp, _vp, _vp, _sz, _vp, _sz, _vp]),
     "gpmpc_predict_workspace_bytes": (_sz, [_i, _i, _i]),
     "gpmpc_predict": (_i, [_i, _i, _vp, _dp, _d, _vp, _vp, _d, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "gpmpc_ml_grad_workspace_bytes": (_sz, [_i, _i]),

@@ -348,3 +348,114 @@ extern "C" int gpmpc_gp_append(int n, int D, const double* X_dev, const double* 
     GPMPC_HIP(hipGetLastError());
     return GPMPC_OK;
 }
+
+// ---------------------------------------------------------------------------
+// Fixed-size training window (no reference counterpart: the reference only grows, src/gpr.py:90-122).  With K = Ky_inv (explicit, from
+// LU: row and column forms are kept apart as in k_append_vw), b = K[:, p], c = K[p, :], d = K[p, p]:
+//   remove point p:   A'_ij = K_ij - b_i c_j / d                        (i, j != p)   -- the inverse of Ky without row / column p
+//   replace point p by x (n stays n), A' never materialised:  kt_i = k_f(x_i, x) (i != p), kt_p = 0, kappa = sigma_f^2 + noise_var
+//     v = K kt - b (c . kt) / d     w = K^T kt - c (b . kt) / d     q = 1 / (kappa - kt . v)
+//     out_ij = K_ij - b_i c_j / d + q v_i w_j (i, j != p)   out_ip = -q v_i   out_pj = -q w_j   out_pp = q
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_kinv_remove(const double* __restrict__ Kinv, size_t ld_in, int n, int p, double* __restrict__ out,
+                                                      size_t ld_out) {
+    const int jo = blockIdx.x * blockDim.x + threadIdx.x, io = blockIdx.y;
+    if (jo >= n - 1) return;
+    const int i = io + (io >= p), j = jo + (jo >= p);                   // compacted: rows / columns after p move up by one
+    const double bd = Kinv[(size_t)i * ld_in + p] / Kinv[(size_t)p * ld_in + p];
+    out[(size_t)io * ld_out + jo] = fma(-bd, Kinv[(size_t)p * ld_in + j], Kinv[(size_t)i * ld_in + j]);
+}
+
+extern "C" int gpmpc_kinv_remove(int n, const double* Kinv_dev, size_t ld_in, int index, double* out_dev, size_t ld_out, void* stream) {
+    if (n < 2 || !Kinv_dev || !out_dev || index < 0 || index >= n || ld_in < (size_t)n || ld_out < (size_t)n - 1 || Kinv_dev == out_dev)
+        return GPMPC_E_ARG;
+    hipLaunchKernelGGL(k_kinv_remove, dim3((n - 1 + 255) / 256, n - 1), dim3(256), 0, (hipStream_t)stream, Kinv_dev, ld_in, n, index, out_dev,
+                       ld_out);
+    GPMPC_HIP(hipGetLastError());
+    return GPMPC_OK;
+}
+
+// Row workgroup r: kt evaluated in place (row p of X is the OLD point and is not read: kt_p = 0; workgroup 0 also stores kt), and four
+// dot products in one pass over i: its rows of K kt and K^T kt, and the scalars c . kt and b . kt (every workgroup evaluates both, in the
+// same fixed order, instead of a launch of their own).  Strided reads: K[i, r] as in k_append_vw, and K[i, p].
+__global__ __launch_bounds__(256) void k_replace_vw(const double* __restrict__ X, int n, int D, int p, const double* __restrict__ xnew, AppendHyp H,
+                                                     const double* __restrict__ Kinv, size_t ld, double* __restrict__ kout,
+                                                     double* __restrict__ v, double* __restrict__ wv) {
+    __shared__ double s_scr[64], s_out[4];
+    const int r = blockIdx.x;
+    double acc[4] = {0.0, 0.0, 0.0, 0.0};
+    for (int i = threadIdx.x; i < n; i += blockDim.x) {
+        double ki = 0.0;
+        if (i != p) {
+            double d2 = 0.0;
+            for (int d = 0; d < D; ++d) { const double t = X[(size_t)i * D + d] - xnew[d]; d2 = fma(t * t, 1.0 / H.lam[d], d2); }
+            ki = H.sf2 * exp(-0.5 * d2);
+        }
+        if (r == 0) kout[i] = ki;
+        acc[0] = fma(Kinv[(size_t)r * ld + i], ki, acc[0]);
+        acc[1] = fma(Kinv[(size_t)i * ld + r], ki, acc[1]);
+        acc[2] = fma(Kinv[(size_t)p * ld + i], ki, acc[2]);
+        acc[3] = fma(Kinv[(size_t)i * ld + p], ki, acc[3]);
+    }
+    block_sum<4>(acc, s_scr, s_out);
+    if (threadIdx.x == 0) {
+        const double d = Kinv[(size_t)p * ld + p];
+        // (entry p of v and w is never read by the fill; it is stored as 0 so that the workspace holds no left-over value)
+        v[r] = r == p ? 0.0 : fma(-Kinv[(size_t)r * ld + p], s_out[2] / d, s_out[0]);
+        wv[r] = r == p ? 0.0 : fma(-Kinv[(size_t)p * ld + r], s_out[3] / d, s_out[1]);
+    }
+}
+
+// Every workgroup evaluates q = 1 / (kappa - kt . v) itself (n products, fixed order), then streams its 256 columns of row i: Ky_inv, Kf
+// and Ky are read and written once, consecutive lanes on consecutive columns; b_i / d is one value per row.
+__global__ __launch_bounds__(256) void k_replace_fill(const double* __restrict__ Kinv, size_t ld_in, const double* __restrict__ v,
+                                                       const double* __restrict__ wv, double kappa, int n, int p, double* __restrict__ out,
+                                                       size_t ld_out, const double* __restrict__ k, const double* __restrict__ Kf_in,
+                                                       const double* __restrict__ Ky_in, size_t ld_k, double* __restrict__ Kf_out,
+                                                       double* __restrict__ Ky_out, double kff, double noise_var) {
+    __shared__ double s_scr[16], s_out[1];
+    double acc[1] = {0.0};
+    for (int i = threadIdx.x; i < n; i += blockDim.x) acc[0] = fma(k[i], v[i], acc[0]);
+    block_sum<1>(acc, s_scr, s_out);
+    const double qq = 1.0 / (kappa - s_out[0]);
+    const int j = blockIdx.x * blockDim.x + threadIdx.x, i = blockIdx.y;
+    if (j >= n) return;
+    double val, kf, ky;
+    if (i != p && j != p) {
+        const double bd = Kinv[(size_t)i * ld_in + p] / Kinv[(size_t)p * ld_in + p];
+        val = fma(qq * v[i], wv[j], fma(-bd, Kinv[(size_t)p * ld_in + j], Kinv[(size_t)i * ld_in + j]));
+        kf = Kf_in[(size_t)i * ld_k + j]; ky = Ky_in[(size_t)i * ld_k + j];
+    } else if (i != p) { val = -qq * v[i]; kf = k[i]; ky = kf; }
+    else if (j != p) { val = -qq * wv[j]; kf = k[j]; ky = kf; }
+    else { val = qq; kf = kff; ky = kff + noise_var; }
+    out[(size_t)i * ld_out + j] = val;
+    Kf_out[(size_t)i * ld_out + j] = kf;
+    Ky_out[(size_t)i * ld_out + j] = ky;
+}
+
+extern "C" size_t gpmpc_gp_replace_workspace_bytes(int n, int D) { (void)D; return n < 1 ? 0 : sizeof(double) * (3 * (size_t)n + 8); }   // v, w, kt
+
+// The whole data update of ONE replaced observation (fixed-size window of the closed loop): slot `slot` of the n training points takes the
+// input x_new; Kf, Ky and Ky_inv of the new point set go from the INPUT buffers into the OUTPUT buffers (not aliased: the caller ping-pongs
+// two sets, as for gpmpc_gp_append).  X_dev still holds the OLD row at `slot`; it is not read.  Two dependent launches, as the append.
+extern "C" int gpmpc_gp_replace(int n, int D, int slot, const double* X_dev, const double* xnew_dev, const double* lambdas_host, double sigma_f,
+                                double noise_var, const double* Kf_in, const double* Ky_in, size_t ld_k_in, const double* Kinv_in, size_t ld_in,
+                                double* Kf_out, double* Ky_out, double* Kinv_out, size_t ld_out, void* workspace, size_t workspace_bytes,
+                                void* stream) {
+    if (n < 1 || D < 1 || D > GPMPC_MAX_D || slot < 0 || slot >= n || !X_dev || !xnew_dev || !lambdas_host || !Kf_in || !Ky_in || !Kinv_in ||
+        !Kf_out || !Ky_out || !Kinv_out || !workspace || ld_in < (size_t)n || ld_k_in < (size_t)n || ld_out < (size_t)n)
+        return GPMPC_E_ARG;
+    if (Kf_in == Kf_out || Ky_in == Ky_out || Kinv_in == Kinv_out) return GPMPC_E_ARG;
+    if (workspace_bytes < gpmpc_gp_replace_workspace_bytes(n, D)) return GPMPC_E_WORKSPACE;
+    hipStream_t s = (hipStream_t)stream;
+    double* v = (double*)workspace; double* wv = v + n; double* k = wv + n;
+    AppendHyp hyp;
+    memset(&hyp, 0, sizeof(hyp));
+    for (int d = 0; d < D; ++d) hyp.lam[d] = lambdas_host[d];
+    hyp.sf2 = sigma_f * sigma_f;
+    hipLaunchKernelGGL(k_replace_vw, dim3(n), dim3(256), 0, s, X_dev, n, D, slot, xnew_dev, hyp, Kinv_in, ld_in, k, v, wv);
+    hipLaunchKernelGGL(k_replace_fill, dim3((n + 255) / 256, n), dim3(256), 0, s, Kinv_in, ld_in, (const double*)v, (const double*)wv,
+                       hyp.sf2 + noise_var, n, slot, Kinv_out, ld_out, (const double*)k, Kf_in, Ky_in, ld_k_in, Kf_out, Ky_out, hyp.sf2, noise_var);
+    GPMPC_HIP(hipGetLastError());
+    return GPMPC_OK;
+}

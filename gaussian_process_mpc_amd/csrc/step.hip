@@ -1699,6 +1699,7 @@ struct gpmpc_cb_cache {
     double* h_in;  double* h_out;      // pinned: [ds + H da] and [1 + H da]
     double* d_in;  double* d_out;      // device mirrors
     void* ws; size_t ws_bytes; int cap_H;
+    long long captures;                // how often the callback graph was captured (gpmpc_pack_callback_captures)
 };
 
 void gpmpc_cb_cache_free(void* c) {
@@ -1722,6 +1723,13 @@ void gpmpc_cb_cache_invalidate(void* c) {
     if (g->stream) (void)hipStreamSynchronize(g->stream);
     if (g->exec) { (void)hipGraphExecDestroy(g->exec); g->exec = nullptr; }
     g->valid = 0;
+}
+
+// number of captures of the callback graph this pack has done so far (tests: a refill of the pack with the padded size and the
+// shared-lambda state unchanged -- every step of the windowed closed loop -- must not re-capture)
+extern "C" long long gpmpc_pack_callback_captures(const gpmpc_pack* p) {
+    const gpmpc_cb_cache* g = p ? (const gpmpc_cb_cache*)p->cb_cache : nullptr;
+    return g ? g->captures : 0;
 }
 
 extern "C" int gpmpc_objective_gradient(gpmpc_pack* p, int H, const double* x0_host, const double* U_host,
@@ -1814,7 +1822,7 @@ extern "C" int gpmpc_objective_gradient(gpmpc_pack* p, int H, const double* x0_h
         e = hipGraphInstantiate(&g->exec, graph, nullptr, nullptr, 0);
         (void)hipGraphDestroy(graph);
         if (e != hipSuccess) { gpmpc_set_error("hipGraphInstantiate", e); return GPMPC_E_LAUNCH; }
-        g->H = H; g->flags = flags; g->cost = *cost; g->valid = 1;
+        g->H = H; g->flags = flags; g->cost = *cost; g->valid = 1; ++g->captures;
     }
     memcpy(g->h_in, x0_host, sizeof(double) * p->ds);
     memcpy(g->h_in + p->ds, U_host, sizeof(double) * (size_t)H * p->da);

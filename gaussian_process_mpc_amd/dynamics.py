@@ -26,13 +26,24 @@ class Dynamics(object):
         self.device = self.gpr_err[0].device
         self._pack = None
         self._pack_key = None
+        # Fixed-size training window (extension; None: the training set grows without bound, as in the reference).  Once num_train has
+        # reached max_train, a single new observation REPLACES the row at `window_slot` in every GP (first-in first-out: slot 0 first,
+        # the oldest row after a bulk load) and the slot advances modulo max_train.  X_train / y_train of the GPs are then in SLOT
+        # order, not chronological order: the rows from `window_slot` on are the older ones.
+        self.max_train = None
+        self.window_slot = 0
 
     def append_train_data(self, state, action, next_state, incremental=False, async_rebuild=None, refresh=None):
         """(state, action, next_state) observations, one or many (src/dynamics.py:39-60).  incremental=True: O(N^2)
         update of every Ky_inv for a single new observation (see GaussianProcessRegression.append_train_data);
         async_rebuild (True / False; None leaves the GPs' setting): the periodic full rebuild of the incremental path on a
         side stream instead of on the step that reaches `rebuild_every`; refresh ("rebuild" / "newton"; None leaves the GPs'
-        setting): a Newton-Schulz polish of the updated inverse instead of that rebuild (GaussianProcessRegression.refresh)."""
+        setting): a Newton-Schulz polish of the updated inverse instead of that rebuild (GaussianProcessRegression.refresh).
+        With `max_train` set: a single observation that arrives at num_train == max_train replaces row `window_slot` (incremental=True:
+        C ABI ``gpmpc_gp_replace``; False: a rebuild on the window's rows); a call that would exceed the budget otherwise keeps the
+        newest max_train rows in chronological order, rebuilds and resets the slot to 0."""
+        if async_rebuild and self.max_train is not None:
+            raise ValueError("max_train (fixed-size window) is not supported together with async_rebuild=True")
         if async_rebuild is not None:
             for g in self.gpr_err:
                 g.async_rebuild = bool(async_rebuild)
@@ -62,6 +73,18 @@ class Dynamics(object):
             x = np.concatenate((state, action), axis=1)
             ys = [next_state[:, i] for i in range(self.state_dim)]
             incremental = False
+        if self.max_train is not None:
+            n_new = 1 if len(state.shape) == 1 else x.shape[0]
+            n_old = self.gpr_err[0].num_train
+            if n_new == 1 and n_old == self.max_train and all(g.num_train == n_old for g in self.gpr_err):
+                self._replace_in_window(np.reshape(x, (1, -1)), np.reshape(next_state, (1, self.state_dim)), incremental, uniform)
+                return
+            if n_old + n_new > self.max_train:
+                x, ys = self._trim_to_window(np.reshape(x, (n_new, -1)), np.reshape(next_state, (n_new, self.state_dim)))
+                if x is None:                                # the GPs held different rows: each was rebuilt on its own
+                    return
+                next_state = np.stack(ys, axis=1)
+                incremental, uniform = False, True
         if not uniform:
             for g, y in zip(self.gpr_err, ys):
                 g.append_train_data(x, y, incremental=incremental)
@@ -80,6 +103,54 @@ class Dynamics(object):
                 modes.append(g._ingest(xx, yy, n_obs, incremental, shared=shared, column=a))
             GaussianProcessRegression.update_many(self.gpr_err, modes)
         self._seen_X = [g.X_train for g in self.gpr_err]
+
+    # -- fixed-size window -------------------------------------------------------------------
+    def _replace_in_window(self, x, y_row, incremental, uniform):
+        """One observation into slot `window_slot` of every GP (num_train == max_train), then the slot advances."""
+        slot = self.window_slot
+        if slot >= self.max_train:
+            slot = 0
+        if not uniform:
+            for a, g in enumerate(self.gpr_err):
+                g.replace_train_data(slot, x, y_row[0, a], incremental=incremental)
+        else:
+            shared = {}
+            modes = [g._ingest_replace(slot, x, y_row[0, a], incremental, shared=shared) for a, g in enumerate(self.gpr_err)]
+            GaussianProcessRegression.update_many(self.gpr_err, modes)
+        self.window_slot = (slot + 1) % self.max_train
+        self._seen_X = [g.X_train for g in self.gpr_err]
+
+    def _trim_to_window(self, x_new, y_new):
+        """A call that would take the training set beyond max_train: the rows every GP holds, in CHRONOLOGICAL order (slot order rotated
+        by window_slot), followed by the new ones; the newest max_train of them are kept and the GPs emptied, so that the caller's bulk
+        path rebuilds on exactly those rows.  Rare (a bulk load into a full window): goes through the host."""
+        m = int(self.max_train)
+        if m < 1:
+            raise ValueError("max_train must be a positive number of training points, got %r" % (self.max_train,))
+        rows_x, rows_y = [], []
+        for a, g in enumerate(self.gpr_err):
+            if g.num_train:
+                Xg, yg = g.X_train.detach().cpu().numpy(), g.y_train.detach().cpu().numpy().reshape(-1)
+                if g.num_train == m and self.window_slot:
+                    Xg, yg = np.roll(Xg, -self.window_slot, axis=0), np.roll(yg, -self.window_slot)
+                rows_x.append(np.concatenate((Xg, x_new), axis=0)[-m:])
+                rows_y.append(np.concatenate((yg, y_new[:, a]))[-m:])
+            else:
+                rows_x.append(x_new[-m:])
+                rows_y.append(y_new[-m:, a])
+            g.X_train = g.y_train = g.Kf = g.Ky = g.Ky_inv = None
+            g.num_train = 0
+            g._beta = None
+            g._pending = None
+        self.window_slot = 0
+        if all(np.array_equal(rx, rows_x[0]) for rx in rows_x[1:]):
+            self._uniform_ok, self._seen_X = True, None          # every GP restarts from the same rows: they can share builds again
+            return rows_x[0], rows_y
+        self._uniform_ok = False
+        for g, rx, ry in zip(self.gpr_err, rows_x, rows_y):
+            g.append_train_data(rx, ry)
+        self._seen_X = [g.X_train for g in self.gpr_err]
+        return None, None
 
     # -- device pack -----------------------------------------------------------------------
     def _key(self):

@@ -36,6 +36,9 @@ class GaussianProcessRegression(object):
         self.x_dim = x_dim
         self.num_train = 0
         self.y_train = None
+        # (num_train, x_dim) device tensor.  Rows are in chronological order while the set only grows (append_train_data); once
+        # replace_train_data / a Dynamics with max_train has overwritten rows they are in SLOT order -- row i is whatever was last stored
+        # in slot i -- and every comparison with a from-scratch build has to use the same row order.  y_train follows X_train.
         self.X_train = None
         self.Kf = None
         self.Ky = None
@@ -138,6 +141,124 @@ class GaussianProcessRegression(object):
             self._append_one_incremental(self.X_train[-1:])
         else:
             self.build_Ky_inv_mat()
+
+    # -- fixed-size window (extension: the reference's training set only grows)
+    def replace_train_data(self, index, x, y, incremental=False):
+        """Overwrite training point `index` (0 <= index < num_train) with the observation (x, y); num_train is unchanged.
+        incremental=False: the reference's own update on the new rows (``build_Ky_inv_mat``).  incremental=True: one O(N^2)
+        library call (C ABI ``gpmpc_gp_replace``) from the current matrices into the other ping-pong buffer set; it counts as one
+        step towards `rebuild_every`, falls back to the rebuild like the incremental append does (hyper-parameters changed
+        since the build, refresh due), and `refresh = "newton"` polishes instead.  X_train / y_train become FRESH tensors: one
+        taken before the call keeps its values."""
+        x = np.reshape(np.asarray(x, dtype=np.float64), (1, self.x_dim))
+        y = np.reshape(np.asarray(y, dtype=np.float64), (1, 1))
+        if self._ingest_replace(index, x, y, incremental) == "replace":
+            self._replace_one_incremental()
+        else:
+            self._replace_args = None
+            self.build_Ky_inv_mat()
+
+    def remove_train_data(self, index, incremental=False):
+        """Drop training point `index`: rows after it move up by one.  incremental=False: ``build_Ky_inv_mat`` on the remaining
+        rows.  incremental=True: the (n - 1)-point inverse from the n-point one in O(N^2) (C ABI ``gpmpc_kinv_remove``), row and
+        column `index` of Kf and Ky deleted; same fall-back rules as the incremental append.  All tensors are fresh ones."""
+        n = self.num_train
+        index = self._window_index(index)
+        if n < 2:
+            raise ValueError("remove_train_data: the last training point cannot be removed")
+        keep = torch.cat((torch.arange(0, index, device=self.device), torch.arange(index + 1, n, device=self.device)))
+        self.X_train = self.X_train.index_select(0, keep)
+        self.y_train = self.y_train.index_select(0, keep)
+        inc = self._incremental_ok(incremental)
+        self._pending = None
+        self.num_train = n - 1
+        if not inc:
+            self.build_Ky_inv_mat()
+            return
+        Kinv = self.Ky_inv if self.Ky_inv.stride(1) == 1 else self.Ky_inv.contiguous()
+        out = torch.empty((n - 1, n - 1), dtype=torch.float64, device=self.device)
+        with torch.cuda.device(self.device):
+            check(lib().gpmpc_kinv_remove(n, ctypes.c_void_p(Kinv.data_ptr()), Kinv.stride(0), index, ptr(out), n - 1,
+                                          stream_ptr(self.device)), "gpmpc_kinv_remove")
+        self.Kf = self.Kf.index_select(0, keep).index_select(1, keep)
+        self.Ky = self.Ky.index_select(0, keep).index_select(1, keep)
+        self.Ky_inv = out
+        self._after_incremental_step()
+
+    def _window_index(self, index):
+        if self.async_rebuild:
+            raise ValueError("replace / remove of a training point is not supported together with async_rebuild=True "
+                             "(the catch-up of a side-stream rebuild replays appends by row range)")
+        index = int(index)
+        if not 0 <= index < self.num_train:
+            raise IndexError("training point %d out of range (num_train = %d)" % (index, self.num_train))
+        return index
+
+    def _incremental_ok(self, incremental):
+        """The O(N^2) updates are only valid on matrices built with the CURRENT hyper-parameters, and their round-off accumulates
+        (see `_ingest`): same rule for replace and remove as for the append."""
+        return bool(incremental and self.Ky_inv is not None and self._built_hypers == self._current_hypers()
+                    and (self._appends_since_rebuild < self.rebuild_every or self.refresh == "newton"))
+
+    def _ingest_replace(self, index, x, y, incremental, shared=None):
+        """Store the row that takes slot `index` and say how the matrices have to follow: "replace" or "full".  X_train and y_train
+        are replaced by fresh tensors (clone, then the new row as kernel arguments, C ABI ``gpmpc_store_host``), never
+        overwritten under a holder.  `shared`: as in `_ingest`, the new X_train is made once for the GPs that held the same one."""
+        index = self._window_index(index)
+        xh = np.ascontiguousarray(np.asarray(x, dtype=np.float64).reshape(self.x_dim))
+        yh = np.ascontiguousarray(np.asarray(y, dtype=np.float64).reshape(1))
+        X_old = self.X_train
+        with torch.cuda.device(self.device):
+            sp = stream_ptr(self.device)
+            if shared is not None and shared.get("X_old") is X_old:
+                X_new = shared["X_new"]
+            else:
+                X_new = X_old.clone(memory_format=torch.contiguous_format)
+                if self.x_dim * 8 <= 512:
+                    check(lib().gpmpc_store_host(ctypes.c_void_p(X_new.data_ptr() + 8 * index * self.x_dim),
+                                                 xh.ctypes.data_as(ctypes.c_void_p), 8 * self.x_dim, sp), "gpmpc_store_host")
+                else:
+                    X_new[index] = torch.tensor(xh).to(self.device)
+                if shared is not None:
+                    shared["X_old"], shared["X_new"] = X_old, X_new
+            y_new = self.y_train.clone(memory_format=torch.contiguous_format)
+            check(lib().gpmpc_store_host(ctypes.c_void_p(y_new.data_ptr() + 8 * index), yh.ctypes.data_as(ctypes.c_void_p), 8, sp),
+                  "gpmpc_store_host")
+        self.X_train, self.y_train = X_new, y_new
+        self._pending = None
+        self._replace_args = (index, X_old)
+        return "replace" if self._incremental_ok(incremental) else "full"
+
+    def _replace_one_incremental(self):
+        """self.X_train / y_train already hold the new row at the slot; Kf, Ky, Ky_inv are those of the old rows.  One library call
+        (C ABI ``gpmpc_gp_replace``) from the current matrices into the other buffer set."""
+        index, X_old = self._replace_args
+        self._replace_args = None
+        n = self.num_train
+        cap, Kf, Ky, Kinv, dst = self._next_buffer_set(n)
+        if not X_old.is_contiguous():
+            X_old = X_old.contiguous()
+        xn = self.X_train[index:index + 1]
+        if not xn.is_contiguous():
+            xn = xn.contiguous()
+        _, lp = host_doubles(self.get_lambdas())
+        vp = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
+        with torch.cuda.device(self.device):
+            check(lib().gpmpc_gp_replace(n, self.x_dim, index, ptr(X_old), ptr(xn), lp, self.get_sigma_f(), self._noise_var(),
+                                         vp(Kf), vp(Ky), Kf.stride(0), vp(Kinv), Kinv.stride(0),
+                                         vp(dst[0]), vp(dst[1]), vp(dst[2]), cap,
+                                         ctypes.c_void_p(self._append_ws.data_ptr()), self._append_ws.numel(), stream_ptr(self.device)),
+                  "gpmpc_gp_replace")
+        self._cur = 1 - self._cur
+        self.Kf, self.Ky, self.Ky_inv = dst[0][:n, :n], dst[1][:n, :n], dst[2][:n, :n]
+        self._after_incremental_step()
+
+    def _after_incremental_step(self):
+        self._beta = None
+        self.version += 1
+        self._appends_since_rebuild += 1
+        if self.refresh == "newton" and self._appends_since_rebuild >= self.rebuild_every:
+            self._newton_refresh()
 
     def _ingest(self, x, y, num_obs, incremental, shared=None, column=0):
         """Store the new rows (src/gpr.py:109-119) and say how the matrices have to follow: "incremental" or "full".
@@ -288,16 +409,15 @@ class GaussianProcessRegression(object):
             self._cap = cap
             self._bufs = [[torch.empty((cap, cap), dtype=torch.float64, device=self.device) for _ in range(3)] for _ in range(2)]
             self._cur = 1                                       # the next write goes to set 0
-            nb = lib().gpmpc_gp_append_workspace_bytes(cap, self.x_dim)
+            nb = max(lib().gpmpc_gp_append_workspace_bytes(cap, self.x_dim), lib().gpmpc_gp_replace_workspace_bytes(cap, self.x_dim))
             self._append_ws = torch.empty(int(nb), dtype=torch.uint8, device=self.device)
         return cap
 
-    def _append_one_incremental(self, x_new):
-        """self.X_train / y_train already hold the new row (last) and num_train counts it; Kf, Ky, Ky_inv still have the
-        old size n.  One library call (C ABI ``gpmpc_gp_append``: k = K_f(X, x_new), the Schur step on Ky_inv, the new row /
-        column of Kf and Ky) from the current matrices into the other buffer set."""
-        n = self.num_train - 1
-        cap = self._append_buffers(n + 1)
+    def _next_buffer_set(self, n1):
+        """The current matrices in a form the library reads in place (unit column stride, one row stride for Kf and Ky) and the buffer
+        set the (n1)-point ones are written into: the one the inputs do NOT live in.  GPs that adopted views of that set keep their
+        matrices: they get copies first.  The caller flips `_cur` after its launch."""
+        cap = self._append_buffers(n1)
         Kf, Ky, Kinv = self.Kf, self.Ky, self.Ky_inv
         if not (Kf.stride(1) == 1 and Ky.stride(1) == 1 and Kf.stride(0) == Ky.stride(0)):
             Kf, Ky = Kf.contiguous(), Ky.contiguous()
@@ -309,10 +429,10 @@ class GaussianProcessRegression(object):
         if any(d.untyped_storage().data_ptr() in base for d in dst):
             dst = self._bufs[self._cur]
             if any(d.untyped_storage().data_ptr() in base for d in dst):
-                raise RuntimeError("incremental append: both buffer sets alias the current matrices")
+                raise RuntimeError("incremental update: both buffer sets alias the current matrices")
             self._cur = 1 - self._cur
         # a GP that adopted views of the set about to be overwritten (and was not re-fed together with this one) keeps its
-        # n-point matrices: it gets copies first
+        # matrices: it gets copies first
         targets = {d.untyped_storage().data_ptr() for d in dst}
         for f in list(getattr(self, "_sharers", ())):
             if f is self:
@@ -321,6 +441,14 @@ class GaussianProcessRegression(object):
                 t = getattr(f, name)
                 if t is not None and t.untyped_storage().data_ptr() in targets:
                     setattr(f, name, t.clone())
+        return cap, Kf, Ky, Kinv, dst
+
+    def _append_one_incremental(self, x_new):
+        """self.X_train / y_train already hold the new row (last) and num_train counts it; Kf, Ky, Ky_inv still have the
+        old size n.  One library call (C ABI ``gpmpc_gp_append``: k = K_f(X, x_new), the Schur step on Ky_inv, the new row /
+        column of Kf and Ky) from the current matrices into the other buffer set."""
+        n = self.num_train - 1
+        cap, Kf, Ky, Kinv, dst = self._next_buffer_set(n + 1)
         X_old = self.X_train[:n]
         if not X_old.is_contiguous():
             X_old = X_old.contiguous()
@@ -489,7 +617,8 @@ class GaussianProcessRegression(object):
         GPs with bit-identical hyper-parameters share ONE set of matrices (every experiment of the reference sets the
         same lambda / sigma_f / sigma_n on all GPs: ds identical O(N^3) inversions per Simulator step there,
         src/simulator.py:55, src/gpr.py:171), and the distinct ones that need a full rebuild are inverted as one batched
-        factorisation of the (k, n, n) stack instead of k in a Python loop."""
+        factorisation of the (k, n, n) stack instead of k in a Python loop.  modes: what `_ingest` / `_ingest_replace` returned
+        for each GP: "incremental" (one appended row), "replace" (one overwritten row, fixed-size window) or "full"."""
         leaders = {}
         for g, mode in zip(gps, modes):
             # followers take over the leader's matrices AND its refresh state (_adopt): a group must agree on the refresh policy too
@@ -499,6 +628,8 @@ class GaussianProcessRegression(object):
         for key, grp in leaders.items():
             if key[2] == "incremental":
                 grp[0]._append_one_incremental(grp[0].X_train[-1:])
+            elif key[2] == "replace":                          # fixed-size window: `_ingest_replace` left the slot with the leader
+                grp[0]._replace_one_incremental()
         by_kind = {}
         for g in full:
             g._build_kf_ky()

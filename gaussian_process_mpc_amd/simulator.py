@@ -12,7 +12,7 @@ class Simulator(object):
     """env: anything with ``reset() -> (obs, info)`` and ``step(action) -> (obs, reward, terminated, truncated, info)``."""
 
     def __init__(self, mpc, env, num_iters=500, record=False, video_folder=None, name_prefix=None, incremental=False,
-                 async_rebuild=False, refresh=None):
+                 async_rebuild=False, refresh=None, max_train=None):
         if record:
             raise NotImplementedError("video recording needs gym's RecordVideo wrapper: wrap the env before passing it in")
         self.mpc = mpc
@@ -22,6 +22,13 @@ class Simulator(object):
         self.incremental = incremental      # O(N^2) Ky_inv append per step instead of the reference's O(N^3) rebuild
         self.async_rebuild = async_rebuild  # ... and its periodic full rebuild on a side stream (off the step's critical path)
         self.refresh = refresh              # ... or "newton": that rebuild replaced by a Newton-Schulz polish (0.6 instead of 2.2 ms at N = 400)
+        # fixed-size training window (Dynamics.max_train): once the training set holds max_train points, every new observation replaces
+        # the oldest one -- constant data-update cost and memory, the device pack is never re-created.  None: it grows, as in the reference
+        self.max_train = max_train
+        if max_train is not None:
+            if async_rebuild:
+                raise ValueError("max_train (fixed-size window) is not supported together with async_rebuild=True")
+            mpc.dynamics.max_train = int(max_train)
 
     def run(self):
         obs, _ = self.env.reset()

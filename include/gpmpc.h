@@ -98,6 +98,9 @@ int gpmpc_pack_reload_tuning(gpmpc_pack* pack);
 /* Number of hipGraph captures gpmpc_rollout(GPMPC_USE_GRAPH) has done for this pack (up to 4 captured call shapes are
  * kept per pack, least recently used replaced).  Diagnostic; no reference counterpart. */
 long long gpmpc_pack_graph_captures(const gpmpc_pack* pack);
+/* Number of captures of the callback graph of gpmpc_objective_gradient this pack has done.  A refill of the pack (gpmpc_pack_resize /
+ * gpmpc_pack_build*) keeps that graph unless the shared-lambda state flips; a new horizon, flags or cost re-capture.  Diagnostic. */
+long long gpmpc_pack_callback_captures(const gpmpc_pack* pack);
 
 /* A few host values (<= 512 bytes, a multiple of 4) -> device memory, ordered on `stream`, consumed before the call returns (they travel
  * as kernel arguments: no pageable-memory copy, no synchronisation).  The closed loop appends ONE observation per step
@@ -353,6 +356,29 @@ int gpmpc_gp_append(int n, int D, const double* X_dev, const double* x_new_dev, 
                     double noise_var, const double* Kf_in, const double* Ky_in, size_t ld_k_in, const double* Ky_inv_in, size_t ld_in,
                     double* Kf_out, double* Ky_out, double* Ky_inv_out, size_t ld_out, void* workspace, size_t workspace_bytes,
                     void* stream);
+
+/* Fixed-size training window (no reference counterpart: the reference's training set only grows).  With K = Ky_inv, b = K[:, p],
+ * c = K[p, :], d = K[p, p] (K comes from LU and is not exactly symmetric: row and column forms are kept apart):
+ *
+ * REMOVE point `index`: out dev [(n-1)][(n-1)] (row stride ld_out >= n - 1) = K_ij - b_i c_j / d over i, j != index, compacted (rows
+ * and columns after `index` move up by one): the inverse of Ky without that row and column.  n >= 2, 0 <= index < n, ld_in >= n,
+ * out must not alias Ky_inv.  One launch, no workspace. */
+int gpmpc_kinv_remove(int n, const double* Ky_inv_dev, size_t ld_in, int index, double* out_dev, size_t ld_out, void* stream);
+
+/* REPLACE point `slot` by the input x_new (n stays n): the whole data update of one observation in a window of constant size, from one
+ * buffer set into the other, argument conventions of gpmpc_gp_append (ld_out >= n).  With kt_i = k_f(x_i, x_new) for i != slot,
+ * kt_slot = 0, kappa = sigma_f^2 + noise_var:
+ *     v = K kt - b (c . kt) / d      w = K^T kt - c (b . kt) / d      q = 1 / (kappa - kt . v)
+ *     Ky_inv_out_ij = K_ij - b_i c_j / d + q v_i w_j  (i, j != slot);  column slot = -q v, row slot = -q w, corner q
+ *     Kf_out, Ky_out: row and column `slot` become kt (corner sigma_f^2, on Ky plus noise_var), everything else is copied
+ * i.e. the removal above and the Schur step of gpmpc_kinv_append in one pass, the new point staying in the old one's place.
+ * X dev [n][D] still holds the OLD row at `slot`; that row is not read.  Two kernel launches (k_replace_vw: kt, v, w;
+ * k_replace_fill: q and the three matrices), no allocation, fixed summation order. */
+size_t gpmpc_gp_replace_workspace_bytes(int n, int D);
+int gpmpc_gp_replace(int n, int D, int slot, const double* X_dev, const double* x_new_dev, const double* lambdas_host, double sigma_f,
+                     double noise_var, const double* Kf_in, const double* Ky_in, size_t ld_k_in, const double* Ky_inv_in, size_t ld_in,
+                     double* Kf_out, double* Ky_out, double* Ky_inv_out, size_t ld_out, void* workspace, size_t workspace_bytes,
+                     void* stream);
 
 /* Gradient of the log marginal likelihood w.r.t. the LOG hyper-parameters in one pass over Ky_inv: replaces the autograd
  * backward through inv / det of update_hyperparams (src/gpr.py:334-338; likelihood src/gpr.py:240-251) and the dense

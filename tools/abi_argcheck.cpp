@@ -74,6 +74,29 @@ int main() {
     EXPECT_NEG(gpmpc_gp_append(4, GPMPC_MAX_D + 1, dummy, dummy, dummy, 1.0, 0.0, dummy, dummy, 8, dummy, 8, dummy, dummy, dummy, 8, dummy, 64, nullptr));
     EXPECT_NEG(gpmpc_gp_append(4, 3, nullptr, dummy, dummy, 1.0, 0.0, dummy, dummy, 8, dummy, 8, dummy, dummy, dummy, 8, dummy, 64, nullptr));
     EXPECT_NEG(gpmpc_gp_append(4, 3, dummy, dummy, dummy, 1.0, 0.0, dummy, dummy, 2, dummy, 8, dummy, dummy, dummy, 8, dummy, 64, nullptr));     // leading dimension < n
+    // fixed-size window: removal and replacement of one training point
+    EXPECT_ZERO(gpmpc_pack_callback_captures(nullptr));
+    EXPECT_NEG(gpmpc_kinv_remove(1, dummy, 8, 0, dummy + 32, 8, nullptr));                  // n < 2
+    EXPECT_NEG(gpmpc_kinv_remove(4, nullptr, 8, 0, dummy, 8, nullptr));
+    EXPECT_NEG(gpmpc_kinv_remove(4, dummy, 8, 0, nullptr, 8, nullptr));
+    EXPECT_NEG(gpmpc_kinv_remove(4, dummy, 8, -1, dummy + 32, 8, nullptr));                 // index out of range
+    EXPECT_NEG(gpmpc_kinv_remove(4, dummy, 8, 4, dummy + 32, 8, nullptr));
+    EXPECT_NEG(gpmpc_kinv_remove(4, dummy, 8, 0, dummy, 8, nullptr));                       // output aliases the input
+    EXPECT_NEG(gpmpc_kinv_remove(4, dummy, 3, 0, dummy + 32, 8, nullptr));                  // leading dimensions
+    EXPECT_NEG(gpmpc_kinv_remove(4, dummy, 8, 0, dummy + 32, 2, nullptr));
+    EXPECT_ZERO(gpmpc_gp_replace_workspace_bytes(0, 3));
+    {
+        double in[3][64] = {{0}}, out[3][64] = {{0}}, ws[32];
+        EXPECT_NEG(gpmpc_gp_replace(0, 3, 0, dummy, dummy, dummy, 1.0, 0.0, in[0], in[1], 8, in[2], 8, out[0], out[1], out[2], 8, ws, sizeof(ws), nullptr));
+        EXPECT_NEG(gpmpc_gp_replace(4, GPMPC_MAX_D + 1, 0, dummy, dummy, dummy, 1.0, 0.0, in[0], in[1], 8, in[2], 8, out[0], out[1], out[2], 8, ws, sizeof(ws), nullptr));
+        EXPECT_NEG(gpmpc_gp_replace(4, 3, -1, dummy, dummy, dummy, 1.0, 0.0, in[0], in[1], 8, in[2], 8, out[0], out[1], out[2], 8, ws, sizeof(ws), nullptr));
+        EXPECT_NEG(gpmpc_gp_replace(4, 3, 4, dummy, dummy, dummy, 1.0, 0.0, in[0], in[1], 8, in[2], 8, out[0], out[1], out[2], 8, ws, sizeof(ws), nullptr));
+        EXPECT_NEG(gpmpc_gp_replace(4, 3, 1, nullptr, dummy, dummy, 1.0, 0.0, in[0], in[1], 8, in[2], 8, out[0], out[1], out[2], 8, ws, sizeof(ws), nullptr));
+        EXPECT_NEG(gpmpc_gp_replace(4, 3, 1, dummy, dummy, dummy, 1.0, 0.0, in[0], in[1], 8, in[2], 8, out[0], out[1], in[2], 8, ws, sizeof(ws), nullptr));   // aliasing
+        EXPECT_NEG(gpmpc_gp_replace(4, 3, 1, dummy, dummy, dummy, 1.0, 0.0, in[0], in[1], 2, in[2], 8, out[0], out[1], out[2], 8, ws, sizeof(ws), nullptr));  // leading dimension < n
+        EXPECT_NEG(gpmpc_gp_replace(4, 3, 1, dummy, dummy, dummy, 1.0, 0.0, in[0], in[1], 8, in[2], 8, out[0], out[1], out[2], 3, ws, sizeof(ws), nullptr));
+        EXPECT_NEG(gpmpc_gp_replace(4, 3, 1, dummy, dummy, dummy, 1.0, 0.0, in[0], in[1], 8, in[2], 8, out[0], out[1], out[2], 8, ws, 16, nullptr));          // workspace too small
+    }
     EXPECT_ZERO(gpmpc_timing_enable(0));
     {   // launch geometry, host-side views (round 5): valid calls exercise the host code under the sanitizers, invalid ones return error codes
         int n_items = -1, traj = -1, col = -1;
