@@ -3,11 +3,14 @@
 src/experiments/pretrain_uncertainty.py: pre-train the GP on random transitions, then run the MPC loop
 (Simulator.run, src/simulator.py:37-60) with the model growing by one observation per step.
 
-    python examples/pendulum_closed_loop.py [--pretrain 200] [--steps 25] [--horizon 10] [--window N]
+    python examples/pendulum_closed_loop.py [--pretrain 200] [--steps 25] [--horizon 10] [--window N] [--nominal identity]
 
 --window N: fixed-size training window -- once the model holds N points every new observation replaces the oldest one (first-in
 first-out), so the cost of the data update and the memory stay constant however long the loop runs (what the solver makes of a model
 that has forgotten its pre-training points is another matter: BASELINE.md section 4w).
+
+--nominal identity: the GPs learn the state DIFFERENCE x_{t+1} - x_t (LinearNominalModel.identity: the nominal model of state a is
+x_a) and the rollout adds the state back exactly; a zero-mean GP on the raw next state reverts to 0 away from the data.
 
 Needs an MI355X and the built library; no gym, no cyipopt (the stand-in solver is scipy's L-BFGS-B on the same
 objective / gradient callbacks, so the trajectories are NOT the reference's Ipopt trajectories)."""
@@ -19,7 +22,7 @@ import time
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from gaussian_process_mpc_amd import PendulumPlant, RiskSensitiveMPC, Simulator   # noqa: E402
+from gaussian_process_mpc_amd import LinearNominalModel, PendulumPlant, RiskSensitiveMPC, Simulator   # noqa: E402
 
 
 def main():
@@ -31,11 +34,13 @@ def main():
     ap.add_argument("--starts", type=int, default=1, help="K > 1: lock-step multi-start solve, one batched rollout per tick (mpc.n_starts)")
     ap.add_argument("--window", type=int, default=None, help="fixed-size training window of N points (Simulator max_train); default: the set grows")
     ap.add_argument("--refresh", choices=("rebuild", "newton"), default=None, help="how the incremental path bounds its round-off")
+    ap.add_argument("--nominal", choices=("none", "identity"), default="none", help="identity: the GPs learn x_{t+1} - x_t, the rollout adds x_t back")
     args = ap.parse_args()
 
     rng = np.random.default_rng(0)
     plant = PendulumPlant()
-    mpc = RiskSensitiveMPC(args.gamma, args.horizon, 2, 1, Q=2 * np.eye(2), R=0.001 * np.eye(1))
+    nominal = LinearNominalModel.identity(2, 1) if args.nominal == "identity" else None
+    mpc = RiskSensitiveMPC(args.gamma, args.horizon, 2, 1, Q=2 * np.eye(2), R=0.001 * np.eye(1), nominal_models=nominal)
     for gp in mpc.dynamics.gpr_err:                      # hypers before data, as in pretrain_uncertainty.py:100-105
         gp.set_lambdas(np.array([0.5, 0.5, 0.5]))
         gp.set_sigma_n(1e-3)
@@ -58,7 +63,8 @@ def main():
     th = np.array([h[0][0] for h in hist])
     print(f"{len(hist)} MPC steps in {dt:.2f} s ({dt / len(hist) * 1e3:.1f} ms per step, solver: {mpc.solver_used}); "
           f"training set {args.pretrain} -> {mpc.dynamics.gpr_err[0].num_train} points"
-          + (f" (window of {args.window}, next slot {mpc.dynamics.window_slot})" if args.window else ""))
+          + (f" (window of {args.window}, next slot {mpc.dynamics.window_slot})" if args.window else "")
+          + (f"; nominal model: {args.nominal}" if nominal else ""))
     print("theta:", np.array2string(th[:: max(1, len(th) // 10)], precision=2))
 
 

@@ -21,7 +21,8 @@ from .mpc import RiskSensitiveMPC                                       # noqa: 
 from .uncertainty_prop import mean_prop_torch, variance_prop_torch, covariance_prop_torch  # noqa: F401
 from .simulator import Simulator, PendulumPlant, CartPolePlant          # noqa: F401
 from .rollout import GPPack, CostParams, rollout, rollout_fullcov, moment_match   # noqa: F401
+from .nominal import LinearNominalModel                                 # noqa: F401
 
 __all__ = ["GaussianProcessRegression", "Dynamics", "RiskSensitiveMPC", "mean_prop_torch",
            "variance_prop_torch", "covariance_prop_torch", "GPPack", "CostParams", "rollout",
-           "rollout_fullcov", "moment_match", "Simulator", "PendulumPlant", "CartPolePlant", "lib", "require_gpu"]
+           "rollout_fullcov", "moment_match", "LinearNominalModel", "Simulator", "PendulumPlant", "CartPolePlant", "lib", "require_gpu"]

@@ -65,6 +65,8 @@ SIGNATURES = {
     "gpmpc_pack_build": (_i, [_vp, _vp, _vp, _vp, _dp, _dp, _vp]),
     "gpmpc_pack_build_strided": (_i, [_vp, _vp, _vp, _vp, _sz, _sz, _dp, _dp, _vp]),
     "gpmpc_pack_build_beta": (_i, [_vp, _vp, _vp, _vp, _dp, _dp, _vp]),
+    "gpmpc_pack_set_nominal": (_i, [_vp, _dp, _dp, _vp]),
+    "gpmpc_pack_get_nominal": (_i, [_vp, _dp, _dp]),
     "gpmpc_pack_enable_fullcov": (_i, [_vp, _vp]),
     "gpmpc_pack_dims": (_i, [_vp] + [ctypes.POINTER(_i)] * 4),
     "gpmpc_pack_shared_lambda": (_i, [_vp]),
@@ -134,6 +136,9 @@ def lib():
 def check(rc, what):
     if rc != 0:
         detail = lib().gpmpc_last_error().decode() if rc == -3 else ""
+        if rc == -5:                       # refusals on a pack with a nominal model say why (others leave the text alone)
+            why = lib().gpmpc_last_error().decode()
+            detail = why if "nominal model" in why else ""
         raise GpmpcError(f"{what} failed: {_ERR.get(rc, rc)} {detail}".strip())
 
 

@@ -607,6 +607,10 @@ extern "C" int gpmpc_rollout_fullcov(const gpmpc_pack* p, int B, int H, const do
     if (!p) return GPMPC_E_ARG;
     if (int rc_dev = gpmpc_check_device(p)) return rc_dev;
     if (!p || !x0 || !U || !cost || !out_means || !out_covs || !out_cost || !workspace || B < 1 || H < 1) return GPMPC_E_ARG;
+    if (p->nominal) {       // (the cross-covariances between the linear part and the GPs are not implemented)
+        gpmpc_set_error_text("gpmpc_rollout_fullcov: the full-covariance rollout does not know the linear nominal model of this pack");
+        return GPMPC_E_STATE;
+    }
     if (!p->built || (p->npairs > 0 && !p->fullcov)) return GPMPC_E_STATE;
     const bool grad = (flags & GPMPC_WANT_GRAD) != 0;
     if (grad && !out_grad) return GPMPC_E_ARG;

@@ -100,6 +100,13 @@ struct gpmpc_pack {
     gpmpc_worklist wl_sh[4];   // items {group, i0, j0, tile}: [0: 256x256 tiles, XCD-sorted | 1: 256x64 | 2: 256x128, XCD-sorted]; .nunits = groups
                                // [3: 256x64 in groups of TWO GPs (the one-launch form of smaller mid-size batches; built when sh_ng > 2 and ds is even)]
     int sh_tiles[3];           // tiles per GP
+    // Linear nominal model (gpmpc_pack_set_nominal): GP a learns the residual of m_a(z) = nom_w[a] . z + nom_b[a], z = (x, u).  The
+    // coefficients live in device memory owned by the pack ([ds][D] weights, then [ds] biases) and are read by the nominal variants of
+    // the head kernel (step.hip) and by the builds that take raw targets: never kernel arguments, so captured launches do not depend on them.
+    int nominal;
+    double* nom_dev;           // [ds * D + ds], allocated by the first gpmpc_pack_set_nominal
+    double* resid_dev;         // [Np][ds] residual targets Y - X n^T - c of the last build from raw targets
+    double nom_host[GPMPC_MAX_DS * (GPMPC_MAX_D + 1)];
 };
 
 // Number of pair-kernel output moments per (trajectory, GP, tile).
@@ -245,6 +252,7 @@ int gpmpc_launch_pair(int D, bool diag, bool grad, int tb, int waves, const Pair
 template <int D> int gpmpc_launch_pair_D(bool diag, bool grad, int tb, int waves, const PairArgs& a, hipStream_t s);
 
 void gpmpc_set_error(const char* what, hipError_t e);
+void gpmpc_set_error_text(const char* text);      // gpmpc_last_error for refusals that are not HIP errors
 // Small host array (<= 512 bytes: hyper-parameters, index pairs) -> device memory, ordered on `s`, with the host bytes CONSUMED BEFORE
 // THE CALL RETURNS: they travel as kernel arguments.  (hipMemcpyAsync from pageable memory may read the host buffer only when the
 // stream gets there -- behind a wait on another stream that can be after the caller has freed it; seen as a wrong K matrix from a

@@ -395,6 +395,10 @@ extern "C" int gpmpc_moment_match(const gpmpc_pack* p, int nq, const double* u, 
     if (!p) return GPMPC_E_ARG;
     if (int rc_dev = gpmpc_check_device(p)) return rc_dev;
     if (!p) return GPMPC_E_ARG;
+    if (p->nominal) {       // (beta of such a pack belongs to the residual targets: the moments would be those of the residual alone)
+        gpmpc_set_error_text("gpmpc_moment_match: single-step moment matching does not know the linear nominal model of this pack");
+        return GPMPC_E_STATE;
+    }
     return gpmpc_moment_match_ex(p, nq, u, S, flags, out_mean, out_var, out_cov, out_l, dmean_du, dmean_dS, dvar_du, dvar_dS,
                                  dcov_du, dcov_dS, workspace, workspace_bytes, stream, p->D);
 }

@@ -80,6 +80,16 @@ __global__ __launch_bounds__(256) void k_pack_weights(const double* __restrict__
     }
 }
 
+// Residual targets of a pack with a linear nominal model: R[i][a] = Y[i][a] - sum_k X[i][k] n_ak - c_a (the GPs learn the residual)
+__global__ void k_pack_residual(const double* __restrict__ X, const double* __restrict__ Y, const double* __restrict__ nom,
+                                int N, int D, int ds, double* __restrict__ R) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x, a = blockIdx.y;
+    if (i >= N) return;
+    double m = nom[ds * D + a];
+    for (int k = 0; k < D; ++k) m = fma(X[(size_t)i * D + k], nom[a * D + k], m);
+    R[(size_t)i * ds + a] = Y[(size_t)i * ds + a] - m;
+}
+
 struct gpmpc_small_payload { unsigned w[128]; };
 __global__ void k_upload_small(gpmpc_small_payload p, unsigned* __restrict__ dst, int nwords) {
     const int i = threadIdx.x;
@@ -469,6 +479,42 @@ extern "C" int gpmpc_pack_resize(gpmpc_pack* p, int n_train) {
     return GPMPC_OK;
 }
 
+// Linear nominal model of the rollout: GP a corrects m_a(z) = weights[a] . z + bias[a].  Both NULL clears it.
+extern "C" int gpmpc_pack_set_nominal(gpmpc_pack* p, const double* weights_host, const double* bias_host, void* stream) {
+    if (!p || ((weights_host == nullptr) != (bias_host == nullptr))) return GPMPC_E_ARG;
+    if (int rc_dev = gpmpc_check_device(p)) return rc_dev;
+    const int on = weights_host ? 1 : 0, nw = p->ds * p->D;
+    if (on) {
+        if (!p->nom_dev && hipMalloc(&p->nom_dev, sizeof(double) * (nw + p->ds)) != hipSuccess) { p->nom_dev = nullptr; return GPMPC_E_ALLOC; }
+        if (!p->resid_dev && hipMalloc(&p->resid_dev, sizeof(double) * (size_t)p->Np * p->ds) != hipSuccess) { p->resid_dev = nullptr; return GPMPC_E_ALLOC; }
+        // (two uploads: ds D + ds doubles can exceed the 512 bytes one carries)
+        if (int rcu = gpmpc_upload_small(p->nom_dev, weights_host, sizeof(double) * nw, (hipStream_t)stream)) return rcu;
+        if (int rcu = gpmpc_upload_small(p->nom_dev + nw, bias_host, sizeof(double) * p->ds, (hipStream_t)stream)) return rcu;
+        memcpy(p->nom_host, weights_host, sizeof(double) * nw);
+        memcpy(p->nom_host + nw, bias_host, sizeof(double) * p->ds);
+    }
+    // a nominal pack runs other kernel instances under another plan: what was captured or measured for the other state is dropped
+    // (new VALUES of a model that stays on change neither: the kernels read them from device memory)
+    if (on != p->nominal) {
+        gpmpc_graph_cache_invalidate(p->graph_cache);
+        gpmpc_cb_cache_invalidate(p->cb_cache);
+        gpmpc_tuned_clear(p->tuned);
+    }
+    p->nominal = on;
+    p->built = 0;                                            // beta belongs to the targets minus the OLD model
+    return GPMPC_OK;
+}
+
+// 1: a nominal model is set (weights_host [ds][D] / bias_host [ds] are filled where not NULL), 0: none
+extern "C" int gpmpc_pack_get_nominal(const gpmpc_pack* p, double* weights_host, double* bias_host) {
+    if (!p) return GPMPC_E_ARG;
+    if (!p->nominal) return 0;
+    const int nw = p->ds * p->D;
+    if (weights_host) memcpy(weights_host, p->nom_host, sizeof(double) * nw);
+    if (bias_host) memcpy(bias_host, p->nom_host + nw, sizeof(double) * p->ds);
+    return 1;
+}
+
 extern "C" int gpmpc_pack_destroy(gpmpc_pack* p) {
     if (!p) return GPMPC_OK;
     if (p->X) (void)hipFree(p->X);
@@ -486,6 +532,8 @@ extern "C" int gpmpc_pack_destroy(gpmpc_pack* p) {
     if (p->fcs_rows) (void)hipFree(p->fcs_rows);
     for (int k = 0; k < 8; ++k) for (int q = 0; q < 3; ++q) if (p->fcs_ustart_dev[k][q]) (void)hipFree(p->fcs_ustart_dev[k][q]);
     if (p->fcs_tiles256_dev) (void)hipFree(p->fcs_tiles256_dev);
+    if (p->nom_dev) (void)hipFree(p->nom_dev);
+    if (p->resid_dev) (void)hipFree(p->resid_dev);
     for (int mode = 0; mode < 2; ++mode)
         for (int k = 0; k < 8; ++k) {
             if (p->wl[mode][k].work_dev) (void)hipFree(p->wl[mode][k].work_dev);
@@ -542,6 +590,10 @@ static int pack_build_impl(gpmpc_pack* p, const double* X_dev, const double* Y_d
     if (int rcu = gpmpc_upload_small(p->lam, lambdas_host, sizeof(double) * p->ds * p->D, s)) return rcu;
     if (int rcu = gpmpc_upload_small(p->sf, sigma_f_host, sizeof(double) * p->ds, s)) return rcu;
     hipLaunchKernelGGL(k_pack_points, dim3((p->Np + 255) / 256), dim3(256), 0, s, X_dev, p->N, p->Np, p->D, p->X, p->XT);
+    if (p->nominal && !y_is_beta) {                          // raw targets: the GPs are trained on what the nominal model leaves
+        hipLaunchKernelGGL(k_pack_residual, dim3((p->N + 255) / 256, p->ds), dim3(256), 0, s, X_dev, Y_dev, p->nom_dev, p->N, p->D, p->ds, p->resid_dev);
+        Y_dev = p->resid_dev;
+    }
     if (y_is_beta)
         hipLaunchKernelGGL(k_pack_copy_beta, dim3((p->Np + 255) / 256, p->ds), dim3(256), 0, s, Y_dev, p->N, p->Np, p->ds, p->beta);
     else

@@ -65,16 +65,29 @@ struct RollArgs {
     // outputs of the tail
     double* out_cost; double* out_grad;
     gpmpc_cost_params cost;
+    const double* nom;   // linear nominal model of the pack: [ds][D] weights, then [ds] biases (nominal kernel variants only), else null
 };
 
 // layout of sp (doubles): 0 c | 1 mu | 2 sf2 | 3 A[D] | 3+D scale[D] | 3+2D dmu_du[D] | 3+3D dmu_ds[D]
 //   with row chunks (hchunks > 1):      1 c_m                                  3+2D B[D]      3+3D unused
 __host__ __device__ static inline int sps_of(int D) { return 3 + 4 * D; }
+// Linear nominal model m_a(z) = n_a . z + c_a (GP a learns the residual): the step's moments become
+//   mu' = mu_g + n . u + c,   var' = var_g + sum_k n_k^2 s_k + 2 sum_k w_k dmu_g/du_k,   w_k = n_k s_k   (Cov[z, g(z)] = S E[grad g])
+// and, with q_i = sum_k w_k B_k v_ik, E1_l = sum_i p_i q_i v_il, E2_l = sum_i p_i q_i v_il^2, M1_l = sum_i p_i v_il, X = 2 sum_k w_k dmu_g/du_k:
+//   dmu'/du_l = dmu_g/du_l + n_l,   dmu'/ds_l = dmu_g/ds_l
+//   dvar'/du_l = dvar_g/du_l + 2 (c_m B_l E1_l - w_l B_l mu_g)
+//   dvar'/ds_l = dvar_g/ds_l + n_l^2 + 2 n_l dmu_g/du_l - 1/2 B_l X + B_l^2 c_m (2 w_l M1_l - E2_l)          (state inputs l only)
+// prep_step forms these ADDENDS once per (trajectory, GP) and leaves them behind the plain entries of sp; finish_step -- in every workgroup
+// of the trajectory -- adds the same stored values in the same order.  Layout of the extension, from sps_of(D):
+//   0 n . u + c | 1 addend of var | 2 addend of dvar/du [D] | 2+D addend of dvar/ds [D] | 2+2D n [D]        (the [D] blocks with the gradient only)
+// The nominal variants run without row chunks (plan_rollout).
+__host__ __device__ static inline int sps_nominal(int D) { return sps_of(D) + 2 + 3 * D; }
 
 // Finish step t (>= 1) for trajectory b: reduce the pair-kernel partials of ALL ds GPs (mean/var of step t land in
 // s_mu / s_var, LDS) and write to global memory the rows this workgroup owns: every GP if own < 0, else GP `own`
 // only (the head kernel runs one workgroup per (trajectory, GP); each recomputes the cheap reduction and owns one GP).
 #define GPMPC_RED_CH 8
+template <bool NOM>
 __device__ static void finish_step(const RollArgs& A, int b, int t, int own, double* s_z /* [ds*nm] */,
                                    double* s_red /* [ds*nm*GPMPC_RED_CH] */, double* s_mu, double* s_var,
                                    double* s_ms /* [MAX_DS*(1+2 MAX_D) + 4 MAX_DS] */) {
@@ -82,7 +95,7 @@ __device__ static void finish_step(const RollArgs& A, int b, int t, int own, dou
     const bool chunked = A.hchunks > 1;
     // the per-GP scalars of step t, fetched in ONE coalesced round trip that overlaps the reduction below (they were read one by
     // one, each its own round trip, by the ds threads that finish the step)
-    __shared__ double s_spv[GPMPC_MAX_DS * (3 + 4 * GPMPC_MAX_D)];
+    __shared__ double s_spv[GPMPC_MAX_DS * (NOM ? 5 + 7 * GPMPC_MAX_D : 3 + 4 * GPMPC_MAX_D)];
     {
         const double* spb = A.sp + ((size_t)(t & 1) * A.B + b) * ds * A.sps;
         for (int e = threadIdx.x; e < ds * A.sps; e += blockDim.x) s_spv[e] = spb[e];
@@ -225,11 +238,13 @@ __device__ static void finish_step(const RollArgs& A, int b, int t, int own, dou
         const double cm = sp[1];                                   // chunked layout only
         const double c = sp[0], mu = chunked ? cm * ms[0] : sp[1], sf2 = sp[2];
         const double T = c * z[0];
-        const double var = sf2 - T - mu * mu;
-        s_mu[a] = mu;
+        const double* ex = sp + sps_of(D);                         // nominal model: the addends prep_step left (mu stays the GP's own mean)
+        const double mu_out = NOM ? mu + ex[0] : mu;
+        const double var = NOM ? (sf2 - T - mu * mu) + ex[1] : sf2 - T - mu * mu;
+        s_mu[a] = mu_out;
         s_var[a] = var;
         if (own < 0 || own == a) {
-            A.means[((size_t)b * (A.H + 1) + t) * ds + a] = mu;
+            A.means[((size_t)b * (A.H + 1) + t) * ds + a] = mu_out;
             A.vars[((size_t)b * (A.H + 1) + t) * ds + a] = var;
             if (A.grad) {
                 const int nc = 2 * ds + A.da;
@@ -242,13 +257,15 @@ __device__ static void finish_step(const RollArgs& A, int b, int t, int own, dou
                     const double dmu_ds = chunked ? -0.5 * mu * Bq + 0.5 * Bq * Bq * cm * ms[1 + D + k] : sp[3 + 3 * D + k];
                     const double dT_du = -4.0 * sc * c * z[1 + k];
                     const double dT_ds = Ak * (c * z[1 + D + k] - 0.5 * T);
-                    const double dv_du = -dT_du - 2.0 * mu * dmu_du;
-                    const double dv_ds = -dT_ds - 2.0 * mu * dmu_ds;
+                    double dv_du = -dT_du - 2.0 * mu * dmu_du;
+                    double dv_ds = -dT_ds - 2.0 * mu * dmu_ds;
+                    double dm_du = dmu_du;
+                    if (NOM) { dm_du += ex[2 + 2 * D + k]; dv_du += ex[2 + k]; dv_ds += ex[2 + D + k]; }
                     if (k < ds) {
-                        jm[k] = dmu_du; jm[ds + k] = dmu_ds;
+                        jm[k] = dm_du; jm[ds + k] = dmu_ds;
                         jv[k] = dv_du;  jv[ds + k] = dv_ds;
                     } else {            // action input: its variance is a constant
-                        jm[2 * ds + (k - ds)] = dmu_du;
+                        jm[2 * ds + (k - ds)] = dm_du;
                         jv[2 * ds + (k - ds)] = dv_du;
                     }
                 }
@@ -260,7 +277,8 @@ __device__ static void finish_step(const RollArgs& A, int b, int t, int own, dou
 
 // Prepare step t (>= 1) for GP a: input moments (mean/var of step t-1 in s_mu / s_var, action t-1), the O(N) mean
 // sums, the pair-kernel parameters.
-template <int D>
+// NOM: 0 no nominal model | 1 linear nominal model, objective only | 2 with the gradient (E1, E2 carried through the row loop)
+template <int D, int NOM>
 __device__ static void prep_step(const RollArgs& A, int b, int t, int a, int chunk, const double* s_mu, const double* s_var,
                                  double* s_u, double* s_s, double* s_scr, double* s_out, double* s_g) {
     const int ds = A.ds;
@@ -268,6 +286,8 @@ __device__ static void prep_step(const RollArgs& A, int b, int t, int a, int chu
     // every thread redoing all D of them, and thread 0 redoing them again at the end, was half of this kernel's time
     // for small batches)
     __shared__ double s_B[GPMPC_MAX_D], s_A[GPMPC_MAX_D], s_sc[GPMPC_MAX_D], s_r1[GPMPC_MAX_D], s_r2[GPMPC_MAX_D];
+    __shared__ double s_n[NOM ? GPMPC_MAX_D : 1], s_wB[NOM ? GPMPC_MAX_D : 1];      // nominal model: n_ak and w_k B_k = n_ak s_k B_k
+    constexpr int NV = 1 + 2 * D + (NOM == 2 ? 2 * D : 0);                          // sums of the row loop: [p | p v | p v^2 | E1 | E2]
     if (threadIdx.x < D) {
         const int k = threadIdx.x;
         double uk, sk;
@@ -286,21 +306,27 @@ __device__ static void prep_step(const RollArgs& A, int b, int t, int a, int chu
         s_sc[k] = sqrt(0.125 / (0.5 * lam + sk));          // the scale of the pair transform h = sc (u - x): pp and G rows use this value
         s_r1[k] = sk / lam + 1.0;                          // factors of det(S/Lambda + I) and det(2S/Lambda + I)
         s_r2[k] = 2.0 * sk / lam + 1.0;
+        if (NOM) {
+            const double nk = A.nom[a * D + k];
+            s_n[k] = nk;
+            s_wB[k] = (nk * sk) * s_B[k];
+        }
     }
     __syncthreads();
     GPMPC_HST(2);
-    double u[D], Bk[D], sck[D];
+    double u[D], Bk[D], sck[D], wB[NOM == 2 ? D : 1];
 #pragma unroll
     for (int k = 0; k < D; ++k) {
         u[k] = s_u[k];
         Bk[k] = s_B[k];
         sck[k] = s_sc[k];
+        if (NOM == 2) wB[k] = s_wB[k];
     }
     double* __restrict__ Grow = A.G ? (A.shared ? (a == 0 ? A.G + (size_t)b * A.Np * A.gw : nullptr)
                                                 : A.G + ((size_t)b * ds + a) * A.Np * A.gw) : nullptr;
-    double v[1 + 2 * D];
+    double v[NV];
 #pragma unroll
-    for (int m = 0; m < 1 + 2 * D; ++m) v[m] = 0.0;
+    for (int m = 0; m < NV; ++m) v[m] = 0.0;
     const bool chunked = A.hchunks > 1;
     const int r0 = chunked ? chunk * A.hrows : 0, r1 = chunked ? (r0 + A.hrows < A.Np ? r0 + A.hrows : A.Np) : A.Np;
     // The points of up to PF row blocks are fetched first (clamped addresses, one round trip for all of them), then the blocks
@@ -328,6 +354,14 @@ __device__ static void prep_step(const RollArgs& A, int b, int t, int a, int chu
             v[0] += p;
 #pragma unroll
             for (int k = 0; k < D; ++k) { v[1 + k] = fma(p, d[k], v[1 + k]); v[1 + D + k] = fma(p * d[k], d[k], v[1 + D + k]); }
+            if (NOM == 2) {
+                double qn = 0.0;
+#pragma unroll
+                for (int k = 0; k < D; ++k) qn = fma(wB[k], d[k], qn);
+                const double pq = p * qn;
+#pragma unroll
+                for (int k = 0; k < D; ++k) { v[1 + 2 * D + k] = fma(pq, d[k], v[1 + 2 * D + k]); v[1 + 3 * D + k] = fma(pq * d[k], d[k], v[1 + 3 * D + k]); }
+            }
             if (Grow) {    // column row of point i: [h (D) | |h|^2 | h_k^2 (k < ds) | pad], h = sc o u - sc o x as in the pair kernel
                 double* g = s_g + threadIdx.x * A.gw;
                 double qh = 0.0;
@@ -352,7 +386,7 @@ __device__ static void prep_step(const RollArgs& A, int b, int t, int a, int chu
         }
     }
     GPMPC_HST(3);
-    block_sum<1 + 2 * D>(v, s_scr, s_out);
+    block_sum<NV>(v, s_scr, s_out);
     GPMPC_HST(4);
     if (chunked) {
         // partial sums of this row chunk; the constants of the step by chunk 0 (the next launch's finish phase forms mu)
@@ -391,18 +425,36 @@ __device__ static void prep_step(const RollArgs& A, int b, int t, int a, int chu
         sp[3 + 3 * D + k] = -0.5 * mu * Bq + 0.5 * Bq * Bq * cm * s_out[1 + D + k];
         pp[k] = sc * s_u[k];
         pp[D + k] = sc;
+        if (NOM) {      // the addends of the nominal model (layout at sps_nominal); every lane forms the two sums over all dimensions in the same order
+            double* ex = sp + sps_of(D);
+            double lin = A.nom[A.ds * D + a], vlin = 0.0, cross = 0.0;
+            for (int l = 0; l < D; ++l) {
+                const double nl = s_n[l], wl = nl * s_s[l];
+                lin = fma(nl, s_u[l], lin);
+                vlin = fma(nl * nl, s_s[l], vlin);
+                cross = fma(wl, -s_B[l] * cm * s_out[1 + l], cross);        // sum_l w_l dmu_g/du_l
+            }
+            if (k == 0) { ex[0] = lin; ex[1] = vlin + 2.0 * cross; }
+            if (NOM == 2) {
+                const double nk = s_n[k], wk = nk * s_s[k];
+                ex[2 + k] = 2.0 * (cm * Bq * s_out[1 + 2 * D + k] - wk * Bq * mu);
+                ex[2 + D + k] = nk * nk + 2.0 * nk * (-Bq * cm * s_out[1 + k]) - 0.5 * Bq * (2.0 * cross)
+                                + Bq * Bq * cm * (2.0 * wk * s_out[1 + k] - s_out[1 + 3 * D + k]);
+                ex[2 + 2 * D + k] = nk;
+            }
+        }
     }
 }
 
 // One workgroup per (trajectory, GP).  The finish phase of step t-1 reads sp/pp/part written by the previous
 // launches and the prep phase overwrites sp/pp of ITS OWN GP only, so workgroups of one trajectory never race.
-template <int D>
+template <int D, int NOM>
 __global__ __launch_bounds__(256) void k_roll_head(RollArgs A, int t) {
     __shared__ double s_z[GPMPC_MAX_DS * (1 + 2 * GPMPC_MAX_D)];
     __shared__ double s_zred[GPMPC_MAX_DS * (1 + 2 * GPMPC_MAX_D) * GPMPC_RED_CH];
     __shared__ double s_mu[GPMPC_MAX_DS], s_var[GPMPC_MAX_DS];
     __shared__ double s_u[GPMPC_MAX_D], s_s[GPMPC_MAX_D];
-    __shared__ double s_scr[16 * (1 + 2 * D)], s_out[1 + 2 * D];
+    __shared__ double s_scr[16 * (1 + 2 * D + (NOM == 2 ? 2 * D : 0))], s_out[1 + 2 * D + (NOM == 2 ? 2 * D : 0)];
     __shared__ double s_g[256 * (2 * D + 2)];             // staging of 256 G rows (gw <= 2D + 2)
     __shared__ double s_ms[GPMPC_MAX_DS * (1 + 2 * GPMPC_MAX_D) + 4 * GPMPC_MAX_DS];      // mean sums | Z0 wave sums
     const int b = blockIdx.x, a = blockIdx.y, chunk = blockIdx.z;
@@ -419,10 +471,10 @@ __global__ __launch_bounds__(256) void k_roll_head(RollArgs A, int t) {
         }
         __syncthreads();
     } else {
-        finish_step(A, b, t - 1, chunk == 0 ? a : A.ds, s_z, s_zred, s_mu, s_var, s_ms);     // rows of GP a are written by chunk 0 only
+        finish_step<NOM != 0>(A, b, t - 1, chunk == 0 ? a : A.ds, s_z, s_zred, s_mu, s_var, s_ms);     // rows of GP a are written by chunk 0 only
     }
     GPMPC_HST(1);
-    prep_step<D>(A, b, t, a, chunk, s_mu, s_var, s_u, s_s, s_scr, s_out, s_g);
+    prep_step<D, NOM>(A, b, t, a, chunk, s_mu, s_var, s_u, s_s, s_scr, s_out, s_g);
     GPMPC_HST(5);
 }
 
@@ -653,7 +705,7 @@ __device__ static double input_cost(int H, int da, const gpmpc_cost_params& C, c
 // reverse sweep over the (2ds) x (2ds+da) step Jacobians.
 // dynamic LDS: [H+1] cost terms | [H+1][2ds] local derivatives | [H*da] grad | [H] input-cost terms | [H or 1][nz*nc] J
 #define GPMPC_TAIL_WORKERS 32
-template <bool ALLJ, int DS>
+template <bool ALLJ, int DS, bool NOM>
 __global__ __launch_bounds__(256) void k_roll_tail(RollArgs A) {
     extern __shared__ double s_dyn[];
     __shared__ double s_z[GPMPC_MAX_DS * (1 + 2 * GPMPC_MAX_D)];
@@ -663,7 +715,7 @@ __global__ __launch_bounds__(256) void k_roll_tail(RollArgs A) {
     const int b = blockIdx.x, ds = A.ds, da = A.da, H = A.H, tid = threadIdx.x;
     const int nz = 2 * ds, nc = 2 * ds + da;
     __shared__ double s_ms[GPMPC_MAX_DS * (1 + 2 * GPMPC_MAX_D) + 4 * GPMPC_MAX_DS];      // mean sums | Z0 wave sums
-    if (!A.finished) finish_step(A, b, H, -1, s_z, s_zred, s_mu, s_var, s_ms);
+    if (!A.finished) finish_step<NOM>(A, b, H, -1, s_z, s_zred, s_mu, s_var, s_ms);
     double* s_ct = s_dyn;
     double* s_dl = s_ct + (H + 1);
     double* s_gU = s_dl + (size_t)(H + 1) * nz;
@@ -795,6 +847,7 @@ static thread_local char g_err[256] = "";
 void gpmpc_set_error(const char* what, hipError_t e) {
     snprintf(g_err, sizeof(g_err), "%s: %s", what, hipGetErrorString(e));
 }
+void gpmpc_set_error_text(const char* text) { snprintf(g_err, sizeof(g_err), "%s", text); }
 extern "C" const char* gpmpc_last_error(void) { return g_err; }
 extern "C" const char* gpmpc_version(void) { return "gpmpc-hip 0.1 (gfx950)"; }
 extern "C" int gpmpc_device_count(void) {
@@ -914,7 +967,12 @@ static void plan_rollout(const gpmpc_pack* p, int B, int H, bool grad, bool diag
     const int D = p->D;
     if (!shape && !tn_over && !lowprec && diag)                 // a measured plan for this call shape
         if (const gpmpc_tuned_entry* te = tuned_lookup(p, B, H, grad)) shape = &te->plan;
-    const gpmpc_tuning& tn = tn_over ? *tn_over : p->tune;        // GPMPC_* overrides, read once at pack creation
+    // A pack with a linear nominal model is planned as under GPMPC_FUSED=0 GPMPC_FUSED_SB=0 GPMPC_PERSIST=0, whatever the overrides say:
+    // only the head / tail kernels of this file know the model (step_fused.h and traj_persist.h keep their own finish code), and their
+    // nominal variants run without row chunks (the extra sums E1, E2 are not carried through mpart).
+    gpmpc_tuning tn_nom;
+    if (p->nominal) { tn_nom = tn_over ? *tn_over : p->tune; tn_nom.fused = 0; tn_nom.fused_sb = 0; tn_nom.persist = 0; tn_nom.hchunks = 1; }
+    const gpmpc_tuning& tn = p->nominal ? tn_nom : (tn_over ? *tn_over : p->tune);        // GPMPC_* overrides, read once at pack creation
     // The selection as it stands (diagonal rollout, da <= 2; every threshold is a measured crossover -- its numbers are in the
     // comment at its line, the method in DESIGN.md section 5, the maps in profiles/r02 and r03/batch_size_map.txt):
     //   W64 = B x tiles(256x64) < ~150 (~400 for N < 512), or N < 256           ONE launch per step, 64-row tiles, staged column loop
@@ -1167,7 +1225,7 @@ static void plan_rollout(const gpmpc_pack* p, int B, int H, bool grad, bool diag
     if (shape) { r->fused = shape->fused; r->pwaves = shape->pwaves; r->png = shape->png; if (r->fused == 3) { r->sb = 0; r->shared = 0; r->nwork = 0; } }
     r->nm = gpmpc_num_moments(D, diag, grad);
     r->pps = D + D * D;
-    r->sps = sps_of(D);
+    r->sps = p->nominal ? sps_nominal(D) : sps_of(D);
     size_t off = 0;
     auto take = [&](size_t n) { size_t o = off; off += (n * sizeof(double) + 255) & ~(size_t)255; return o; };
     r->off_pp = take((size_t)B * p->ds * r->pps);
@@ -1313,8 +1371,9 @@ extern "C" int gpmpc_plan_describe(const gpmpc_pack* p, int B, int H, unsigned f
         wgs = (long)((B + r.tb - 1) / r.tb) * r.nwork;
     }
     const int tl = r.shared && r.fused != 2 ? (r.sh_list == 0 ? 0 : (r.sh_list == 1 ? 2 : 4)) : r.tiling;
-    snprintf(out, out_bytes, "form=%s kernel=%s tiling=%dx%d workgroups=%ld launches_per_step=%d split=%d tb=%d shared=%d hchunks=%d workspace=%zu",
-             form, kern, cfg[tl][0], cfg[tl][1], wgs, r.fused == 3 ? 0 : (r.fused ? 1 : 2), S, r.tb, r.shared, r.hchunks, r.total);
+    snprintf(out, out_bytes, "form=%s kernel=%s tiling=%dx%d workgroups=%ld launches_per_step=%d split=%d tb=%d shared=%d hchunks=%d workspace=%zu%s",
+             form, kern, cfg[tl][0], cfg[tl][1], wgs, r.fused == 3 ? 0 : (r.fused ? 1 : 2), S, r.tb, r.shared, r.hchunks, r.total,
+             p->nominal ? " nominal=1" : "");
     return GPMPC_OK;
 }
 
@@ -1347,7 +1406,10 @@ static int launch_step_fused(int D, bool grad, int ns2, int q, int ng, const Fus
 
 template <int D>
 static void launch_head(const RollArgs& A, int t, hipStream_t s) {
-    hipLaunchKernelGGL(k_roll_head<D>, dim3(A.B, A.ds, A.hchunks > 1 ? A.hchunks : 1), dim3(256), 0, s, A, t);
+    const dim3 grid(A.B, A.ds, A.hchunks > 1 ? A.hchunks : 1);
+    if (!A.nom) hipLaunchKernelGGL((k_roll_head<D, 0>), grid, dim3(256), 0, s, A, t);
+    else if (A.grad) hipLaunchKernelGGL((k_roll_head<D, 2>), grid, dim3(256), 0, s, A, t);
+    else hipLaunchKernelGGL((k_roll_head<D, 1>), grid, dim3(256), 0, s, A, t);
 }
 
 // ext_jac: caller-owned [B][H][2ds][2ds+da] buffer for the step Jacobians instead of the workspace's (gpmpc_rollout_jac);
@@ -1362,6 +1424,10 @@ static int enqueue_rollout(const gpmpc_pack* p, int B, int H, const double* x0, 
     if (grad && !out_grad) return GPMPC_E_ARG;
     const int lowprec = (flags & GPMPC_FP32_ALL) ? 2 : ((flags & GPMPC_FP32_ACCUM) ? 1 : 0);
     if (lowprec && grad) return GPMPC_E_ARG;                   // the sweep modes are objective only
+    if (lowprec && p->nominal) {
+        gpmpc_set_error_text("gpmpc_rollout: the GPMPC_FP32_* modes do not know the linear nominal model of this pack");
+        return GPMPC_E_STATE;
+    }
     RollPlan r;
     plan_rollout(p, B, H, grad, true, &r, lowprec != 0, shape);
     if (workspace_bytes < r.total) return GPMPC_E_WORKSPACE;
@@ -1383,6 +1449,11 @@ static int enqueue_rollout(const gpmpc_pack* p, int B, int H, const double* x0, 
     A.work = p->wl[0][r.tiling].contiguous ? nullptr : p->wl[0][r.tiling].work_dev;
     A.perm = p->wl[0][r.tiling].contiguous ? nullptr : p->wl[0][r.tiling].perm_dev;
     A.out_cost = out_cost; A.out_grad = out_grad; A.cost = *cost;
+    A.nom = p->nominal ? p->nom_dev : nullptr;
+    if (A.nom && (r.fused || r.hchunks > 1)) {                 // (a plan handed in from outside: the nominal variants exist for the two-launch form only)
+        gpmpc_set_error_text("gpmpc_rollout: plan without a nominal variant on a nominal pack");
+        return GPMPC_E_STATE;
+    }
     if (r.shared) {                                          // partial sums laid out [GP][tile]
         A.shared = 1; A.ust_inline = 1; A.work = nullptr; A.perm = nullptr;
         for (int a = 0; a <= p->ds; ++a) A.ust[a] = a * p->sh_tiles[r.sh_list];
@@ -1485,8 +1556,11 @@ static int enqueue_rollout(const gpmpc_pack* p, int B, int H, const double* x0, 
     const size_t lds = allj ? lds_all : lds_one;
 #define GPMPC_TAIL_CASE(DSV)                                                                             \
     case DSV:                                                                                            \
-        if (allj) hipLaunchKernelGGL((k_roll_tail<true, DSV>), dim3(B), dim3(256), lds, s, A);           \
-        else hipLaunchKernelGGL((k_roll_tail<false, DSV>), dim3(B), dim3(256), lds, s, A);               \
+        if (A.nom) {                                                                                     \
+            if (allj) hipLaunchKernelGGL((k_roll_tail<true, DSV, true>), dim3(B), dim3(256), lds, s, A);     \
+            else hipLaunchKernelGGL((k_roll_tail<false, DSV, true>), dim3(B), dim3(256), lds, s, A);         \
+        } else if (allj) hipLaunchKernelGGL((k_roll_tail<true, DSV, false>), dim3(B), dim3(256), lds, s, A); \
+        else hipLaunchKernelGGL((k_roll_tail<false, DSV, false>), dim3(B), dim3(256), lds, s, A);        \
         break;
     switch (p->ds) {
         GPMPC_TAIL_CASE(1) GPMPC_TAIL_CASE(2) GPMPC_TAIL_CASE(3) GPMPC_TAIL_CASE(4)

@@ -5,10 +5,13 @@
 attached when the actions require grad).
 The batched entry ``rollout`` is the build's extension (the reference handles one trajectory per call).
 """
+import warnings
+
 import numpy as np
 import torch
 
 from .gpr import GaussianProcessRegression
+from .nominal import LinearNominalModel, stack_linear
 from .autograd import RolloutFunction, wants_grad
 from .rollout import CostParams, GPPack, rollout, rollout_fullcov
 
@@ -26,6 +29,7 @@ class Dynamics(object):
         self.device = self.gpr_err[0].device
         self._pack = None
         self._pack_key = None
+        self._nominal_warned = False
         # Fixed-size training window (extension; None: the training set grows without bound, as in the reference).  Once num_train has
         # reached max_train, a single new observation REPLACES the row at `window_slot` in every GP (first-in first-out: slot 0 first,
         # the oldest row after a bulk load) and the slot advances modulo max_train.  X_train / y_train of the GPs are then in SLOT
@@ -158,15 +162,37 @@ class Dynamics(object):
         # Ky_inv, exp(log_lambdas), y_train, sigma_f of every GP, X_train of GP 0.  Tensors are keyed by OBJECT and
         # autograd version (the key holds the references, so an id cannot be reused by a later tensor): this runs on
         # every solver callback, and exp / tolist of the hyper-parameters per call cost as much as a small rollout.
+        # ... and, last, the coefficients of the linear nominal models the rollout adds back (None: no such models)
         return [(g.version, g.num_train, g.log_lambdas, g.log_lambdas._version, g.log_sigma_f, g.log_sigma_f._version)
-                for g in self.gpr_err]
+                for g in self.gpr_err] + [self._nominal_key()]
+
+    def _nominal_key(self):
+        ms = self.nominal_models                         # (runs on every solver callback: no array work here)
+        if ms is None:
+            return None
+        if len(ms) == self.state_dim and all(isinstance(m, LinearNominalModel) for m in ms):
+            return tuple(m.key for m in ms)
+        self._linear_nominal()                           # (warns, once)
+        return None
+
+    def _linear_nominal(self):
+        """(W, b) when every nominal model is a LinearNominalModel: the rollout then honours them.  Other callables are honoured by the GPs
+        only (beta, predictions, hyper-parameter training), as in the reference (src/dynamics.py:64): said once, as a warning."""
+        if self.nominal_models is None:
+            return None
+        lin = stack_linear(self.nominal_models, self.state_dim, self.action_dim)
+        if lin is None and not getattr(self, "_nominal_warned", False):
+            self._nominal_warned = True
+            warnings.warn("Dynamics: the rollout ignores nominal models that are not LinearNominalModel (they enter the GPs' residual "
+                          "targets only); its means, variances, cost and gradient are those of the zero-mean GPs", stacklevel=3)
+        return lin
 
     @staticmethod
     def _same_key(a, b):
-        if a is None or b is None or len(a) != len(b):
+        if a is None or b is None or len(a) != len(b) or a[-1] != b[-1]:
             return False
         return all(x[0] == y[0] and x[1] == y[1] and x[2] is y[2] and x[3] == y[3] and x[4] is y[4] and x[5] == y[5]
-                   for x, y in zip(a, b))
+                   for x, y in zip(a[:-1], b[:-1]))
 
     def pack(self):
         """The device-resident constants of the rollout, rebuilt only when data or hypers changed."""
@@ -183,8 +209,9 @@ class Dynamics(object):
             lam = np.stack([g.get_lambdas() for g in self.gpr_err])
             sf = np.array([g.get_sigma_f() for g in self.gpr_err])
             # the closed loop appends one observation per step: refill the existing pack while its padded size fits
-            if self._pack is None or not self._pack.rebuild(g0.X_train, Y, Kinv, lam, sf):
-                self._pack = GPPack(g0.X_train, Y, Kinv, lam, sf, device=self.device)
+            nominal = self._linear_nominal()            # (Y stays the raw targets: the library removes the linear model on the device)
+            if self._pack is None or not self._pack.rebuild(g0.X_train, Y, Kinv, lam, sf, nominal=nominal):
+                self._pack = GPPack(g0.X_train, Y, Kinv, lam, sf, device=self.device, nominal=nominal)
             self._pack_key = key
         return self._pack
 
@@ -195,6 +222,8 @@ class Dynamics(object):
         if cost is None:     # propagation only: a zero cost keeps the fused tail trivial
             cost = CostParams(0.0, np.zeros((self.state_dim, self.state_dim)), np.zeros((self.action_dim, self.action_dim)))
         if full_covariance:
+            if self._linear_nominal() is not None:
+                raise NotImplementedError("full_covariance=True is not supported with linear nominal models")
             return rollout_fullcov(self.pack(), curr_state, actions, cost, want_grad=want_grad)
         return rollout(self.pack(), curr_state, actions, cost, want_grad=want_grad, want_traj=True)
 

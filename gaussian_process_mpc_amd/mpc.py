@@ -31,7 +31,9 @@ except Exception:                       # pragma: no cover
 
 
 class RiskSensitiveMPC:
-    def __init__(self, gamma, horizon, state_dim, input_dim, Q, R, R_delta=None, full_covariance=False):
+    def __init__(self, gamma, horizon, state_dim, input_dim, Q, R, R_delta=None, full_covariance=False, nominal_models=None):
+        # nominal_models (extension; the reference passes None, src/mpc.py:45): one callable per state dimension, handed to Dynamics.  A list
+        # of LinearNominalModel is honoured by the rollout, the callbacks and the multi-start solve; other callables by the GPs only.
         # full_covariance=True propagates the whole state covariance (off-diagonal terms from the exact
         # cross-covariances): the extension the reference leaves as a TODO (src/dynamics.py:184), BASELINE config 5.
         self.full_covariance = full_covariance
@@ -42,7 +44,7 @@ class RiskSensitiveMPC:
         self.Q = Q
         self.R = R
         self.R_delta = R_delta
-        self.dynamics = Dynamics(self.state_dim, self.input_dim, nominal_models=None)
+        self.dynamics = Dynamics(self.state_dim, self.input_dim, nominal_models=nominal_models)
         self.device = self.dynamics.device
         self.Q_tor = torch.tensor(np.asarray(self.Q), device=self.device).type(torch.float64)
         self.R_tor = torch.tensor(np.asarray(self.R), device=self.device).type(torch.float64)

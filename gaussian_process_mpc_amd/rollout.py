@@ -52,18 +52,55 @@ class GPPack:
     GaussianProcessRegression hold, src/dynamics.py:33-37, src/gpr.py:24-36) folded into
     the per-data-update constants of the rollout (beta, weight matrices)."""
 
-    def __init__(self, X, Y, Ky_inv, lambdas, sigma_f, device=None, y_is_beta=False):
+    def __init__(self, X, Y, Ky_inv, lambdas, sigma_f, device=None, y_is_beta=False, nominal=None):
         """Y: (N, ds) targets, or the beta vectors themselves when ``y_is_beta`` (then Ky_inv may be
-        None: only means and cross-covariances are meaningful)."""
+        None: only means and cross-covariances are meaningful).
+        nominal: (W (ds, D), b (ds,) or scalar) of a linear nominal model m_a(z) = W[a] . z + b[a], z = (x, u): Y stays the RAW targets, the
+        library forms beta from Y - X W^T - b and the rollout adds the model back exactly (with ``y_is_beta`` beta is taken as given)."""
         self.device = device if device is not None else require_gpu()
         self._h = None
         self.generation = 0          # bumped by every (re)build: caches keyed on the pack object include it
         self._ws = {}
         self._graph_bufs = {}
         self.fullcov = False
-        self._fill(X, Y, Ky_inv, lambdas, sigma_f, y_is_beta)
+        self._nominal = None
+        self._fill(X, Y, Ky_inv, lambdas, sigma_f, y_is_beta, nominal)
 
-    def _fill(self, X, Y, Ky_inv, lambdas, sigma_f, y_is_beta):
+    def _set_nominal(self, nominal):
+        """Hand a changed model to the library (switching it on or off re-plans the pack: scratch sizes change)."""
+        if nominal is not None:
+            W = np.ascontiguousarray(np.asarray(nominal[0], dtype=np.float64).reshape(self.ds, self.D))
+            b = np.ascontiguousarray(np.broadcast_to(np.asarray(nominal[1], dtype=np.float64).reshape(-1), (self.ds,)))
+            if not (np.all(np.isfinite(W)) and np.all(np.isfinite(b))):
+                raise ValueError("nominal model coefficients must be finite")
+            nominal = (W, b)
+        old = self.nominal                               # (as the LIBRARY holds it: the handle may have been given another model directly)
+        if (nominal is None and old is None) or (nominal is not None and old is not None and np.array_equal(nominal[0], old[0])
+                                                 and np.array_equal(nominal[1], old[1])):
+            return
+        with torch.cuda.device(self.device):
+            if nominal is None:
+                check(lib().gpmpc_pack_set_nominal(self._h, None, None, stream_ptr()), "gpmpc_pack_set_nominal")
+            else:
+                check(lib().gpmpc_pack_set_nominal(self._h, host_doubles(nominal[0])[1], host_doubles(nominal[1])[1], stream_ptr()),
+                      "gpmpc_pack_set_nominal")
+        if (nominal is None) != (old is None):
+            self._graph_bufs = {}
+            self._ws = {}
+        self._nominal = nominal
+
+    @property
+    def nominal(self):
+        """(W (ds, D), b (ds,)) of the pack's linear nominal model as the library holds it, or None."""
+        if self._h is None:
+            return None
+        W, b = np.zeros((self.ds, self.D)), np.zeros(self.ds)
+        rc = lib().gpmpc_pack_get_nominal(self._h, host_doubles(W)[1], host_doubles(b)[1])
+        if rc < 0:
+            check(rc, "gpmpc_pack_get_nominal")
+        return (W, b) if rc == 1 else None
+
+    def _fill(self, X, Y, Ky_inv, lambdas, sigma_f, y_is_beta, nominal=None):
         self.X = _dev(X, self.device)
         Y = _dev(Y, self.device)
         self.Y = Y.reshape(self.X.shape[0], -1)
@@ -90,6 +127,7 @@ class GPPack:
             with torch.cuda.device(self.device):       # the pack's HBM buffers belong to THIS device, whatever is current
                 check(lib().gpmpc_pack_create(ctypes.byref(h), self.N, self.ds, self.da), "gpmpc_pack_create")
             self._h = h
+        self._set_nominal(nominal)
         _, lp = host_doubles(self.lambdas)
         _, sp = host_doubles(self.sigma_f)
         with torch.cuda.device(self.device):
@@ -106,9 +144,10 @@ class GPPack:
         self.Np = npad.value
         self.generation += 1
 
-    def rebuild(self, X, Y, Ky_inv, lambdas, sigma_f):
+    def rebuild(self, X, Y, Ky_inv, lambdas, sigma_f, nominal="keep"):
         """Refill THIS pack for new data / hyper-parameters when its allocation fits (same device, dimensions and padded
-        size): no allocation, the library handle survives.  Returns False (pack untouched) when it does not fit."""
+        size): no allocation, the library handle survives.  Returns False (pack untouched) when it does not fit.
+        nominal: as in the constructor; None clears the model, the default keeps the one the pack has."""
         Xs = X.shape
         n, D = int(Xs[0]), int(Xs[1])
         ds = int(Y.shape[1]) if len(Y.shape) > 1 else 1
@@ -117,7 +156,8 @@ class GPPack:
         with torch.cuda.device(self.device):
             if n != self.N:
                 check(lib().gpmpc_pack_resize(self._h, n), "gpmpc_pack_resize")
-        self._fill(X, Y, Ky_inv, lambdas, sigma_f, False)      # (cross-covariance weights, if enabled, follow every build)
+        self._fill(X, Y, Ky_inv, lambdas, sigma_f, False,      # (cross-covariance weights, if enabled, follow every build)
+                   self._nominal if isinstance(nominal, str) and nominal == "keep" else nominal)
         return True
 
     def __del__(self):
@@ -337,6 +377,9 @@ def rollout_fullcov(pack, x0, U, cost, want_grad=True):
     """Like :func:`rollout` but propagating the FULL state covariance (C ABI ``gpmpc_rollout_fullcov``;
     BASELINE config 5).  Returns cost (B,), grad (B,H,da), means (B,H+1,ds), covs (B,H+1,ds,ds)."""
     dev = pack.device
+    if pack._nominal is not None:
+        raise NotImplementedError("the full-covariance rollout does not support a pack with a linear nominal model "
+                                  "(its cross-covariances with the linear part are not implemented)")
     if not pack.fullcov:
         pack.enable_fullcov()
     U = _dev(U, dev)
@@ -367,6 +410,9 @@ def moment_match(pack, u, S, want_cov=False, want_grad=False, bug_compatible=Fal
     """Exact moment matching of all ds GPs for nq Gaussian inputs N(u, S) with full S
     (C ABI ``gpmpc_moment_match``).  u: (nq, D) or (D,); S: (nq, D, D) or (D, D)."""
     dev = pack.device
+    if pack._nominal is not None:
+        raise NotImplementedError("moment_match does not support a pack with a linear nominal model: it would return the moments of "
+                                  "the residual GPs alone")
     u = _dev(u, dev).reshape(-1, pack.D)
     nq = u.shape[0]
     S = _dev(S, dev).reshape(nq, pack.D, pack.D)

@@ -136,6 +136,23 @@ int gpmpc_pack_build_beta(gpmpc_pack* pack, const double* X_dev, const double* b
                           const double* Ky_inv_dev, const double* lambdas_host,
                           const double* sigma_f_host, void* stream);
 
+/* Linear nominal model (no reference counterpart: src/dynamics.py:64 leaves nominal models out of the rollout).  GP a then models
+ * the residual of m_a(z) = weights[a] . z + bias[a], z = (x, u): weights host [ds][D], bias host [ds], copied into device memory owned by
+ * the pack before the call returns.  Both NULL clears the model; exactly one NULL is GPMPC_E_ARG.
+ *  - The pack is "not built" afterwards (GPMPC_E_STATE) until the next gpmpc_pack_build*.  gpmpc_pack_build and
+ *    gpmpc_pack_build_strided take the RAW targets and form beta from Y - X weights^T - bias on the device; gpmpc_pack_build_beta takes
+ *    beta as given (the caller has already removed the nominal model from the targets).  gpmpc_pack_resize keeps the model.
+ *  - gpmpc_rollout (plain and GPMPC_USE_GRAPH), gpmpc_rollout_jac and gpmpc_objective_gradient propagate
+ *    mu' = mu_g + n . u + c,  var' = var_g + sum_k n_k^2 s_k + 2 sum_k n_k s_k dmu_g/du_k  (exact for a linear model) with the matching
+ *    step Jacobians, in the two-launch form (head kernel + pair kernel per horizon step): gpmpc_plan_describe appends "nominal=1".
+ *  - Switching the model on or off drops the captured graphs and the measured plans of the pack; new coefficients of a model that
+ *    stays on do not (the kernels read them from device memory).
+ *  - gpmpc_rollout_fullcov, gpmpc_moment_match and the GPMPC_FP32_* modes do not know the model: GPMPC_E_STATE on a nominal pack,
+ *    with the reason in gpmpc_last_error. */
+int gpmpc_pack_set_nominal(gpmpc_pack* pack, const double* weights_host, const double* bias_host, void* stream);
+/* 1: a nominal model is set (its coefficients are copied to weights_host / bias_host where these are not NULL), 0: none; GPMPC_E_ARG. */
+int gpmpc_pack_get_nominal(const gpmpc_pack* pack, double* weights_host, double* bias_host);
+
 /* Allocate and maintain the cross-covariance weight matrices (one N x N matrix per GP pair a < b): needed by
  * gpmpc_rollout_fullcov and by the analytic cross-covariance Jacobians of gpmpc_moment_match.  Without it
  * cross-covariances are evaluated by a direct N^2 kernel, forward only. */
