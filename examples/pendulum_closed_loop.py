@@ -4,6 +4,7 @@ src/experiments/pretrain_uncertainty.py: pre-train the GP on random transitions,
 (Simulator.run, src/simulator.py:37-60) with the model growing by one observation per step.
 
     python examples/pendulum_closed_loop.py [--pretrain 200] [--steps 25] [--horizon 10] [--window N] [--nominal identity]
+                                            [--max-speed V [--prob P]]
 
 --window N: fixed-size training window -- once the model holds N points every new observation replaces the oldest one (first-in
 first-out), so the cost of the data update and the memory stay constant however long the loop runs (what the solver makes of a model
@@ -11,6 +12,10 @@ that has forgotten its pre-training points is another matter: BASELINE.md sectio
 
 --nominal identity: the GPs learn the state DIFFERENCE x_{t+1} - x_t (LinearNominalModel.identity: the nominal model of state a is
 x_a) and the rollout adds the state back exactly; a zero-mean GP on the raw next state reverts to 0 away from the data.
+
+--max-speed V [--prob P]: chance bound |theta_dot| <= V on every predicted state, each side held with probability P (default 0.95) on
+the predicted mean plus Phi^-1(P) predicted standard deviations (RiskSensitiveMPC.set_state_bounds).  The stand-in solver is then scipy's
+SLSQP on the objective / gradient / constraints / jacobian callbacks -- one device pass per iterate.
 
 Needs an MI355X and the built library; no gym, no cyipopt (the stand-in solver is scipy's L-BFGS-B on the same
 objective / gradient callbacks, so the trajectories are NOT the reference's Ipopt trajectories)."""
@@ -35,6 +40,8 @@ def main():
     ap.add_argument("--window", type=int, default=None, help="fixed-size training window of N points (Simulator max_train); default: the set grows")
     ap.add_argument("--refresh", choices=("rebuild", "newton"), default=None, help="how the incremental path bounds its round-off")
     ap.add_argument("--nominal", choices=("none", "identity"), default="none", help="identity: the GPs learn x_{t+1} - x_t, the rollout adds x_t back")
+    ap.add_argument("--max-speed", type=float, default=None, help="chance bound on |theta_dot| over the horizon (state constraints)")
+    ap.add_argument("--prob", type=float, default=0.95, help="one-sided satisfaction probability of --max-speed")
     args = ap.parse_args()
 
     rng = np.random.default_rng(0)
@@ -55,6 +62,17 @@ def main():
     mpc.set_lb([-2.0]); mpc.set_ub([2.0])
     mpc.set_xref(np.zeros(2))
     mpc.n_starts = args.starts
+    solves = []
+    if args.max_speed is not None:
+        mpc.set_state_bounds([None, -args.max_speed], [None, args.max_speed], args.prob)
+        solve = mpc.get_optimal_trajectory
+
+        def logged(obs, **kw):                           # keep every step's solver report
+            plan = solve(obs, **kw)
+            if mpc.last_solve_info is not None:          # (None while the model is empty, or under Ipopt)
+                solves.append(dict(mpc.last_solve_info))
+            return plan
+        mpc.get_optimal_trajectory = logged
 
     sim = Simulator(mpc, plant, num_iters=args.steps, incremental=True, refresh=args.refresh, max_train=args.window)
     t0 = time.perf_counter()
@@ -65,6 +83,11 @@ def main():
           f"training set {args.pretrain} -> {mpc.dynamics.gpr_err[0].num_train} points"
           + (f" (window of {args.window}, next slot {mpc.dynamics.window_slot})" if args.window else "")
           + (f"; nominal model: {args.nominal}" if nominal else ""))
+    if args.max_speed is not None:
+        sp = np.array([abs(h[0][1]) for h in hist])
+        print(f"|theta_dot| <= {args.max_speed} with probability {args.prob}: largest visited {sp.max():.3f}; "
+              f"{sum(s['success'] for s in solves)} of {len(solves)} solves report success, "
+              f"largest predicted violation {max((s['max_violation'] for s in solves), default=float('nan')):.2e}")
     print("theta:", np.array2string(th[:: max(1, len(th) // 10)], precision=2))
 
 

@@ -20,9 +20,9 @@ from .dynamics import Dynamics                                          # noqa: 
 from .mpc import RiskSensitiveMPC                                       # noqa: F401
 from .uncertainty_prop import mean_prop_torch, variance_prop_torch, covariance_prop_torch  # noqa: F401
 from .simulator import Simulator, PendulumPlant, CartPolePlant          # noqa: F401
-from .rollout import GPPack, CostParams, rollout, rollout_fullcov, moment_match   # noqa: F401
+from .rollout import GPPack, CostParams, StateConstraints, rollout, rollout_constraints, rollout_fullcov, moment_match   # noqa: F401
 from .nominal import LinearNominalModel                                 # noqa: F401
 
 __all__ = ["GaussianProcessRegression", "Dynamics", "RiskSensitiveMPC", "mean_prop_torch",
-           "variance_prop_torch", "covariance_prop_torch", "GPPack", "CostParams", "rollout",
+           "variance_prop_torch", "covariance_prop_torch", "GPPack", "CostParams", "StateConstraints", "rollout", "rollout_constraints",
            "rollout_fullcov", "moment_match", "LinearNominalModel", "Simulator", "PendulumPlant", "CartPolePlant", "lib", "require_gpu"]

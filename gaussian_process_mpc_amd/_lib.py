@@ -15,6 +15,7 @@ LIB_PATH = os.environ.get("GPMPC_LIB_PATH") or os.path.join(_HERE, "csrc", "libg
 
 MAX_D = 8
 MAX_DS = 8
+MAX_CONS = 16
 WANT_GRAD = 1
 COV_BUG_COMPAT = 2
 USE_GRAPH = 4
@@ -44,6 +45,14 @@ class CostParamsC(ctypes.Structure):
                 ("last_u", ctypes.c_double * MAX_D),
                 ("has_R_delta", ctypes.c_int),
                 ("reserved", ctypes.c_int)]
+
+
+class StateConstraintsC(ctypes.Structure):
+    _fields_ = [("n_rows", ctypes.c_int),
+                ("reserved", ctypes.c_int),
+                ("A", ctypes.c_double * (MAX_CONS * MAX_DS)),
+                ("b", ctypes.c_double * MAX_CONS),
+                ("kappa", ctypes.c_double * MAX_CONS)]
 
 
 _vp, _i, _d, _sz, _u = ctypes.c_void_p, ctypes.c_int, ctypes.c_double, ctypes.c_size_t, ctypes.c_uint
@@ -78,6 +87,10 @@ SIGNATURES = {
     "gpmpc_rollout_jac_workspace_bytes": (_sz, [_vp, _i, _i]),
     "gpmpc_rollout_jac": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "gpmpc_rollout_vjp": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "gpmpc_rollout_constraints": (_i, [_i, _i, _i, _i, ctypes.POINTER(StateConstraintsC), _vp, _vp, _vp, _vp, _vp, _vp]),
+    "gpmpc_rollout_constrained_workspace_bytes": (_sz, [_vp, _i, _i, _u]),
+    "gpmpc_rollout_constrained": (_i, [_vp, _i, _i, _vp, _vp, ctypes.POINTER(CostParamsC), ctypes.POINTER(StateConstraintsC), _u,
+                                       _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "gpmpc_rollout_workspace_bytes": (_sz, [_vp, _i, _i, _u]),
     "gpmpc_plan_describe": (_i, [_vp, _i, _i, _u, ctypes.c_char_p, _sz]),
     "gpmpc_pack_autotune": (_i, [_vp, _i, _i, _u, ctypes.c_char_p, _sz]),

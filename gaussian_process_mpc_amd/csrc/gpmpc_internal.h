@@ -253,6 +253,8 @@ template <int D> int gpmpc_launch_pair_D(bool diag, bool grad, int tb, int waves
 
 void gpmpc_set_error(const char* what, hipError_t e);
 void gpmpc_set_error_text(const char* text);      // gpmpc_last_error for refusals that are not HIP errors
+// GPMPC_OK, or GPMPC_E_ARG with the reason in gpmpc_last_error: n_rows outside 1..GPMPC_MAX_CONS, a negative or NaN kappa (constraints.hip)
+int gpmpc_check_constraints(const gpmpc_state_constraints* cons, const char* who);
 // Small host array (<= 512 bytes: hyper-parameters, index pairs) -> device memory, ordered on `s`, with the host bytes CONSUMED BEFORE
 // THE CALL RETURNS: they travel as kernel arguments.  (hipMemcpyAsync from pageable memory may read the host buffer only when the
 // stream gets there -- behind a wait on another stream that can be after the caller has freed it; seen as a wrong K matrix from a

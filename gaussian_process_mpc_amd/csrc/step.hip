@@ -2173,3 +2173,42 @@ extern "C" int gpmpc_rollout_vjp(int B, int H, int ds, int da, const double* jac
     GPMPC_HIP(hipGetLastError());
     return GPMPC_OK;
 }
+
+// ---------------------------------------------------------------------------
+// Rollout + state chance constraints in one device pass (kernel: constraints.hip)
+// ---------------------------------------------------------------------------
+static int constrained_flags_ok(unsigned flags) {
+    if (flags & ~GPMPC_WANT_GRAD) {
+        gpmpc_set_error_text("gpmpc_rollout_constrained: only GPMPC_WANT_GRAD is accepted (no GPMPC_USE_GRAPH, no GPMPC_FP32_* mode in this version)");
+        return 0;
+    }
+    return 1;
+}
+
+extern "C" size_t gpmpc_rollout_constrained_workspace_bytes(const gpmpc_pack* p, int B, int H, unsigned flags) {
+    if (!p || B < 1 || H < 1 || !constrained_flags_ok(flags)) return 0;
+    return gpmpc_rollout_workspace_bytes(p, B, H, flags);   // the step Jacobians, means and variances live in the rollout's own workspace
+}
+
+extern "C" int gpmpc_rollout_constrained(const gpmpc_pack* p, int B, int H, const double* x0, const double* U,
+                                         const gpmpc_cost_params* cost, const gpmpc_state_constraints* cons, unsigned flags,
+                                         double* out_means, double* out_vars, double* out_cost, double* out_grad, double* out_g,
+                                         double* out_gjac, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!p || !x0 || !U || !cost || !cons || !out_cost || !out_g || !workspace || B < 1 || H < 1) return GPMPC_E_ARG;
+    if (!constrained_flags_ok(flags)) return GPMPC_E_ARG;
+    const bool grad = (flags & GPMPC_WANT_GRAD) != 0;
+    if (grad && (!out_grad || !out_gjac)) return GPMPC_E_ARG;
+    if (int rc = gpmpc_check_constraints(cons, "gpmpc_rollout_constrained")) return rc;
+    if (int rc_dev = gpmpc_check_device(p)) return rc_dev;
+    if (!p->built) return GPMPC_E_STATE;
+    GraphModeGuard mode(0);
+    RollPlan r;                                             // the plan enqueue_rollout takes for this call: where it keeps J_t, means, variances
+    plan_rollout(p, B, H, grad, true, &r, false);
+    if (workspace_bytes < r.total) return GPMPC_E_WORKSPACE;
+    if (int rc = enqueue_rollout(p, B, H, x0, U, cost, flags, out_means, out_vars, out_cost, out_grad, workspace, workspace_bytes, stream))
+        return rc;
+    char* ws = (char*)workspace;
+    return gpmpc_rollout_constraints(B, H, p->ds, p->da, cons, out_means ? out_means : (const double*)(ws + r.off_means),
+                                     out_vars ? out_vars : (const double*)(ws + r.off_vars),
+                                     grad ? (const double*)(ws + r.off_jac) : nullptr, out_g, grad ? out_gjac : nullptr, stream);
+}

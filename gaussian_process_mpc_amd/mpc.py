@@ -14,13 +14,17 @@ forced by moving the rollout into one fused HIP call:
   lock-step (multistart.py): every solver iteration is ONE ``evaluate_batch`` call of K candidate plans -- sharded over the
   ranks when ``torch.distributed`` is initialised -- and the best local optimum is returned.  ``n_starts = 1`` (the default)
   is the reference's single zero-start solve (src/mpc.py:292-326).
+* ``set_state_constraints`` / ``set_state_bounds`` (extension; the reference's ``constraints`` returns 0, src/mpc.py:257-267): linear chance
+  constraints A mu_t + kappa sd_t <= b on every predicted state.  ``constraints(x)`` / ``jacobian(x)`` then return their values and the
+  dense Jacobian from the SAME device pass as cost and gradient (``gpmpc_rollout_constrained``), and the cyipopt problem gets
+  m = H m_c rows.  Without constraints set nothing changes.
 """
 import numpy as np
 import torch
 
 from .autograd import CostFunction, wants_grad
 from .dynamics import Dynamics
-from .rollout import CostParams, cost_full, rollout, rollout_fullcov
+from .rollout import CostParams, StateConstraints, cost_full, rollout, rollout_fullcov
 
 try:                                    # the solver binding is optional (not installed in the build image)
     import cyipopt                      # noqa: F401
@@ -69,6 +73,9 @@ class RiskSensitiveMPC:
                                    "patience": 8, "line_points": 4}      # 4 step lengths per start and tick: one batch of 4 K plans
         self.last_solve_info = None
         self._solve_count = 0
+        self.state_constraints = None                    # rollout.StateConstraints, or None (the reference's unconstrained problem)
+        self.curr_g = None
+        self.curr_g_jac = None
 
     # -- setters (src/mpc.py:72-116)
     def set_ub(self, ub):
@@ -87,6 +94,26 @@ class RiskSensitiveMPC:
     def set_uref(self, u_ref):
         assert len(u_ref) == self.input_dim
         self.u_ref = torch.tensor(np.asarray(u_ref), device=self.device).type(torch.float64)
+        self._cache_key = None
+
+    # -- state chance constraints (extension)
+    def set_state_constraints(self, A, b, prob=None, kappa=None):
+        """Rows A[r] . mu_t + kappa[r] sd_t[r] <= b[r] on every predicted state t = 1..H (rollout.StateConstraints: exactly one of
+        ``prob`` -- one-sided satisfaction probability -- and ``kappa``)."""
+        sc = StateConstraints(A, b, kappa=kappa, prob=prob)
+        if sc.ds != self.state_dim:
+            raise ValueError("constraint rows must have one coefficient per state dimension")
+        self.state_constraints = sc
+        self._cache_key = None
+
+    def set_state_bounds(self, lb, ub, prob):
+        """Chance bounds lb[k] <= x_k <= ub[k], each held with probability ``prob``; None / +-inf entries are unbounded."""
+        self.state_constraints = StateConstraints.box(lb, ub, self.state_dim, prob=prob)
+        self._cache_key = None
+
+    def clear_state_constraints(self):
+        self.state_constraints = None
+        self.curr_g = self.curr_g_jac = None
         self._cache_key = None
 
     # -- cost
@@ -145,8 +172,21 @@ class RiskSensitiveMPC:
         cs, pack, cp = self.curr_state, self.dynamics.pack(), self._cost_params()
         key = (x.tobytes(), None if cs is None else cs._version, bool(self.full_covariance), pack.generation)
         held = getattr(self, "_cache_held", (None, None, None))    # kept alive so that `is` cannot alias later objects
-        if key != self._cache_key or cs is not held[0] or pack is not held[1] or cp is not held[2]:
+        sc = self.state_constraints
+        if sc is not None:
             if self.full_covariance:
+                raise NotImplementedError("state constraints under the full-covariance rollout are not implemented "
+                                          "(q = a^T Sigma_t a and that path's Jacobian layout: a follow-up)")
+            key = key + (id(sc),)
+        if key != self._cache_key or cs is not held[0] or pack is not held[1] or cp is not held[2]:
+            if sc is not None:
+                # ONE device pass for Ipopt's four callbacks on one x: cost, gradient, g and its dense Jacobian
+                r = rollout(pack, cs, x.reshape(1, self.horizon, self.input_dim), cp, want_grad=True, want_traj=False, constraints=sc)
+                self.curr_cost = float(r["cost"][0].item())
+                self.curr_grad = r["grad"][0].cpu().numpy()
+                self.curr_g = r["g"][0].cpu().numpy().reshape(-1)
+                self.curr_g_jac = r["g_jac"][0].cpu().numpy()
+            elif self.full_covariance:
                 r = rollout_fullcov(pack, cs, x.reshape(self.horizon, self.input_dim), cp, want_grad=True)
                 self.curr_cost = float(r["cost"][0].item())
                 self.curr_grad = r["grad"][0].cpu().numpy()
@@ -175,16 +215,33 @@ class RiskSensitiveMPC:
         return self._evaluate(x)[1]
 
     def constraints(self, x):
-        return 0
+        """0 without state constraints (src/mpc.py:257-262); else g flattened to (H m_c,), row (t-1) m_c + r, feasible where <= 0."""
+        if self.state_constraints is None:
+            return 0
+        self._evaluate(x)
+        return self.curr_g
 
     def jacobian(self, x):
-        return np.zeros(x.shape)
+        """Zeros without state constraints (src/mpc.py:264-267); else the dense (H m_c, H da) Jacobian flattened row-major (cyipopt's
+        default dense structure)."""
+        if self.state_constraints is None:
+            return np.zeros(x.shape)
+        self._evaluate(x)
+        return self.curr_g_jac.reshape(-1)
 
     # -- batched evaluation (extension)
-    def evaluate_batch(self, U, curr_state=None, want_grad=True):
+    def evaluate_batch(self, U, curr_state=None, want_grad=True, constraints=False):
         """U: (B, H, da) candidates from one (ds,) or per-candidate (B, ds) start state.
-        Returns the rollout dict (device tensors: cost (B,), grad (B,H,da), means, vars)."""
+        Returns the rollout dict (device tensors: cost (B,), grad (B,H,da), means, vars).
+        constraints=True: also g (B, H, m_c) and, with want_grad, g_jac (B, H m_c, H da) of the state constraints that are set."""
         cs = self.curr_state if curr_state is None else curr_state
+        if constraints:
+            if self.state_constraints is None:
+                raise ValueError("no state constraints are set (set_state_constraints / set_state_bounds)")
+            if self.full_covariance:
+                raise NotImplementedError("state constraints under the full-covariance rollout are not implemented")
+            return rollout(self.dynamics.pack(), cs, U, self._cost_params(), want_grad=want_grad, want_traj=True,
+                           constraints=self.state_constraints)
         if self.full_covariance:
             return rollout_fullcov(self.dynamics.pack(), cs, U, self._cost_params(), want_grad=want_grad)
         return rollout(self.dynamics.pack(), cs, U, self._cost_params(), want_grad=want_grad, want_traj=True)
@@ -205,12 +262,23 @@ class RiskSensitiveMPC:
         x0 = np.zeros(shape=len(self.last_traj))          # warm start deliberately off, src/mpc.py:292-293
         lb, ub = self.horizon * list(self.lb), self.horizon * list(self.ub)
         K = self.n_starts if n_starts is None else n_starts
+        sc = self.state_constraints
+        if sc is not None and self.full_covariance:
+            raise NotImplementedError("state constraints under the full-covariance rollout are not implemented "
+                                      "(q = a^T Sigma_t a and that path's Jacobian layout: a follow-up)")
+        if sc is not None and K > 1:
+            raise NotImplementedError("the lock-step multi-start solve is unconstrained: use n_starts = 1 with state constraints "
+                                      "(a constrained multi-start, e.g. an augmented Lagrangian over the batched evaluation, is a follow-up)")
         if K > 1:
             x = self._solve_multistart(K, lb, ub)
             self.last_traj = x
             return np.reshape(x, (self.horizon, self.input_dim))
         if HAVE_CYIPOPT:
-            nlp = cyipopt.Problem(n=len(x0), m=0, problem_obj=self, lb=lb, ub=ub, cl=[0], cu=[0])
+            if sc is None:
+                nlp = cyipopt.Problem(n=len(x0), m=0, problem_obj=self, lb=lb, ub=ub, cl=[0], cu=[0])
+            else:
+                m = self.horizon * sc.m                  # g <= 0: cl = -2e19 is Ipopt's "no lower bound"
+                nlp = cyipopt.Problem(n=len(x0), m=m, problem_obj=self, lb=lb, ub=ub, cl=[-2e19] * m, cu=[0] * m)
             for k, v in (("mu_strategy", "adaptive"), ("accept_every_trial_step", "yes"), ("max_iter", 300),
                          ("tol", 1e-4), ("acceptable_tol", 1e-4), ("constr_viol_tol", 1e-4), ("compl_inf_tol", 1e-4),
                          ("dual_inf_tol", 1e-4), ("mu_target", 1e-4), ("acceptable_iter", 3), ("sb", "yes"),
@@ -229,6 +297,18 @@ class RiskSensitiveMPC:
         from scipy.optimize import minimize
         big = 1e15
         bounds = [(None if l <= -big else l, None if u >= big else u) for l, u in zip(lb, ub)]
+        if self.state_constraints is not None:
+            # SLSQP wants c(x) >= 0: c = -g.  Same callbacks as Ipopt would use; objective, gradient, g and its Jacobian on one x are
+            # one device pass (the cache of _evaluate)
+            m_c, n = self.state_constraints.m, len(x0)
+            cons = {"type": "ineq", "fun": lambda v: -np.asarray(self.constraints(v)),
+                    "jac": lambda v: -np.asarray(self.jacobian(v)).reshape(self.horizon * m_c, n)}
+            res = minimize(lambda v: self.objective(v), x0, jac=lambda v: np.asarray(self.gradient(v)).reshape(-1),
+                           method="SLSQP", bounds=bounds, constraints=[cons], options={"maxiter": 300, "ftol": 1e-10})
+            self.solver_used = "scipy-slsqp"
+            self.last_solve_info = {"success": bool(res.success), "max_violation": float(np.max(self.constraints(res.x))),
+                                    "iterations": int(res.nit), "message": str(res.message)}
+            return res.x
         res = minimize(lambda v: self.objective(v), x0, jac=lambda v: np.asarray(self.gradient(v)).reshape(-1),
                        method="L-BFGS-B", bounds=bounds, options={"maxiter": 300, "ftol": 1e-10, "gtol": 1e-4})
         self.solver_used = "scipy-lbfgsb"

@@ -10,7 +10,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import CostParamsC, check, lib, ptr, require_gpu, stream_ptr, host_doubles
+from ._lib import CostParamsC, StateConstraintsC, check, lib, ptr, require_gpu, stream_ptr, host_doubles
 
 
 def _dev(a, device):
@@ -45,6 +45,71 @@ class CostParams:
         c.x_ref[:self.ds] = xr.tolist()
         c.u_ref[:self.da] = ur.tolist()
         self.c = c
+
+
+class StateConstraints:
+    """Linear chance constraints on the state, held at every horizon step t = 1..H (C ABI ``gpmpc_state_constraints``; no reference
+    counterpart: src/mpc.py:257-267 returns 0):
+
+        g[t, r] = A[r] . mu_t + kappa[r] * sqrt(sum_k A[r, k]^2 var_t[k]) - b[r]  <=  0
+
+    A: (m_c, ds) or (ds,); b: (m_c,) or scalar.  Exactly one of ``kappa`` (>= 0) and ``prob`` (one-sided satisfaction probability in
+    [0.5, 1), kappa = Phi^-1(prob)), each a scalar or one value per row; kappa = 0 (prob = 0.5) constrains the mean only.
+    The rollout does not clamp negative variances: a non-positive variance sum counts as sd = 0 (the row is then its mean part, in value
+    and derivative); NaN passes through to every row of that step."""
+
+    def __init__(self, A, b, kappa=None, prob=None):
+        if (kappa is None) == (prob is None):
+            raise ValueError("give exactly one of kappa and prob")
+        A = np.atleast_2d(np.asarray(A, dtype=np.float64))
+        m, ds = A.shape
+        if not 1 <= m <= _lib.MAX_CONS:
+            raise ValueError(f"1 to {_lib.MAX_CONS} constraint rows are supported, got {m}")
+        if not 1 <= ds <= _lib.MAX_DS:
+            raise ValueError("state dimension exceeds the library limits")
+        b = np.broadcast_to(np.asarray(b, dtype=np.float64).reshape(-1), (m,)).copy()
+        if prob is not None:
+            from statistics import NormalDist
+            pr = np.broadcast_to(np.asarray(prob, dtype=np.float64).reshape(-1), (m,))
+            if not np.all((pr >= 0.5) & (pr < 1.0)):
+                raise ValueError("prob must lie in [0.5, 1): kappa = Phi^-1(prob) >= 0")
+            kap = np.array([NormalDist().inv_cdf(float(v)) if v > 0.5 else 0.0 for v in pr])
+        else:
+            kap = np.broadcast_to(np.asarray(kappa, dtype=np.float64).reshape(-1), (m,)).copy()
+            if not np.all(kap >= 0.0):                      # (NaN fails too)
+                raise ValueError("kappa must be >= 0")
+        if not (np.all(np.isfinite(A)) and np.all(np.isfinite(b)) and np.all(np.isfinite(kap))):
+            raise ValueError("constraint rows must be finite")
+        self.A, self.b, self.kappa = A, b, kap
+        self.m, self.ds = m, ds
+        c = StateConstraintsC()
+        c.n_rows = m
+        c.A[:m * ds] = A.reshape(-1).tolist()
+        c.b[:m] = b.tolist()
+        c.kappa[:m] = kap.tolist()
+        self.c = c
+
+    @classmethod
+    def box(cls, lb, ub, state_dim, prob=None, kappa=None):
+        """Rows x_k <= ub[k] and -x_k <= -lb[k] for every finite bound (``None`` and +-inf entries produce no row; ``lb`` / ``ub`` may
+        themselves be None), upper bounds first, each group in state order."""
+        rows, rhs = [], []
+        for bound, sign in ((ub, 1.0), (lb, -1.0)):
+            if bound is None:
+                continue
+            bound = list(bound)
+            if len(bound) != state_dim:
+                raise ValueError("one bound (or None) per state dimension")
+            for k, v in enumerate(bound):
+                if v is None or not np.isfinite(v):
+                    continue
+                a = np.zeros(state_dim)
+                a[k] = sign
+                rows.append(a)
+                rhs.append(sign * float(v))
+        if not rows:
+            raise ValueError("no finite bound given")
+        return cls(np.array(rows), np.array(rhs), kappa=kappa, prob=prob)
 
 
 class GPPack:
@@ -294,8 +359,11 @@ class GPPack:
         return out
 
 
-def rollout(pack, x0, U, cost, want_grad=True, want_traj=True, graph=False, precision="fp64"):
+def rollout(pack, x0, U, cost, want_grad=True, want_traj=True, graph=False, precision="fp64", constraints=None):
     """B shooting rollouts + cost (+ gradient) in one call (C ABI ``gpmpc_rollout``).
+
+    constraints: a :class:`StateConstraints` -- the same device pass also returns g (B, H, m_c) and, with ``want_grad``, g_jac
+    (B, H m_c, H da) (C ABI ``gpmpc_rollout_constrained``; fp64, no graph replay).  None: the function is exactly what it was.
 
     x0: (B, ds) or (ds,); U: (B, H, da) or (H, da).  Returns a dict of CUDA tensors:
     cost (B,), grad (B, H, da), means (B, H+1, ds), vars (B, H+1, ds).
@@ -307,6 +375,11 @@ def rollout(pack, x0, U, cost, want_grad=True, want_traj=True, graph=False, prec
     precision: "fp64" (default), or -- objective only, for the tolerance sweep of BASELINE config 3 -- "fp32acc" (N^2
     products and sum in fp32) / "fp32" (exponent and exp in fp32 too).  Single precision fails the variance tolerance
     by orders of magnitude (profiles/r01/fp32_sweep.txt); it is a measurement aid, not a fast path."""
+    if constraints is not None:
+        if graph or precision != "fp64":
+            raise ValueError("a rollout with state constraints runs in fp64 as plain launches: graph=True and the reduced-precision modes "
+                             "are not supported")
+        return _rollout_constrained(pack, x0, U, cost, constraints, want_grad, want_traj)
     dev = pack.device
     U_host = None
     if graph and not isinstance(U, torch.Tensor):          # solver callbacks hand numpy: stage through pinned memory
@@ -370,6 +443,57 @@ def rollout(pack, x0, U, cost, want_grad=True, want_traj=True, graph=False, prec
         check(lib().gpmpc_rollout(pack.handle, B, H, ptr(x0), ptr(U), ctypes.byref(cost.c), flags,
                                   ptr(out.get("means")), ptr(out.get("vars")), ptr(out["cost"]), ptr(out.get("grad")),
                                   ctypes.c_void_p(ws.data_ptr()), ws.numel(), stream_ptr()), "gpmpc_rollout")
+    return out
+
+
+def _rollout_constrained(pack, x0, U, cost, sc, want_grad, want_traj):
+    dev = pack.device
+    U = _dev(U, dev)
+    if U.dim() == 2:
+        U = U.unsqueeze(0)
+    B, H, da = U.shape
+    x0 = _dev(x0, dev).reshape(-1, pack.ds)
+    if x0.shape[0] == 1 and B > 1:
+        x0 = x0.expand(B, pack.ds).contiguous()
+    if da != pack.da or x0.shape[0] != B or cost.ds != pack.ds or cost.da != pack.da:
+        raise ValueError("shape mismatch between pack, x0, U and cost parameters")
+    if sc.ds != pack.ds:
+        raise ValueError("the constraint rows have %d state coefficients, the pack has %d states" % (sc.ds, pack.ds))
+    flags = _lib.WANT_GRAD if want_grad else 0
+    e = lambda *shape: torch.empty(shape, dtype=torch.float64, device=dev)  # noqa: E731
+    out = {"cost": e(B), "g": e(B, H, sc.m)}
+    if want_grad:
+        out["grad"], out["g_jac"] = e(B, H, da), e(B, H * sc.m, H * da)
+    if want_traj:
+        out["means"], out["vars"] = e(B, H + 1, pack.ds), e(B, H + 1, pack.ds)
+    ws = pack.workspace(lib().gpmpc_rollout_constrained_workspace_bytes(pack.handle, B, H, flags))
+    with torch.cuda.device(dev):
+        check(lib().gpmpc_rollout_constrained(pack.handle, B, H, ptr(x0), ptr(U), ctypes.byref(cost.c), ctypes.byref(sc.c), flags,
+                                              ptr(out.get("means")), ptr(out.get("vars")), ptr(out["cost"]), ptr(out.get("grad")),
+                                              ptr(out["g"]), ptr(out.get("g_jac")), ctypes.c_void_p(ws.data_ptr()), ws.numel(),
+                                              stream_ptr()), "gpmpc_rollout_constrained")
+    return out
+
+
+def rollout_constraints(means, vars, jac, sc, ds, da):
+    """Constraint values and Jacobian of given trajectories (C ABI ``gpmpc_rollout_constraints``; a pure function of what
+    ``gpmpc_rollout_jac`` returns, any pack or plan).  means, vars: (B, H+1, ds); jac: (B, H, 2ds, 2ds+da) or None (values only).
+    Returns {"g": (B, H, m_c)[, "g_jac": (B, H m_c, H da)]}."""
+    dev = means.device if isinstance(means, torch.Tensor) and means.is_cuda else require_gpu()
+    means, vars = _dev(means, dev), _dev(vars, dev)
+    if means.dim() == 2:
+        means, vars = means.unsqueeze(0), vars.unsqueeze(0)
+    B, H1, ds_ = means.shape
+    H = H1 - 1
+    if ds_ != ds or sc.ds != ds or tuple(vars.shape) != (B, H1, ds):
+        raise ValueError("shape mismatch between means, vars and the constraint rows")
+    out = {"g": torch.empty((B, H, sc.m), dtype=torch.float64, device=dev)}
+    if jac is not None:
+        jac = _dev(jac, dev).reshape(B, H, 2 * ds, 2 * ds + da)
+        out["g_jac"] = torch.empty((B, H * sc.m, H * da), dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        check(lib().gpmpc_rollout_constraints(B, H, ds, da, ctypes.byref(sc.c), ptr(means), ptr(vars), ptr(jac), ptr(out["g"]),
+                                              ptr(out.get("g_jac")), stream_ptr()), "gpmpc_rollout_constraints")
     return out
 
 

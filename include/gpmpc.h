@@ -284,6 +284,49 @@ int gpmpc_rollout_vjp(int B, int H, int state_dim, int action_dim, const double*
                       const double* g_means, const double* g_vars, double* out_gU, double* out_gx0, void* stream);
 
 /* ---------------------------------------------------------------------------
+ * Linear chance constraints on the state (no reference counterpart: RiskSensitiveMPC.constraints returns 0 and jacobian zeros,
+ * src/mpc.py:257-267).  n_rows rows (a_r, b_r, kappa_r), a_r in R^ds, kappa_r >= 0, held at every horizon step t = 1..H (step 0 is the
+ * current state and does not depend on U):
+ *     g[t][r] = a_r . mu_t + kappa_r sd[t][r] - b_r  <= 0,    q = sum_k a_rk^2 var_tk,   sd = sqrt(q)
+ * kappa = Phi^-1(p) keeps the row with one-sided probability p under the predicted Gaussian; kappa = 0 constrains the mean only.
+ * The rollout does not clamp negative variances: q <= 0 gives sd = 0 and NO variance part in the derivative (the row is then its mean
+ * part); a NaN mean or variance of step t makes every row of step t NaN -- values and derivatives, 0 * NaN included -- and no other step's.
+ *     out_g    dev [B][H][n_rows]
+ *     out_gjac dev [B][H * n_rows][H * da]: row (t-1) n_rows + r, column tau da + j = d g[t][r] / d u_tau[j]
+ *              = sum_k a_rk S_t[k][c] + (kappa_r / (2 sd)) sum_k a_rk^2 S_t[ds+k][c],  S_t = d(mu_t, var_t)/dU;
+ *              columns tau >= t are stored as exactly 0.0 (causality): EVERY element is written, the buffer needs no memset.
+ * One forward-sensitivity sweep over the step Jacobians (k_rollout_constraints, csrc/constraints.hip), one lane per column.
+ * ------------------------------------------------------------------------- */
+#define GPMPC_MAX_CONS 16
+typedef struct gpmpc_state_constraints {
+    int n_rows;
+    int reserved;
+    double A[GPMPC_MAX_CONS * GPMPC_MAX_DS];          /* [n_rows][ds] row-major in the leading n_rows*ds entries */
+    double b[GPMPC_MAX_CONS];
+    double kappa[GPMPC_MAX_CONS];
+} gpmpc_state_constraints;
+
+/* Pure function of a propagated trajectory, like gpmpc_rollout_vjp: any pack, any plan, with a nominal model or without.
+ * means_dev, vars_dev [B][H+1][ds] and jac_dev [B][H][2ds][2ds+da] as gpmpc_rollout_jac (or gpmpc_rollout_constrained) left them; the
+ * state columns of step 1's Jacobian are never read.  out_gjac NULL: values only (jac_dev is then not read and may be NULL).
+ * GPMPC_E_ARG -- before anything is launched -- on a NULL cons / means / vars / out_g, out_gjac without jac_dev, n_rows outside
+ * 1..GPMPC_MAX_CONS, a negative or NaN kappa, dimensions out of range. */
+int gpmpc_rollout_constraints(int B, int H, int state_dim, int action_dim, const gpmpc_state_constraints* cons_host,
+                              const double* means_dev, const double* vars_dev, const double* jac_dev,
+                              double* out_g, double* out_gjac, void* stream);
+
+/* gpmpc_rollout and the constraints in ONE device pass: the launches of gpmpc_rollout of this shape (as one batch: no concurrent
+ * sub-batches) with the step Jacobians kept in the workspace, then k_rollout_constraints on the same stream.  out_cost, out_grad,
+ * out_means, out_vars are bit-identical to gpmpc_rollout's under the same plan.  Without GPMPC_WANT_GRAD: cost and constraint values
+ * only (out_grad, out_gjac not written, may be NULL).  out_means / out_vars may be NULL (kept in the workspace).
+ * flags: GPMPC_WANT_GRAD or 0; GPMPC_USE_GRAPH and the GPMPC_FP32_* modes are GPMPC_E_ARG (text in gpmpc_last_error). */
+size_t gpmpc_rollout_constrained_workspace_bytes(const gpmpc_pack* pack, int B, int H, unsigned flags);
+int gpmpc_rollout_constrained(const gpmpc_pack* pack, int B, int H, const double* x0_dev, const double* U_dev,
+                              const gpmpc_cost_params* cost_host, const gpmpc_state_constraints* cons_host, unsigned flags,
+                              double* out_means, double* out_vars, double* out_cost, double* out_grad,
+                              double* out_g, double* out_gjac, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------
  * Full-covariance form of the hot path (BASELINE config 5): the state distribution carries the whole ds x ds
  * covariance; off-diagonal terms are the exact cross-covariances Cov[f_a, f_b] (covariance_prop_torch,
  * src/tools/uncertainty_prop.py:402-465, consistent form).  The reference's rollout propagates variances only
