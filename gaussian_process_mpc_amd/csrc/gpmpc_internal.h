@@ -32,7 +32,7 @@ struct gpmpc_worklist {
 
 // Tuning overrides (GPMPC_* environment variables), read ONCE per pack -- at gpmpc_pack_create and again on
 // gpmpc_pack_reload_tuning -- never on the per-call path (a solver loop issues thousands of B = 1 rollouts per second).
-// -1 / 0 = not set: the measured defaults of plan_rollout / plan_mom apply.
+// -1 / 0 = not set: the measured defaults of plan.hip::gpmpc_choose_shape / plan_mom apply.
 struct gpmpc_tuning {
     int pair_sb;     // GPMPC_PAIR_SB     0 staged kernel | 1 scalar broadcast | -1 unset
     int tiling;      // GPMPC_TILING      0..6 | -1 unset
@@ -89,7 +89,7 @@ struct gpmpc_pack {
     double sf_host[GPMPC_MAX_DS];
     void* graph_cache;         // captured rollout (GPMPC_USE_GRAPH), owned by step.hip
     void* cb_cache;            // buffers + captured graph of gpmpc_objective_gradient (solver callbacks), owned by step.hip
-    void* tuned;               // plans measured by gpmpc_pack_autotune (gpmpc_tuned_table, step.hip), or null
+    void* tuned;               // shapes measured by gpmpc_pack_autotune (gpmpc_tuned_table, plan.h), or null
     void* lock;                // host lock of the pack's own streams / events / caches (std::recursive_mutex, step.hip::PackGuard)
     // [0: variance units only | 1: + cross units][0: 256x256 tiles | 1: 64x64 | 2: 256x64 | 3: 64x128 | 4: 256x128 | 5: 256x32 | 6: 256x16
     //  (4...6: mode 0 only)]

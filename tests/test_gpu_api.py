@@ -826,7 +826,7 @@ def test_autotune_measures_and_keeps_the_fastest_plan(G):
 
 def test_default_plan_is_within_reach_of_the_measured_best_between_generations(G):
     """Round 5 (review item 5): in the region the round-4 rule was more than 5 % off -- small training sets at batches between one and
-    two generations of whole-horizon workgroups, B ~ 260...450 -- the plan chosen by the cost model (step.hip::plan_rollout) is held to the
+    two generations of whole-horizon workgroups, B ~ 260...450 -- the plan chosen by the cost model (plan.hip::gpmpc_choose_shape) is held to the
     plan gpmpc_pack_autotune measures as fastest on this device: within 10 % on each of six shapes (5 % is the grid's own bar,
     profiles/r05/autotune_grid.txt; the extra margin is timing noise of a sub-millisecond measurement inside a test run), and at most
     two of the six beyond 5 %."""

@@ -1,6 +1,6 @@
 """Every pair-kernel template instance the dispatchers can select for D <= 7 is held to a CPU checker.
 
-The rollout picks its kernel by the amount of work (csrc/step.hip::plan_rollout, csrc/moment.hip::plan_mom):
+The rollout picks its kernel by the amount of work (csrc/plan.hip::gpmpc_choose_shape, csrc/moment.hip::plan_mom):
 
     whole horizon in one launch (traj_persist.h)          B >= ~0.7 trajectories per CU, N <= 512: one workgroup per trajectory
     one launch per step, 64-row tiles (step_fused.h)      small batches (the staged pair_kernel.h with GPMPC_FUSED=0 / full S)

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Rollouts/s over (N, state_dim, batch size): where each kernel shape of plan_rollout (step.hip) sits against the
+"""Rollouts/s over (N, state_dim, batch size): where each kernel shape of gpmpc_choose_shape (plan.hip) sits against the
 pair-evaluation rate of the large-batch kernel.  Objective + gradient, inputs resident, each rollout replayed as one
 hipGraph up to B = 128.  `eff` = pairs/s relative to the pair rate measured at the largest batch of the same (N, ds).
 

@@ -24,7 +24,7 @@ import sys
 EXEMPT = [
     # bug-compatible direct cross-covariance (moment.hip), D >= 7: D x D arrays per thread, never on the rollout path
     (r"^k_cross_cov<[78], true>", (16, 1200)),
-    # D >= 7 whole-horizon instances: plan_rollout never takes the whole-horizon form for D >= 7 (step.hip); forced
+    # D >= 7 whole-horizon instances: gpmpc_choose_shape never takes the whole-horizon form for D >= 7 (plan.hip); forced
     # only by tests/test_gpu_instances.py, which holds every one of them to the C port
     (r"^k_traj_persist<[78], ", (32, 128)),
     # one-launch-per-step kernel for D >= 7 (no BASELINE config beyond C4's D = 7, ds = 6, which runs the <7, 6, true, 0, 1> instance
