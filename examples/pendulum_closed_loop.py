@@ -4,7 +4,7 @@ src/experiments/pretrain_uncertainty.py: pre-train the GP on random transitions,
 (Simulator.run, src/simulator.py:37-60) with the model growing by one observation per step.
 
     python examples/pendulum_closed_loop.py [--pretrain 200] [--steps 25] [--horizon 10] [--window N] [--nominal identity]
-                                            [--max-speed V [--prob P]]
+                                            [--max-speed V [--prob P]] [--solver mppi [--samples K] [--iters I]]
 
 --window N: fixed-size training window -- once the model holds N points every new observation replaces the oldest one (first-in
 first-out), so the cost of the data update and the memory stay constant however long the loop runs (what the solver makes of a model
@@ -16,6 +16,10 @@ x_a) and the rollout adds the state back exactly; a zero-mean GP on the raw next
 --max-speed V [--prob P]: chance bound |theta_dot| <= V on every predicted state, each side held with probability P (default 0.95) on
 the predicted mean plus Phi^-1(P) predicted standard deviations (RiskSensitiveMPC.set_state_bounds).  The stand-in solver is then scipy's
 SLSQP on the objective / gradient / constraints / jacobian callbacks -- one device pass per iterate.
+
+--solver mppi [--samples K] [--iters I]: the sampling planner on the device (RiskSensitiveMPC.solver = "mppi", mppi.py): K perturbed copies
+of the previous plan per iteration as one objective-only batch, no gradient; with --max-speed the bound is its feasibility rule.  Works
+with --nominal identity (the rollout honours the model).
 
 Needs an MI355X and the built library; no gym, no cyipopt (the stand-in solver is scipy's L-BFGS-B on the same
 objective / gradient callbacks, so the trajectories are NOT the reference's Ipopt trajectories)."""
@@ -42,6 +46,9 @@ def main():
     ap.add_argument("--nominal", choices=("none", "identity"), default="none", help="identity: the GPs learn x_{t+1} - x_t, the rollout adds x_t back")
     ap.add_argument("--max-speed", type=float, default=None, help="chance bound on |theta_dot| over the horizon (state constraints)")
     ap.add_argument("--prob", type=float, default=0.95, help="one-sided satisfaction probability of --max-speed")
+    ap.add_argument("--solver", choices=("default", "mppi"), default="default", help="mppi: the sampling planner on the device")
+    ap.add_argument("--samples", type=int, default=64, help="--solver mppi: samples per iteration")
+    ap.add_argument("--iters", type=int, default=30, help="--solver mppi: iterations per solve")
     args = ap.parse_args()
 
     rng = np.random.default_rng(0)
@@ -62,6 +69,9 @@ def main():
     mpc.set_lb([-2.0]); mpc.set_ub([2.0])
     mpc.set_xref(np.zeros(2))
     mpc.n_starts = args.starts
+    if args.solver == "mppi":
+        mpc.solver = "mppi"
+        mpc.mppi_options.update(samples=args.samples, iterations=args.iters)
     solves = []
     if args.max_speed is not None:
         mpc.set_state_bounds([None, -args.max_speed], [None, args.max_speed], args.prob)

@@ -16,6 +16,7 @@ LIB_PATH = os.environ.get("GPMPC_LIB_PATH") or os.path.join(_HERE, "csrc", "libg
 MAX_D = 8
 MAX_DS = 8
 MAX_CONS = 16
+MPPI_MAX_SAMPLES = 4096
 WANT_GRAD = 1
 COV_BUG_COMPAT = 2
 USE_GRAPH = 4
@@ -55,6 +56,19 @@ class StateConstraintsC(ctypes.Structure):
                 ("kappa", ctypes.c_double * MAX_CONS)]
 
 
+class MppiParamsC(ctypes.Structure):
+    _fields_ = [("n_samples", ctypes.c_int),
+                ("iterations", ctypes.c_int),
+                ("sigma", ctypes.c_double * MAX_D),
+                ("sigma_decay", ctypes.c_double),
+                ("beta", ctypes.c_double),
+                ("seed", ctypes.c_ulonglong),
+                ("call_index", ctypes.c_uint),
+                ("reserved", ctypes.c_uint),
+                ("lb", ctypes.c_double * MAX_D),
+                ("ub", ctypes.c_double * MAX_D)]
+
+
 _vp, _i, _d, _sz, _u = ctypes.c_void_p, ctypes.c_int, ctypes.c_double, ctypes.c_size_t, ctypes.c_uint
 _dp = ctypes.POINTER(ctypes.c_double)
 
@@ -91,6 +105,11 @@ SIGNATURES = {
     "gpmpc_rollout_constrained_workspace_bytes": (_sz, [_vp, _i, _i, _u]),
     "gpmpc_rollout_constrained": (_i, [_vp, _i, _i, _vp, _vp, ctypes.POINTER(CostParamsC), ctypes.POINTER(StateConstraintsC), _u,
                                        _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "gpmpc_mppi_sample": (_i, [_i, _i, _i, ctypes.POINTER(MppiParamsC), _i, _vp, _vp, _vp, _vp, _vp]),
+    "gpmpc_mppi_update": (_i, [_i, _i, _i, _i, _d, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "gpmpc_mppi_solve_workspace_bytes": (_sz, [_vp, _i, ctypes.POINTER(MppiParamsC), ctypes.POINTER(StateConstraintsC)]),
+    "gpmpc_mppi_solve": (_i, [_vp, _i, _vp, _vp, ctypes.POINTER(CostParamsC), ctypes.POINTER(StateConstraintsC),
+                              ctypes.POINTER(MppiParamsC), _vp, _vp, _vp, _vp, _sz, _vp]),
     "gpmpc_rollout_workspace_bytes": (_sz, [_vp, _i, _i, _u]),
     "gpmpc_plan_describe": (_i, [_vp, _i, _i, _u, ctypes.c_char_p, _sz]),
     "gpmpc_pack_autotune": (_i, [_vp, _i, _i, _u, ctypes.c_char_p, _sz]),
@@ -149,6 +168,8 @@ def lib():
 def check(rc, what):
     if rc != 0:
         detail = lib().gpmpc_last_error().decode() if rc == -3 else ""
+        if rc == -1 and "mppi" in what:    # the planner's refusals say which parameter
+            detail = lib().gpmpc_last_error().decode()
         if rc == -5:                       # refusals on a pack with a nominal model say why (others leave the text alone)
             why = lib().gpmpc_last_error().decode()
             detail = why if "nominal model" in why else ""

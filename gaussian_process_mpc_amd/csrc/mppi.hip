@@ -1,0 +1,357 @@
+// MPPI (model-predictive path integral) planner on the device (include/gpmpc.h): K perturbed copies of the current plan
+// are rolled out as ONE objective-only batch, the plan moves to their softmin-weighted mean, the best sample seen is kept.
+//
+//   k_mppi_sample   U[k][c] = clamp(mean[c] + sigma_j decay^it eps[k][c], lb_j, ub_j),  c = t da + j;  slot k = 0 is the mean itself.
+//                   eps is counter-based (Philox4x32-10 + Box-Muller): a pure function of (seed, call index, iteration, element), whatever
+//                   the grid.  One thread = one Philox counter = two normals = the elements e = 2p, 2p + 1 of the flattened [K][n] block.
+//   k_mppi_update   scores the batch (cost, or total constraint violation while nothing is feasible), keeps the best sample, and writes
+//                   the softmin-weighted mean.  Lanes run along c (coalesced rows of U), the four waves of a workgroup take a quarter of
+//                   the samples each and are combined through LDS in a fixed order; scores and weights are recomputed by every workgroup
+//                   (K <= 4096 values: cheaper than a second launch).  No atomics: every sum has one fixed order, the result for column c
+//                   does not depend on the grid.
+//
+// Summation orders (tests/mppi_reference.py restates them; the trace of a solve is compared exactly):
+//   v_k       sequential over the H m_c constraint values of sample k, v <- v + max(g, 0)
+//   sums over k (sum of the finite scores, sum of the weights): thread i of 256 adds the terms k = i, i + 256, ... in ascending order,
+//             then the 256 partial sums are folded in halves, p[i] <- p[i] + p[i + h], h = 128, 64, ... 1
+//   mean[c]   wave w adds w_k U[k][c] over its quarter of the samples in ascending k (zero weights skipped), the four are added in wave
+//             order, one division by the sum of the weights
+#include "gpmpc_internal.h"
+#include <cmath>
+
+#define MPPI_THREADS 256
+
+// ---------------------------------------------------------------------------
+// Philox4x32-10 (Salmon et al., "Parallel random numbers: as easy as 1, 2, 3", SC'11)
+// ---------------------------------------------------------------------------
+struct Philox4 { unsigned w[4]; };
+
+__host__ __device__ inline Philox4 philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1) {
+    for (int r = 0; r < 10; ++r) {
+        if (r) { k0 += 0x9E3779B9u; k1 += 0xBB67AE85u; }
+        const unsigned long long p0 = 0xD2511F53ull * c0, p1 = 0xCD9E8D57ull * c2;
+        const unsigned n0 = (unsigned)(p1 >> 32) ^ c1 ^ k0, n1 = (unsigned)p1;
+        const unsigned n2 = (unsigned)(p0 >> 32) ^ c3 ^ k1, n3 = (unsigned)p0;
+        c0 = n0; c1 = n1; c2 = n2; c3 = n3;
+    }
+    return Philox4{{c0, c1, c2, c3}};
+}
+
+// 53 random bits -> a uniform strictly inside (0, 1) (but for one rounding to 1 in 2^53 draws, which Box-Muller maps to eps = 0)
+__device__ __forceinline__ double mppi_uniform(unsigned hi, unsigned lo) {
+    return ((double)(hi >> 5) * 67108864.0 + (double)(lo >> 6) + 0.5) * 0x1p-53;
+}
+
+// grid: ceil(max(ceil(K n / 2), K ds) / 256) x 256 threads.  P travels by value: sigma, bounds, seed and call index are kernel arguments.
+__global__ __launch_bounds__(MPPI_THREADS) void k_mppi_sample(int n, int da, int ds, gpmpc_mppi_params P, unsigned iteration, double scale,
+                                                              const double* __restrict__ mean, const double* __restrict__ x0,
+                                                              double* __restrict__ U, double* __restrict__ x0b) {
+    const long p = (long)blockIdx.x * MPPI_THREADS + threadIdx.x;
+    const long total = (long)P.n_samples * n;
+    if (x0b && p < (long)P.n_samples * ds) x0b[p] = x0[p % ds];          // the start state once per sample, for the rollout
+    const long e0 = 2 * p;
+    if (e0 >= total) return;
+    const Philox4 r = philox4x32_10((unsigned)p, (unsigned)((unsigned long long)p >> 32), iteration, P.call_index,
+                                    (unsigned)P.seed, (unsigned)(P.seed >> 32));
+    const double u1 = mppi_uniform(r.w[0], r.w[1]), u2 = mppi_uniform(r.w[2], r.w[3]);
+    const double rad = sqrt(-2.0 * log(u1));
+    double sn, cs;
+    sincospi(2.0 * u2, &sn, &cs);
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        const long e = e0 + h;
+        if (e >= total) break;                                           // an odd last element uses half a counter
+        const int c = (int)(e % n), j = c % da;
+        const double m = mean[c];
+        const double v = m + (P.sigma[j] * scale) * (rad * (h ? sn : cs));
+        U[e] = e < n ? m : fmin(fmax(v, P.lb[j]), P.ub[j]);              // slot 0 is the mean, bit for bit: its noise is discarded
+    }
+}
+
+// ---------------------------------------------------------------------------
+// update
+// ---------------------------------------------------------------------------
+// fold 256 per-thread values in halves (fixed order); the total is returned to every thread.  `red` is free again after the call.
+__device__ __forceinline__ double mppi_fold_sum(double v, double* red) {
+    const int t = threadIdx.x;
+    red[t] = v;
+    __syncthreads();
+    for (int h = MPPI_THREADS / 2; h >= 1; h >>= 1) {
+        if (t < h) red[t] = red[t] + red[t + h];
+        __syncthreads();
+    }
+    const double s = red[0];
+    __syncthreads();
+    return s;
+}
+__device__ __forceinline__ int mppi_fold_count(int v, int* red) {
+    const int t = threadIdx.x;
+    red[t] = v;
+    __syncthreads();
+    for (int h = MPPI_THREADS / 2; h >= 1; h >>= 1) {
+        if (t < h) red[t] += red[t + h];
+        __syncthreads();
+    }
+    const int s = red[0];
+    __syncthreads();
+    return s;
+}
+
+// grid: ceil(n / 64) workgroups of 256 threads; workgroup x owns the columns [64 x, 64 x + 64) of mean and best.
+// best_in / best_out [2 + n] = (violation, cost, plan) must not alias: every workgroup decides from the OLD key, and every element of
+// best_out is written (the old entry where the new key is not strictly smaller).  mean is written, never read; untouched with no sample alive.
+__global__ __launch_bounds__(MPPI_THREADS) void k_mppi_update(int K, int n, int m, double beta, const double* __restrict__ U,
+                                                              const double* __restrict__ cost, const double* __restrict__ g,
+                                                              double* __restrict__ mean, const double* __restrict__ best_in,
+                                                              double* __restrict__ best_out, double* __restrict__ trace) {
+    __shared__ double sw[GPMPC_MPPI_MAX_SAMPLES];       // v_k (NaN: dead), then the score s_k, then the weight w_k
+    __shared__ double red[MPPI_THREADS];
+    __shared__ int redi[MPPI_THREADS];
+    __shared__ double part[4][64];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const double inf = __builtin_huge_val();
+
+    // 1. violation and liveness of every sample
+    int nfeas = 0, nalive = 0;
+    for (int k = tid; k < K; k += MPPI_THREADS) {
+        const double ck = cost[k];
+        bool dead = ck != ck;
+        double v = 0.0;
+        if (g) {
+            const double* __restrict__ gk = g + (size_t)k * m;
+            for (int i = 0; i < m; ++i) {
+                const double gi = gk[i];
+                dead |= gi != gi;
+                v = v + (gi > 0.0 ? gi : 0.0);
+            }
+        }
+        sw[k] = dead ? __builtin_nan("") : v;
+        nalive += dead ? 0 : 1;
+        nfeas += (!dead && v == 0.0) ? 1 : 0;
+    }
+    nfeas = mppi_fold_count(nfeas, redi);
+    nalive = mppi_fold_count(nalive, redi);
+    const double old_v = best_in[0], old_c = best_in[1];
+    const int c = blockIdx.x * 64 + lane;
+    if (nalive == 0) {                                  // (uniform over the grid) nothing to learn from: mean and best stay
+        if (wave == 0 && c < n) best_out[2 + c] = best_in[2 + c];
+        if (blockIdx.x == 0 && tid == 0) {
+            best_out[0] = old_v; best_out[1] = old_c;
+            trace[0] = old_v; trace[1] = old_c; trace[2] = 0.0; trace[3] = 0.0; trace[4] = inf; trace[5] = 0.0;
+        }
+        return;
+    }
+    const bool restore = nfeas == 0;                    // feasibility restoration: the score is the violation
+
+    // 2. scores; candidates are the feasible samples, or the alive ones under restoration.  argmin with the lowest index on ties
+    double bs = inf, fsum = 0.0;
+    int bk = 0x7fffffff, nfin = 0;
+    for (int k = tid; k < K; k += MPPI_THREADS) {
+        const double v = sw[k];
+        const bool cand = restore ? v == v : v == 0.0;
+        const double s = cand ? (restore ? v : cost[k]) : inf;
+        sw[k] = cand ? s : __builtin_nan("");           // NaN marks a sample that is no candidate (a candidate's score may be +inf)
+        if (cand && (bk == 0x7fffffff || s < bs)) { bs = s; bk = k; }
+        const bool fin = cand && s - s == 0.0;          // finite
+        fsum = fsum + (fin ? s : 0.0);
+        nfin += fin ? 1 : 0;
+    }
+    red[tid] = bs; redi[tid] = bk;
+    __syncthreads();
+    for (int h = MPPI_THREADS / 2; h >= 1; h >>= 1) {
+        if (tid < h) {
+            const double s2 = red[tid + h]; const int k2 = redi[tid + h];
+            const int k1 = redi[tid];
+            if (k2 != 0x7fffffff && (k1 == 0x7fffffff || s2 < red[tid] || (s2 == red[tid] && k2 < k1))) { red[tid] = s2; redi[tid] = k2; }
+        }
+        __syncthreads();
+    }
+    const double smin = red[0];
+    const int kstar = redi[0];
+    __syncthreads();
+    fsum = mppi_fold_sum(fsum, red);
+    nfin = mppi_fold_count(nfin, redi);
+
+    // 3. temperature and weights
+    const double T = nfin > 0 ? beta * (fsum / (double)nfin - smin) : 0.0;
+    const bool soft = T > 0.0 && T < inf;               // else: weight 1 on the candidates that tie with the minimum
+    double wsum = 0.0;
+    for (int k = tid; k < K; k += MPPI_THREADS) {
+        const double s = sw[k];
+        double w = 0.0;
+        if (s == s) {
+            if (soft) w = (s - s == 0.0) ? exp(-(s - smin) / T) : 0.0;
+            else w = s == smin ? 1.0 : 0.0;
+        }
+        sw[k] = w;
+        wsum = wsum + w;
+    }
+    wsum = mppi_fold_sum(wsum, red);                    // (its barriers also publish sw) >= 1: the weight of kstar is exp(0) or 1
+
+    // 4. weighted mean of this workgroup's columns
+    const int kq = (K + 3) / 4, k0 = wave * kq, k1 = (k0 + kq < K) ? k0 + kq : K;
+    double acc = 0.0;
+    if (c < n)
+        for (int k = k0; k < k1; ++k) {
+            const double w = sw[k];
+            if (w != 0.0) acc = acc + w * U[(size_t)k * n + c];
+        }
+    part[wave][lane] = acc;
+    __syncthreads();
+
+    // 5. the best sample seen: key (violation, cost), lexicographic, replaced only by a strictly smaller one
+    const double new_v = restore ? smin : 0.0, new_c = cost[kstar];
+    const bool better = new_v < old_v || (new_v == old_v && new_c < old_c);
+    if (wave == 0 && c < n) {
+        mean[c] = (((part[0][lane] + part[1][lane]) + part[2][lane]) + part[3][lane]) / wsum;
+        best_out[2 + c] = better ? U[(size_t)kstar * n + c] : best_in[2 + c];
+    }
+    if (blockIdx.x == 0 && tid == 0) {
+        const double bv = better ? new_v : old_v, bc = better ? new_c : old_c;
+        best_out[0] = bv; best_out[1] = bc;
+        trace[0] = bv; trace[1] = bc; trace[2] = (double)nfeas; trace[3] = (double)nalive; trace[4] = smin; trace[5] = T;
+    }
+}
+
+// ---------------------------------------------------------------------------
+// host entries
+// ---------------------------------------------------------------------------
+static int mppi_refuse(const char* who, const char* what) {
+    char text[200];
+    snprintf(text, sizeof(text), "%s: %s", who, what);
+    gpmpc_set_error_text(text);
+    return GPMPC_E_ARG;
+}
+
+// the part of the parameters that needs no dimension
+static int mppi_check_scalars(const gpmpc_mppi_params* P, const char* who) {
+    char text[120];
+    if (!P) return GPMPC_E_ARG;
+    if (P->n_samples < 1 || P->n_samples > GPMPC_MPPI_MAX_SAMPLES) {
+        snprintf(text, sizeof(text), "n_samples = %d outside 1..%d", P->n_samples, GPMPC_MPPI_MAX_SAMPLES);
+        return mppi_refuse(who, text);
+    }
+    if (P->iterations < 1) { snprintf(text, sizeof(text), "iterations = %d is less than 1", P->iterations); return mppi_refuse(who, text); }
+    if (!(P->sigma_decay > 0.0)) { snprintf(text, sizeof(text), "sigma_decay = %g is not positive", P->sigma_decay); return mppi_refuse(who, text); }
+    if (!(P->beta > 0.0)) { snprintf(text, sizeof(text), "beta = %g is not positive", P->beta); return mppi_refuse(who, text); }
+    return GPMPC_OK;
+}
+
+static int mppi_check_inputs(const gpmpc_mppi_params* P, int da, const char* who) {
+    char text[120];
+    for (int j = 0; j < da; ++j) {
+        if (!(P->sigma[j] > 0.0)) { snprintf(text, sizeof(text), "sigma[%d] = %g is not positive", j, P->sigma[j]); return mppi_refuse(who, text); }
+        if (!(P->lb[j] <= P->ub[j])) {                      // lb > ub, or a NaN bound
+            snprintf(text, sizeof(text), "lb[%d] = %g exceeds ub[%d] = %g", j, P->lb[j], j, P->ub[j]);
+            return mppi_refuse(who, text);
+        }
+    }
+    return GPMPC_OK;
+}
+
+static int mppi_dims_ok(int H, int ds, int da) {
+    return H >= 1 && da >= 1 && da <= GPMPC_MAX_D && ds >= 0 && ds <= GPMPC_MAX_DS && (long)H * da <= 64L * 65535;      // (n as in constraints.hip)
+}
+
+static int mppi_launch_sample(int H, int ds, int da, const gpmpc_mppi_params& P, int iteration, const double* mean, const double* x0,
+                              double* U, double* x0b, hipStream_t s) {
+    const long n = (long)H * da, pairs = ((long)P.n_samples * n + 1) / 2, states = x0b ? (long)P.n_samples * ds : 0;
+    const long threads = pairs > states ? pairs : states;
+    const double scale = pow(P.sigma_decay, (double)iteration);
+    hipLaunchKernelGGL(k_mppi_sample, dim3((unsigned)((threads + MPPI_THREADS - 1) / MPPI_THREADS)), dim3(MPPI_THREADS), 0, s, (int)n, da, ds,
+                       P, (unsigned)iteration, scale, mean, x0, U, x0b);
+    GPMPC_HIP(hipGetLastError());
+    return GPMPC_OK;
+}
+
+extern "C" int gpmpc_mppi_sample(int H, int ds, int da, const gpmpc_mppi_params* P, int iteration, const double* mean, const double* x0,
+                                 double* out_U, double* out_x0_batch, void* stream) {
+    if (!P || !mean || !out_U || iteration < 0 || !mppi_dims_ok(H, ds, da) || (out_x0_batch && (!x0 || ds < 1))) return GPMPC_E_ARG;
+    if (int rc = mppi_check_scalars(P, "gpmpc_mppi_sample")) return rc;
+    if (int rc = mppi_check_inputs(P, da, "gpmpc_mppi_sample")) return rc;
+    return mppi_launch_sample(H, ds, da, *P, iteration, mean, x0, out_U, out_x0_batch, (hipStream_t)stream);
+}
+
+extern "C" int gpmpc_mppi_update(int K, int H, int da, int n_rows, double beta, const double* U, const double* cost, const double* g,
+                                 double* mean, const double* best_in, double* best_out, double* out_trace, void* stream) {
+    if (!U || !cost || !mean || !best_in || !best_out || !out_trace || !mppi_dims_ok(H, 0, da)) return GPMPC_E_ARG;
+    if (K < 1 || K > GPMPC_MPPI_MAX_SAMPLES) return mppi_refuse("gpmpc_mppi_update", "the number of samples is outside 1..GPMPC_MPPI_MAX_SAMPLES");
+    if (!(beta > 0.0)) return mppi_refuse("gpmpc_mppi_update", "beta is not positive");
+    if (best_in == best_out) return mppi_refuse("gpmpc_mppi_update", "best_in and best_out must be different buffers");
+    if (n_rows < 0 || n_rows > GPMPC_MAX_CONS || (g != nullptr) != (n_rows > 0))
+        return mppi_refuse("gpmpc_mppi_update", "constraint values and n_rows in 1..GPMPC_MAX_CONS are given together (NULL and 0 without constraints)");
+    const int n = H * da;
+    hipLaunchKernelGGL(k_mppi_update, dim3((n + 63) / 64), dim3(MPPI_THREADS), 0, (hipStream_t)stream, K, n, H * n_rows, beta, U, cost, g, mean,
+                       best_in, best_out, out_trace);
+    GPMPC_HIP(hipGetLastError());
+    return GPMPC_OK;
+}
+
+// workspace of a solve: U [K][n] | x0 [K][ds] | cost [K] | g [K][H m_c] | mean [n] | best x 2 [2 + n] | the rollout's own workspace
+struct MppiLayout { size_t off_U, off_x0, off_cost, off_g, off_mean, off_best[2], off_roll, roll_bytes, total; };
+static size_t mppi_align(size_t b) { return (b + 255) & ~(size_t)255; }
+static MppiLayout mppi_layout(const gpmpc_pack* p, int H, int K, int m_c) {
+    MppiLayout L;
+    const size_t n = (size_t)H * p->da, d = sizeof(double);
+    size_t o = 0;
+    L.off_U = o; o += mppi_align(d * K * n);
+    L.off_x0 = o; o += mppi_align(d * K * p->ds);
+    L.off_cost = o; o += mppi_align(d * K);
+    L.off_g = o; o += mppi_align(d * K * H * m_c);
+    L.off_mean = o; o += mppi_align(d * n);
+    L.off_best[0] = o; o += mppi_align(d * (2 + n));
+    L.off_best[1] = o; o += mppi_align(d * (2 + n));
+    L.off_roll = o;
+    L.roll_bytes = m_c ? gpmpc_rollout_constrained_workspace_bytes(p, K, H, 0) : gpmpc_rollout_workspace_bytes(p, K, H, 0);
+    L.total = o + mppi_align(L.roll_bytes);
+    return L;
+}
+
+extern "C" size_t gpmpc_mppi_solve_workspace_bytes(const gpmpc_pack* p, int H, const gpmpc_mppi_params* P, const gpmpc_state_constraints* cons) {
+    if (!p || !P || P->n_samples < 1 || P->n_samples > GPMPC_MPPI_MAX_SAMPLES) return 0;
+    if (cons && (cons->n_rows < 1 || cons->n_rows > GPMPC_MAX_CONS)) return 0;
+    if (!mppi_dims_ok(H, p->ds, p->da)) return 0;
+    return mppi_layout(p, H, P->n_samples, cons ? cons->n_rows : 0).total;
+}
+
+extern "C" int gpmpc_mppi_solve(const gpmpc_pack* p, int H, const double* x0, const double* start, const gpmpc_cost_params* cost,
+                                const gpmpc_state_constraints* cons, const gpmpc_mppi_params* P, double* out_U, double* out_best,
+                                double* out_trace, void* workspace, size_t workspace_bytes, void* stream) {
+    const char* who = "gpmpc_mppi_solve";
+    if (!p || !x0 || !start || !cost || !P || !out_U || !out_best || !out_trace || !workspace || H < 1) return GPMPC_E_ARG;
+    if (int rc = mppi_check_scalars(P, who)) return rc;                  // (before the pack is looked at)
+    if (cons) if (int rc = gpmpc_check_constraints(cons, who)) return rc;
+    if (int rc_dev = gpmpc_check_device(p)) return rc_dev;
+    if (!mppi_dims_ok(H, p->ds, p->da)) return GPMPC_E_ARG;
+    if (int rc = mppi_check_inputs(P, p->da, who)) return rc;
+    if (!p->built) return GPMPC_E_STATE;
+    const int K = P->n_samples, n = H * p->da, m_c = cons ? cons->n_rows : 0;
+    const MppiLayout L = mppi_layout(p, H, K, m_c);
+    if (workspace_bytes < L.total) return GPMPC_E_WORKSPACE;
+    hipStream_t s = (hipStream_t)stream;
+    char* ws = (char*)workspace;
+    double *U = (double*)(ws + L.off_U), *x0b = (double*)(ws + L.off_x0), *cst = (double*)(ws + L.off_cost), *g = (double*)(ws + L.off_g);
+    double *mean = (double*)(ws + L.off_mean), *best[2] = {(double*)(ws + L.off_best[0]), (double*)(ws + L.off_best[1])};
+    // best = (+inf, +inf, start plan), mean = start plan
+    const double key0[2] = {__builtin_huge_val(), __builtin_huge_val()};
+    if (int rc = gpmpc_upload_small(best[0], key0, sizeof(key0), s)) return rc;
+    GPMPC_HIP(hipMemcpyAsync(best[0] + 2, start, sizeof(double) * n, hipMemcpyDeviceToDevice, s));
+    GPMPC_HIP(hipMemcpyAsync(mean, start, sizeof(double) * n, hipMemcpyDeviceToDevice, s));
+    for (int it = 0; it < P->iterations; ++it) {
+        if (int rc = mppi_launch_sample(H, p->ds, p->da, *P, it, mean, x0, U, x0b, s)) return rc;
+        int rc;
+        if (cons)
+            rc = gpmpc_rollout_constrained(p, K, H, x0b, U, cost, cons, 0, nullptr, nullptr, cst, nullptr, g, nullptr, ws + L.off_roll,
+                                           L.roll_bytes, stream);
+        else
+            rc = gpmpc_rollout(p, K, H, x0b, U, cost, 0, nullptr, nullptr, cst, nullptr, ws + L.off_roll, L.roll_bytes, stream);
+        if (rc) return rc;
+        rc = gpmpc_mppi_update(K, H, p->da, m_c, P->beta, U, cst, cons ? g : nullptr, mean, best[it & 1], best[(it + 1) & 1],
+                               out_trace + 6 * (size_t)it, stream);
+        if (rc) return rc;
+    }
+    const double* fin = best[P->iterations & 1];
+    GPMPC_HIP(hipMemcpyAsync(out_best, fin, sizeof(double) * 2, hipMemcpyDeviceToDevice, s));
+    GPMPC_HIP(hipMemcpyAsync(out_U, fin + 2, sizeof(double) * n, hipMemcpyDeviceToDevice, s));
+    return GPMPC_OK;
+}

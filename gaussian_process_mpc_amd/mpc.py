@@ -18,6 +18,10 @@ forced by moving the rollout into one fused HIP call:
   constraints A mu_t + kappa sd_t <= b on every predicted state.  ``constraints(x)`` / ``jacobian(x)`` then return their values and the
   dense Jacobian from the SAME device pass as cost and gradient (``gpmpc_rollout_constrained``), and the cyipopt problem gets
   m = H m_c rows.  Without constraints set nothing changes.
+* ``solver = "mppi"`` (extension; ``mpc.solver`` or ``get_optimal_trajectory(x, solver="mppi")``): the sampling planner of mppi.py -- K
+  perturbed copies of the previous plan, shifted by one step, rolled out as one objective-only batch per iteration, the whole search one
+  enqueue on the device (``gpmpc_mppi_solve``).  State constraints that are set become its feasibility rule.  ``solver = None`` (the
+  default) is everything above, unchanged.
 """
 import numpy as np
 import torch
@@ -74,6 +78,10 @@ class RiskSensitiveMPC:
         self.last_solve_info = None
         self._solve_count = 0
         self.state_constraints = None                    # rollout.StateConstraints, or None (the reference's unconstrained problem)
+        # sampling planner (extension; mppi.py): None = the solvers above | "mppi".  sigma None: a quarter of the box width of each input,
+        # 1 along an unbounded one; the seed and the solve count (the call index) fix every sample
+        self.solver = None
+        self.mppi_options = {"samples": 64, "iterations": 30, "sigma": None, "decay": 0.9, "beta": 0.1, "seed": 0}
         self.curr_g = None
         self.curr_g_jac = None
 
@@ -251,7 +259,16 @@ class RiskSensitiveMPC:
         return r["cost"].cpu().numpy(), r["grad"].cpu().numpy()
 
     # -- solve (src/mpc.py:269-330)
-    def get_optimal_trajectory(self, curr_state, n_starts=None):
+    def get_optimal_trajectory(self, curr_state, n_starts=None, solver=None):
+        solver = getattr(self, "solver", None) if solver is None else solver
+        if solver not in (None, "mppi"):
+            raise ValueError("solver must be None or 'mppi', got %r" % (solver,))
+        if solver == "mppi":
+            if (self.n_starts if n_starts is None else n_starts) > 1:
+                raise ValueError("solver='mppi' is one search over its own samples: it does not combine with n_starts > 1")
+            if self.full_covariance:
+                raise NotImplementedError("solver='mppi' runs the diagonal rollout (gpmpc_mppi_solve): MPPI over the full-covariance "
+                                          "rollout is not implemented")
         if self.train_empty:
             if self.dynamics.gpr_err[0].num_train > 0:
                 self.train_empty = False
@@ -263,6 +280,10 @@ class RiskSensitiveMPC:
         lb, ub = self.horizon * list(self.lb), self.horizon * list(self.ub)
         K = self.n_starts if n_starts is None else n_starts
         sc = self.state_constraints
+        if solver == "mppi":
+            x = self._solve_mppi()
+            self.last_traj = x
+            return np.reshape(x, (self.horizon, self.input_dim))
         if sc is not None and self.full_covariance:
             raise NotImplementedError("state constraints under the full-covariance rollout are not implemented "
                                       "(q = a^T Sigma_t a and that path's Jacobian layout: a follow-up)")
@@ -313,6 +334,33 @@ class RiskSensitiveMPC:
                        method="L-BFGS-B", bounds=bounds, options={"maxiter": 300, "ftol": 1e-10, "gtol": 1e-4})
         self.solver_used = "scipy-lbfgsb"
         return res.x
+
+    def _solve_mppi(self):
+        """The sampling planner (mppi.mppi_solve) from the previous plan shifted by one step (zeros on the first solve); the call index of
+        the noise is the solve count (shared with the multi-start's start sampler), so a loop of solves is reproducible from ``mppi_options["seed"]``."""
+        from .mppi import mppi_solve
+        opt = self.mppi_options
+        H, da = self.horizon, self.input_dim
+        big = 1e15                                                        # (the setters' "no bound", as _solve_without_ipopt reads it)
+        lb = np.array([-np.inf if v <= -big else v for v in self.lb], dtype=np.float64)
+        ub = np.array([np.inf if v >= big else v for v in self.ub], dtype=np.float64)
+        sigma = opt.get("sigma")
+        if sigma is None:
+            sigma = np.where(np.isfinite(ub - lb), 0.25 * (ub - lb), 1.0)
+        start = np.zeros((H, da))
+        if self.solver_used is not None:                                  # (whichever solver made the previous plan)
+            prev = np.asarray(self.last_traj, dtype=np.float64).reshape(H, da)
+            start = np.clip(np.concatenate((prev[1:], prev[-1:]), axis=0), lb, ub)
+        r = mppi_solve(self.dynamics.pack(), self.curr_state, start, self._cost_params(), constraints=self.state_constraints,
+                       samples=int(opt.get("samples", 64)), iterations=int(opt.get("iterations", 30)), sigma=sigma,
+                       decay=float(opt.get("decay", 0.9)), beta=float(opt.get("beta", 0.1)), seed=int(opt.get("seed", 0)),
+                       call_index=self._solve_count, lb=lb, ub=ub)
+        self._solve_count += 1
+        self.solver_used = "mppi x%d" % int(opt.get("samples", 64))
+        self.last_solve_info = {"cost": r["cost"], "violation": r["violation"], "feasible": r["feasible"], "success": r["feasible"],
+                                "max_violation": r["violation"], "iterations": int(opt.get("iterations", 30)), "trace": r["trace"]}
+        self._cache_key = None
+        return r["U"].reshape(-1)
 
     def _solve_multistart(self, K, lb, ub):
         """K starts advanced together (multistart.lockstep_lbfgs): one batched rollout of K plans per solver iteration, replayed as

@@ -327,6 +327,65 @@ int gpmpc_rollout_constrained(const gpmpc_pack* pack, int B, int H, const double
                               double* out_g, double* out_gjac, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------
+ * MPPI planner on the device (no reference counterpart; DESIGN.md section 3c, kernels in csrc/mppi.hip).  Per iteration: K perturbed copies
+ * of the current plan (the "mean") are rolled out as ONE objective-only batch, the best sample seen is kept, the mean moves to the
+ * softmin-weighted average of the samples.  With state constraints a sample is feasible when none of its rows is violated; while no sample
+ * is feasible the score is the total violation (feasibility restoration).  n = H * action_dim, column c = t * action_dim + j.
+ * ------------------------------------------------------------------------- */
+#define GPMPC_MPPI_MAX_SAMPLES 4096
+typedef struct gpmpc_mppi_params {
+    int n_samples;                     /* K, 1..GPMPC_MPPI_MAX_SAMPLES */
+    int iterations;                    /* >= 1 (gpmpc_mppi_solve) */
+    double sigma[GPMPC_MAX_D];         /* standard deviation of the perturbation of input j, > 0, in the leading action_dim entries */
+    double sigma_decay;                /* > 0: iteration `it` perturbs with sigma * sigma_decay^it */
+    double beta;                       /* > 0: temperature = beta * (mean of the finite scores - smallest score) */
+    unsigned long long seed;           /* Philox key */
+    unsigned int call_index;           /* last word of the Philox counter: one value per solve gives every solve its own stream */
+    unsigned int reserved;
+    double lb[GPMPC_MAX_D];            /* box of input j; -inf / +inf allowed, lb <= ub */
+    double ub[GPMPC_MAX_D];
+} gpmpc_mppi_params;
+
+/* out_U dev [K][n]: out_U[k][c] = clamp(mean[c] + sigma_j * sigma_decay^iteration * eps[k][c], lb_j, ub_j), j = c mod action_dim; row 0 is
+ * mean itself, bit for bit (its noise is generated and discarded).  eps is standard normal and a pure function of (seed, call_index,
+ * iteration, element e = k * n + c): Philox4x32-10 with key (seed low, seed high) and counter (p low, p high, iteration, call_index),
+ * p = e / 2, gives the words w0..w3; u1 = ((w0 >> 5) * 2^26 + (w1 >> 6) + 1/2) * 2^-53, u2 likewise from (w2, w3); Box-Muller with
+ * r = sqrt(-2 ln u1): even e takes r cos(2 pi u2), odd e r sin(2 pi u2).  Every element of out_U is written.
+ * mean dev [n].  out_x0_batch dev [K][state_dim] or NULL: x0 dev [state_dim] repeated K times, the start states of the rollout (x0 and
+ * state_dim are not looked at otherwise).  params->iterations is not used here.
+ * GPMPC_E_ARG -- before anything is launched, text in gpmpc_last_error -- on n_samples outside 1..GPMPC_MPPI_MAX_SAMPLES, a sigma, beta
+ * or sigma_decay that is not positive (NaN included), lb > ub, iteration < 0, dimensions out of range. */
+int gpmpc_mppi_sample(int H, int state_dim, int action_dim, const gpmpc_mppi_params* params_host, int iteration,
+                      const double* mean_dev, const double* x0_dev, double* out_U, double* out_x0_batch, void* stream);
+
+/* One update from an evaluated batch.  U dev [K][n]; cost dev [K]; g dev [K][H][n_rows] or NULL with n_rows = 0 (no constraints).
+ *   v_k = sum over (t, r) of max(g, 0) (0 without constraints); a sample with a NaN in cost or g is dead; feasible = alive and v_k == 0.
+ *   Candidates: the feasible samples, score s_k = cost_k -- or, when none is feasible, the alive samples, s_k = v_k.
+ *   k* = the candidate of smallest score, lowest index on ties; its key is (0, cost) when feasible, else (v, cost).
+ *   best_out [2 + n] = (key, plan) of k* where that key is lexicographically STRICTLY smaller than best_in's, else best_in.  best_in and
+ *     best_out must be different buffers (every workgroup decides from the old key); a search starts from (+inf, +inf, start plan).
+ *   T = beta * (mean of the finite scores - s_min); w_k = exp(-(s_k - s_min) / T) for finite scores, 0 otherwise; where T is not a positive
+ *     finite number, w_k = 1 on the candidates with s_k == s_min, 0 elsewhere.  mean dev [n] <- sum w_k U_k / sum w_k (written, not read).
+ *   No sample alive: mean is not touched, best_out = best_in.
+ *   out_trace dev [6] = (best violation, best cost, samples feasible, samples alive, s_min, T); (., ., 0, 0, +inf, 0) with none alive.
+ * Every sum has a fixed order (no atomics): results are bit-reproducible and do not depend on the grid. */
+int gpmpc_mppi_update(int n_samples, int H, int action_dim, int n_rows, double beta, const double* U_dev, const double* cost_dev,
+                      const double* g_dev, double* mean_dev, const double* best_in, double* best_out, double* out_trace, void* stream);
+
+/* The whole search on ONE stream without a host synchronisation: for each of params->iterations iterations gpmpc_mppi_sample,
+ * gpmpc_rollout (cons NULL) or gpmpc_rollout_constrained, each with flags 0 and as they are, gpmpc_mppi_update.  A pack with a linear
+ * nominal model needs nothing: the rollout honours it.  x0 dev [ds]; start dev [n] the plan the search starts from.
+ *   out_U dev [n]: the best plan seen; out_best dev [2] its (violation, cost): feasible when the violation is 0;
+ *   out_trace dev [iterations][6], one row per update.  The caller copies them out once, after the call.
+ * GPMPC_E_ARG as gpmpc_mppi_sample plus iterations < 1 and bad constraint rows, before anything is launched; GPMPC_E_STATE on a pack that
+ * is not built; GPMPC_E_WORKSPACE. */
+size_t gpmpc_mppi_solve_workspace_bytes(const gpmpc_pack* pack, int H, const gpmpc_mppi_params* params_host,
+                                        const gpmpc_state_constraints* cons_host);
+int gpmpc_mppi_solve(const gpmpc_pack* pack, int H, const double* x0_dev, const double* start_dev, const gpmpc_cost_params* cost_host,
+                     const gpmpc_state_constraints* cons_host, const gpmpc_mppi_params* params_host, double* out_U, double* out_best,
+                     double* out_trace, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------
  * Full-covariance form of the hot path (BASELINE config 5): the state distribution carries the whole ds x ds
  * covariance; off-diagonal terms are the exact cross-covariances Cov[f_a, f_b] (covariance_prop_torch,
  * src/tools/uncertainty_prop.py:402-465, consistent form).  The reference's rollout propagates variances only
