@@ -4,7 +4,7 @@ src/experiments/pretrain_uncertainty.py: pre-train the GP on random transitions,
 (Simulator.run, src/simulator.py:37-60) with the model growing by one observation per step.
 
     python examples/pendulum_closed_loop.py [--pretrain 200] [--steps 25] [--horizon 10] [--window N] [--nominal identity]
-                                            [--max-speed V [--prob P]] [--solver mppi [--samples K] [--iters I]]
+                                            [--max-speed V [--prob P]] [--solver mppi [--samples K] [--iters I]] [--solver lbfgs [--starts K]]
 
 --window N: fixed-size training window -- once the model holds N points every new observation replaces the oldest one (first-in
 first-out), so the cost of the data update and the memory stay constant however long the loop runs (what the solver makes of a model
@@ -20,6 +20,10 @@ SLSQP on the objective / gradient / constraints / jacobian callbacks -- one devi
 --solver mppi [--samples K] [--iters I]: the sampling planner on the device (RiskSensitiveMPC.solver = "mppi", mppi.py): K perturbed copies
 of the previous plan per iteration as one objective-only batch, no gradient; with --max-speed the bound is its feasibility rule.  Works
 with --nominal identity (the rollout honours the model).
+
+--solver lbfgs [--starts K]: the lock-step multi-start L-BFGS search with its state machine on the device (RiskSensitiveMPC.solver =
+"lbfgs", device_lbfgs.py): K starts, one batched rollout with gradient and one small kernel per tick, no host in between.  Not with
+--max-speed (the search is unconstrained).
 
 Needs an MI355X and the built library; no gym, no cyipopt (the stand-in solver is scipy's L-BFGS-B on the same
 objective / gradient callbacks, so the trajectories are NOT the reference's Ipopt trajectories)."""
@@ -46,7 +50,8 @@ def main():
     ap.add_argument("--nominal", choices=("none", "identity"), default="none", help="identity: the GPs learn x_{t+1} - x_t, the rollout adds x_t back")
     ap.add_argument("--max-speed", type=float, default=None, help="chance bound on |theta_dot| over the horizon (state constraints)")
     ap.add_argument("--prob", type=float, default=0.95, help="one-sided satisfaction probability of --max-speed")
-    ap.add_argument("--solver", choices=("default", "mppi"), default="default", help="mppi: the sampling planner on the device")
+    ap.add_argument("--solver", choices=("default", "mppi", "lbfgs"), default="default",
+                    help="mppi: the sampling planner on the device; lbfgs: the multi-start L-BFGS search on the device (--starts K)")
     ap.add_argument("--samples", type=int, default=64, help="--solver mppi: samples per iteration")
     ap.add_argument("--iters", type=int, default=30, help="--solver mppi: iterations per solve")
     args = ap.parse_args()
@@ -72,6 +77,8 @@ def main():
     if args.solver == "mppi":
         mpc.solver = "mppi"
         mpc.mppi_options.update(samples=args.samples, iterations=args.iters)
+    if args.solver == "lbfgs":
+        mpc.solver = "lbfgs"
     solves = []
     if args.max_speed is not None:
         mpc.set_state_bounds([None, -args.max_speed], [None, args.max_speed], args.prob)

@@ -23,7 +23,9 @@ from .simulator import Simulator, PendulumPlant, CartPolePlant          # noqa: 
 from .rollout import GPPack, CostParams, StateConstraints, rollout, rollout_constraints, rollout_fullcov, moment_match   # noqa: F401
 from .nominal import LinearNominalModel                                 # noqa: F401
 from .mppi import mppi_sample, mppi_update, mppi_solve                  # noqa: F401
+from .device_lbfgs import lbfgs_start, lbfgs_tick, lbfgs_solve, lbfgs_state_view, lbfgs_state_fields   # noqa: F401
 
 __all__ = ["GaussianProcessRegression", "Dynamics", "RiskSensitiveMPC", "mean_prop_torch",
            "variance_prop_torch", "covariance_prop_torch", "GPPack", "CostParams", "StateConstraints", "rollout", "rollout_constraints",
-           "rollout_fullcov", "moment_match", "LinearNominalModel", "mppi_sample", "mppi_update", "mppi_solve", "Simulator", "PendulumPlant", "CartPolePlant", "lib", "require_gpu"]
+           "rollout_fullcov", "moment_match", "LinearNominalModel", "mppi_sample", "mppi_update", "mppi_solve", "lbfgs_start", "lbfgs_tick", "lbfgs_solve", "lbfgs_state_view", "lbfgs_state_fields",
+           "Simulator", "PendulumPlant", "CartPolePlant", "lib", "require_gpu"]

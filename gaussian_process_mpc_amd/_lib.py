@@ -17,6 +17,8 @@ MAX_D = 8
 MAX_DS = 8
 MAX_CONS = 16
 MPPI_MAX_SAMPLES = 4096
+LBFGS_MAX_STARTS = 256
+LBFGS_MAX_HISTORY = 16
 WANT_GRAD = 1
 COV_BUG_COMPAT = 2
 USE_GRAPH = 4
@@ -69,6 +71,17 @@ class MppiParamsC(ctypes.Structure):
                 ("ub", ctypes.c_double * MAX_D)]
 
 
+class LbfgsParamsC(ctypes.Structure):
+    _fields_ = [("n_starts", ctypes.c_int),
+                ("history", ctypes.c_int),
+                ("gtol", ctypes.c_double),
+                ("ftol", ctypes.c_double),
+                ("c1", ctypes.c_double),
+                ("min_step", ctypes.c_double),
+                ("lb", ctypes.c_double * MAX_D),
+                ("ub", ctypes.c_double * MAX_D)]
+
+
 _vp, _i, _d, _sz, _u = ctypes.c_void_p, ctypes.c_int, ctypes.c_double, ctypes.c_size_t, ctypes.c_uint
 _dp = ctypes.POINTER(ctypes.c_double)
 
@@ -110,6 +123,11 @@ SIGNATURES = {
     "gpmpc_mppi_solve_workspace_bytes": (_sz, [_vp, _i, ctypes.POINTER(MppiParamsC), ctypes.POINTER(StateConstraintsC)]),
     "gpmpc_mppi_solve": (_i, [_vp, _i, _vp, _vp, ctypes.POINTER(CostParamsC), ctypes.POINTER(StateConstraintsC),
                               ctypes.POINTER(MppiParamsC), _vp, _vp, _vp, _vp, _sz, _vp]),
+    "gpmpc_lbfgs_state_bytes": (_sz, [_i, _i, _i, _i]),
+    "gpmpc_lbfgs_start": (_i, [_i, _i, _i, ctypes.POINTER(LbfgsParamsC), _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "gpmpc_lbfgs_tick": (_i, [_i, _i, ctypes.POINTER(LbfgsParamsC), _vp, _vp, _vp, _sz, _vp]),
+    "gpmpc_lbfgs_solve_workspace_bytes": (_sz, [_vp, _i, ctypes.POINTER(LbfgsParamsC)]),
+    "gpmpc_lbfgs_solve": (_i, [_vp, _i, _vp, _vp, ctypes.POINTER(CostParamsC), ctypes.POINTER(LbfgsParamsC), _i, _i, _vp, _sz, _vp]),
     "gpmpc_rollout_workspace_bytes": (_sz, [_vp, _i, _i, _u]),
     "gpmpc_plan_describe": (_i, [_vp, _i, _i, _u, ctypes.c_char_p, _sz]),
     "gpmpc_pack_autotune": (_i, [_vp, _i, _i, _u, ctypes.c_char_p, _sz]),
@@ -168,7 +186,7 @@ def lib():
 def check(rc, what):
     if rc != 0:
         detail = lib().gpmpc_last_error().decode() if rc == -3 else ""
-        if rc == -1 and "mppi" in what:    # the planner's refusals say which parameter
+        if rc == -1 and ("mppi" in what or "lbfgs" in what):    # the planners' refusals say which parameter
             detail = lib().gpmpc_last_error().decode()
         if rc == -5:                       # refusals on a pack with a nominal model say why (others leave the text alone)
             why = lib().gpmpc_last_error().decode()

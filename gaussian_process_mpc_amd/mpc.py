@@ -22,6 +22,9 @@ forced by moving the rollout into one fused HIP call:
   perturbed copies of the previous plan, shifted by one step, rolled out as one objective-only batch per iteration, the whole search one
   enqueue on the device (``gpmpc_mppi_solve``).  State constraints that are set become its feasibility rule.  ``solver = None`` (the
   default) is everything above, unchanged.
+* ``solver = "lbfgs"`` (extension): the lock-step multi-start search with its state machine on the device (device_lbfgs.py,
+  ``gpmpc_lbfgs_solve``) -- ``n_starts`` starts from ``make_starts``, options from ``multistart_options`` plus ``check_every``, the ticks
+  enqueued without a device-to-host copy in between.  Unconstrained, diagonal rollout only.
 """
 import numpy as np
 import torch
@@ -78,7 +81,7 @@ class RiskSensitiveMPC:
         self.last_solve_info = None
         self._solve_count = 0
         self.state_constraints = None                    # rollout.StateConstraints, or None (the reference's unconstrained problem)
-        # sampling planner (extension; mppi.py): None = the solvers above | "mppi".  sigma None: a quarter of the box width of each input,
+        # sampling planner (extension; mppi.py): None = the solvers above | "mppi" | "lbfgs" (device_lbfgs.py, options: multistart_options).  sigma None: a quarter of the box width of each input,
         # 1 along an unbounded one; the seed and the solve count (the call index) fix every sample
         self.solver = None
         self.mppi_options = {"samples": 64, "iterations": 30, "sigma": None, "decay": 0.9, "beta": 0.1, "seed": 0}
@@ -261,8 +264,15 @@ class RiskSensitiveMPC:
     # -- solve (src/mpc.py:269-330)
     def get_optimal_trajectory(self, curr_state, n_starts=None, solver=None):
         solver = getattr(self, "solver", None) if solver is None else solver
-        if solver not in (None, "mppi"):
-            raise ValueError("solver must be None or 'mppi', got %r" % (solver,))
+        if solver not in (None, "mppi", "lbfgs"):
+            raise ValueError("solver must be None, 'mppi' or 'lbfgs', got %r" % (solver,))
+        if solver == "lbfgs":
+            if getattr(self, "state_constraints", None) is not None:
+                raise NotImplementedError("solver='lbfgs' is unconstrained: state constraints under the device multi-start search (an "
+                                          "augmented Lagrangian over the batched evaluation) are not implemented")
+            if self.full_covariance:
+                raise NotImplementedError("solver='lbfgs' runs the diagonal rollout (gpmpc_lbfgs_solve): the search over the full-covariance "
+                                          "rollout is not implemented")
         if solver == "mppi":
             if (self.n_starts if n_starts is None else n_starts) > 1:
                 raise ValueError("solver='mppi' is one search over its own samples: it does not combine with n_starts > 1")
@@ -282,6 +292,10 @@ class RiskSensitiveMPC:
         sc = self.state_constraints
         if solver == "mppi":
             x = self._solve_mppi()
+            self.last_traj = x
+            return np.reshape(x, (self.horizon, self.input_dim))
+        if solver == "lbfgs":
+            x = self._solve_device_lbfgs(max(int(K), 1), lb, ub)
             self.last_traj = x
             return np.reshape(x, (self.horizon, self.input_dim))
         if sc is not None and self.full_covariance:
@@ -361,6 +375,32 @@ class RiskSensitiveMPC:
                                 "max_violation": r["violation"], "iterations": int(opt.get("iterations", 30)), "trace": r["trace"]}
         self._cache_key = None
         return r["U"].reshape(-1)
+
+    def _solve_device_lbfgs(self, K, lb, ub):
+        """The lock-step multi-start search on the device (device_lbfgs.lbfgs_solve): the starts, the seed and the solve count are those of
+        ``_solve_multistart``; the ticks run as enqueues of ``check_every`` (rollout, tick kernel) pairs without the host in between."""
+        from .device_lbfgs import lbfgs_solve
+        from .multistart import make_starts
+        opt = self.multistart_options
+        n, H, da = self.horizon * self.input_dim, self.horizon, self.input_dim
+        warm = None
+        if opt.get("warm", True) and self.solver_used is not None:        # the previous plan shifted by one step, last input repeated
+            prev = np.asarray(self.last_traj, dtype=np.float64).reshape(H, da)
+            warm = np.concatenate((prev[1:], prev[-1:]), axis=0).reshape(-1)
+        rng = np.random.default_rng([int(opt.get("seed", 0)), self._solve_count])
+        self._solve_count += 1
+        X0 = make_starts(K, n, lb, ub, rng, warm=warm, spread=float(opt.get("spread", 1.0)))
+        U, cost, info = lbfgs_solve(self.dynamics.pack(), self.curr_state, X0.reshape(K, H, da), self._cost_params(),
+                                    lb=np.asarray(self.lb, dtype=np.float64), ub=np.asarray(self.ub, dtype=np.float64),
+                                    max_ticks=int(opt.get("max_ticks", 150)), history=int(opt.get("history", 8)),
+                                    gtol=float(opt.get("gtol", 1e-4)), ftol=float(opt.get("ftol", 1e-10)),
+                                    check_every=int(opt.get("check_every", 8)))
+        info["starts"] = K
+        info["sharded_over"] = 1
+        self.last_solve_info = info
+        self.solver_used = f"device-lbfgs x{K}"
+        self._cache_key = None
+        return U.reshape(-1)
 
     def _solve_multistart(self, K, lb, ub):
         """K starts advanced together (multistart.lockstep_lbfgs): one batched rollout of K plans per solver iteration, replayed as

@@ -386,6 +386,88 @@ int gpmpc_mppi_solve(const gpmpc_pack* pack, int H, const double* x0_dev, const 
                      double* out_trace, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------
+ * Lock-step multi-start L-BFGS on the device (no reference counterpart; DESIGN.md section 3d, kernels in csrc/lbfgs.hip).  K bounded
+ * quasi-Newton searches advance together: one tick is one evaluation of the K trial points (a B = K rollout with gradient) and one step
+ * of every start's state machine (accept the trial point and form a new two-loop direction, or halve the step).  The rule is that of
+ * multistart.lockstep_lbfgs with line_points = 1 and no patience.  n = H * action_dim, column c = t * action_dim + j, m = history.
+ *
+ * The state of a search is ONE caller-owned buffer of doubles (integers and flags are stored as doubles, exactly).  With
+ * r(x) = x rounded up to a multiple of 32, the fields follow each other in this order, offsets in doubles:
+ *     summary   32         [0] starts not yet done, [1] best = argmin F (lowest index on ties; 0 when no F is finite), [2] F[best],
+ *                          [3] K, [4] n, [5] m; the rest 0
+ *     plan      r(n)       X[best]
+ *     F         r(K)       value at X (+inf: a start that is not alive)
+ *     converged r(K)       1: done by gtol, ftol or min_step
+ *     alive     r(K)       0: the first point had a non-finite value or gradient
+ *     iters     r(K)       accepted steps
+ *     ticks     r(K)       ticks this start has taken part in (the largest is the tick count of the host search)
+ *     done      r(K)
+ *     A         r(K)       step length of the current trial point
+ *     cnt       r(K)       pairs stored, 0..m
+ *     head      r(K)       ring slot of the NEWEST pair: pair j (0 = newest) is in slot (head + j) mod m
+ *     rho       r(K m)     [K][m] by slot, 1 / (s . y)
+ *     X, G, D   r(K n) x 3 point, gradient, direction, each [K][n]
+ *     U         r(K n)     [K][H][action_dim]: the trial points XT (X where done) -- the batch the next evaluation reads
+ *     S, Y      r(K m n) x 2   [K][m][n] by slot
+ * gpmpc_lbfgs_state_bytes is 8 times the sum of these sizes.  Everything before G is what a caller reads back after a search.
+ * ------------------------------------------------------------------------- */
+#define GPMPC_LBFGS_MAX_STARTS 256
+#define GPMPC_LBFGS_MAX_HISTORY 16
+typedef struct gpmpc_lbfgs_params {
+    int n_starts;                      /* K, 1..GPMPC_LBFGS_MAX_STARTS */
+    int history;                       /* m, 1..GPMPC_LBFGS_MAX_HISTORY */
+    double gtol;                       /* >= 0: done when max |g_free| <= gtol */
+    double ftol;                       /* >= 0: done when an accepted step gains (F - ft) <= ftol max(|F|, |ft|, 1) */
+    double c1;                         /* >= 0: Armijo constant, ft <= F + c1 G . (XT - X) */
+    double min_step;                   /* >= 0: done when A max|D| < min_step after a halving */
+    double lb[GPMPC_MAX_D];            /* box of input j; -inf / +inf allowed, lb <= ub */
+    double ub[GPMPC_MAX_D];
+} gpmpc_lbfgs_params;
+
+/* 0 on K, history or dimensions out of range. */
+size_t gpmpc_lbfgs_state_bytes(int n_starts, int H, int action_dim, int history);
+
+/* The start step.  X0 dev [K][n]; cost dev [K], grad dev [K][n]: the evaluation of clip(X0).
+ *   X = clip(X0); a start with a non-finite cost or gradient is not alive: F = +inf, G = 0, done.  cnt = 0, the pairs are zeroed.
+ *   free = not((x <= lb and g > 0) or (x >= ub and g < 0));  D = -g on the free components, A = min(1, 1 / |g_free|_2);
+ *   done where max |g_free| <= gtol (converged where also alive);  U = clip(X + A D), X where done.  Then the summary (below).
+ * cost and grad BOTH NULL: only U = clip(X0) is written -- the batch the start evaluation runs on -- nothing else of the state.
+ * out_x0_batch dev [K][state_dim] or NULL: x0 dev [state_dim] repeated K times (x0 and state_dim are not looked at otherwise).
+ * GPMPC_E_ARG -- before anything is launched, text in gpmpc_last_error -- on n_starts or history out of range, a gtol, ftol, c1 or
+ * min_step that is negative or NaN, lb > ub (or a NaN bound), dimensions out of range; GPMPC_E_WORKSPACE when state_bytes is too small. */
+int gpmpc_lbfgs_start(int H, int state_dim, int action_dim, const gpmpc_lbfgs_params* params_host, const double* X0_dev,
+                      const double* cost_dev, const double* grad_dev, const double* x0_dev, double* out_x0_batch,
+                      void* state, size_t state_bytes, void* stream);
+
+/* One tick from the evaluation (ft, gt) = (cost [K], grad [K][n]) of the batch U of the state.  Per start, s = U - X:
+ *   a done start is left bit for bit as it is;
+ *   ok = finite(ft) and finite(gt) and ft <= F + c1 G . s;
+ *   ok:      y = gt - G; the pair (s, y, 1 / s.y) becomes the newest one where s.y > 1e-10 sqrt((s.s)(y.y)), cnt = min(cnt + 1, m);
+ *            small = (F - ft) <= ftol max(|F|, |ft|, 1);  X, F, G = U, ft, gt;  iters += 1;
+ *            D = the two-loop recursion over the cnt stored pairs, newest first, on the gradient masked by `free`, scaled by
+ *            s.y / y.y of the newest pair where y.y > 0, masked again; where D . g_free is not < 0 or D is not finite: D = -g_free and
+ *            cnt = 0;  A = 1 with pairs stored, else min(1, 1 / |g_free|_2);  done and converged where small or max |g_free| <= gtol;
+ *   not ok:  A = A / 2; done and converged where A max|D| < min_step.  X, G and the pairs are not touched.
+ *   U = clip(X + A D), X where done.  Then the summary: best, F[best], plan = X[best], the count of starts not done.
+ * Every dot product is a per-lane sum over c = lane, lane + 64, ... in ascending order followed by a butterfly over the 64 lanes
+ * (partner lane ^ 32, ^ 16, ... ^ 1); no atomics: the result of a start is bit-reproducible and independent of K.
+ * GPMPC_E_ARG / GPMPC_E_WORKSPACE as gpmpc_lbfgs_start. */
+int gpmpc_lbfgs_tick(int H, int action_dim, const gpmpc_lbfgs_params* params_host, const double* cost_dev, const double* grad_dev,
+                     void* state, size_t state_bytes, void* stream);
+
+/* The search on ONE stream without a host synchronisation.  With first_tick == 0: U = clip(X0), gpmpc_rollout, the start step.  Then
+ * n_ticks times (gpmpc_rollout with GPMPC_WANT_GRAD over the K rows of U, as it is; the tick), then the summary.  first_tick > 0 continues
+ * from the state a previous call left in the SAME workspace (X0 is not read): between two calls the caller may read the summary and stop
+ * once no start is left.  A pack with a linear nominal model needs nothing: the rollout honours it.
+ *   x0 dev [ds]; X0 dev [K][n].  The workspace BEGINS with the state (layout above); the caller copies what it needs from there.
+ * GPMPC_E_ARG as gpmpc_lbfgs_start plus first_tick < 0 and n_ticks < 0, before anything is launched; GPMPC_E_STATE on a pack that is not
+ * built; GPMPC_E_WORKSPACE. */
+size_t gpmpc_lbfgs_solve_workspace_bytes(const gpmpc_pack* pack, int H, const gpmpc_lbfgs_params* params_host);
+int gpmpc_lbfgs_solve(const gpmpc_pack* pack, int H, const double* x0_dev, const double* X0_dev, const gpmpc_cost_params* cost_host,
+                      const gpmpc_lbfgs_params* params_host, int first_tick, int n_ticks, void* workspace, size_t workspace_bytes,
+                      void* stream);
+
+/* ---------------------------------------------------------------------------
  * Full-covariance form of the hot path (BASELINE config 5): the state distribution carries the whole ds x ds
  * covariance; off-diagonal terms are the exact cross-covariances Cov[f_a, f_b] (covariance_prop_torch,
  * src/tools/uncertainty_prop.py:402-465, consistent form).  The reference's rollout propagates variances only
