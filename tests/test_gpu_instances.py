@@ -16,6 +16,8 @@ D <= 7 and action_dim in {1, 2} through all shapes by the batch size and compare
 ports under oracle/cport (pinned to the torch oracle and to the reference's fixtures by tests/test_oracle_golden.py):
 means 1e-5, variances / covariances 1e-4 (BASELINE north star), cost 1e-6, gradient 1e-4.
 Reference: src/dynamics.py:126-191, src/tools/uncertainty_prop.py:296-465, src/mpc.py:156-255.
+Every problem here has sigma_f = 1 for all GPs, zero references and a diagonal Q (synth_problem): tests/test_gpu_offgrid.py runs the same forms
+with per-GP amplitudes in [0.6, 1.8], non-zero x_ref / u_ref and a coupled Q.
 """
 import numpy as np
 import pytest
