@@ -5,6 +5,7 @@ src/experiments/pretrain_uncertainty.py: pre-train the GP on random transitions,
 
     python examples/pendulum_closed_loop.py [--pretrain 200] [--steps 25] [--horizon 10] [--window N] [--nominal identity]
                                             [--max-speed V [--prob P]] [--solver mppi [--samples K] [--iters I]] [--solver lbfgs [--starts K]]
+                                            [--max-speed V --solver auglag [--starts K]]
 
 --window N: fixed-size training window -- once the model holds N points every new observation replaces the oldest one (first-in
 first-out), so the cost of the data update and the memory stay constant however long the loop runs (what the solver makes of a model
@@ -24,6 +25,9 @@ with --nominal identity (the rollout honours the model).
 --solver lbfgs [--starts K]: the lock-step multi-start L-BFGS search with its state machine on the device (RiskSensitiveMPC.solver =
 "lbfgs", device_lbfgs.py): K starts, one batched rollout with gradient and one small kernel per tick, no host in between.  Not with
 --max-speed (the search is unconstrained).
+
+--solver auglag [--starts K]: the constrained multi-start on the device (RiskSensitiveMPC.solver = "auglag", device_auglag.py): an augmented
+Lagrangian over the batched constrained rollout, K starts, multipliers and penalties updated on the device.  Needs --max-speed.
 
 Needs an MI355X and the built library; no gym, no cyipopt (the stand-in solver is scipy's L-BFGS-B on the same
 objective / gradient callbacks, so the trajectories are NOT the reference's Ipopt trajectories)."""
@@ -50,8 +54,9 @@ def main():
     ap.add_argument("--nominal", choices=("none", "identity"), default="none", help="identity: the GPs learn x_{t+1} - x_t, the rollout adds x_t back")
     ap.add_argument("--max-speed", type=float, default=None, help="chance bound on |theta_dot| over the horizon (state constraints)")
     ap.add_argument("--prob", type=float, default=0.95, help="one-sided satisfaction probability of --max-speed")
-    ap.add_argument("--solver", choices=("default", "mppi", "lbfgs"), default="default",
-                    help="mppi: the sampling planner on the device; lbfgs: the multi-start L-BFGS search on the device (--starts K)")
+    ap.add_argument("--solver", choices=("default", "mppi", "lbfgs", "auglag"), default="default",
+                    help="mppi: the sampling planner on the device; lbfgs: the multi-start L-BFGS search on the device (--starts K); "
+                         "auglag: the constrained multi-start on the device (--max-speed V, --starts K)")
     ap.add_argument("--samples", type=int, default=64, help="--solver mppi: samples per iteration")
     ap.add_argument("--iters", type=int, default=30, help="--solver mppi: iterations per solve")
     args = ap.parse_args()
@@ -79,6 +84,10 @@ def main():
         mpc.mppi_options.update(samples=args.samples, iterations=args.iters)
     if args.solver == "lbfgs":
         mpc.solver = "lbfgs"
+    if args.solver == "auglag":
+        if args.max_speed is None:
+            ap.error("--solver auglag needs --max-speed (without constraints use --solver lbfgs)")
+        mpc.solver = "auglag"
     solves = []
     if args.max_speed is not None:
         mpc.set_state_bounds([None, -args.max_speed], [None, args.max_speed], args.prob)

@@ -82,6 +82,18 @@ class LbfgsParamsC(ctypes.Structure):
                 ("ub", ctypes.c_double * MAX_D)]
 
 
+class AuglagParamsC(ctypes.Structure):
+    _fields_ = [("inner", LbfgsParamsC),
+                ("rho0", ctypes.c_double),
+                ("growth", ctypes.c_double),
+                ("shrink", ctypes.c_double),
+                ("rho_max", ctypes.c_double),
+                ("lam_max", ctypes.c_double),
+                ("feas_tol", ctypes.c_double),
+                ("inner_ticks", ctypes.c_int),
+                ("reserved", ctypes.c_int)]
+
+
 _vp, _i, _d, _sz, _u = ctypes.c_void_p, ctypes.c_int, ctypes.c_double, ctypes.c_size_t, ctypes.c_uint
 _dp = ctypes.POINTER(ctypes.c_double)
 
@@ -128,6 +140,12 @@ SIGNATURES = {
     "gpmpc_lbfgs_tick": (_i, [_i, _i, ctypes.POINTER(LbfgsParamsC), _vp, _vp, _vp, _sz, _vp]),
     "gpmpc_lbfgs_solve_workspace_bytes": (_sz, [_vp, _i, ctypes.POINTER(LbfgsParamsC)]),
     "gpmpc_lbfgs_solve": (_i, [_vp, _i, _vp, _vp, ctypes.POINTER(CostParamsC), ctypes.POINTER(LbfgsParamsC), _i, _i, _vp, _sz, _vp]),
+    "gpmpc_auglag_state_bytes": (_sz, [_i, _i, _i, _i]),
+    "gpmpc_auglag_merit": (_i, [_i, _i, _i, _i] + [_vp] * 9),
+    "gpmpc_auglag_outer": (_i, [_i, _i, _i, ctypes.POINTER(AuglagParamsC), _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "gpmpc_auglag_solve_workspace_bytes": (_sz, [_vp, _i, ctypes.POINTER(StateConstraintsC), ctypes.POINTER(AuglagParamsC)]),
+    "gpmpc_auglag_solve": (_i, [_vp, _i, _vp, _vp, ctypes.POINTER(CostParamsC), ctypes.POINTER(StateConstraintsC),
+                                ctypes.POINTER(AuglagParamsC), _i, _i, _vp, _sz, _vp]),
     "gpmpc_rollout_workspace_bytes": (_sz, [_vp, _i, _i, _u]),
     "gpmpc_plan_describe": (_i, [_vp, _i, _i, _u, ctypes.c_char_p, _sz]),
     "gpmpc_pack_autotune": (_i, [_vp, _i, _i, _u, ctypes.c_char_p, _sz]),
@@ -186,7 +204,7 @@ def lib():
 def check(rc, what):
     if rc != 0:
         detail = lib().gpmpc_last_error().decode() if rc == -3 else ""
-        if rc == -1 and ("mppi" in what or "lbfgs" in what):    # the planners' refusals say which parameter
+        if rc == -1 and ("mppi" in what or "lbfgs" in what or "auglag" in what):    # the planners' refusals say which parameter
             detail = lib().gpmpc_last_error().decode()
         if rc == -5:                       # refusals on a pack with a nominal model say why (others leave the text alone)
             why = lib().gpmpc_last_error().decode()

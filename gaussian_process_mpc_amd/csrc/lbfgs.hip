@@ -12,39 +12,11 @@
 // memory.  Every dot product: the lane's partial sum over its c in ascending order, then a butterfly over the wave (partner lane ^ 32, ^ 16,
 // ... ^ 1; a + b is commutative, so every lane holds the same bits).  No atomics: a start's result does not depend on K or the grid.
 // Branches are taken on wave-uniform values only (the reductions' results); a rejected trial point never reaches X, G or the pairs.
-#include "gpmpc_internal.h"
+#include "lbfgs_internal.h"
 #include <cmath>
 
 #define LBFGS_Q_LDS 2048                // the two-loop vector q lives in LDS up to this n, in the D row of the state (global) beyond
-
-// offsets in doubles (include/gpmpc.h)
-struct LbfgsLayout { long sum, plan, F, conv, alive, iters, ticks, done, A, cnt, head, rho, X, G, D, U, S, Y, total; };
-
-static long lbfgs_r(long x) { return (x + 31) & ~31L; }
-static LbfgsLayout lbfgs_layout(int K, long n, int m) {
-    LbfgsLayout L;
-    long o = 0;
-    L.sum = o; o += 32;
-    L.plan = o; o += lbfgs_r(n);
-    L.F = o; o += lbfgs_r(K);
-    L.conv = o; o += lbfgs_r(K);
-    L.alive = o; o += lbfgs_r(K);
-    L.iters = o; o += lbfgs_r(K);
-    L.ticks = o; o += lbfgs_r(K);
-    L.done = o; o += lbfgs_r(K);
-    L.A = o; o += lbfgs_r(K);
-    L.cnt = o; o += lbfgs_r(K);
-    L.head = o; o += lbfgs_r(K);
-    L.rho = o; o += lbfgs_r((long)K * m);
-    L.X = o; o += lbfgs_r(K * n);
-    L.G = o; o += lbfgs_r(K * n);
-    L.D = o; o += lbfgs_r(K * n);
-    L.U = o; o += lbfgs_r(K * n);
-    L.S = o; o += lbfgs_r(K * n * m);
-    L.Y = o; o += lbfgs_r(K * n * m);
-    L.total = o;
-    return L;
-}
+// (LbfgsLayout, the offsets of the state's fields, is in lbfgs_internal.h: auglag.hip runs its inner search through the launches below)
 
 __device__ __forceinline__ double lbfgs_wave_sum(double v) {
 #pragma unroll
@@ -298,7 +270,7 @@ __global__ __launch_bounds__(256) void k_lbfgs_finish(int K, int n, int m, Lbfgs
 // ---------------------------------------------------------------------------
 // host entries
 // ---------------------------------------------------------------------------
-static int lbfgs_refuse(const char* who, const char* what) {
+int lbfgs_refuse(const char* who, const char* what) {
     char text[200];
     snprintf(text, sizeof(text), "%s: %s", who, what);
     gpmpc_set_error_text(text);
@@ -306,7 +278,7 @@ static int lbfgs_refuse(const char* who, const char* what) {
 }
 
 // the part of the parameters that needs no dimension
-static int lbfgs_check_scalars(const gpmpc_lbfgs_params* P, const char* who) {
+int lbfgs_check_scalars(const gpmpc_lbfgs_params* P, const char* who) {
     char text[120];
     if (!P) return GPMPC_E_ARG;
     if (P->n_starts < 1 || P->n_starts > GPMPC_LBFGS_MAX_STARTS) {
@@ -324,7 +296,7 @@ static int lbfgs_check_scalars(const gpmpc_lbfgs_params* P, const char* who) {
     return GPMPC_OK;
 }
 
-static int lbfgs_check_inputs(const gpmpc_lbfgs_params* P, int da, const char* who) {
+int lbfgs_check_inputs(const gpmpc_lbfgs_params* P, int da, const char* who) {
     char text[120];
     for (int j = 0; j < da; ++j)
         if (!(P->lb[j] <= P->ub[j])) {                      // lb > ub, or a NaN bound
@@ -334,7 +306,7 @@ static int lbfgs_check_inputs(const gpmpc_lbfgs_params* P, int da, const char* w
     return GPMPC_OK;
 }
 
-static int lbfgs_dims_ok(int H, int ds, int da) {
+int lbfgs_dims_ok(int H, int ds, int da) {
     return H >= 1 && da >= 1 && da <= GPMPC_MAX_D && ds >= 0 && ds <= GPMPC_MAX_DS && (long)H * da <= 64L * 65535;      // (n as in constraints.hip)
 }
 
@@ -343,18 +315,18 @@ extern "C" size_t gpmpc_lbfgs_state_bytes(int K, int H, int da, int m) {
     return sizeof(double) * (size_t)lbfgs_layout(K, (long)H * da, m).total;
 }
 
-static int lbfgs_launch_finish(int n, const gpmpc_lbfgs_params& P, const LbfgsLayout& L, double* st, hipStream_t s) {
+int lbfgs_launch_finish(int n, const gpmpc_lbfgs_params& P, const LbfgsLayout& L, double* st, hipStream_t s) {
     hipLaunchKernelGGL(k_lbfgs_finish, dim3(1), dim3(256), 0, s, P.n_starts, n, P.history, L, st);
     GPMPC_HIP(hipGetLastError());
     return GPMPC_OK;
 }
-static int lbfgs_launch_start(int n, int ds, int da, const gpmpc_lbfgs_params& P, const LbfgsLayout& L, const double* X0, const double* cost,
+int lbfgs_launch_start(int n, int ds, int da, const gpmpc_lbfgs_params& P, const LbfgsLayout& L, const double* X0, const double* cost,
                               const double* grad, const double* x0, double* x0b, double* st, hipStream_t s) {
     hipLaunchKernelGGL(k_lbfgs_start, dim3(P.n_starts), dim3(64), 0, s, n, da, ds, P, L, X0, cost, grad, x0, x0b, st);
     GPMPC_HIP(hipGetLastError());
     return GPMPC_OK;
 }
-static int lbfgs_launch_tick(int n, int da, const gpmpc_lbfgs_params& P, const LbfgsLayout& L, const double* cost, const double* grad,
+int lbfgs_launch_tick(int n, int da, const gpmpc_lbfgs_params& P, const LbfgsLayout& L, const double* cost, const double* grad,
                              double* st, hipStream_t s) {
     hipLaunchKernelGGL(k_lbfgs_tick, dim3(P.n_starts), dim3(64), 0, s, n, da, P, L, cost, grad, st);
     GPMPC_HIP(hipGetLastError());

@@ -25,6 +25,9 @@ forced by moving the rollout into one fused HIP call:
 * ``solver = "lbfgs"`` (extension): the lock-step multi-start search with its state machine on the device (device_lbfgs.py,
   ``gpmpc_lbfgs_solve``) -- ``n_starts`` starts from ``make_starts``, options from ``multistart_options`` plus ``check_every``, the ticks
   enqueued without a device-to-host copy in between.  Unconstrained, diagonal rollout only.
+* ``solver = "auglag"`` (extension): the constrained multi-start on the device (device_auglag.py, ``gpmpc_auglag_solve``) -- an augmented
+  Lagrangian over the batched constrained rollout with the search above as its inner solver; ``n_starts`` starts, options from
+  ``auglag_options``.  Needs state constraints; diagonal rollout only.
 """
 import numpy as np
 import torch
@@ -85,6 +88,9 @@ class RiskSensitiveMPC:
         # 1 along an unbounded one; the seed and the solve count (the call index) fix every sample
         self.solver = None
         self.mppi_options = {"samples": 64, "iterations": 30, "sigma": None, "decay": 0.9, "beta": 0.1, "seed": 0}
+        # constrained multi-start on the device (extension; device_auglag.py): the keyword options of auglag_solve
+        self.auglag_options = {"outer": 8, "inner_ticks": 25, "rho0": 10.0, "growth": 10.0, "shrink": 0.25, "rho_max": 1e8, "lam_max": 1e12,
+                               "feas_tol": 1e-4, "history": 8, "gtol": 1e-6, "ftol": 1e-12, "check_outer": 1}
         self.curr_g = None
         self.curr_g_jac = None
 
@@ -264,8 +270,14 @@ class RiskSensitiveMPC:
     # -- solve (src/mpc.py:269-330)
     def get_optimal_trajectory(self, curr_state, n_starts=None, solver=None):
         solver = getattr(self, "solver", None) if solver is None else solver
-        if solver not in (None, "mppi", "lbfgs"):
-            raise ValueError("solver must be None, 'mppi' or 'lbfgs', got %r" % (solver,))
+        if solver not in (None, "mppi", "lbfgs", "auglag"):
+            raise ValueError("solver must be None, 'mppi', 'lbfgs' or 'auglag', got %r" % (solver,))
+        if solver == "auglag":
+            if getattr(self, "state_constraints", None) is None:
+                raise ValueError("solver='auglag' is the constrained multi-start: without state constraints use solver='lbfgs'")
+            if self.full_covariance:
+                raise NotImplementedError("solver='auglag' runs the diagonal rollout (gpmpc_auglag_solve): state constraints under the "
+                                          "full-covariance rollout are not implemented")
         if solver == "lbfgs":
             if getattr(self, "state_constraints", None) is not None:
                 raise NotImplementedError("solver='lbfgs' is unconstrained: state constraints under the device multi-start search (an "
@@ -292,6 +304,10 @@ class RiskSensitiveMPC:
         sc = self.state_constraints
         if solver == "mppi":
             x = self._solve_mppi()
+            self.last_traj = x
+            return np.reshape(x, (self.horizon, self.input_dim))
+        if solver == "auglag":
+            x = self._solve_device_auglag(max(int(K), 1), lb, ub)
             self.last_traj = x
             return np.reshape(x, (self.horizon, self.input_dim))
         if solver == "lbfgs":
@@ -399,6 +415,31 @@ class RiskSensitiveMPC:
         info["sharded_over"] = 1
         self.last_solve_info = info
         self.solver_used = f"device-lbfgs x{K}"
+        self._cache_key = None
+        return U.reshape(-1)
+
+    def _solve_device_auglag(self, K, lb, ub):
+        """The constrained multi-start on the device (device_auglag.auglag_solve): the starts, the seed and the solve count are those of
+        ``_solve_device_lbfgs`` (``spread``, ``seed``, ``warm`` from ``multistart_options``); everything else from ``auglag_options``."""
+        from .device_auglag import auglag_solve
+        from .multistart import make_starts
+        opt, ms = self.auglag_options, self.multistart_options
+        n, H, da = self.horizon * self.input_dim, self.horizon, self.input_dim
+        warm = None
+        if ms.get("warm", True) and self.solver_used is not None:         # the previous plan shifted by one step, last input repeated
+            prev = np.asarray(self.last_traj, dtype=np.float64).reshape(H, da)
+            warm = np.concatenate((prev[1:], prev[-1:]), axis=0).reshape(-1)
+        rng = np.random.default_rng([int(ms.get("seed", 0)), self._solve_count])
+        self._solve_count += 1
+        X0 = make_starts(K, n, lb, ub, rng, warm=warm, spread=float(ms.get("spread", 1.0)))
+        U, cost, info = auglag_solve(self.dynamics.pack(), self.curr_state, X0.reshape(K, H, da), self._cost_params(), self.state_constraints,
+                                     lb=np.asarray(self.lb, dtype=np.float64), ub=np.asarray(self.ub, dtype=np.float64), **opt)
+        best = info["best"]
+        info["starts"] = K
+        info["success"] = bool(info["feasible"][best])
+        info["max_violation"] = float(info["violation"][best])
+        self.last_solve_info = info
+        self.solver_used = f"device-auglag x{K}"
         self._cache_key = None
         return U.reshape(-1)
 

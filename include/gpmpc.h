@@ -468,6 +468,87 @@ int gpmpc_lbfgs_solve(const gpmpc_pack* pack, int H, const double* x0_dev, const
                       void* stream);
 
 /* ---------------------------------------------------------------------------
+ * Constrained multi-start on the device: an augmented Lagrangian over gpmpc_rollout_constrained, the lock-step L-BFGS above as the inner
+ * search (no reference counterpart; DESIGN.md section 3e, kernels in csrc/auglag.hip).  Per start: R = H * n_rows constraint values
+ * g_i <= 0 (row i = (t-1) n_rows + r), multipliers lam_i >= 0, one penalty rho > 0.
+ *     t_i = lam_i + rho g_i;   psi_i = t_i where t_i > 0, 0 where t_i <= 0 (a NaN passes through)
+ *     M       = f + (1 / (2 rho)) sum_i (psi_i^2 - lam_i^2)          i ascending, one chain
+ *     dM[c]   = df[c] + sum_i psi_i g_jac[i][c]                      i ascending, one FMA chain per column from 0, then added to df[c]
+ * A row with psi_i == 0 is NOT READ: whatever an inactive row of g_jac holds cannot reach dM.  A non-finite f or g_i makes M non-finite
+ * (the tick then rejects the trial point, the start step marks the start not alive); dM of such a start is unspecified.
+ *
+ * The state of a solve is ONE caller-owned buffer of doubles, fields rounded up to 32 as above (R = H * n_rows), in this order:
+ *     summary   32         [0] alive starts not yet settled, [1] best = argmin of the incumbent keys (violation, cost), lowest index on
+ *                          ties, [2] [3] that key, [4] K, [5] n, [6] R; the rest 0
+ *     plan      r(n)       the incumbent plan of `best`
+ *     rho       r(K)       penalty
+ *     V_prev    r(K)       V of the last update (+inf before the first)
+ *     v         r(K)       max_i max(g_i, 0) of the last outer step (+inf before the first)
+ *     f         r(K)       cost of the last outer step (+inf before the first)
+ *     inc_v     r(K)       incumbent key: 0 where the incumbent is feasible (v <= feas_tol), else its v; +inf: none yet
+ *     inc_f     r(K)       incumbent key: its cost
+ *     alive     r(K)       the inner search's alive flag (1 before the first search)
+ *     settled   r(K)       1: at the last update V <= feas_tol and the inner search had converged
+ *     lam       r(K R)     [K][R]
+ *     inc_x     r(K n)     [K][n] incumbent plans (clip(X0) before the first outer step)
+ * gpmpc_auglag_state_bytes is 8 times the sum of these sizes (0 on K, n_rows or dimensions out of range).
+ * ------------------------------------------------------------------------- */
+typedef struct gpmpc_auglag_params {
+    gpmpc_lbfgs_params inner;          /* the inner search: n_starts = K, history, gtol, ftol, c1, min_step, the box */
+    double rho0;                       /* > 0: the penalty every start begins with */
+    double growth;                     /* >= 1: rho <- min(rho_max, growth rho) where V > shrink V_prev */
+    double shrink;                     /* in (0, 1] */
+    double rho_max;                    /* > 0 */
+    double lam_max;                    /* >= 0: multipliers are clipped to [0, lam_max] */
+    double feas_tol;                   /* >= 0: a point is feasible when max_i g_i <= feas_tol */
+    int inner_ticks;                   /* >= 1: ticks of the inner search per outer iteration (gpmpc_auglag_solve) */
+    int reserved;
+} gpmpc_auglag_params;
+
+size_t gpmpc_auglag_state_bytes(int n_starts, int H, int action_dim, int n_rows);
+
+/* Merit value and gradient of K starts from one evaluation.  f dev [K], grad dev [K][n], g dev [K][R], g_jac dev [K][R][n] as
+ * gpmpc_rollout_constrained left them; lam dev [K][R], rho dev [K] -> out_M dev [K], out_grad dev [K][n] (every element written; must
+ * not alias an input).  One lane per column (k_al_merit); a start's result depends neither on K nor on the grid.
+ * GPMPC_E_ARG on a NULL pointer, K < 1, n_rows outside 1..GPMPC_MAX_CONS, dimensions out of range. */
+int gpmpc_auglag_merit(int n_starts, int H, int action_dim, int n_rows, const double* f_dev, const double* grad_dev, const double* g_dev,
+                       const double* gjac_dev, const double* lam_dev, const double* rho_dev, double* out_M, double* out_grad, void* stream);
+
+/* One outer step of every start (K = params->inner.n_starts) from the evaluation f dev [K], g dev [K][R] of the points X dev [K][n]:
+ *   a start with a non-finite f or g is dead for this step: NOTHING of it is written;
+ *   v = max_i max(g_i, 0);  key = (0, f) where v <= feas_tol, else (v, f);  the incumbent (inc_v, inc_f, inc_x) becomes (key, X) where
+ *     the key is lexicographically STRICTLY smaller;  the fields v and f take (v, f);
+ *   with update != 0, in this order:  V = max_i |max(g_i, -lam_i / rho)| (old lam, rho);  lam_i <- min(lam_max, max(0, lam_i + rho g_i))
+ *     (old rho);  rho <- min(rho_max, growth rho) where V > shrink V_prev;  V_prev <- V;  settled <- V <= feas_tol and conv[k] != 0.
+ *   conv dev [K] or NULL (= 0 everywhere): the `converged` field of the inner search at entry.
+ * Then the summary and the plan (k_al_finish); alive dev [K] or NULL: the inner search's `alive` field, copied into the state's first.
+ * GPMPC_E_ARG -- before anything is launched, text in gpmpc_last_error -- as gpmpc_auglag_solve's parameter checks; GPMPC_E_WORKSPACE. */
+int gpmpc_auglag_outer(int H, int action_dim, int n_rows, const gpmpc_auglag_params* params_host, int update, const double* f_dev,
+                       const double* g_dev, const double* X_dev, const double* conv_dev, const double* alive_dev, void* state,
+                       size_t state_bytes, void* stream);
+
+/* The solve on ONE stream without a host synchronisation.  With E = gpmpc_rollout_constrained(GPMPC_WANT_GRAD) over the K rows of the
+ * inner state's U:
+ *   first_outer == 0:  the state above is initialised, U = clip(X0)
+ *   for o = first_outer .. first_outer + n_outer - 1:
+ *       o > 0: U <- X;   E;   the outer step (update = o > 0);   the merit with the new lam, rho;   gpmpc_lbfgs_start's step on (M, dM)
+ *       from a copy of the points: history, step length and flags are reset;   inner_ticks x (E, merit, the tick of gpmpc_lbfgs_tick)
+ *   finally:  U <- X;  E;  the outer step without update (incumbents only);  both summaries.
+ * first_outer > 0 continues from the state a previous call left in the SAME workspace (X0 is not read): between two calls the caller may
+ * read the summary and stop once summary[0] is 0.  A pack with a linear nominal model needs nothing.
+ *   x0 dev [ds]; X0 dev [K][n].  The workspace BEGINS with the state (layout above), followed at gpmpc_auglag_state_bytes (a multiple of
+ *   256) by the inner search's state (layout of gpmpc_lbfgs_state_bytes, F = the merit at X).
+ * GPMPC_E_ARG -- before anything is launched, text in gpmpc_last_error -- on everything gpmpc_lbfgs_solve refuses in `inner`, a rho0,
+ * growth or rho_max that is not positive (NaN included), growth < 1, shrink outside (0, 1], a negative or NaN feas_tol / lam_max,
+ * inner_ticks < 1, first_outer < 0, n_outer < 0, and what gpmpc_rollout_constraints refuses in the rows; GPMPC_E_STATE on a pack that is
+ * not built; GPMPC_E_WORKSPACE. */
+size_t gpmpc_auglag_solve_workspace_bytes(const gpmpc_pack* pack, int H, const gpmpc_state_constraints* cons_host,
+                                          const gpmpc_auglag_params* params_host);
+int gpmpc_auglag_solve(const gpmpc_pack* pack, int H, const double* x0_dev, const double* X0_dev, const gpmpc_cost_params* cost_host,
+                       const gpmpc_state_constraints* cons_host, const gpmpc_auglag_params* params_host, int first_outer, int n_outer,
+                       void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------
  * Full-covariance form of the hot path (BASELINE config 5): the state distribution carries the whole ds x ds
  * covariance; off-diagonal terms are the exact cross-covariances Cov[f_a, f_b] (covariance_prop_torch,
  * src/tools/uncertainty_prop.py:402-465, consistent form).  The reference's rollout propagates variances only
