@@ -87,10 +87,10 @@ struct gpmpc_pack {
     double* sf;     // dev [ds]
     double lam_host[GPMPC_MAX_DS][GPMPC_MAX_D];
     double sf_host[GPMPC_MAX_DS];
-    void* graph_cache;         // captured rollout (GPMPC_USE_GRAPH), owned by step.hip
-    void* cb_cache;            // buffers + captured graph of gpmpc_objective_gradient (solver callbacks), owned by step.hip
+    void* graph_cache;         // captured rollout (GPMPC_USE_GRAPH), owned by graph.hip
+    void* cb_cache;            // buffers + captured graph of gpmpc_objective_gradient (solver callbacks), owned by graph.hip
     void* tuned;               // shapes measured by gpmpc_pack_autotune (gpmpc_tuned_table, plan.h), or null
-    void* lock;                // host lock of the pack's own streams / events / caches (std::recursive_mutex, step.hip::PackGuard)
+    void* lock;                // host lock of the pack's own streams / events / caches (std::recursive_mutex, runtime.hip; rollout.h::PackGuard)
     // [0: variance units only | 1: + cross units][0: 256x256 tiles | 1: 64x64 | 2: 256x64 | 3: 64x128 | 4: 256x128 | 5: 256x32 | 6: 256x16
     //  (4...6: mode 0 only)]
     gpmpc_worklist wl[2][8];   // [7] (diagonal rollout only, D >= 6): balanced runs of up to 256 columns, one workgroup generation per trajectory (pack.hip)
@@ -272,9 +272,9 @@ static inline int gpmpc_check_device(const gpmpc_pack* p) {
 enum { GPMPC_TIME_FULL = 0, GPMPC_TIME_FIRST = 1, GPMPC_TIME_FUSED = 2, GPMPC_TIME_CLASSES = 3 };
 void gpmpc_tuned_free(void* table);
 void gpmpc_tuned_clear(void* table);
-void* gpmpc_lock_create();
+void* gpmpc_lock_create();                          // runtime.hip
 void gpmpc_lock_destroy(void* lock);
-void gpmpc_graph_cache_free(void* cache);
+void gpmpc_graph_cache_free(void* cache);           // graph.hip (these four)
 void gpmpc_cb_cache_free(void* cache);
 void gpmpc_graph_cache_invalidate(void* cache);     // drop the captured graphs, keep streams / events / buffers
 void gpmpc_cb_cache_invalidate(void* cache);

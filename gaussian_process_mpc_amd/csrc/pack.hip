@@ -262,7 +262,7 @@ static int build_worklist(int Np, int it, int jt, int ds, int npairs, bool xcd_s
     hipError_t e = hipMalloc(&w->work_dev, sizeof(int) * 4 * (size_t)n);
     if (e == hipSuccess) e = hipMemcpy(w->work_dev, h, sizeof(int) * 4 * (size_t)n, hipMemcpyHostToDevice);
     w->perm_dev = nullptr;
-    if (e == hipSuccess && !w->contiguous) {                      // per-unit index of the re-ordered list (finish_step, step.hip)
+    if (e == hipSuccess && !w->contiguous) {                      // per-unit index of the re-ordered list (finish_step, roll_dev.h)
         int* perm = (int*)malloc(sizeof(int) * (size_t)n);
         int fill[GPMPC_MAX_DS + GPMPC_MAX_PAIRS + 1];
         for (int u = 0; u <= ds + npairs; ++u) fill[u] = w->ustart_host[u];

@@ -1,9 +1,10 @@
 // Planning of the diagonal rollout (plan.hip): WHAT a call launches -- a RollShape -- and WHERE its buffers lie in the workspace -- a
-// RollLayout.  step.hip enqueues from the two; moment.hip::plan_mom and the full-covariance plan (fullcov.hip) are separate.
+// RollLayout.  step.hip::gpmpc_enqueue_rollout (rollout.h) enqueues from the two; moment.hip::plan_mom and the full-covariance plan
+// (fullcov.hip) are separate.
 #pragma once
 #include "gpmpc_internal.h"
 
-// doubles per (trajectory, GP) of the head kernel's scalars `sp`, without / with a linear nominal model (the layouts: step.hip)
+// doubles per (trajectory, GP) of the head kernel's scalars `sp`, without / with a linear nominal model (the layouts: roll_dev.h)
 __host__ __device__ static inline int sps_of(int D) { return 3 + 4 * D; }
 __host__ __device__ static inline int sps_nominal(int D) { return sps_of(D) + 2 + 3 * D; }
 

@@ -1,7 +1,7 @@
 // Plan selection of the diagonal rollout: which kernels a call of a given shape launches (gpmpc_choose_shape: the tuned table and every
 // measured threshold), how its workspace is laid out (gpmpc_layout_for), into how many concurrent sub-batches it is split
 // (gpmpc_split_count, gpmpc_split_slices), and the two entry points that only plan: gpmpc_rollout_workspace_bytes, gpmpc_plan_describe.
-// No kernel lives here; step.hip enqueues what is decided here.
+// No kernel lives here; step.hip::gpmpc_enqueue_rollout enqueues what is decided here (graph.hip and autotune.hip call it).
 #include "plan.h"
 #include <cstdlib>
 
@@ -27,7 +27,7 @@ RollShape gpmpc_choose_shape(const gpmpc_pack* p, int B, int H, bool grad, bool 
     RollShape shape;
     RollShape* const r = &shape;
     // A pack with a linear nominal model is planned as under GPMPC_FUSED=0 GPMPC_FUSED_SB=0 GPMPC_PERSIST=0, whatever the overrides say:
-    // only the head / tail kernels of step.hip know the model (step_fused.h and traj_persist.h keep their own finish code), and their
+    // only the head / tail kernels (step.hip, step_tail.hip) know the model (step_fused.h and traj_persist.h keep their own finish code), and their
     // nominal variants run without row chunks (the extra sums E1, E2 are not carried through mpart).
     gpmpc_tuning tn_nom;
     if (p->nominal) { tn_nom = tn_over ? *tn_over : p->tune; tn_nom.fused = 0; tn_nom.fused_sb = 0; tn_nom.persist = 0; tn_nom.hchunks = 1; }

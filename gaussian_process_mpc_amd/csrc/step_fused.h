@@ -16,7 +16,7 @@
 //                                16 of a tile's 64 columns, 4 per wave (a workgroup is confined to one CU: more waves per
 //                                workgroup do not spread the column loop, more workgroups do); else Q = 1, 16 columns per wave
 //   nwg      <= .. < nwg + ds  : GP a: mean sums of step t over the N points                     (step.hip::prep_step)
-//   nwg + ds <= ..             : GP a: outputs and Jacobian rows of step t-1                     (step.hip::finish_step);
+//   nwg + ds <= ..             : GP a: outputs and Jacobian rows of step t-1                     (roll_dev.h::finish_step);
 //                                nothing in the next launch waits for these, only the tail kernel does
 //
 // Inside a workgroup every global load that depends on nothing computed in this launch is issued FIRST, into registers
@@ -121,7 +121,7 @@ static __device__ unsigned long long g_fused_wg[2 * 8192];         // [start | e
 // loop reads through scalar loads are computed by the workgroup itself for ITS 64 columns (wave 0, one column per lane),
 // stored to a scratch slot of its own, and read back after s_waitcnt vmcnt(0) (the stores have reached L2), an s_dcache_inv
 // (the scalar cache may hold the slot's previous contents) and the workgroup barrier.
-// layout of sp (doubles), as step.hip: 0 c | 1 mu | 2 sf2 | 3 A[D] | 3+D scale[D] | 3+2D dmu_du[D] | 3+3D dmu_ds[D]
+// layout of sp (doubles), as roll_dev.h: 0 c | 1 mu | 2 sf2 | 3 A[D] | 3+D scale[D] | 3+2D dmu_du[D] | 3+3D dmu_ds[D]
 #ifndef GPMPC_FUSED_SB_W4_FROM
 #define GPMPC_FUSED_SB_W4_FROM 6    /* input dimension from which the 256-row forms are compiled for 4 waves per SIMD (A/B knob) */
 #endif
@@ -783,7 +783,7 @@ void k_step_fused(FusedArgs A, int t) {
 
     const int a = am;
     if (role == 2) {
-        // ---- GP a: outputs and Jacobian rows of step t-1 (step.hip::finish_step) ---------------------------------------
+        // ---- GP a: outputs and Jacobian rows of step t-1 (roll_dev.h::finish_step) ---------------------------------------
         if (t == 1) {
             if (a == 0 && tid < DS) {
                 A.means[((size_t)b * (A.H + 1)) * DS + tid] = s_mu[tid];

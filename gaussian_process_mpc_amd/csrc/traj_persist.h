@@ -19,7 +19,7 @@
 //        re-deriving the row side whenever the range enters a new (GP, row block); moments are summed per lane across the row blocks of
 //        a GP and reduced once per GP (a range touches at most two GPs)
 //     4  fixed-order combine of the waves' partial sums; mean, variance and the (2 ds) x (2 ds + da) step Jacobian of every GP
-//        (step.hip::finish_step); the outputs are the next step's input moments
+//        (roll_dev.h::finish_step); the outputs are the next step's input moments
 //   The training inputs X live in LDS for the whole kernel, M (a few MB) is L2 / Infinity-Cache resident across the workgroups.
 // Same expressions as the step-per-launch forms (step.hip, step_fused.h, pair_kernel_sb.h); summation orders differ, results agree to
 // rounding.  Static ranges, partial sums written (not atomically added), fixed-order combines: bit-reproducible run to run.
