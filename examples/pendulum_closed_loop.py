@@ -5,7 +5,7 @@ src/experiments/pretrain_uncertainty.py: pre-train the GP on random transitions,
 
     python examples/pendulum_closed_loop.py [--pretrain 200] [--steps 25] [--horizon 10] [--window N] [--nominal identity]
                                             [--max-speed V [--prob P]] [--solver mppi [--samples K] [--iters I]] [--solver lbfgs [--starts K]]
-                                            [--max-speed V --solver auglag [--starts K]]
+                                            [--max-speed V --solver auglag [--starts K]] [--track AMPLITUDE,PERIOD [--terminal W]]
 
 --window N: fixed-size training window -- once the model holds N points every new observation replaces the oldest one (first-in
 first-out), so the cost of the data update and the memory stay constant however long the loop runs (what the solver makes of a model
@@ -28,6 +28,11 @@ with --nominal identity (the rollout honours the model).
 
 --solver auglag [--starts K]: the constrained multi-start on the device (RiskSensitiveMPC.solver = "auglag", device_auglag.py): an augmented
 Lagrangian over the batched constrained rollout, K starts, multipliers and penalties updated on the device.  Needs --max-speed.
+
+--track AMPLITUDE,PERIOD [--terminal W]: theta follows AMPLITUDE cos(2 pi k / PERIOD) (k in MPC steps) instead of being regulated to 0:
+the reference window of every step goes into the controller's ONE cost schedule (RiskSensitiveMPC.reference = fn), whose rows live in
+device memory -- the solver-callback graph is captured once for the whole loop (printed: gpmpc_pack_callback_captures), where calling
+set_xref every step would capture it every step.  --terminal W: terminal weight W Q on the last predicted state (mpc.Q_terminal).
 
 Needs an MI355X and the built library; no gym, no cyipopt (the stand-in solver is scipy's L-BFGS-B on the same
 objective / gradient callbacks, so the trajectories are NOT the reference's Ipopt trajectories)."""
@@ -59,10 +64,15 @@ def main():
                          "auglag: the constrained multi-start on the device (--max-speed V, --starts K)")
     ap.add_argument("--samples", type=int, default=64, help="--solver mppi: samples per iteration")
     ap.add_argument("--iters", type=int, default=30, help="--solver mppi: iterations per solve")
+    ap.add_argument("--track", default=None, metavar="AMPLITUDE,PERIOD", help="theta follows AMPLITUDE cos(2 pi k / PERIOD), k in MPC steps")
+    ap.add_argument("--terminal", type=float, default=None, help="terminal weight W Q on the last predicted state (mpc.Q_terminal)")
     args = ap.parse_args()
 
     rng = np.random.default_rng(0)
     plant = PendulumPlant()
+    if args.track is not None:                           # start on the reference: the first point of the sinusoid, at rest
+        amp, period = (float(v) for v in args.track.split(","))
+        plant = PendulumPlant(init_state=(amp, 0.0))
     nominal = LinearNominalModel.identity(2, 1) if args.nominal == "identity" else None
     mpc = RiskSensitiveMPC(args.gamma, args.horizon, 2, 1, Q=2 * np.eye(2), R=0.001 * np.eye(1), nominal_models=nominal)
     for gp in mpc.dynamics.gpr_err:                      # hypers before data, as in pretrain_uncertainty.py:100-105
@@ -88,6 +98,16 @@ def main():
         if args.max_speed is None:
             ap.error("--solver auglag needs --max-speed (without constraints use --solver lbfgs)")
         mpc.solver = "auglag"
+    track = None
+    if args.track is not None:
+        w = 2.0 * np.pi / period
+
+        def track(k):                                    # (theta, theta_dot) of steps k .. k + H; theta_dot in rad/s (dt = plant.dt)
+            t = np.arange(k, k + args.horizon + 1)
+            return np.column_stack((amp * np.cos(w * t), -amp * w / plant.dt * np.sin(w * t)))
+        mpc.reference = track
+    if args.terminal is not None:
+        mpc.Q_terminal = args.terminal * 2 * np.eye(2)
     solves = []
     if args.max_speed is not None:
         mpc.set_state_bounds([None, -args.max_speed], [None, args.max_speed], args.prob)
@@ -114,6 +134,12 @@ def main():
         print(f"|theta_dot| <= {args.max_speed} with probability {args.prob}: largest visited {sp.max():.3f}; "
               f"{sum(s['success'] for s in solves)} of {len(solves)} solves report success, "
               f"largest predicted violation {max((s['max_violation'] for s in solves), default=float('nan')):.2e}")
+    if track is not None:
+        from gaussian_process_mpc_amd import lib
+        want = np.array([track(k)[0, 0] for k in range(len(th))])
+        print(f"tracking {args.track}: RMS error of theta {np.sqrt(np.mean((th - want) ** 2)):.4f} rad over {len(th)} steps "
+              f"(second half: {np.sqrt(np.mean((th - want)[len(th) // 2:] ** 2)):.4f}); "
+              f"gpmpc_pack_callback_captures = {lib().gpmpc_pack_callback_captures(mpc.dynamics.pack().handle)}")
     print("theta:", np.array2string(th[:: max(1, len(th) // 10)], precision=2))
 
 

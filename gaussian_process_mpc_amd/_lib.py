@@ -47,7 +47,7 @@ class CostParamsC(ctypes.Structure):
                 ("u_ref", ctypes.c_double * MAX_D),
                 ("last_u", ctypes.c_double * MAX_D),
                 ("has_R_delta", ctypes.c_int),
-                ("reserved", ctypes.c_int)]
+                ("schedule_id", ctypes.c_int)]
 
 
 class StateConstraintsC(ctypes.Structure):
@@ -123,6 +123,11 @@ SIGNATURES = {
     "gpmpc_moment_match": (_i, [_vp, _i, _vp, _vp, _u] + [_vp] * 10 + [_vp, _sz, _vp]),
     "gpmpc_cost": (_i, [_i, _i, _i, _i, ctypes.POINTER(CostParamsC), _vp, _vp, _vp, _vp, _vp]),
     "gpmpc_cost_grad": (_i, [_i, _i, _i, _i, ctypes.POINTER(CostParamsC)] + [_vp] * 8),
+    "gpmpc_cost_schedule_create": (_i, [_i, _i, _i, ctypes.POINTER(_i)]),
+    "gpmpc_cost_schedule_destroy": (_i, [_i]),
+    "gpmpc_cost_schedule_set": (_i, [_i, _i, _dp, _dp, _dp, _vp]),
+    "gpmpc_cost_schedule_set_dev": (_i, [_i, _i, _vp, _vp, _vp, _vp]),
+    "gpmpc_cost_schedule_get": (_i, [_i] + [ctypes.POINTER(_i)] * 5 + [ctypes.POINTER(_vp)]),
     "gpmpc_rollout_jac_workspace_bytes": (_sz, [_vp, _i, _i]),
     "gpmpc_rollout_jac": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "gpmpc_rollout_vjp": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -206,6 +211,9 @@ def check(rc, what):
         detail = lib().gpmpc_last_error().decode() if rc == -3 else ""
         if rc == -1 and ("mppi" in what or "lbfgs" in what or "auglag" in what):    # the planners' refusals say which parameter
             detail = lib().gpmpc_last_error().decode()
+        if rc == -1 and not detail:        # refusals of a cost schedule say which and why
+            why = lib().gpmpc_last_error().decode()
+            detail = why if "cost schedule" in why else ""
         if rc == -5:                       # refusals on a pack with a nominal model say why (others leave the text alone)
             why = lib().gpmpc_last_error().decode()
             detail = why if "nominal model" in why else ""

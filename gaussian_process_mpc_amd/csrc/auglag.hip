@@ -318,6 +318,10 @@ extern "C" int gpmpc_auglag_solve(const gpmpc_pack* p, int H, const double* x0, 
     if (!lbfgs_dims_ok(H, p->ds, p->da)) return GPMPC_E_ARG;
     if (int rc = lbfgs_check_inputs(&P->inner, p->da, who)) return rc;
     if (!p->built) return GPMPC_E_STATE;
+    {   // the rollouts below would refuse a bad cost schedule too, but only after the first kernels of this solve
+        gpmpc_sched_ref sched;
+        if (int rcs = gpmpc_schedule_resolve(cost, p->ds, p->da, H, "gpmpc_auglag_solve", &sched)) return rcs;
+    }
     const gpmpc_lbfgs_params& PI = P->inner;
     const int K = PI.n_starts, n = H * p->da, R = H * cons->n_rows, ds = p->ds, da = p->da;
     const AlLayout L = al_layout(K, n, R);

@@ -83,11 +83,14 @@ __device__ static double state_cost(int ds, const gpmpc_cost_params& C, const do
 }
 
 // Input-cost terms (src/mpc.py:188-198) for one trajectory; optionally accumulates d/dU into gU [H][da].
-__device__ static double input_cost(int H, int da, const gpmpc_cost_params& C, const double* U, double* gU) {
+// uref_rows: SCHED: the [H][da] input references of a cost schedule; else not read (C.u_ref at every step)
+template <bool SCHED>
+__device__ static double input_cost(int H, int da, const gpmpc_cost_params& C, const double* uref_rows, const double* U, double* gU) {
     double c = 0.0;
     for (int j = 0; j < H; ++j) {
         double d[GPMPC_MAX_D];
-        for (int k = 0; k < da; ++k) d[k] = U[j * da + k] - C.u_ref[k];
+        const double* ur = SCHED ? uref_rows + (size_t)j * da : C.u_ref;
+        for (int k = 0; k < da; ++k) d[k] = U[j * da + k] - ur[k];
         for (int k = 0; k < da; ++k) {
             double rd = 0.0, rtd = 0.0;
             for (int l = 0; l < da; ++l) { rd += C.R[k * da + l] * d[l]; rtd += C.R[l * da + k] * d[l]; }
@@ -122,7 +125,131 @@ __global__ void k_cost_full(int B, int H, int ds, int da, gpmpc_cost_params C, c
                             nullptr, d_means ? d_covs + o * ds * ds : nullptr);
     }
     if (d_U) for (int q = 0; q < H * da; ++q) d_U[(size_t)b * H * da + q] = 0.0;
-    total += input_cost(H, da, C, U + (size_t)b * H * da, d_U ? d_U + (size_t)b * H * da : nullptr);
+    total += input_cost<false>(H, da, C, nullptr, U + (size_t)b * H * da, d_U ? d_U + (size_t)b * H * da : nullptr);
+    out[b] = total;
+}
+
+// state_cost with the state dimension known at compile time and the reference and weight of THIS step as arguments (xref [DS],
+// Qw [DS][DS]): the same operations in the same order, the elimination in registers (row swaps as predicated moves).  For the schedule
+// variant of the stand-alone cost below.
+template <int DS>
+__device__ static double state_cost_sched(const double g, const double* __restrict__ xref, const double* __restrict__ Qw,
+                                          const double* __restrict__ mu, const double* __restrict__ Sig, double* dmu, double* dsig) {
+    double e[DS], sg[DS][DS], Q[DS][DS];
+#pragma unroll
+    for (int k = 0; k < DS; ++k) {
+        e[k] = mu[k] - xref[k];
+#pragma unroll
+        for (int l = 0; l < DS; ++l) { sg[k][l] = Sig[k * DS + l]; Q[k][l] = Qw[k * DS + l]; }
+    }
+    if (g == 0.0) {
+        double c = 0.0;
+#pragma unroll
+        for (int k = 0; k < DS; ++k) {
+            double qe = 0.0, qte = 0.0;
+#pragma unroll
+            for (int l = 0; l < DS; ++l) { qe += Q[k][l] * e[l]; c += Q[k][l] * sg[l][k]; }
+            c += e[k] * qe;
+            if (dmu) {
+#pragma unroll
+                for (int l = 0; l < DS; ++l) qte += Q[l][k] * e[l];
+                dmu[k] = qe + qte;
+#pragma unroll
+                for (int l = 0; l < DS; ++l) dsig[k * DS + l] = Q[l][k];
+            }
+        }
+        return c;
+    }
+    double w[DS][2 * DS];          // augmented [I + gamma Q Sig | Q]
+#pragma unroll
+    for (int r = 0; r < DS; ++r)
+#pragma unroll
+        for (int cc = 0; cc < DS; ++cc) {
+            double s = 0.0;
+#pragma unroll
+            for (int l = 0; l < DS; ++l) s += Q[r][l] * sg[l][cc];
+            w[r][cc] = (r == cc ? 1.0 : 0.0) + g * s;
+            w[r][DS + cc] = Q[r][cc];
+        }
+    double det = 1.0;
+#pragma unroll
+    for (int k = 0; k < DS; ++k) {           // Gauss-Jordan with partial pivoting
+        int piv = k;
+        double best = fabs(w[k][k]);
+#pragma unroll
+        for (int r = k + 1; r < DS; ++r) { const double v = fabs(w[r][k]); if (v > best) { best = v; piv = r; } }
+#pragma unroll
+        for (int r = k + 1; r < DS; ++r) {
+            const bool sw = piv == r;
+#pragma unroll
+            for (int cc = 0; cc < 2 * DS; ++cc) {
+                const double a = w[k][cc], bb = w[r][cc];
+                w[k][cc] = sw ? bb : a;
+                w[r][cc] = sw ? a : bb;
+            }
+        }
+        if (piv != k) det = -det;
+        const double pv = w[k][k];
+        det *= pv;
+        const double inv = 1.0 / pv;
+#pragma unroll
+        for (int cc = 0; cc < 2 * DS; ++cc) w[k][cc] *= inv;
+#pragma unroll
+        for (int r = 0; r < DS; ++r) {
+            if (r == k) continue;
+            const double f = w[r][k];
+#pragma unroll
+            for (int cc = 0; cc < 2 * DS; ++cc) w[r][cc] = fma(-f, w[k][cc], w[r][cc]);
+        }
+    }
+    double ze[DS], zte[DS], quad = 0.0;
+#pragma unroll
+    for (int k = 0; k < DS; ++k) {
+        double s = 0.0, st = 0.0;
+#pragma unroll
+        for (int l = 0; l < DS; ++l) { s += w[k][DS + l] * e[l]; st += w[l][DS + k] * e[l]; }
+        ze[k] = s; zte[k] = st;
+        quad += e[k] * s;
+    }
+    if (dmu) {
+#pragma unroll
+        for (int k = 0; k < DS; ++k) {
+            dmu[k] = ze[k] + zte[k];
+#pragma unroll
+            for (int l = 0; l < DS; ++l) dsig[k * DS + l] = w[l][DS + k] - g * zte[k] * ze[l];
+        }
+    }
+    return log(det) / g + quad;
+}
+
+// k_cost_full with a cost schedule (include/gpmpc.h): step i measures mu_i against row i of the schedule, step H under Q_f where one is
+// set, input j against u_ref[j].  One thread per trajectory, like k_cost_full; the derivative outputs are written straight to memory.
+template <int DS>
+__global__ __launch_bounds__(64) void k_cost_sched(int B, int H, int da, gpmpc_cost_params C, const double* __restrict__ sched, int H_max,
+                                                   const double* __restrict__ means, const double* __restrict__ covs,
+                                                   const double* __restrict__ U, double* out, double* d_means, double* d_covs, double* d_U) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    double total = 0.0;
+    for (int i = 0; i <= H; ++i) {
+        const size_t o = (size_t)b * (H + 1) + i;
+        double xr[DS], Qw[DS * DS];
+        const double* __restrict__ xs = sched + (size_t)i * DS;
+#pragma unroll
+        for (int k = 0; k < DS; ++k) xr[k] = xs[k];
+#pragma unroll
+        for (int q = 0; q < DS * DS; ++q) Qw[q] = C.Q[q];
+        if (i == H) {
+            const double* __restrict__ qf = sched + gpmpc_sched_off_q(H_max, DS, da);
+            const double has = qf[DS * DS];
+#pragma unroll
+            for (int q = 0; q < DS * DS; ++q) { const double v = qf[q]; Qw[q] = has != 0.0 ? v : Qw[q]; }
+        }
+        total += state_cost_sched<DS>(C.gamma, xr, Qw, means + o * DS, covs + o * DS * DS, d_means ? d_means + o * DS : nullptr,
+                                      d_means ? d_covs + o * DS * DS : nullptr);
+    }
+    if (d_U) for (int q = 0; q < H * da; ++q) d_U[(size_t)b * H * da + q] = 0.0;
+    total += input_cost<true>(H, da, C, sched + gpmpc_sched_off_u(H_max, DS), U + (size_t)b * H * da, d_U ? d_U + (size_t)b * H * da : nullptr);
     out[b] = total;
 }
 
@@ -164,6 +291,23 @@ extern "C" int gpmpc_cost_grad(int B, int H, int ds, int da, const gpmpc_cost_pa
         return GPMPC_E_ARG;
     const int ng = (d_means != nullptr) + (d_covs != nullptr) + (d_U != nullptr);
     if (ng != 0 && ng != 3) return GPMPC_E_ARG;            // all three derivative outputs or none
+    gpmpc_sched_ref sched;
+    if (int rcs = gpmpc_schedule_resolve(cost, ds, da, H, "gpmpc_cost", &sched)) return rcs;
+    if (sched.dev) {
+#define GPMPC_COST_SCHED(DSV)                                                                                                        \
+    case DSV:                                                                                                                        \
+        hipLaunchKernelGGL(k_cost_sched<DSV>, dim3((B + 63) / 64), dim3(64), 0, (hipStream_t)stream, B, H, da, *cost, sched.dev,     \
+                           sched.H_max, means, covs, U, out_cost, d_means, d_covs, d_U);                                             \
+        break;
+        switch (ds) {
+            GPMPC_COST_SCHED(1) GPMPC_COST_SCHED(2) GPMPC_COST_SCHED(3) GPMPC_COST_SCHED(4)
+            GPMPC_COST_SCHED(5) GPMPC_COST_SCHED(6) GPMPC_COST_SCHED(7) GPMPC_COST_SCHED(8)
+            default: return GPMPC_E_ARG;
+        }
+#undef GPMPC_COST_SCHED
+        GPMPC_HIP(hipGetLastError());
+        return GPMPC_OK;
+    }
     hipLaunchKernelGGL(k_cost_full, dim3((B + 63) / 64), dim3(64), 0, (hipStream_t)stream, B, H, ds, da, *cost, means,
                        covs, U, out_cost, d_means, d_covs, d_U);
     GPMPC_HIP(hipGetLastError());

@@ -29,6 +29,7 @@ struct FcArgs {
     double* dmean_du; double* dmean_dS; double* dcov_du; double* dcov_dS;
     double* out_cost; double* out_grad;
     gpmpc_cost_params cost;
+    const double* sched; int sched_hmax;   // cost schedule of the call (include/gpmpc.h), read by k_fc_tail<DS, true> only, else null
 };
 
 // step t >= 1: record the state of step t-1 and assemble the input distribution of step t
@@ -63,15 +64,15 @@ __global__ void k_fc_assemble(FcArgs A, int t) {
 // One lane per horizon step; the state dimension is a template parameter so that the ds x 2ds elimination lives in registers (as
 // runtime-indexed LDS scratch the H + 1 terms were ~70 us of dependent LDS round trips at ds = 4).  Partial pivoting by
 // compare-and-swap of whole rows (no runtime-indexed row).
+// xref [DS], Qw [DS][DS]: the reference and the weight of THIS step (C.x_ref and C.Q, or a row of a cost schedule and its Q_f).
 template <int DS>
-__device__ static double fc_state_cost(const gpmpc_cost_params& C, const double* __restrict__ mu, const double* __restrict__ Sig,
-                                       double* dmu, double* dSig) {
-    const double g = C.gamma;
+__device__ static double fc_state_cost(const double g, const double* __restrict__ xref, const double* __restrict__ Qw,
+                                       const double* __restrict__ mu, const double* __restrict__ Sig, double* dmu, double* dSig) {
     double sg[DS * DS], e[DS], w[DS][2 * DS];
 #pragma unroll
     for (int k = 0; k < DS * DS; ++k) sg[k] = Sig[k];
 #pragma unroll
-    for (int k = 0; k < DS; ++k) e[k] = mu[k] - C.x_ref[k];
+    for (int k = 0; k < DS; ++k) e[k] = mu[k] - xref[k];
     double det = 1.0;
 #pragma unroll
     for (int r = 0; r < DS; ++r)
@@ -79,9 +80,9 @@ __device__ static double fc_state_cost(const gpmpc_cost_params& C, const double*
         for (int c = 0; c < DS; ++c) {
             double s = 0.0;
 #pragma unroll
-            for (int l = 0; l < DS; ++l) s += C.Q[r * DS + l] * sg[l * DS + c];
+            for (int l = 0; l < DS; ++l) s += Qw[r * DS + l] * sg[l * DS + c];
             w[r][c] = (r == c ? 1.0 : 0.0) + g * s;
-            w[r][DS + c] = C.Q[r * DS + c];
+            w[r][DS + c] = Qw[r * DS + c];
         }
     if (g != 0.0) {
 #pragma unroll
@@ -113,7 +114,7 @@ __device__ static double fc_state_cost(const gpmpc_cost_params& C, const double*
     for (int k = 0; k < DS; ++k) {
         double s = 0.0, st = 0.0;
 #pragma unroll
-        for (int l = 0; l < DS; ++l) { s += w[k][DS + l] * e[l]; st += w[l][DS + k] * e[l]; trq += C.Q[k * DS + l] * sg[l * DS + k]; }
+        for (int l = 0; l < DS; ++l) { s += w[k][DS + l] * e[l]; st += w[l][DS + k] * e[l]; trq += Qw[k * DS + l] * sg[l * DS + k]; }
         ze[k] = s; zte[k] = st;
         quad += e[k] * s;
     }
@@ -132,11 +133,14 @@ __device__ static double fc_state_cost(const gpmpc_cost_params& C, const double*
     return (g == 0.0 ? trq : log(det) / g) + quad;
 }
 
-__device__ static double fc_input_cost(int H, int da, const gpmpc_cost_params& C, const double* U, double* gU) {
+// uref_rows: SCHED: the [H][da] input references of a cost schedule; else not read (C.u_ref at every step)
+template <bool SCHED>
+__device__ static double fc_input_cost(int H, int da, const gpmpc_cost_params& C, const double* uref_rows, const double* U, double* gU) {
     double c = 0.0;
     for (int j = 0; j < H; ++j) {
         double d[GPMPC_MAX_D];
-        for (int k = 0; k < da; ++k) d[k] = U[j * da + k] - C.u_ref[k];
+        const double* ur = SCHED ? uref_rows + (size_t)j * da : C.u_ref;
+        for (int k = 0; k < da; ++k) d[k] = U[j * da + k] - ur[k];
         for (int k = 0; k < da; ++k) {
             double rd = 0.0, rtd = 0.0;
             for (int l = 0; l < da; ++l) { rd += C.R[k * da + l] * d[l]; rtd += C.R[l * da + k] * d[l]; }
@@ -166,7 +170,8 @@ __device__ static double fc_input_cost(int H, int da, const gpmpc_cost_params& C
 // (the D entries of u, the ds x ds state block of S; the action block of S is constant), each lane with its quarter of the
 // ds + ds^2 terms, the Jacobian values of step t-1 loaded while step t is summed: the sweep used to be 64 lanes x 30 entries x 20
 // dependent global round trips (230 us at H = 20, a tenth of a B = 1 rollout).
-template <int DS>
+// SCHED: the call has a cost schedule: lane i reads its row x_ref[i] (lane H also Q_f, has_Qf), lane 0 the rows u_ref[j]; nothing else differs.
+template <int DS, bool SCHED = false>
 __global__ __launch_bounds__(256) void k_fc_tail(FcArgs A) {
     extern __shared__ double s_dyn[];
     constexpr int ds = DS;
@@ -181,9 +186,27 @@ __global__ __launch_bounds__(256) void k_fc_tail(FcArgs A) {
     for (int r = tid; r < H * da; r += blockDim.x) { s_U[r] = A.U[(size_t)b * H * da + r]; s_gU[r] = 0.0; }
     const double* mu = A.out_means + (size_t)b * (H + 1) * ds;
     const double* Sg = A.out_covs + (size_t)b * (H + 1) * ds * ds;
-    for (int i = tid; i <= H; i += blockDim.x)
-        s_ct[i] = fc_state_cost<DS>(A.cost, mu + i * ds, Sg + i * ds * ds,
-                                    A.grad ? s_dl + (size_t)i * nz : nullptr, A.grad ? s_dl + (size_t)i * nz + ds : nullptr);
+    for (int i = tid; i <= H; i += blockDim.x) {
+        if constexpr (SCHED) {
+            double xr[DS], Qw[DS * DS];
+            const double* __restrict__ xs = A.sched + (size_t)i * DS;
+#pragma unroll
+            for (int k = 0; k < DS; ++k) xr[k] = xs[k];
+#pragma unroll
+            for (int q = 0; q < DS * DS; ++q) Qw[q] = A.cost.Q[q];
+            if (i == H) {
+                const double* __restrict__ qf = A.sched + gpmpc_sched_off_q(A.sched_hmax, DS, da);
+                const double has = qf[DS * DS];
+#pragma unroll
+                for (int q = 0; q < DS * DS; ++q) { const double v = qf[q]; Qw[q] = has != 0.0 ? v : Qw[q]; }
+            }
+            s_ct[i] = fc_state_cost<DS>(A.cost.gamma, xr, Qw, mu + i * ds, Sg + i * ds * ds,
+                                        A.grad ? s_dl + (size_t)i * nz : nullptr, A.grad ? s_dl + (size_t)i * nz + ds : nullptr);
+        } else {
+            s_ct[i] = fc_state_cost<DS>(A.cost.gamma, A.cost.x_ref, A.cost.Q, mu + i * ds, Sg + i * ds * ds,
+                                        A.grad ? s_dl + (size_t)i * nz : nullptr, A.grad ? s_dl + (size_t)i * nz + ds : nullptr);
+        }
+    }
     // the entry / term assignment of the sweep and the first prefetch (independent of the cost terms)
     const int n = tid >> 2, c4 = tid & 3, ne = D + ds * ds;
     const bool on = A.grad && n < ne;
@@ -211,7 +234,7 @@ __global__ __launch_bounds__(256) void k_fc_tail(FcArgs A) {
     if (tid == 0) {
         double total = 0.0;
         for (int i = 0; i <= H; ++i) total += s_ct[i];
-        total += fc_input_cost(H, da, A.cost, s_U, A.grad ? s_gU : nullptr);
+        total += fc_input_cost<SCHED>(H, da, A.cost, SCHED ? A.sched + gpmpc_sched_off_u(A.sched_hmax, DS) : nullptr, s_U, A.grad ? s_gU : nullptr);
         A.out_cost[b] = total;
     }
     if (!A.grad) return;
@@ -546,7 +569,16 @@ static int run_fc2(const gpmpc_pack* p, const FcPlan2& r, FcArgs& T, bool grad, 
 }
 
 static int launch_fc_tail(const FcArgs& A, int B, size_t lds, hipStream_t s) {
-    switch (A.ds) {
+    if (A.sched) switch (A.ds) {
+        case 1: hipLaunchKernelGGL((k_fc_tail<1, true>), dim3(B), dim3(256), lds, s, A); break;
+        case 2: hipLaunchKernelGGL((k_fc_tail<2, true>), dim3(B), dim3(256), lds, s, A); break;
+        case 3: hipLaunchKernelGGL((k_fc_tail<3, true>), dim3(B), dim3(256), lds, s, A); break;
+        case 4: hipLaunchKernelGGL((k_fc_tail<4, true>), dim3(B), dim3(256), lds, s, A); break;
+        case 5: hipLaunchKernelGGL((k_fc_tail<5, true>), dim3(B), dim3(256), lds, s, A); break;
+        case 6: hipLaunchKernelGGL((k_fc_tail<6, true>), dim3(B), dim3(256), lds, s, A); break;
+        default: return GPMPC_E_ARG;
+    }
+    else switch (A.ds) {
         case 1: hipLaunchKernelGGL(k_fc_tail<1>, dim3(B), dim3(256), lds, s, A); break;
         case 2: hipLaunchKernelGGL(k_fc_tail<2>, dim3(B), dim3(256), lds, s, A); break;
         case 3: hipLaunchKernelGGL(k_fc_tail<3>, dim3(B), dim3(256), lds, s, A); break;
@@ -614,6 +646,8 @@ extern "C" int gpmpc_rollout_fullcov(const gpmpc_pack* p, int B, int H, const do
     if (!p->built || (p->npairs > 0 && !p->fullcov)) return GPMPC_E_STATE;
     const bool grad = (flags & GPMPC_WANT_GRAD) != 0;
     if (grad && !out_grad) return GPMPC_E_ARG;
+    gpmpc_sched_ref sched;
+    if (int rcs = gpmpc_schedule_resolve(cost, p->ds, p->da, H, "gpmpc_rollout_fullcov", &sched)) return rcs;
     FcPlan r;
     plan_fc(p, B, H, grad, &r);
     FcPlan2 r2;
@@ -626,6 +660,7 @@ extern "C" int gpmpc_rollout_fullcov(const gpmpc_pack* p, int B, int H, const do
     memset(&A, 0, sizeof(A));
     A.B = B; A.H = H; A.ds = p->ds; A.da = p->da; A.D = p->D; A.grad = grad ? 1 : 0;
     A.x0 = x0; A.U = U;
+    A.sched = sched.dev; A.sched_hmax = sched.H_max;
     const size_t nz = ds + ds * ds;
     const size_t lds = sizeof(double) * ((size_t)GPMPC_FC_WORKERS * ds * 2 * ds + (H + 1) + (size_t)(H + 1) * nz + 2 * nz + D + D * D + 2 * (size_t)H * p->da);
     if (lds > 60 * 1024) return GPMPC_E_ARG;

@@ -255,6 +255,17 @@ void gpmpc_set_error(const char* what, hipError_t e);
 void gpmpc_set_error_text(const char* text);      // gpmpc_last_error for refusals that are not HIP errors
 // GPMPC_OK, or GPMPC_E_ARG with the reason in gpmpc_last_error: n_rows outside 1..GPMPC_MAX_CONS, a negative or NaN kappa (constraints.hip)
 int gpmpc_check_constraints(const gpmpc_state_constraints* cons, const char* who);
+// Cost schedules (schedule.hip; layout in include/gpmpc.h): offsets, in doubles, of the parts behind x_ref, from the dimensions the
+// buffer was created with.  A cost kernel gets the buffer and H_max as launch arguments (both fixed for the life of an id) and reads
+// everything else -- rows, Q_f, has_Qf -- from the buffer.
+__host__ __device__ inline size_t gpmpc_sched_off_u(int H_max, int ds) { return (size_t)(H_max + 1) * ds; }
+__host__ __device__ inline size_t gpmpc_sched_off_q(int H_max, int ds, int da) { return gpmpc_sched_off_u(H_max, ds) + (size_t)H_max * da; }
+__host__ __device__ inline size_t gpmpc_sched_off_flags(int H_max, int ds, int da) { return gpmpc_sched_off_q(H_max, ds, da) + (size_t)ds * ds; }
+struct gpmpc_sched_ref { const double* dev; int H_max; };      // dev null: the call has no schedule
+// The id of cost->schedule_id as its buffer, for a call of these dimensions and horizon.  GPMPC_OK (out->dev null where the id is 0), or
+// GPMPC_E_ARG with the reason in gpmpc_last_error -- an unknown or destroyed id, other dimensions, a horizon above the schedule's --, or
+// GPMPC_E_DEVICE.  No device work: every entry that takes cost_host calls it before its first launch or graph replay.
+int gpmpc_schedule_resolve(const gpmpc_cost_params* cost, int ds, int da, int H, const char* who, gpmpc_sched_ref* out);
 // Small host array (<= 512 bytes: hyper-parameters, index pairs) -> device memory, ordered on `s`, with the host bytes CONSUMED BEFORE
 // THE CALL RETURNS: they travel as kernel arguments.  (hipMemcpyAsync from pageable memory may read the host buffer only when the
 // stream gets there -- behind a wait on another stream that can be after the caller has freed it; seen as a wrong K matrix from a

@@ -233,6 +233,10 @@ extern "C" int gpmpc_objective_gradient(gpmpc_pack* p, int H, const double* x0_h
     if (!p || !x0_host || !U_host || !cost || !out_host || H < 1) return GPMPC_E_ARG;
     if (!p->built) return GPMPC_E_STATE;
     if (int rc_dev = gpmpc_check_device(p)) return rc_dev;
+    {   // a cost schedule is looked up on EVERY call, before a replay: the captured launches hold its buffer, not its state
+        gpmpc_sched_ref sched;
+        if (int rcs = gpmpc_schedule_resolve(cost, p->ds, p->da, H, "gpmpc_objective_gradient", &sched)) return rcs;
+    }
     PackGuard lock(p);                                      // the entry owns per-pack staging buffers and is synchronous: one caller at a time
     // per-kernel events cannot be recorded inside a captured graph: with timing on the same work is enqueued uncaptured
     const bool eager = gpmpc_timing_on();
@@ -329,6 +333,10 @@ extern "C" int gpmpc_rollout(const gpmpc_pack* p, int B, int H, const double* x0
                              double* out_cost, double* out_grad, void* workspace, size_t workspace_bytes, void* stream) {
     if (!p || !cost) return GPMPC_E_ARG;
     if (int rc_dev = gpmpc_check_device(p)) return rc_dev;
+    {   // (as in gpmpc_objective_gradient: before a replay)
+        gpmpc_sched_ref sched;
+        if (int rcs = gpmpc_schedule_resolve(cost, p->ds, p->da, H, "gpmpc_rollout", &sched)) return rcs;
+    }
     const bool graph = (flags & GPMPC_USE_GRAPH) && !gpmpc_timing_on();
     GraphModeGuard mode(graph ? 1 : 0);
     const RollCall c{p, B, H, x0, U, cost, flags, out_means, out_vars, out_cost, out_grad, workspace, workspace_bytes, (hipStream_t)stream};

@@ -394,6 +394,10 @@ extern "C" int gpmpc_lbfgs_solve(const gpmpc_pack* p, int H, const double* x0, c
     if (!lbfgs_dims_ok(H, p->ds, p->da)) return GPMPC_E_ARG;
     if (int rc = lbfgs_check_inputs(P, p->da, who)) return rc;
     if (!p->built) return GPMPC_E_STATE;
+    {   // the rollouts below would refuse a bad cost schedule too, but only after the first kernels of this solve
+        gpmpc_sched_ref sched;
+        if (int rcs = gpmpc_schedule_resolve(cost, p->ds, p->da, H, "gpmpc_lbfgs_solve", &sched)) return rcs;
+    }
     const int K = P->n_starts, n = H * p->da;
     const LbfgsLayout L = lbfgs_layout(K, n, P->history);
     const LbfgsWorkspace W = lbfgs_workspace(p, H, K, L);

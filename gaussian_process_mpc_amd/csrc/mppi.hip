@@ -325,6 +325,10 @@ extern "C" int gpmpc_mppi_solve(const gpmpc_pack* p, int H, const double* x0, co
     if (!mppi_dims_ok(H, p->ds, p->da)) return GPMPC_E_ARG;
     if (int rc = mppi_check_inputs(P, p->da, who)) return rc;
     if (!p->built) return GPMPC_E_STATE;
+    {   // the rollouts below would refuse a bad cost schedule too, but only after the first kernels of this solve
+        gpmpc_sched_ref sched;
+        if (int rcs = gpmpc_schedule_resolve(cost, p->ds, p->da, H, "gpmpc_mppi_solve", &sched)) return rcs;
+    }
     const int K = P->n_samples, n = H * p->da, m_c = cons ? cons->n_rows : 0;
     const MppiLayout L = mppi_layout(p, H, K, m_c);
     if (workspace_bytes < L.total) return GPMPC_E_WORKSPACE;

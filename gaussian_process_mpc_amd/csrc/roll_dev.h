@@ -38,6 +38,8 @@ struct RollArgs {
     double* out_cost; double* out_grad;
     gpmpc_cost_params cost;
     const double* nom;   // linear nominal model of the pack: [ds][D] weights, then [ds] biases (nominal kernel variants only), else null
+    const double* sched; // cost schedule of the call (include/gpmpc.h: x_ref rows | u_ref rows | Q_f | has_Qf, H), read by the schedule variants of
+    int sched_hmax;      // the tail kernel only, else null; the H_max its offsets are formed from
 };
 
 // layout of sp (doubles): 0 c | 1 mu | 2 sf2 | 3 A[D] | 3+D scale[D] | 3+2D dmu_du[D] | 3+3D dmu_ds[D]

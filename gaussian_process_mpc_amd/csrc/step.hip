@@ -260,6 +260,8 @@ int gpmpc_enqueue_rollout(const RollCall& c) {
     if (!p->built) return GPMPC_E_STATE;
     const bool grad = (c.flags & GPMPC_WANT_GRAD) != 0;
     if (grad && !c.out_grad) return GPMPC_E_ARG;
+    gpmpc_sched_ref sched;                                     // (entries that replay a graph or launch before they come here have resolved it already)
+    if (int rcs = gpmpc_schedule_resolve(c.cost, p->ds, p->da, H, "gpmpc_rollout", &sched)) return rcs;
     const int lowprec = (c.flags & GPMPC_FP32_ALL) ? 2 : ((c.flags & GPMPC_FP32_ACCUM) ? 1 : 0);
     if (lowprec && grad) return GPMPC_E_ARG;                   // the sweep modes are objective only
     if (lowprec && p->nominal) {
@@ -288,6 +290,7 @@ int gpmpc_enqueue_rollout(const RollCall& c) {
     A.perm = p->wl[0][r.tiling].contiguous ? nullptr : p->wl[0][r.tiling].perm_dev;
     A.out_cost = c.out_cost; A.out_grad = c.out_grad; A.cost = *c.cost;
     A.nom = p->nominal ? p->nom_dev : nullptr;
+    A.sched = sched.dev; A.sched_hmax = sched.H_max;
     if (A.nom && (r.fused || r.hchunks > 1)) {     // (a plan handed in from outside: the nominal variants exist for the two-launch form only)
         gpmpc_set_error_text("gpmpc_rollout: plan without a nominal variant on a nominal pack");
         return GPMPC_E_STATE;

@@ -7,12 +7,13 @@
 // Input-cost terms of ONE step j (src/mpc.py:188-198) with their gradient w.r.t. U_j written (not accumulated) to gUj:
 // lets the tail evaluate the H steps on H threads.  The R_delta term couples neighbours: step j owns
 // d/dU_j of both (U_j - U_{j-1})^T R_d (U_j - U_{j-1}) and (U_{j+1} - U_j)^T R_d (U_{j+1} - U_j).
-__device__ static double input_cost_step(int j, int H, int da, const gpmpc_cost_params& C, const double* __restrict__ U,
-                                         double* gUj) {
+// uref: the input reference of step j (C.u_ref, or row j of a cost schedule).
+__device__ static double input_cost_step(int j, int H, int da, const gpmpc_cost_params& C, const double* __restrict__ uref,
+                                         const double* __restrict__ U, double* gUj) {
     double d[GPMPC_MAX_D], dd[GPMPC_MAX_D], dn[GPMPC_MAX_D];
     for (int k = 0; k < da; ++k) {
         const double uj = U[j * da + k];
-        d[k] = uj - C.u_ref[k];
+        d[k] = uj - uref[k];
         dd[k] = uj - (j == 0 ? C.last_u[k] : U[(j - 1) * da + k]);
         dn[k] = (j + 1 < H) ? U[(j + 1) * da + k] - uj : 0.0;
     }
@@ -39,17 +40,17 @@ __device__ static double input_cost_step(int j, int H, int da, const gpmpc_cost_
 // The same cost term for a DIAGONAL covariance with the state dimension known at compile time: everything lives in
 // registers (the generic version, cost.hip::state_cost, walks an LDS scratch and the kernel-argument Q with run-time indices, ~20 k
 // cycles of dependent latency per call at ds = 3, which was most of the tail kernel for small batches).
+// xref [DS] and Qw [DS][DS]: the reference and the weight of THIS step (C.x_ref and C.Q, or a row of a cost schedule and its Q_f).
 template <int DS>
-__device__ static double state_cost_diag(const gpmpc_cost_params& C, const double* __restrict__ mu,
-                                         const double* __restrict__ var, double* dmu, double* dvar) {
-    const double g = C.gamma;
+__device__ static double state_cost_diag(const double g, const double* __restrict__ xref, const double* __restrict__ Qw,
+                                         const double* __restrict__ mu, const double* __restrict__ var, double* dmu, double* dvar) {
     double e[DS], Q[DS][DS], sg[DS];
 #pragma unroll
     for (int k = 0; k < DS; ++k) {
-        e[k] = mu[k] - C.x_ref[k];
+        e[k] = mu[k] - xref[k];
         sg[k] = var[k];
 #pragma unroll
-        for (int l = 0; l < DS; ++l) Q[k][l] = C.Q[k * DS + l];
+        for (int l = 0; l < DS; ++l) Q[k][l] = Qw[k * DS + l];
     }
     if (g == 0.0) {
         double c = 0.0;
@@ -127,7 +128,10 @@ __device__ static double state_cost_diag(const gpmpc_cost_params& C, const doubl
 // reverse sweep over the (2ds) x (2ds+da) step Jacobians.
 // dynamic LDS: [H+1] cost terms | [H+1][2ds] local derivatives | [H*da] grad | [H] input-cost terms | [H or 1][nz*nc] J
 #define GPMPC_TAIL_WORKERS 32
-template <bool ALLJ, int DS, bool NOM>
+// SCHED: the call has a cost schedule (A.sched).  Worker i reads ITS row x_ref[i] -- DS independent loads, issued before the LU --, the
+// worker of step H also Q_f and has_Qf; the input-cost thread of step j reads u_ref[j].  No LDS and no barrier beyond the plain variant's,
+// and the same expressions in the same order: a schedule that repeats C.x_ref / C.u_ref gives the plain variant's bits.
+template <bool ALLJ, int DS, bool NOM, bool SCHED = false>
 __global__ __launch_bounds__(256) void k_roll_tail(RollArgs A) {
     extern __shared__ double s_dyn[];
     __shared__ double s_z[GPMPC_MAX_DS * (1 + 2 * GPMPC_MAX_D)];
@@ -149,12 +153,31 @@ __global__ __launch_bounds__(256) void k_roll_tail(RollArgs A) {
         const double* Jb = A.jac + (size_t)b * H * nz * nc;
         for (int q = tid; q < H * nz * nc; q += blockDim.x) s_J[q] = Jb[q];
     }
-    for (int i = tid; i <= H && tid < GPMPC_TAIL_WORKERS; i += GPMPC_TAIL_WORKERS)
-        s_ct[i] = state_cost_diag<DS>(A.cost, mu + i * ds, var + i * ds, A.grad ? s_dl + i * nz : nullptr,
-                                      A.grad ? s_dl + i * nz + ds : nullptr);
+    for (int i = tid; i <= H && tid < GPMPC_TAIL_WORKERS; i += GPMPC_TAIL_WORKERS) {
+        if constexpr (SCHED) {
+            double xr[DS], Qw[DS * DS];
+            const double* __restrict__ xs = A.sched + (size_t)i * DS;
+#pragma unroll
+            for (int k = 0; k < DS; ++k) xr[k] = xs[k];
+#pragma unroll
+            for (int q = 0; q < DS * DS; ++q) Qw[q] = A.cost.Q[q];
+            if (i == H) {                                 // the terminal weight, where one is set (workgroup-uniform value, one worker)
+                const double* __restrict__ qf = A.sched + gpmpc_sched_off_q(A.sched_hmax, DS, da);
+                const double has = qf[DS * DS];
+#pragma unroll
+                for (int q = 0; q < DS * DS; ++q) { const double v = qf[q]; Qw[q] = has != 0.0 ? v : Qw[q]; }
+            }
+            s_ct[i] = state_cost_diag<DS>(A.cost.gamma, xr, Qw, mu + i * ds, var + i * ds, A.grad ? s_dl + i * nz : nullptr,
+                                          A.grad ? s_dl + i * nz + ds : nullptr);
+        } else {
+            s_ct[i] = state_cost_diag<DS>(A.cost.gamma, A.cost.x_ref, A.cost.Q, mu + i * ds, var + i * ds, A.grad ? s_dl + i * nz : nullptr,
+                                          A.grad ? s_dl + i * nz + ds : nullptr);
+        }
+    }
     // input-cost terms: one thread per step, on the waves that do not carry the state-cost workers
     for (int j = tid - 64; j >= 0 && j < H; j += blockDim.x - 64)
-        s_ci[j] = input_cost_step(j, H, da, A.cost, A.U + (size_t)b * H * da, A.grad ? s_gU + j * da : nullptr);
+        s_ci[j] = input_cost_step(j, H, da, A.cost, SCHED ? A.sched + gpmpc_sched_off_u(A.sched_hmax, DS) + (size_t)j * da : A.cost.u_ref,
+                                  A.U + (size_t)b * H * da, A.grad ? s_gU + j * da : nullptr);
     // ALLJ: the Jacobians of ALL steps fit in LDS: fetch them in one round of independent loads while the cost terms are
     // finished, then wave 0 runs the whole reverse sweep alone -- no workgroup barriers, no exposed global-load latency
     // per step (small batches: 29 -> 16 us at H = 20).  Otherwise: one step per iteration, the Jacobian of the next
@@ -223,7 +246,13 @@ int gpmpc_launch_roll_tail(const RollArgs& A, bool grad, hipStream_t s) {
     const size_t lds = allj ? lds_all : lds_one;
     const int rc = gpmpc_dispatch_dim<1>(A.ds, [&](auto d) {
         constexpr int DS = decltype(d)::value;
-        if (A.nom) {
+        if (A.sched) {                                       // the schedule variants (the pack's ds is the schedule's: resolved by the enqueue)
+            if (A.nom) {
+                if (allj) hipLaunchKernelGGL((k_roll_tail<true, DS, true, true>), dim3(B), dim3(256), lds, s, A);
+                else hipLaunchKernelGGL((k_roll_tail<false, DS, true, true>), dim3(B), dim3(256), lds, s, A);
+            } else if (allj) hipLaunchKernelGGL((k_roll_tail<true, DS, false, true>), dim3(B), dim3(256), lds, s, A);
+            else hipLaunchKernelGGL((k_roll_tail<false, DS, false, true>), dim3(B), dim3(256), lds, s, A);
+        } else if (A.nom) {
             if (allj) hipLaunchKernelGGL((k_roll_tail<true, DS, true>), dim3(B), dim3(256), lds, s, A);
             else hipLaunchKernelGGL((k_roll_tail<false, DS, true>), dim3(B), dim3(256), lds, s, A);
         } else if (allj) hipLaunchKernelGGL((k_roll_tail<true, DS, false>), dim3(B), dim3(256), lds, s, A);

@@ -28,13 +28,17 @@ forced by moving the rollout into one fused HIP call:
 * ``solver = "auglag"`` (extension): the constrained multi-start on the device (device_auglag.py, ``gpmpc_auglag_solve``) -- an augmented
   Lagrangian over the batched constrained rollout with the search above as its inner solver; ``n_starts`` starts, options from
   ``auglag_options``.  Needs state constraints; diagonal rollout only.
+* ``set_reference_trajectory`` / ``mpc.reference = fn`` / ``mpc.Q_terminal`` (extension; the reference measures every step against one
+  ``x_ref`` under one ``Q``): references that change along the horizon and a terminal weight, through ONE ``rollout.CostSchedule`` owned
+  by the controller.  Its rows live in device memory, so the solver-callback graph of the closed loop is captured once however often
+  the window moves.  Every callback, batch evaluation, ``cost_torch`` and solver reads it; with none of the three set nothing changes.
 """
 import numpy as np
 import torch
 
 from .autograd import CostFunction, wants_grad
 from .dynamics import Dynamics
-from .rollout import CostParams, StateConstraints, cost_full, rollout, rollout_fullcov
+from .rollout import CostParams, CostSchedule, StateConstraints, cost_full, rollout, rollout_fullcov
 
 try:                                    # the solver binding is optional (not installed in the build image)
     import cyipopt                      # noqa: F401
@@ -93,6 +97,58 @@ class RiskSensitiveMPC:
                                "feas_tol": 1e-4, "history": 8, "gtol": 1e-6, "ftol": 1e-12, "check_outer": 1}
         self.curr_g = None
         self.curr_g_jac = None
+        # time-varying references and terminal weight (extension; rollout.CostSchedule).  Q_terminal: (ds, ds) or None, with or without a
+        # reference trajectory (without one the schedule repeats x_ref / u_ref).  reference: None, or fn(k) -> X_ref (H+1, ds) or
+        # (X_ref, U_ref), asked for the window of step k = step_index before every solve; step_index counts get_optimal_trajectory calls.
+        self.Q_terminal = None
+        self.reference = None
+        self.step_index = 0
+        self._ref_traj = None
+        self._sched = None                               # the CostSchedule, created by the first solve that needs one
+        self._sched_sig = None                           # what it holds: (versions, sources), see _active_schedule
+
+    # -- reference trajectory and terminal weight (extension)
+    def set_reference_trajectory(self, X_ref, U_ref=None, Q_terminal=None):
+        """References of the next solves: X_ref (H+1, ds) for the predicted states 0..H, U_ref (H, da) or None = zeros.  Q_terminal, if
+        given, also sets ``mpc.Q_terminal``.  ``x_ref`` / ``u_ref`` are ignored while a trajectory is set."""
+        X = np.array(X_ref, dtype=np.float64).reshape(self.horizon + 1, self.state_dim)
+        U = None if U_ref is None else np.array(U_ref, dtype=np.float64).reshape(self.horizon, self.input_dim)
+        if not (np.all(np.isfinite(X)) and (U is None or np.all(np.isfinite(U)))):
+            raise ValueError("the reference trajectory must be finite")
+        self._ref_traj = (X, U)
+        if Q_terminal is not None:
+            self.Q_terminal = Q_terminal
+        self._cache_key = None
+
+    def clear_reference_trajectory(self):
+        """Back to ``x_ref`` / ``u_ref`` (``Q_terminal`` and ``reference`` are attributes: set them to None to drop them)."""
+        self._ref_traj = None
+        self._cache_key = None
+
+    def _active_schedule(self):
+        """The controller's ONE cost schedule with the current references written into it, or None when neither a reference trajectory
+        nor a terminal weight is set.  Rewritten (in stream order, same device buffer) only when what it holds has changed: sources are
+        compared by identity and tensor version, as ``_cost_params`` compares Q and R -- assign a new ``Q_terminal`` rather than writing
+        into the array it holds.  (Attributes are read with a default: the class is also built without its constructor.)"""
+        traj, Qt = getattr(self, "_ref_traj", None), getattr(self, "Q_terminal", None)
+        if traj is None and Qt is None:
+            return None
+        H, ds, da = self.horizon, self.state_dim, self.input_dim
+        srcs = (traj, Qt) if traj is not None else (self.x_ref, self.u_ref, Qt)
+        vers = tuple(t._version if isinstance(t, torch.Tensor) else None for t in srcs)
+        sched, old = getattr(self, "_sched", None), getattr(self, "_sched_sig", None)
+        if sched is None:
+            sched = self._sched = CostSchedule(H, ds, da, device=self.device)
+        if old is None or old[0] != vers or len(old[1]) != len(srcs) or any(x is not y for x, y in zip(old[1], srcs)):
+            to_np = lambda t: t.detach().cpu().numpy().astype(np.float64) if isinstance(t, torch.Tensor) else np.asarray(t, dtype=np.float64)  # noqa: E731
+            if traj is not None:
+                X, U = traj
+            else:
+                X, U = np.tile(to_np(self.x_ref).reshape(1, ds), (H + 1, 1)), np.tile(to_np(self.u_ref).reshape(1, da), (H, 1))
+            sched.set(X, U, None if Qt is None else np.ascontiguousarray(to_np(Qt)).reshape(ds, ds))
+            self._sched_sig = (vers, srcs)                   # (the sources are kept alive: `is` cannot alias later objects)
+            self._cache_key = None
+        return sched
 
     # -- setters (src/mpc.py:72-116)
     def set_ub(self, ub):
@@ -140,14 +196,15 @@ class RiskSensitiveMPC:
         last_u = np.asarray(self.last_traj, dtype=np.float64)[0:self.input_dim] if self.R_delta is not None else None
         # rebuilt only when one of its inputs changes: the solver calls this once per callback and the device-to-host
         # copies of x_ref / u_ref alone cost as much as a small rollout
-        objs = (self.Q, self.R, self.R_delta, xr, ur)             # kept alive by the cache: `is` cannot alias new objects
+        sched = self._active_schedule()                           # (its CONTENTS are not part of the key: they live on the device)
+        objs = (self.Q, self.R, self.R_delta, xr, ur, sched)      # kept alive by the cache: `is` cannot alias new objects
         vers = tuple(t._version if isinstance(t, torch.Tensor) else None for t in objs)
         key = (self.gamma, vers, None if last_u is None else last_u.tobytes())
         old = getattr(self, "_cp_state", None)
         if old is None or old[0] != key or any(a is not b for a, b in zip(old[1], objs)):
             to_np = lambda t: t.detach().cpu().numpy().astype(np.float64) if isinstance(t, torch.Tensor) else np.asarray(t, dtype=np.float64)  # noqa: E731
             self._cp = CostParams(self.gamma, self.Q, self.R, R_delta=self.R_delta, x_ref=to_np(xr), u_ref=to_np(ur),
-                                  last_u=last_u)
+                                  last_u=last_u, schedule=sched)
             self._cp_state = (key, objs)
         return self._cp
 
@@ -171,7 +228,8 @@ class RiskSensitiveMPC:
         """Risk-sensitive cost incl. the input-rate term for FULL covariance matrices
         (src/mpc.py:156-200) on the device; x / sig may be lists of tensors or stacked tensors.  Differentiable
         like the reference's: if any of x, sig, u carries a graph the result does too (autograd.CostFunction), so
-        ``cost_torch(...).backward()`` fills ``u.grad`` as src/mpc.py:251 does."""
+        ``cost_torch(...).backward()`` fills ``u.grad`` as src/mpc.py:251 does.  With a reference trajectory or a terminal weight set the
+        controller's schedule applies (x has horizon + 1 rows at most) and ``x_ref`` / ``u_ref`` are ignored."""
         xs = torch.stack([t.reshape(-1) for t in x]) if isinstance(x, (list, tuple)) else torch.as_tensor(x)
         ss = torch.stack(list(sig)) if isinstance(sig, (list, tuple)) else torch.as_tensor(sig)
         ss = ss.reshape(xs.shape[0], self.state_dim, self.state_dim)
@@ -291,6 +349,11 @@ class RiskSensitiveMPC:
             if self.full_covariance:
                 raise NotImplementedError("solver='mppi' runs the diagonal rollout (gpmpc_mppi_solve): MPPI over the full-covariance "
                                           "rollout is not implemented")
+        k = getattr(self, "step_index", 0)
+        self.step_index = k + 1
+        if getattr(self, "reference", None) is not None:                   # the sliding window of this step, written into the one schedule before the solve
+            r = self.reference(k)
+            self.set_reference_trajectory(*(r if isinstance(r, tuple) else (r,)))
         if self.train_empty:
             if self.dynamics.gpr_err[0].num_train > 0:
                 self.train_empty = False

@@ -19,10 +19,73 @@ def _dev(a, device):
     return torch.as_tensor(np.ascontiguousarray(np.asarray(a, dtype=np.float64)), device=device)
 
 
-class CostParams:
-    """Parameters of RiskSensitiveMPC.cost_torch (reference src/mpc.py:156-200)."""
+class CostSchedule:
+    """Time-varying references and a terminal weight for every cost of the library (C ABI ``gpmpc_cost_schedule_*``; no reference
+    counterpart: src/mpc.py holds one x_ref, one u_ref, one Q).  ONE device buffer for horizons up to ``H_max``, owned by the library and
+    addressed by ``id``; its contents are read by the cost kernels from device memory, so a :meth:`set` between two graph replays takes
+    effect without a new capture.  Hand it to ``CostParams(..., schedule=cs)``; ``x_ref`` / ``u_ref`` of those parameters are then ignored."""
 
-    def __init__(self, gamma, Q, R, R_delta=None, x_ref=None, u_ref=None, last_u=None):
+    def __init__(self, H_max, ds, da, device=None):
+        self.device = device if device is not None else require_gpu()
+        self.H_max, self.ds, self.da = int(H_max), int(ds), int(da)
+        self.H = 0
+        self.has_Q_terminal = False
+        self.id = 0
+        out = ctypes.c_int(0)
+        with torch.cuda.device(self.device):
+            check(lib().gpmpc_cost_schedule_create(self.H_max, self.ds, self.da, ctypes.byref(out)), "gpmpc_cost_schedule_create")
+        self.id = out.value
+
+    def set(self, X_ref, U_ref=None, Q_terminal=None):
+        """X_ref (H+1, ds), U_ref (H, da) or None = zeros, Q_terminal (ds, ds) or None = no terminal weight; H <= H_max.  Host arrays
+        (checked for finiteness, consumed before the call returns), or CUDA float64 tensors on the schedule's device (copied in stream
+        order without the host; all of them tensors then)."""
+        dev_form = isinstance(X_ref, torch.Tensor) and X_ref.is_cuda
+        shape = tuple(X_ref.shape)
+        if len(shape) != 2 or shape[1] != self.ds or shape[0] < 2:
+            raise ValueError("X_ref must be (H + 1, %d), got %s" % (self.ds, shape))
+        H = shape[0] - 1
+        if U_ref is not None and tuple(np.shape(U_ref)) != (H, self.da):
+            raise ValueError("U_ref must be (%d, %d), got %s" % (H, self.da, tuple(np.shape(U_ref))))
+        if Q_terminal is not None and tuple(np.shape(Q_terminal)) != (self.ds, self.ds):
+            raise ValueError("Q_terminal must be (%d, %d), got %s" % (self.ds, self.ds, tuple(np.shape(Q_terminal))))
+        with torch.cuda.device(self.device):
+            if dev_form:
+                t = [None if a is None else _dev(a, self.device) for a in (X_ref, U_ref, Q_terminal)]
+                check(lib().gpmpc_cost_schedule_set_dev(self.id, H, ptr(t[0]), ptr(t[1]), ptr(t[2]), stream_ptr()), "gpmpc_cost_schedule_set_dev")
+            else:
+                h = [None if a is None else host_doubles(a) for a in (X_ref, U_ref, Q_terminal)]
+                check(lib().gpmpc_cost_schedule_set(self.id, H, *[None if a is None else a[1] for a in h], stream_ptr()),
+                      "gpmpc_cost_schedule_set")
+        self.H, self.has_Q_terminal = H, Q_terminal is not None
+        return self
+
+    def get(self):
+        """What the library holds: dict with H_max, ds, da, H, has_Q_terminal and the device pointer ``ptr`` (constant for the life of the id)."""
+        v = [ctypes.c_int() for _ in range(5)]
+        p = ctypes.c_void_p()
+        check(lib().gpmpc_cost_schedule_get(self.id, *[ctypes.byref(x) for x in v], ctypes.byref(p)), "gpmpc_cost_schedule_get")
+        return dict(H_max=v[0].value, ds=v[1].value, da=v[2].value, H=v[3].value, has_Q_terminal=bool(v[4].value), ptr=p.value)
+
+    def close(self):
+        """Destroy the schedule (the library waits for the device first).  Cost parameters that still name the id are refused afterwards."""
+        if self.id:
+            i, self.id = self.id, 0
+            with torch.cuda.device(self.device):
+                check(lib().gpmpc_cost_schedule_destroy(i), "gpmpc_cost_schedule_destroy")
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class CostParams:
+    """Parameters of RiskSensitiveMPC.cost_torch (reference src/mpc.py:156-200).  schedule: a :class:`CostSchedule` whose rows replace
+    ``x_ref`` / ``u_ref`` and whose terminal weight, where set, replaces ``Q`` at the last step."""
+
+    def __init__(self, gamma, Q, R, R_delta=None, x_ref=None, u_ref=None, last_u=None, schedule=None):
         Q = np.atleast_2d(np.asarray(Q, dtype=np.float64))
         R = np.atleast_2d(np.asarray(R, dtype=np.float64))
         self.ds, self.da = Q.shape[0], R.shape[0]
@@ -44,6 +107,11 @@ class CostParams:
         ur = np.zeros(self.da) if u_ref is None else np.asarray(u_ref, dtype=np.float64).reshape(-1)
         c.x_ref[:self.ds] = xr.tolist()
         c.u_ref[:self.da] = ur.tolist()
+        if schedule is not None:
+            if (schedule.ds, schedule.da) != (self.ds, self.da):
+                raise ValueError("the cost schedule has dimensions (%d, %d), the cost (%d, %d)" % (schedule.ds, schedule.da, self.ds, self.da))
+            c.schedule_id = int(schedule.id)
+        self.schedule = schedule             # (kept alive with the parameters that name it)
         self.c = c
 
 

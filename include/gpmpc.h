@@ -207,8 +207,41 @@ typedef struct gpmpc_cost_params {
     double u_ref[GPMPC_MAX_D];
     double last_u[GPMPC_MAX_D];                       /* last_traj[0:da], src/mpc.py:192 */
     int has_R_delta;
-    int reserved;
+    int schedule_id;                                  /* 0: none.  Else the id of a cost schedule (below): x_ref and u_ref above are then IGNORED */
 } gpmpc_cost_params;
+
+/* ---------------------------------------------------------------------------
+ * Cost schedule: time-varying references and a terminal weight (no reference counterpart: RiskSensitiveMPC holds one x_ref, one u_ref
+ * and one Q, src/mpc.py:20-60).  A schedule is ONE device buffer owned by the library, addressed by a positive id that travels in
+ * gpmpc_cost_params::schedule_id.  Its device layout, in doubles, fixed at creation (the device pointer of an id never changes):
+ *     x_ref [H_max + 1][ds] | u_ref [H_max][da] | Q_f [ds][ds] | has_Qf, H     (the two flags stored as doubles, exactly: every load stays 8-byte aligned)
+ * Meaning in a cost of horizon H_call <= H (the H of the last set; a shorter call uses the leading rows):
+ *     state term of step i (0 <= i <= H_call):  e = mu_i - x_ref[i], weight Q_f where i == H_call and has_Qf, else Q of the struct -- in the
+ *         quadratic form, the log-determinant and the gamma == 0 trace alike;
+ *     input term of step j (0 <= j < H_call):   d = U_j - u_ref[j];   the R_delta term and last_u are as without a schedule.
+ * The contents are read from device memory by the cost kernels, never passed as kernel arguments: a captured launch sequence
+ * (GPMPC_USE_GRAPH, gpmpc_objective_gradient) keys on the id -- it is part of the struct -- and NOT on the contents, so a set between two
+ * replays takes effect without a new capture.  Every entry point that takes cost_host resolves the id on the host first and returns
+ * GPMPC_E_ARG, with a text in gpmpc_last_error, before any launch or graph replay, on an unknown or destroyed id, a ds / da that is not the
+ * call's, or a call horizon above the schedule's H (GPMPC_E_DEVICE: the schedule lives on another device).
+ * The table of ids is guarded by a host lock: create / destroy / set / get and calls that use schedules may run on concurrent host
+ * threads.  A set is ordered on ITS stream: work on another stream that reads the same id while it is being rewritten is the caller's race,
+ * as with U.  Ids count up from 1 and are not reused within a process.
+ *   create   H_max >= 1, ds in 1..GPMPC_MAX_DS, da in 0..GPMPC_MAX_D; the buffer starts as zeros with H = 0 (unusable until the first set).
+ *   destroy  waits for the device, then frees the buffer (GPMPC_E_DEVICE, nothing freed, where the current device is not the schedule's).
+ *   set      x_ref_host [H + 1][ds]; u_ref_host [H][da] or NULL = zeros; Q_terminal_host [ds][ds] or NULL = no terminal weight (general: it
+ *            need be neither symmetric nor diagonal).  H in 1..H_max, every value finite: GPMPC_E_ARG with a text otherwise, before anything
+ *            is enqueued.  The host arrays are consumed before the call returns: they travel as kernel arguments in pieces of 512 bytes (the
+ *            mechanism of gpmpc_store_host and gpmpc_pack_set_nominal, internally gpmpc_upload_small).  A refused or failed set leaves the
+ *            schedule's H and terminal-weight flag as they were.
+ *   set_dev  the same from device arrays, copied in stream order without the host (a closed loop that rolls its window on the device); the
+ *            values cannot be checked for finiteness.
+ *   get      any of the outputs may be NULL; *dev_out is the buffer (layout above). */
+int gpmpc_cost_schedule_create(int H_max, int state_dim, int action_dim, int* id_out);
+int gpmpc_cost_schedule_destroy(int id);
+int gpmpc_cost_schedule_set(int id, int H, const double* x_ref_host, const double* u_ref_host, const double* Q_terminal_host, void* stream);
+int gpmpc_cost_schedule_set_dev(int id, int H, const double* x_ref_dev, const double* u_ref_dev, const double* Q_terminal_dev, void* stream);
+int gpmpc_cost_schedule_get(int id, int* H_max, int* state_dim, int* action_dim, int* H, int* has_Q_terminal, const double** dev_out);
 
 /* Cost of B given trajectories with FULL covariance matrices (parity with cost_torch on
  * arbitrary, even non-symmetric, Sigma): means dev [B][H+1][ds], covs dev [B][H+1][ds][ds],

@@ -5,7 +5,9 @@ each rollout replayed as one hipGraph and synchronised (the latency a solver cal
 variant are compared with those of the first (bitwise with --bitwise, else rtol 1e-6).
 
     python tools/lib_ab.py --variants base=gaussian_process_mpc_amd/csrc/libgpmpc_hip_r03.so new=gaussian_process_mpc_amd/csrc/libgpmpc_hip.so \
-        [--variants 'x=lib.so,GPMPC_TILING=5'] [--eager] [--queued] [--shared-lambda] --shapes N:ds:da:H:B,...
+        [--variants 'x=lib.so,GPMPC_TILING=5'] [--eager] [--queued] [--callback] [--shared-lambda] --shapes N:ds:da:H:B,...
+
+--callback: B = 1 shapes go through the host-in / host-out solver callback (gpmpc_objective_gradient) instead of gpmpc_rollout.
 """
 import argparse, json, os, subprocess, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -36,6 +38,12 @@ def child(a):
         cost = CostParams(-1.0, pb["Q"], pb["R"])
         x0, U = torch.as_tensor(pb["x0"][:B], device=dev), torch.as_tensor(pb["U"][:B, :H], device=dev)
         run = lambda: rollout(pack, x0, U, cost, want_traj=False, graph=not a.eager)     # noqa: E731
+        if a.callback and B == 1:
+            x0h, Uh = pb["x0"][0].copy(), pb["U"][0, :H].copy()
+
+            def run():
+                cg = pack.objective_gradient(x0h, Uh, cost)
+                return {"cost": torch.as_tensor(cg[:1]), "grad": torch.as_tensor(cg[1:])}
         r = run(); torch.cuda.synchronize()
         grad = r["grad"].cpu().numpy().copy(); cst = r["cost"].cpu().numpy().copy()
         for _ in range(5): run()
@@ -57,7 +65,7 @@ def child(a):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--variants", nargs="+", action="append", default=[])
-    ap.add_argument("--eager", action="store_true"); ap.add_argument("--queued", action="store_true")
+    ap.add_argument("--eager", action="store_true"); ap.add_argument("--queued", action="store_true"); ap.add_argument("--callback", action="store_true")
     ap.add_argument("--shared-lambda", action="store_true"); ap.add_argument("--bitwise", action="store_true")
     ap.add_argument("--rounds", type=int, default=2)
     ap.add_argument("--child-out", default="")
@@ -80,7 +88,7 @@ def main():
                 env[kv.split("=")[0]] = kv.split("=")[1]
             tmp = f"/tmp/lib_ab_{os.getpid()}_{name}.json"
             cmd = [sys.executable, os.path.abspath(__file__), "--child-out", tmp] + (["--eager"] if a.eager else []) + \
-                  (["--queued"] if a.queued else []) + (["--shared-lambda"] if a.shared_lambda else []) + ["--shapes", ",".join(a.shapes)]
+                  (["--queued"] if a.queued else []) + (["--callback"] if a.callback else []) + (["--shared-lambda"] if a.shared_lambda else []) + ["--shapes", ",".join(a.shapes)]
             p = subprocess.run(cmd, env=env, capture_output=True, text=True)
             if p.returncode != 0:
                 print(f"variant {name} failed:\n{p.stderr[-2000:]}", flush=True)
