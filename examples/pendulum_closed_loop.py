@@ -6,6 +6,7 @@ src/experiments/pretrain_uncertainty.py: pre-train the GP on random transitions,
     python examples/pendulum_closed_loop.py [--pretrain 200] [--steps 25] [--horizon 10] [--window N] [--nominal identity]
                                             [--max-speed V [--prob P]] [--solver mppi [--samples K] [--iters I]] [--solver lbfgs [--starts K]]
                                             [--max-speed V --solver auglag [--starts K]] [--track AMPLITUDE,PERIOD [--terminal W]]
+                                            [--obs-var V [--process-var sigma_n]]
 
 --window N: fixed-size training window -- once the model holds N points every new observation replaces the oldest one (first-in
 first-out), so the cost of the data update and the memory stay constant however long the loop runs (what the solver makes of a model
@@ -34,6 +35,11 @@ the reference window of every step goes into the controller's ONE cost schedule 
 device memory -- the solver-callback graph is captured once for the whole loop (printed: gpmpc_pack_callback_captures), where calling
 set_xref every step would capture it every step.  --terminal W: terminal weight W Q on the last predicted state (mpc.Q_terminal).
 
+--obs-var V [--process-var sigma_n]: the controller sees the state through Gaussian measurement noise of variance V (per component) and is
+told so: V I is the covariance of the start state of every prediction (RiskSensitiveMPC.set_initial_covariance -- where an estimator runs, its
+covariance goes there, before every solve; the values live in device memory, the callback graph is captured once).  --process-var sigma_n
+adds each GP's noise variance to its predicted variance at every step: the spread of the next STATE, not of the latent function.
+
 Needs an MI355X and the built library; no gym, no cyipopt (the stand-in solver is scipy's L-BFGS-B on the same
 objective / gradient callbacks, so the trajectories are NOT the reference's Ipopt trajectories)."""
 import argparse
@@ -45,6 +51,24 @@ import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from gaussian_process_mpc_amd import LinearNominalModel, PendulumPlant, RiskSensitiveMPC, Simulator   # noqa: E402
+
+
+class NoisyObservation(object):
+    """The plant seen through additive Gaussian measurement noise of variance ``var`` per component (the plant's own state stays exact)."""
+
+    def __init__(self, plant, var, rng):
+        self.plant, self.sd, self.rng = plant, float(np.sqrt(var)), rng
+
+    def _see(self, obs):
+        return np.asarray(obs, dtype=np.float64) + self.sd * self.rng.standard_normal(np.shape(obs))
+
+    def reset(self):
+        obs, info = self.plant.reset()
+        return self._see(obs), info
+
+    def step(self, action):
+        obs, *rest = self.plant.step(action)
+        return (self._see(obs), *rest)
 
 
 def main():
@@ -66,6 +90,8 @@ def main():
     ap.add_argument("--iters", type=int, default=30, help="--solver mppi: iterations per solve")
     ap.add_argument("--track", default=None, metavar="AMPLITUDE,PERIOD", help="theta follows AMPLITUDE cos(2 pi k / PERIOD), k in MPC steps")
     ap.add_argument("--terminal", type=float, default=None, help="terminal weight W Q on the last predicted state (mpc.Q_terminal)")
+    ap.add_argument("--obs-var", type=float, default=None, metavar="V", help="measurement-noise variance on what the controller sees; V I is its initial covariance")
+    ap.add_argument("--process-var", choices=("sigma_n",), default=None, help="sigma_n: add each GP's noise variance to its predicted variance")
     args = ap.parse_args()
 
     rng = np.random.default_rng(0)
@@ -120,7 +146,16 @@ def main():
             return plan
         mpc.get_optimal_trajectory = logged
 
-    sim = Simulator(mpc, plant, num_iters=args.steps, incremental=True, refresh=args.refresh, max_train=args.window)
+    env = plant
+    if args.obs_var is not None or args.process_var is not None:
+        if args.obs_var is not None and not args.obs_var >= 0.0:
+            ap.error("--obs-var must be >= 0")
+        mpc.set_noise_model(process_var=args.process_var)
+        if args.obs_var is not None:
+            env = NoisyObservation(plant, args.obs_var, np.random.default_rng(1))
+            mpc.set_initial_covariance(args.obs_var * np.eye(2))      # (constant here; an estimator would hand in its P before every solve)
+
+    sim = Simulator(mpc, env, num_iters=args.steps, incremental=True, refresh=args.refresh, max_train=args.window)
     t0 = time.perf_counter()
     hist = sim.run()
     dt = time.perf_counter() - t0
@@ -140,6 +175,10 @@ def main():
         print(f"tracking {args.track}: RMS error of theta {np.sqrt(np.mean((th - want) ** 2)):.4f} rad over {len(th)} steps "
               f"(second half: {np.sqrt(np.mean((th - want)[len(th) // 2:] ** 2)):.4f}); "
               f"gpmpc_pack_callback_captures = {lib().gpmpc_pack_callback_captures(mpc.dynamics.pack().handle)}")
+    if args.obs_var is not None or args.process_var is not None:
+        P, av, w = mpc.dynamics.pack().noise
+        print(f"noise model: init_cov diag {np.diag(P)}, action_var {av}, process_var {w}"
+              + (f"; true theta at the end {plant.state[0]:.3f} (seen: {th[-1]:.3f})" if args.obs_var is not None else ""))
     print("theta:", np.array2string(th[:: max(1, len(th) // 10)], precision=2))
 
 

@@ -115,6 +115,8 @@ SIGNATURES = {
     "gpmpc_pack_build_beta": (_i, [_vp, _vp, _vp, _vp, _dp, _dp, _vp]),
     "gpmpc_pack_set_nominal": (_i, [_vp, _dp, _dp, _vp]),
     "gpmpc_pack_get_nominal": (_i, [_vp, _dp, _dp]),
+    "gpmpc_pack_set_noise": (_i, [_vp, _dp, _dp, _dp, _vp]),
+    "gpmpc_pack_get_noise": (_i, [_vp, _dp, _dp, _dp]),
     "gpmpc_pack_enable_fullcov": (_i, [_vp, _vp]),
     "gpmpc_pack_dims": (_i, [_vp] + [ctypes.POINTER(_i)] * 4),
     "gpmpc_pack_shared_lambda": (_i, [_vp]),

@@ -5,7 +5,7 @@
 // the build's extension of Dynamics.forward_propagate_torch + RiskSensitiveMPC.objective/gradient to full Sigma,
 // oracled by composing the reference's own single-step functions (oracle/gpmpc_oracle.py).
 //
-// Per step: k_fc_assemble builds (u_t, S_t) = ([mu_{t-1}; U_{t-1}], blkdiag(Sigma_{t-1}, float32(1e-3) I)) for every
+// Per step: k_fc_assemble builds (u_t, S_t) = ([mu_{t-1}; U_{t-1}], blkdiag(Sigma_{t-1}, diag(action_var))) for every
 // trajectory, gpmpc_moment_match evaluates means, full covariance and their Jacobians (one pair-kernel launch over the
 // ds variance units and the ds(ds-1)/2 cross units), the Jacobians of all steps are kept, and k_fc_tail evaluates the
 // risk-sensitive cost with full Sigma (src/mpc.py:179-198) and runs the reverse sweep.
@@ -30,6 +30,7 @@ struct FcArgs {
     double* out_cost; double* out_grad;
     gpmpc_cost_params cost;
     const double* sched; int sched_hmax;   // cost schedule of the call (include/gpmpc.h), read by k_fc_tail<DS, true> only, else null
+    const double* noise;                   // noise model of the pack (gpmpc_pack::noise_dev), read by k_fc_assemble
 };
 
 // step t >= 1: record the state of step t-1 and assemble the input distribution of step t
@@ -45,7 +46,9 @@ __global__ void k_fc_assemble(FcArgs A, int t) {
         const double m = (t == 1) ? A.x0[(size_t)b * ds + k] : A.mean[(size_t)b * ds + k];
         om[k] = m; u[k] = m;
         for (int l = 0; l < ds; ++l) {
-            const double c = (t == 1) ? (k == l ? GPMPC_INIT_VAR : 0.0) : A.cov[((size_t)b * ds + k) * ds + l];
+            // t == 1: init_cov of the pack's noise model; later: the step's covariance, process_var on its diagonal
+            double c = (t == 1) ? A.noise[k * ds + l] : A.cov[((size_t)b * ds + k) * ds + l];
+            if (t > 1 && k == l) c += A.noise[gpmpc_noise_off_process(ds, da) + k];
             oc[k * ds + l] = c;
             S[k * D + l] = c;
         }
@@ -54,7 +57,7 @@ __global__ void k_fc_assemble(FcArgs A, int t) {
     if (t > H) return;                        // final call: only records step H
     for (int k = 0; k < da; ++k) {
         u[ds + k] = A.U[((size_t)b * H + (t - 1)) * da + k];
-        for (int l = 0; l < da; ++l) S[(ds + k) * D + ds + l] = (k == l) ? GPMPC_ACTION_VAR : 0.0;
+        for (int l = 0; l < da; ++l) S[(ds + k) * D + ds + l] = (k == l) ? A.noise[gpmpc_noise_off_action(ds) + k] : 0.0;
     }
 }
 
@@ -290,6 +293,7 @@ struct FcHeadArgs {
     int rsplit, zbase;            // row chunks per unit (RS); role index of blockIdx.z = 0 (see k_fc_head)
     const double* part0;          // [B][nwork] Z0 partial sums of the pair kernel, contiguous
     double* out_means; double* out_covs;
+    const double* noise;          // noise model of the pack (gpmpc_pack::noise_dev)
 };
 
 template <int D>
@@ -397,7 +401,7 @@ __global__ __launch_bounds__(256) void k_fc_head(FcHeadArgs A, int t) {
                 const double mu = sp[1], sf2 = sp[2];
                 const double T = c * s_z0[tid];
                 s_mu[tid] = mu;
-                s_cv[tid * ds + tid] = sf2 - T - mu * mu;
+                s_cv[tid * ds + tid] = (sf2 + A.noise[gpmpc_noise_off_process(ds, A.da) + tid]) - T - mu * mu;      // process_var on the diagonal
             } else {
                 const int pr = tid - ds, a = M.pair_ab[2 * pr], b = M.pair_ab[2 * pr + 1];
                 const double mua = A.sp_prev[((size_t)q * nunits + a) * M.sps + 1], mub = A.sp_prev[((size_t)q * nunits + b) * M.sps + 1];
@@ -420,9 +424,9 @@ __global__ __launch_bounds__(256) void k_fc_head(FcHeadArgs A, int t) {
             const int k = tid / D, l = tid - k * D;
             double c = 0.0;
             if (k < ds && l < ds) {
-                c = (t == 1) ? (k == l ? GPMPC_INIT_VAR : 0.0) : s_cv[k * ds + l];
+                c = (t == 1) ? A.noise[k * ds + l] : s_cv[k * ds + l];          // t == 1: init_cov of the pack's noise model
                 if (rec) A.out_covs[(((size_t)q * (H + 1) + (t - 1)) * ds + k) * ds + l] = c;
-            } else if (k >= ds && l >= ds) c = (k == l) ? GPMPC_ACTION_VAR : 0.0;
+            } else if (k >= ds && l >= ds) c = (k == l) ? A.noise[gpmpc_noise_off_action(ds) + (k - ds)] : 0.0;
             sh.S[tid] = c;
         }
     }
@@ -531,6 +535,7 @@ static int run_fc2(const gpmpc_pack* p, const FcPlan2& r, FcArgs& T, bool grad, 
     M.G = (double*)(ws + r.off_G); M.gw = r.gw; M.ns2 = p->ds;
     A.x0 = T.x0; A.U = T.U; A.B = B; A.H = H; A.da = p->da;
     A.out_means = T.out_means; A.out_covs = T.out_covs;
+    A.noise = p->noise_dev;
     double* sp[2] = {(double*)(ws + r.off_sp0), (double*)(ws + r.off_sp1)};
     T.dmean_du = (double*)(ws + r.off_dmu); T.dmean_dS = (double*)(ws + r.off_dmS);
     T.dcov_du = (double*)(ws + r.off_dcu); T.dcov_dS = (double*)(ws + r.off_dcS);
@@ -661,6 +666,7 @@ extern "C" int gpmpc_rollout_fullcov(const gpmpc_pack* p, int B, int H, const do
     A.B = B; A.H = H; A.ds = p->ds; A.da = p->da; A.D = p->D; A.grad = grad ? 1 : 0;
     A.x0 = x0; A.U = U;
     A.sched = sched.dev; A.sched_hmax = sched.H_max;
+    A.noise = p->noise_dev;
     const size_t nz = ds + ds * ds;
     const size_t lds = sizeof(double) * ((size_t)GPMPC_FC_WORKERS * ds * 2 * ds + (H + 1) + (size_t)(H + 1) * nz + 2 * nz + D + D * D + 2 * (size_t)H * p->da);
     if (lds > 60 * 1024) return GPMPC_E_ARG;

@@ -9,9 +9,16 @@
 #define GPMPC_WAVE 64
 
 // Variance of the initial state and of the action noise, as the reference has them
-// (src/dynamics.py:148 float64 1e-3; src/dynamics.py:162 float32 1e-3 promoted to float64).
+// (src/dynamics.py:148 float64 1e-3; src/dynamics.py:162 float32 1e-3 promoted to float64): the DEFAULTS of the pack's noise model
+// (gpmpc_pack_set_noise), uploaded by gpmpc_pack_create.  No kernel names them: every rollout form reads the model from the pack.
 #define GPMPC_INIT_VAR   1e-3
 #define GPMPC_ACTION_VAR ((double)1e-3f)
+// Noise model of the rollout, one device buffer per pack (gpmpc_pack::noise_dev), in doubles:
+//   init_cov [ds][ds] | action_var [da] | process_var [ds]
+// The diagonal rollout reads diag(init_cov); the full-covariance rollout the whole matrix.
+#define GPMPC_NOISE_MAX (GPMPC_MAX_DS * GPMPC_MAX_DS + GPMPC_MAX_D + GPMPC_MAX_DS)
+__host__ __device__ inline int gpmpc_noise_off_action(int ds) { return ds * ds; }
+__host__ __device__ inline int gpmpc_noise_off_process(int ds, int da) { return ds * ds + da; }
 
 #define GPMPC_MAX_PAIRS (GPMPC_MAX_DS * (GPMPC_MAX_DS - 1) / 2)
 
@@ -107,6 +114,11 @@ struct gpmpc_pack {
     double* nom_dev;           // [ds * D + ds], allocated by the first gpmpc_pack_set_nominal
     double* resid_dev;         // [Np][ds] residual targets Y - X n^T - c of the last build from raw targets
     double nom_host[GPMPC_MAX_DS * (GPMPC_MAX_D + 1)];
+    // Noise model (gpmpc_pack_set_noise; layout at GPMPC_NOISE_MAX): allocated and filled with the defaults at creation, read by every
+    // rollout form through a pointer in its argument struct -- never kernel arguments, so captured launches do not depend on the values,
+    // and no kernel instance or plan does either: a set drops nothing.
+    double* noise_dev;         // [ds * ds + da + ds]
+    double noise_host[GPMPC_NOISE_MAX];
 };
 
 // Number of pair-kernel output moments per (trajectory, GP, tile).
@@ -222,6 +234,7 @@ struct FusedArgs {
     int tiles;                             // one lambda for all GPs: tiles per GP (partial sums are laid out [GP][tile], nwork = ds * tiles)
     const int* ncol;                       // device: columns that carry weight (N rounded up to 8, <= Np; gpmpc_pack::ncol_dev): tile column loops end there
     int xcdmap;                            // 256-row forms, several trajectories: XCD-aware dispatch order (step_fused.h; set by the plan from B x ntile)
+    const double* noise;                   // noise model of the pack (gpmpc_pack::noise_dev)
 };
 template <int D> int gpmpc_launch_step_fused_D(bool grad, int ns2, int q, int ng, const FusedArgs& a, int t, hipStream_t s);
 // XCD-aware dispatch order of the one-launch form (step_fused.h): linear workgroup id L of a (gx, nB) grid whose first nt columns are tile
@@ -243,6 +256,7 @@ struct PersistArgs {
     double* gscr;                                  // [B][ds][Np][GW] column rows, one slot per workgroup
     const int* ncol;                               // device: columns that carry weight (N rounded up to 8, <= Np); gpmpc_pack::ncol_dev
     int total;                                     // (host bookkeeping) columns of the flattened (GP, row block, column) space at ncol = Np
+    const double* noise;                           // noise model of the pack (gpmpc_pack::noise_dev)
 };
 template <int D> int gpmpc_launch_persist_D(bool grad, int ns2, int waves, int ng, const PersistArgs& a, hipStream_t s);
 

@@ -391,6 +391,13 @@ extern "C" int gpmpc_pack_reload_tuning(gpmpc_pack* p) {
     return GPMPC_OK;
 }
 
+// The defaults of the noise model (the reference's constants), written into the parts asked for of a [GPMPC_NOISE_MAX] host image
+static void noise_defaults(int ds, int da, double* img, bool init, bool action, bool process) {
+    if (init) for (int k = 0; k < ds; ++k) for (int l = 0; l < ds; ++l) img[k * ds + l] = k == l ? GPMPC_INIT_VAR : 0.0;
+    if (action) for (int j = 0; j < da; ++j) img[gpmpc_noise_off_action(ds) + j] = GPMPC_ACTION_VAR;
+    if (process) for (int a = 0; a < ds; ++a) img[gpmpc_noise_off_process(ds, da) + a] = 0.0;
+}
+
 extern "C" int gpmpc_pack_create(gpmpc_pack** out, int n_train, int state_dim, int action_dim) {
     if (!out || n_train < 1 || state_dim < 1 || action_dim < 0) return GPMPC_E_ARG;
     const int D = state_dim + action_dim;
@@ -420,6 +427,11 @@ extern "C" int gpmpc_pack_create(gpmpc_pack** out, int n_train, int state_dim, i
         for (int k = 0; k < p->npairs; ++k) { hab[2 * k] = p->pair_a[k]; hab[2 * k + 1] = p->pair_b[k]; }
         e = hipMalloc(&p->pair_ab_dev, sizeof(int) * 2 * p->npairs);
         if (e == hipSuccess) e = hipMemcpy(p->pair_ab_dev, hab, sizeof(int) * 2 * p->npairs, hipMemcpyHostToDevice);
+    }
+    if (e == hipSuccess) e = hipMalloc(&p->noise_dev, sizeof(double) * GPMPC_NOISE_MAX);
+    if (e == hipSuccess) {
+        noise_defaults(p->ds, p->da, p->noise_host, true, true, true);
+        e = hipMemcpy(p->noise_dev, p->noise_host, sizeof(double) * GPMPC_NOISE_MAX, hipMemcpyHostToDevice);
     }
     bool ok = e == hipSuccess;
     // 256-row workgroups: 512 / 1024 rows would cut the G-row re-reads 2x / 4x but ran 8 % / 46 % slower on C3 (C4: -1 %).
@@ -515,6 +527,71 @@ extern "C" int gpmpc_pack_get_nominal(const gpmpc_pack* p, double* weights_host,
     return 1;
 }
 
+// Noise model of the rollout (layout and defaults: gpmpc_internal.h).  A NULL part is reset to its default.  Everything is checked on the
+// host image first: a refused set has touched neither the pack nor the device.
+extern "C" int gpmpc_pack_set_noise(gpmpc_pack* p, const double* init_cov_host, const double* action_var_host, const double* process_var_host,
+                                    void* stream) {
+    if (!p) return GPMPC_E_ARG;
+    const int ds = p->ds, da = p->da, oa = gpmpc_noise_off_action(ds), ow = gpmpc_noise_off_process(ds, da), n = ow + ds;
+    double img[GPMPC_NOISE_MAX];
+    memset(img, 0, sizeof(img));
+    noise_defaults(ds, da, img, !init_cov_host, !action_var_host, !process_var_host);
+    char msg[160];
+    if (init_cov_host) {
+        double pmax = 0.0;
+        for (int e = 0; e < ds * ds; ++e) {
+            const double v = init_cov_host[e];
+            if (!(v - v == 0.0)) { snprintf(msg, sizeof(msg), "gpmpc_pack_set_noise: init_cov[%d][%d] is not finite", e / ds, e % ds); gpmpc_set_error_text(msg); return GPMPC_E_ARG; }
+            if (fabs(v) > pmax) pmax = fabs(v);
+        }
+        for (int k = 0; k < ds; ++k) {
+            if (init_cov_host[k * ds + k] < 0.0) { snprintf(msg, sizeof(msg), "gpmpc_pack_set_noise: init_cov[%d][%d] is negative", k, k); gpmpc_set_error_text(msg); return GPMPC_E_ARG; }
+            for (int l = 0; l < ds; ++l) {
+                const double a = init_cov_host[k * ds + l], b = init_cov_host[l * ds + k];
+                if (fabs(a - b) > 1e-12 * pmax) { snprintf(msg, sizeof(msg), "gpmpc_pack_set_noise: init_cov is not symmetric at [%d][%d]", k, l); gpmpc_set_error_text(msg); return GPMPC_E_ARG; }
+                img[k * ds + l] = k == l ? a : 0.5 * (a + b);          // the mean of each off-diagonal pair
+            }
+        }
+    }
+    for (int part = 0; part < 2; ++part) {
+        const double* src = part ? process_var_host : action_var_host;
+        const int cnt = part ? ds : da, off = part ? ow : oa;
+        if (!src) continue;
+        for (int j = 0; j < cnt; ++j) {
+            const double v = src[j];
+            if (!(v - v == 0.0) || v < 0.0) {
+                snprintf(msg, sizeof(msg), "gpmpc_pack_set_noise: %s[%d] is %s", part ? "process_var" : "action_var", j, v < 0.0 ? "negative" : "not finite");
+                gpmpc_set_error_text(msg);
+                return GPMPC_E_ARG;
+            }
+            img[off + j] = v;
+        }
+    }
+    if (int rc_dev = gpmpc_check_device(p)) return rc_dev;
+    // (pieces of 64 doubles: what one upload carries; ds^2 + da + ds <= 80)
+    // (the host mirror follows piece by piece: should a launch fail -- a HIP error, not a refusal --, it still says what the device holds)
+    for (int o = 0; o < n; o += 64) {
+        const int m = n - o < 64 ? n - o : 64;
+        if (int rcu = gpmpc_upload_small(p->noise_dev + o, img + o, sizeof(double) * m, (hipStream_t)stream)) return rcu;
+        memcpy(p->noise_host + o, img + o, sizeof(double) * m);
+    }
+    // nothing is dropped: no kernel instance, plan or captured launch depends on the values (the kernels read them from device memory)
+    return GPMPC_OK;
+}
+
+// 1: some part differs from its default, 0: none does (the three parts are copied out where not NULL); GPMPC_E_ARG
+extern "C" int gpmpc_pack_get_noise(const gpmpc_pack* p, double* init_cov_host, double* action_var_host, double* process_var_host) {
+    if (!p) return GPMPC_E_ARG;
+    const int ds = p->ds, da = p->da, oa = gpmpc_noise_off_action(ds), ow = gpmpc_noise_off_process(ds, da);
+    if (init_cov_host) memcpy(init_cov_host, p->noise_host, sizeof(double) * ds * ds);
+    if (action_var_host) memcpy(action_var_host, p->noise_host + oa, sizeof(double) * da);
+    if (process_var_host) memcpy(process_var_host, p->noise_host + ow, sizeof(double) * ds);
+    double def[GPMPC_NOISE_MAX];
+    noise_defaults(ds, da, def, true, true, true);
+    for (int e = 0; e < ow + ds; ++e) if (p->noise_host[e] != def[e]) return 1;
+    return 0;
+}
+
 extern "C" int gpmpc_pack_destroy(gpmpc_pack* p) {
     if (!p) return GPMPC_OK;
     if (p->X) (void)hipFree(p->X);
@@ -533,6 +610,7 @@ extern "C" int gpmpc_pack_destroy(gpmpc_pack* p) {
     for (int k = 0; k < 8; ++k) for (int q = 0; q < 3; ++q) if (p->fcs_ustart_dev[k][q]) (void)hipFree(p->fcs_ustart_dev[k][q]);
     if (p->fcs_tiles256_dev) (void)hipFree(p->fcs_tiles256_dev);
     if (p->nom_dev) (void)hipFree(p->nom_dev);
+    if (p->noise_dev) (void)hipFree(p->noise_dev);
     if (p->resid_dev) (void)hipFree(p->resid_dev);
     for (int mode = 0; mode < 2; ++mode)
         for (int k = 0; k < 8; ++k) {

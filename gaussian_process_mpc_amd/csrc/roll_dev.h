@@ -40,9 +40,11 @@ struct RollArgs {
     const double* nom;   // linear nominal model of the pack: [ds][D] weights, then [ds] biases (nominal kernel variants only), else null
     const double* sched; // cost schedule of the call (include/gpmpc.h: x_ref rows | u_ref rows | Q_f | has_Qf, H), read by the schedule variants of
     int sched_hmax;      // the tail kernel only, else null; the H_max its offsets are formed from
+    const double* noise; // noise model of the pack (gpmpc_pack::noise_dev; layout in gpmpc_internal.h), read by the head kernel
 };
 
-// layout of sp (doubles): 0 c | 1 mu | 2 sf2 | 3 A[D] | 3+D scale[D] | 3+2D dmu_du[D] | 3+3D dmu_ds[D]
+// layout of sp (doubles): 0 c | 1 mu | 2 sf2 + w | 3 A[D] | 3+D scale[D] | 3+2D dmu_du[D] | 3+3D dmu_ds[D]
+//   (w: the GP's process_var of the pack's noise model, added ONCE by whoever writes sp[2]: var = sp[2] - T - mu^2; c_m keeps the plain sf2)
 //   with row chunks (hchunks > 1):      1 c_m                                  3+2D B[D]      3+3D unused
 // (sps_of(D) = 3 + 4 D doubles: plan.h)
 // Linear nominal model m_a(z) = n_a . z + c_a (GP a learns the residual): the step's moments become

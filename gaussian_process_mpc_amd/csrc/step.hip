@@ -59,7 +59,7 @@ __device__ static void prep_step(const RollArgs& A, int b, int t, int a, int chu
             sk = s_var[k];
         } else {
             uk = A.U[((size_t)b * A.H + (t - 1)) * A.da + (k - ds)];
-            sk = GPMPC_ACTION_VAR;
+            sk = A.noise[gpmpc_noise_off_action(ds) + (k - ds)];      // action_var of the pack's noise model
         }
         const double lam = A.lam[a * D + k];
         s_u[k] = uk;
@@ -163,7 +163,7 @@ __device__ static void prep_step(const RollArgs& A, int b, int t, int a, int chu
             const double cm = sf2 / sqrt(detm), c = 1.0 / sqrt(detv);
             double* sp = A.sp + (((size_t)(t & 1) * A.B + b) * ds + a) * A.sps;
             double* pp = A.pp + ((size_t)b * ds + a) * A.pps;
-            if (k == 0) { sp[0] = c; sp[1] = cm; sp[2] = sf2; }
+            if (k == 0) { sp[0] = c; sp[1] = cm; sp[2] = sf2 + A.noise[gpmpc_noise_off_process(ds, A.da) + a]; }
             const double sc = s_sc[k];
             sp[3 + k] = s_A[k]; sp[3 + D + k] = sc;
             sp[3 + 2 * D + k] = s_B[k];
@@ -181,7 +181,7 @@ __device__ static void prep_step(const RollArgs& A, int b, int t, int a, int chu
         const double mu = cm * s_out[0];
         double* sp = A.sp + (((size_t)(t & 1) * A.B + b) * ds + a) * A.sps;   // other parity than the finish phase reads
         double* pp = A.pp + ((size_t)b * ds + a) * A.pps;
-        if (k == 0) { sp[0] = c; sp[1] = mu; sp[2] = sf2; }
+        if (k == 0) { sp[0] = c; sp[1] = mu; sp[2] = sf2 + A.noise[gpmpc_noise_off_process(ds, A.da) + a]; }
         const double Bq = s_B[k], sc = s_sc[k];
         sp[3 + k] = s_A[k]; sp[3 + D + k] = sc;
         sp[3 + 2 * D + k] = -Bq * cm * s_out[1 + k];
@@ -225,11 +225,12 @@ __global__ __launch_bounds__(256) void k_roll_head(RollArgs A, int t) {
     if (t == 1) {
         if (threadIdx.x < A.ds) {
             const double x = A.x0[(size_t)b * A.ds + threadIdx.x];
+            const double v0 = A.noise[threadIdx.x * (A.ds + 1)];          // diag(init_cov) of the pack's noise model
             s_mu[threadIdx.x] = x;
-            s_var[threadIdx.x] = GPMPC_INIT_VAR;
+            s_var[threadIdx.x] = v0;
             if (a == 0 && chunk == 0) {
                 A.means[((size_t)b * (A.H + 1)) * A.ds + threadIdx.x] = x;
-                A.vars[((size_t)b * (A.H + 1)) * A.ds + threadIdx.x] = GPMPC_INIT_VAR;
+                A.vars[((size_t)b * (A.H + 1)) * A.ds + threadIdx.x] = v0;
             }
         }
         __syncthreads();
@@ -291,6 +292,7 @@ int gpmpc_enqueue_rollout(const RollCall& c) {
     A.out_cost = c.out_cost; A.out_grad = c.out_grad; A.cost = *c.cost;
     A.nom = p->nominal ? p->nom_dev : nullptr;
     A.sched = sched.dev; A.sched_hmax = sched.H_max;
+    A.noise = p->noise_dev;
     if (A.nom && (r.fused || r.hchunks > 1)) {     // (a plan handed in from outside: the nominal variants exist for the two-launch form only)
         gpmpc_set_error_text("gpmpc_rollout: plan without a nominal variant on a nominal pack");
         return GPMPC_E_STATE;
@@ -315,6 +317,7 @@ int gpmpc_enqueue_rollout(const RollCall& c) {
         const int T = p->Np / 64;
         Q.total = ((p->ds + r.png - 1) / r.png) * 32 * T * (T + 1);
         Q.ncol = p->ncol_dev;
+        Q.noise = p->noise_dev;
         const int rc = gpmpc_timed_persist(p->D, grad, p->ds, r.pwaves, r.png, Q, s);
         if (rc != GPMPC_OK) return rc;
         A.finished = 1;
@@ -338,6 +341,7 @@ int gpmpc_enqueue_rollout(const RollCall& c) {
         F.sps = L.sps; F.nm = L.nm;
         F.gscr = r.fused == 2 ? (double*)(ws + L.off_G) : nullptr;
         F.ncol = p->ncol_dev;
+        F.noise = p->noise_dev;
         // XCD-aware dispatch order (step_fused.h): measured against the natural order (tools/lib_ab.py, profiles/r05/ab19_xcdmap*.txt; N:ds:B
         // gain): 2048:4: B = 2 -1 %, 3 +2 %, 4 +4 %, 6 +8 %, 8 +6 %; 1024:4: 2 -2 %, 4 -2.5 / +2 %, 8 +4 %, 16 / 24 level; 512:3: 32 / 64 +3 / +2 %;
         // 300:4:32 +16 %; one lambda: 2048:4:8 +8 %, 1024:4:32 +14 %, 512:3:64 +14 %, 300:4:64 +10 %.  As a candidate of gpmpc_pack_autotune

@@ -234,11 +234,16 @@ void k_step_fused(FusedArgs A, int t) {
     double lam_k = 0.0, sp_c = 0.0, sp_mu = 0.0, sp_sf2 = 0.0, u_act = 0.0, spp_v = 0.0;
     if (w == 0) {                                                   // wave-uniform branch: no exec masking, no wait
         lam_k = A.lam[a_own * D + kd];
+        // Noise model of the pack: the input variance of lane k that is NOT a result of step t-1 -- diag(init_cov)_k at t == 1, action_var
+        // of an action lane at every step -- arrives in sp_c, which those lanes do not otherwise use (a register of its own across this
+        // phase cost an occupancy step in a fifth of the instances).
+        const double* nz = A.noise + (lane < DS ? kg * (DS + 1) : gpmpc_noise_off_action(DS) + (kd - DS));
         if (t > 1) {
             const double* sp = A.sp + (((size_t)pprev * A.B + b) * DS + kg) * A.sps;
-            sp_c = sp[0]; sp_mu = sp[1]; sp_sf2 = sp[2];
+            sp_c = *(lane < DS ? sp : nz); sp_mu = sp[1]; sp_sf2 = sp[2];
         } else {
             sp_mu = A.x0[(size_t)b * DS + kg];
+            sp_c = *nz;
         }
         if (DA > 0) u_act = A.U[((size_t)b * A.H + (t - 1)) * DA + (lane >= DS && lane < D ? lane - DS : 0)];
     }
@@ -323,6 +328,7 @@ void k_step_fused(FusedArgs A, int t) {
     // mean sums: this thread's first points (the loop below loads the ones beyond)
     constexpr int PF = SB ? 1 : 2;                                  // (mid-size form: registers; N >= 1024 loops anyway)
     double xpt[PF][D], bpt[PF], sf_a = 0.0;
+    __shared__ double s_wa;                                         // process_var of GP am (mean workgroups)
     if (role == 1) {
 #pragma unroll
         for (int r = 0; r < PF; ++r) {
@@ -333,6 +339,15 @@ void k_step_fused(FusedArgs A, int t) {
             bpt[r] = i < Np ? bv : 0.0;
         }
         sf_a = A.sf[am];
+        // process_var of GP am: global -> LDS directly, one dword per lane of lanes 0 and 1 (as the exp table above: no register held while
+        // it flies; a VGPR pair live from here to the last block costs an occupancy step in a fifth of the instances).  Drained in front of
+        // the barrier that ends phase 1; read in the last block, many barriers later, under whatever exec mask.
+        if (tid < 2) {
+            typedef const void __attribute__((address_space(1))) gvoid_w;
+            typedef void __attribute__((address_space(3))) lvoid_w;
+            __builtin_amdgcn_global_load_lds((gvoid_w*)((const unsigned*)(A.noise + gpmpc_noise_off_process(DS, DA) + am) + tid),
+                                             (lvoid_w*)((unsigned*)&s_wa + tid), 4, 0, 0);
+        }
     }
     GPMPC_STAMP(1);
 
@@ -367,7 +382,7 @@ void k_step_fused(FusedArgs A, int t) {
         const int k = tid;
         double uk, sk;
         if (k < DS) {
-            if (t == 1) { uk = sp_mu; sk = GPMPC_INIT_VAR; }
+            if (t == 1) { uk = sp_mu; sk = sp_c; }                // diag(init_cov)_k
             else {
                 const int kk = k < DS ? k : 0;
                 const double z0 = s_zw[kk];
@@ -377,7 +392,7 @@ void k_step_fused(FusedArgs A, int t) {
             }
             s_mu[k < DS ? k : 0] = uk; s_var[k < DS ? k : 0] = sk;
         } else {
-            uk = u_act; sk = GPMPC_ACTION_VAR;                    // src/dynamics.py:162
+            uk = u_act; sk = sp_c;                                // action_var (default: src/dynamics.py:162)
         }
         s_uin[k] = uk; s_sin[k] = sk;
         // sqrt(0.125 / x) as rsqrt(8 x): v_rsq_f64 + refinement instead of a division and a square root, which were ~900
@@ -787,7 +802,7 @@ void k_step_fused(FusedArgs A, int t) {
         if (t == 1) {
             if (a == 0 && tid < DS) {
                 A.means[((size_t)b * (A.H + 1)) * DS + tid] = s_mu[tid];
-                A.vars[((size_t)b * (A.H + 1)) * DS + tid] = GPMPC_INIT_VAR;
+                A.vars[((size_t)b * (A.H + 1)) * DS + tid] = s_var[tid];      // diag(init_cov), as every workgroup of this launch read it
             }
             return;
         }
@@ -900,7 +915,7 @@ void k_step_fused(FusedArgs A, int t) {
         const double cm = sf2 / sqrt(detm), c = 1.0 / sqrt(detv);
         const double mu = cm * s_out[0];
         double* sp = A.sp + (((size_t)pcur * A.B + b) * DS + a) * A.sps;
-        if (k == 0) { sp[0] = c; sp[1] = mu; sp[2] = sf2; }
+        if (k == 0) { sp[0] = c; sp[1] = mu; sp[2] = sf2 + s_wa; }      // (sp[2]: the constant of var = sp[2] - T - mu^2, roll_dev.h)
         const double Bq = s_B[k];
         sp[3 + k] = s_A[k]; sp[3 + D + k] = s_sck[k];
         sp[3 + 2 * D + k] = -Bq * cm * s_out[1 + k];

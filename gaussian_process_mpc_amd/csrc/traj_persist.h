@@ -115,7 +115,7 @@ __global__ __launch_bounds__(1024, 4) void k_traj_persist(PersistArgs A) {
     __shared__ double s_z[DS * NM], s_ms[DS * NV];
     __shared__ double s_uin[D], s_sin[D];
     __shared__ double s_B[DS * D], s_Ak[DS * D], s_sc[DS * D], s_cv[DS * D], s_r1[DS * D], s_r2[DS * D];
-    __shared__ double s_c[DS], s_cm[DS], s_sf2[DS], s_lam[DS * D], s_avar;
+    __shared__ double s_c[DS], s_cm[DS], s_sf2[DS], s_lam[DS * D], s_avar[DA > 0 ? DA : 1];
     __shared__ int s_rng[17], s_ga[16];            // range boundaries of the waves in the flattened column space; GP a range starts in
     const int b = blockIdx.x, tid = threadIdx.x, nthr = blockDim.x;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6), NW = nthr >> 6;
@@ -177,12 +177,13 @@ __global__ __launch_bounds__(1024, 4) void k_traj_persist(PersistArgs A) {
         s_rng[tid] = lo;
         if (tid < NW) s_ga[tid] = lo < total ? lo / per_gp : nun;
     }
-    if (tid == 0) s_avar = GPMPC_ACTION_VAR;                   // (a constant read from LDS per step: held in a register pair it was a spill)
+    // action_var of the pack's noise model (constants read from LDS per step: held in a register pair it was a spill)
+    if (tid < DA) s_avar[tid] = A.noise[gpmpc_noise_off_action(DS) + tid];
     if (tid < DS * D) s_lam[tid] = A.lam[tid];             // (read per step from LDS: a register held across the step loop is a spill)
-    if (tid < DS) { s_uin[tid] = A.x0[(size_t)b * DS + tid]; s_sin[tid] = GPMPC_INIT_VAR; }
+    if (tid < DS) { s_uin[tid] = A.x0[(size_t)b * DS + tid]; s_sin[tid] = A.noise[tid * (DS + 1)]; }      // diag(init_cov)
     if (tid < DS) {
         A.means[((size_t)b * (A.H + 1)) * DS + tid] = s_uin[tid];
-        A.vars[((size_t)b * (A.H + 1)) * DS + tid] = GPMPC_INIT_VAR;
+        A.vars[((size_t)b * (A.H + 1)) * DS + tid] = s_sin[tid];
     }
     double* __restrict__ Gs = A.gscr + (size_t)b * DS * Np * GW;
 
@@ -201,7 +202,7 @@ __global__ __launch_bounds__(1024, 4) void k_traj_persist(PersistArgs A) {
         const int ln = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, tz)), tiz = w * 64 + ln, l8 = ln * 8;
         GPMPC_PST(0);
         // ---- 1: input moments of the action dimensions, then the per-(GP, dimension) scalars ------------------------------------
-        if (DA > 0 && tiz >= DS && tiz < D) { s_uin[tiz] = s_U[(t - 1) * DA + (tiz - DS)]; s_sin[tiz] = s_avar; }
+        if (DA > 0 && tiz >= DS && tiz < D) { s_uin[tiz] = s_U[(t - 1) * DA + (tiz - DS)]; s_sin[tiz] = s_avar[tiz - DS]; }
         GPMPC_LDS_BARRIER();
         if (tiz < DS * D) {
             const int a = tiz / D, k = tiz - a * D;
@@ -561,7 +562,8 @@ __global__ __launch_bounds__(1024, 4) void k_traj_persist(PersistArgs A) {
             double detm = 1.0, detv = 1.0;
             for (int l = 0; l < D; ++l) { detm *= s_r1[a * D + l]; detv *= s_r2[a * D + l]; }
             const double sf = A.sf[a], sf2 = sf * sf;
-            s_sf2[a] = sf2; s_cm[a] = sf2 / sqrt(detm); s_c[a] = 1.0 / sqrt(detv);
+            // s_sf2: the constant of var = s_sf2 - T - mu^2, with the GP's process_var (both uses below read this one value); c_m keeps sf2
+            s_sf2[a] = sf2 + A.noise[gpmpc_noise_off_process(DS, DA) + a]; s_cm[a] = sf2 / sqrt(detm); s_c[a] = 1.0 / sqrt(detv);
         }
         // every (GP, moment) sum by a ROW of 16 lanes, one lane per wave of the workgroup (round 5: one thread per sum walked the 16
         // waves in a chain of dependent LDS reads, ~3 k cycles of a 9.5 k phase); fixed order: rows as (0 + 1) + (2 + 3), then the

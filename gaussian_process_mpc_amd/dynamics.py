@@ -13,7 +13,7 @@ import torch
 from .gpr import GaussianProcessRegression
 from .nominal import LinearNominalModel, stack_linear
 from .autograd import RolloutFunction, wants_grad
-from .rollout import CostParams, GPPack, rollout, rollout_fullcov
+from .rollout import CostParams, GPPack, noise_arrays, rollout, rollout_fullcov
 
 
 class Dynamics(object):
@@ -30,6 +30,8 @@ class Dynamics(object):
         self._pack = None
         self._pack_key = None
         self._nominal_warned = False
+        self._noise = None                               # (init_cov, action_var, process_var | "sigma_n") of set_noise_model, or None
+        self._noise_applied = None                       # (pack, sigma_n sources) the model was last written to
         # Fixed-size training window (extension; None: the training set grows without bound, as in the reference).  Once num_train has
         # reached max_train, a single new observation REPLACES the row at `window_slot` in every GP (first-in first-out: slot 0 first,
         # the oldest row after a bulk load) and the slot advances modulo max_train.  X_train / y_train of the GPs are then in SLOT
@@ -213,7 +215,43 @@ class Dynamics(object):
             if self._pack is None or not self._pack.rebuild(g0.X_train, Y, Kinv, lam, sf, nominal=nominal):
                 self._pack = GPPack(g0.X_train, Y, Kinv, lam, sf, device=self.device, nominal=nominal)
             self._pack_key = key
+        self._apply_noise(self._pack)
         return self._pack
+
+    # -- noise model (extension) -----------------------------------------------------------
+    def set_noise_model(self, init_cov=None, action_var=None, process_var=None):
+        """Noise model of every rollout of this object (GPPack.set_noise): init_cov (ds, ds) or a (ds,) diagonal, action_var (da,),
+        process_var (ds,) -- or the string "sigma_n": each GP's current sigma_n^2, so that the propagated variance is that of the next
+        STATE (Sigma_t+1 = Sigma^f + Sigma_w) rather than of the latent function; it follows later hyper-parameter updates.  None: that
+        part's default; all None: the reference's constants.  Stored here and re-applied whenever this object creates a new pack (the
+        training set outgrowing its padded size); on the pack that exists it is one small set -- not a rebuild, and not part of the
+        rebuild key."""
+        follow = isinstance(process_var, str)
+        if follow and process_var != "sigma_n":
+            raise ValueError('process_var: an array of %d variances or the string "sigma_n", got %r' % (self.state_dim, process_var))
+        P, av, pv = noise_arrays(self.state_dim, self.action_dim, init_cov, action_var, None if follow else process_var)
+        for name, arr in (("init_cov", P), ("action_var", av), ("process_var", pv)):
+            if arr is not None and not np.all(np.isfinite(arr)):
+                raise ValueError("%s must be finite" % name)
+        self._noise = (P, av, "sigma_n" if follow else pv)
+        self._noise_applied = None
+        if self._pack is not None:
+            self._apply_noise(self._pack)
+
+    def _apply_noise(self, pack):
+        """Write the stored model into ``pack`` if it does not hold it yet (runs on every solver callback: identity checks only)."""
+        nm = getattr(self, "_noise", None)
+        if nm is None:                                   # never set: a pack starts with the defaults
+            return
+        P, av, pv = nm
+        src = tuple((g.log_sigma_n, g.log_sigma_n._version) for g in self.gpr_err) if isinstance(pv, str) else None
+        old = getattr(self, "_noise_applied", None)
+        if old is not None and old[0] is pack and (src is None or all(a[0] is b[0] and a[1] == b[1] for a, b in zip(src, old[1]))):
+            return
+        if src is not None:
+            pv = np.array([float(g.get_sigma_n()) ** 2 for g in self.gpr_err])
+        pack.set_noise(P, av, pv)
+        self._noise_applied = (pack, src)
 
     # -- rollout ---------------------------------------------------------------------------
     def rollout(self, curr_state, actions, cost=None, want_grad=False, full_covariance=False):

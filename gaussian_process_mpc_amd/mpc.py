@@ -150,6 +150,21 @@ class RiskSensitiveMPC:
             self._cache_key = None
         return sched
 
+    # -- noise model (extension)
+    def set_noise_model(self, init_cov=None, action_var=None, process_var=None):
+        """Noise model of the prediction (Dynamics.set_noise_model): covariance of the start state, variance of each input, and a process
+        variance added to every predicted state (an array, or "sigma_n" for the GPs' own noise).  Every solver and callback follows it,
+        under ``full_covariance=True`` with the whole ``init_cov`` matrix, else with its diagonal."""
+        self.dynamics.set_noise_model(init_cov=init_cov, action_var=action_var, process_var=process_var)
+        self._cache_key = None
+
+    def set_initial_covariance(self, P):
+        """The per-solve call of an estimator-driven loop: the covariance of the state handed to the next ``get_optimal_trajectory``
+        ((ds, ds), or a (ds,) diagonal); the other parts of the model stay.  One small device copy: captured graphs are replayed."""
+        nm = getattr(self.dynamics, "_noise", None) or (None, None, None)
+        self.dynamics.set_noise_model(init_cov=P, action_var=nm[1], process_var=nm[2])
+        self._cache_key = None
+
     # -- setters (src/mpc.py:72-116)
     def set_ub(self, ub):
         assert len(ub) == self.input_dim

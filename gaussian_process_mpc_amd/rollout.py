@@ -180,6 +180,36 @@ class StateConstraints:
         return cls(np.array(rows), np.array(rhs), kappa=kappa, prob=prob)
 
 
+def noise_arrays(ds, da, init_cov=None, action_var=None, process_var=None):
+    """The three parts of a noise model as contiguous float64 arrays of the pack's shapes (None stays None): shapes are checked here, values
+    by the library."""
+    P = av = pv = None
+    if init_cov is not None:
+        P = np.asarray(init_cov, dtype=np.float64)
+        if P.ndim == 0:
+            P = np.full(ds, float(P))
+        if P.ndim == 1:
+            if P.shape[0] != ds:
+                raise ValueError(f"init_cov: a vector of {ds} variances or a ({ds}, {ds}) matrix, got shape {P.shape}")
+            P = np.diag(P)
+        if P.shape != (ds, ds):
+            raise ValueError(f"init_cov: a vector of {ds} variances or a ({ds}, {ds}) matrix, got shape {P.shape}")
+        P = np.ascontiguousarray(P)
+    if action_var is not None:
+        av = np.asarray(action_var, dtype=np.float64)
+        if av.ndim > 1 or (av.ndim == 1 and av.shape[0] != da):
+            raise ValueError(f"action_var: {da} variances, got shape {av.shape}")
+        av = np.ascontiguousarray(np.broadcast_to(av, (da,)))
+        if da == 0:
+            av = None
+    if process_var is not None:
+        pv = np.asarray(process_var, dtype=np.float64)
+        if pv.ndim > 1 or (pv.ndim == 1 and pv.shape[0] != ds):
+            raise ValueError(f"process_var: {ds} variances, got shape {pv.shape}")
+        pv = np.ascontiguousarray(np.broadcast_to(pv, (ds,)))
+    return P, av, pv
+
+
 class GPPack:
     """Device-resident state of ``ds`` GPs sharing X (reference: what Dynamics +
     GaussianProcessRegression hold, src/dynamics.py:33-37, src/gpr.py:24-36) folded into
@@ -232,6 +262,34 @@ class GPPack:
         if rc < 0:
             check(rc, "gpmpc_pack_get_nominal")
         return (W, b) if rc == 1 else None
+
+    def set_noise(self, init_cov=None, action_var=None, process_var=None):
+        """Noise model of the rollout (C ABI ``gpmpc_pack_set_noise``), shared by all trajectories of a call.
+        init_cov: covariance of the start state, (ds, ds) symmetric or a (ds,) vector taken as a diagonal (a scalar: that value on the
+        diagonal); the diagonal rollout uses its diagonal, ``rollout_fullcov`` the whole matrix.  action_var: (da,) variance of each input at
+        every step (a scalar is broadcast).  process_var: (ds,) added to the predicted variance of each state at every step t >= 1.
+        None resets a part to its default (1e-3 I, float32(1e-3), 0); all None restores the defaults.  The values are read from device
+        memory by the kernels: no captured graph, plan or buffer of the pack is dropped."""
+        if isinstance(process_var, str):
+            raise ValueError('process_var="sigma_n" is understood by Dynamics.set_noise_model: a pack does not know the noise of its GPs')
+        P, av, pv = noise_arrays(self.ds, self.da, init_cov, action_var, process_var)
+        hp = lambda a: None if a is None else host_doubles(a)[1]  # noqa: E731
+        with torch.cuda.device(self.device):
+            check(lib().gpmpc_pack_set_noise(self._h, hp(P), hp(av), hp(pv), stream_ptr()), "gpmpc_pack_set_noise")
+        return self
+
+    @property
+    def noise(self):
+        """(init_cov (ds, ds), action_var (da,), process_var (ds,)) as the library holds them."""
+        P, av, pv = np.zeros((self.ds, self.ds)), np.zeros(max(self.da, 1)), np.zeros(self.ds)
+        rc = lib().gpmpc_pack_get_noise(self._h, host_doubles(P)[1], host_doubles(av)[1], host_doubles(pv)[1])
+        if rc < 0:
+            check(rc, "gpmpc_pack_get_noise")
+        return P, av[:self.da], pv
+
+    @property
+    def noise_is_default(self):
+        return lib().gpmpc_pack_get_noise(self._h, None, None, None) == 0
 
     def _fill(self, X, Y, Ky_inv, lambdas, sigma_f, y_is_beta, nominal=None):
         self.X = _dev(X, self.device)

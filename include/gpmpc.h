@@ -153,6 +153,32 @@ int gpmpc_pack_set_nominal(gpmpc_pack* pack, const double* weights_host, const d
 /* 1: a nominal model is set (its coefficients are copied to weights_host / bias_host where these are not NULL), 0: none; GPMPC_E_ARG. */
 int gpmpc_pack_get_nominal(const gpmpc_pack* pack, double* weights_host, double* bias_host);
 
+/* Noise model of the rollout, shared by all trajectories of a call (the reference hard-codes the first two, src/dynamics.py:148,162, and
+ * has no third):
+ *     init_cov    host [ds][ds], symmetric   default 1e-3 I          covariance of the start state.  gpmpc_rollout and everything on top of it
+ *                                                                    use its diagonal (stored as vars[b][0][:]); gpmpc_rollout_fullcov the whole
+ *                                                                    matrix (stored as covs[b][0])
+ *     action_var  host [da]                  default float32(1e-3)   variance of input j at every step
+ *     process_var host [ds]                  default 0               added to the predicted variance of state a at every step t >= 1:
+ *                                                                    var_a = (sf_a^2 + w_a) - T - mu^2, in the full-covariance rollout on the
+ *                                                                    diagonal of Sigma_t.  An additive constant: no Jacobian changes.
+ * A NULL part is reset to its default; all three NULL restores the defaults (with which every call returns what it returned before this
+ * entry point existed, bit for bit).  The values live in ONE device buffer owned by the pack, allocated and filled with the defaults by
+ * gpmpc_pack_create and kept by gpmpc_pack_resize; the kernels read them from there, never as kernel arguments, and there is no variant
+ * of any kernel for a model that is set: a set drops no captured graph and no measured plan, and a new init_cov before every solve replays
+ * the one captured graph (gpmpc_pack_callback_captures stays as it is).  The host arrays are consumed before the call returns; the copy is
+ * enqueued on `stream`.  set belongs to the functions that MODIFY a pack: the caller orders it against rollouts on other streams.
+ * (Up to two launches carry the values; if one fails -- GPMPC_E_LAUNCH --, gpmpc_pack_get_noise still reports what the device holds.)
+ * GPMPC_E_ARG with a text in gpmpc_last_error, the pack left as it was and nothing enqueued: a non-finite value; a negative diagonal entry
+ * of init_cov; a negative entry of action_var or process_var; |P_kl - P_lk| > 1e-12 max |P| (else the mean of each off-diagonal pair is
+ * stored).  Zero variances are legal (an exactly known start state or input: B_k = 1 / lambda_k).
+ * gpmpc_moment_match takes S from its caller and does not read the model.  Not provided: a different init_cov per trajectory of a batch, a
+ * full process-noise matrix, gradients with respect to the noise parameters, state feedback inside the prediction. */
+int gpmpc_pack_set_noise(gpmpc_pack* pack, const double* init_cov_host, const double* action_var_host, const double* process_var_host,
+                         void* stream);
+/* The three parts into the arrays that are not NULL.  1: some part differs from its default, 0: none does; GPMPC_E_ARG. */
+int gpmpc_pack_get_noise(const gpmpc_pack* pack, double* init_cov_host, double* action_var_host, double* process_var_host);
+
 /* Allocate and maintain the cross-covariance weight matrices (one N x N matrix per GP pair a < b): needed by
  * gpmpc_rollout_fullcov and by the analytic cross-covariance Jacobians of gpmpc_moment_match.  Without it
  * cross-covariances are evaluated by a direct N^2 kernel, forward only. */
