@@ -19,7 +19,7 @@ def lib():
             _LIB.gpmpc_cpu_rollout_fullcov.restype = ctypes.c_int
             return _LIB
         so = os.path.join(_HERE, "libgpmpc_cpu.so")
-        srcs = [os.path.join(_HERE, f) for f in ("gpmpc_cpu.c", "gpmpc_cpu_fullcov.c", "gpmpc_cpu_ld.c")]
+        srcs = [os.path.join(_HERE, f) for f in ("gpmpc_cpu.c", "gpmpc_cpu_fullcov.c", "gpmpc_cpu_ld.c", "gpmpc_cpu_given.c")]
         if not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(f) for f in srcs):
             subprocess.run(["make", "-C", _HERE], check=True, capture_output=True)
         _LIB = ctypes.CDLL(so)
@@ -107,3 +107,108 @@ def moment_match_fullcov(X, Ky_inv, Y, lambdas, sigma_f, u, S, nthreads=0):
     if rc != 0:
         raise RuntimeError(f"gpmpc_cpu_moment_match_fullcov failed: {rc}")
     return mean, cov
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# oracle/cport/gpmpc_cpu_given.c: one step and the whole rollout on GIVEN constants, in double ("d") and long double ("ld")
+# ------------------------------------------------------------------------------------------------------------------------------
+_dbl = lambda a: np.ascontiguousarray(np.asarray(a, dtype=np.float64))          # noqa: E731
+_dp = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_double))               # noqa: E731
+
+
+def constants(pb, Ky_inv):
+    """(beta (ds, N), W (ds, N, N)) by their numpy definitions (tests/test_gpu_parity.py::test_pack_constants), in the layout of
+    ``GPPack.beta()`` / ``GPPack.weights()``: the pair (i <= j) at W[a, j, i], off-diagonal pairs doubled, zeros elsewhere."""
+    X, Y, lam, sf, K = _dbl(pb["X"]), _dbl(pb["Y"]), _dbl(pb["lambdas"]), _dbl(pb["sigma_f"]), _dbl(Ky_inv)
+    N, ds = X.shape[0], Y.shape[1]
+    beta, W = np.zeros((ds, N)), np.zeros((ds, N, N))
+    for a in range(ds):
+        beta[a] = K[a] @ Y[:, a]
+        d2 = np.zeros((N, N))
+        for k in range(X.shape[1]):                           # (dimension by dimension: no N x N x D temporary at N = 2310)
+            d2 += (X[:, None, k] - X[None, :, k]) ** 2 / lam[a, k]
+        M = (0.5 * (K[a] + K[a].T) - np.outer(beta[a], beta[a])) * np.exp(-0.25 * d2) * sf[a] ** 4
+        W[a] = (np.triu(M, 1) * 2 + np.diag(np.diag(M))).T
+    return beta, W
+
+
+def constants_ld(pb, Ky_inv):
+    """The same constants with every operation in long double, as gpmpc_cpu_ld.c builds them: numpy ``longdouble`` arrays."""
+    X, Y, lam, sf, K = _dbl(pb["X"]), _dbl(pb["Y"]), _dbl(pb["lambdas"]), _dbl(pb["sigma_f"]), _dbl(Ky_inv)
+    N, ds = X.shape[0], Y.shape[1]
+    assert np.dtype(np.longdouble).itemsize == 16 and np.finfo(np.longdouble).nmant == 63, "x87 extended precision expected"
+    beta, W = np.zeros((ds, N), dtype=np.longdouble), np.zeros((ds, N, N), dtype=np.longdouble)
+    f = lib().gpmpc_given_constants_ld
+    f.restype = ctypes.c_int
+    rc = f(N, ds, X.shape[1], _dp(X), _dp(K), _dp(Y), _dp(lam), _dp(sf), ctypes.c_void_p(beta.ctypes.data), ctypes.c_void_p(W.ctypes.data))
+    if rc != 0:
+        raise RuntimeError(f"gpmpc_given_constants_ld failed: {rc}")
+    return beta, W
+
+
+def _given_args(pb, beta, W):
+    """The leading arguments every gpmpc_given_* entry takes; the arrays are returned too, to keep them alive over the call."""
+    X, lam, sf = _dbl(pb["X"]), _dbl(pb["lambdas"]), _dbl(pb["sigma_f"])
+    N, ds = X.shape[0], pb["ds"]
+    cld = int(np.asarray(W).dtype == np.longdouble)
+    dt = np.longdouble if cld else np.float64
+    assert np.asarray(beta).dtype == dt
+    beta = np.ascontiguousarray(np.asarray(beta)[:, :N], dtype=dt)
+    W = np.ascontiguousarray(W, dtype=dt)
+    Np = W.shape[-1]
+    assert beta.shape == (ds, N) and W.shape == (ds, Np, Np) and Np >= N
+    return (N, Np, ds), (_dp(X), _dp(lam), _dp(sf), ctypes.c_void_p(beta.ctypes.data), ctypes.c_void_p(W.ctypes.data), cld), (X, lam, sf, beta, W)
+
+
+def _given_fn(name, prec):
+    assert prec in ("d", "ld", "cd", "cld")
+    f = getattr(lib(), "%s_%s" % (name, prec))
+    f.restype = ctypes.c_int
+    return f
+
+
+def given_step_diag(pb, beta, W, u, s, prec="ld", nthreads=0):
+    """nq diagonal moment-matching steps on given constants: u, s (nq, D) -> dict(mean, var, A_mean, A_var, A_exp), each (nq, ds)."""
+    (N, Np, ds), cargs, keep = _given_args(pb, beta, W)
+    D = pb["ds"] + pb["da"]
+    u, s = _dbl(u).reshape(-1, D), _dbl(s).reshape(-1, D)
+    nq = u.shape[0]
+    out = [np.zeros((nq, ds)) for _ in range(5)]
+    rc = _given_fn("gpmpc_given_step_diag", prec)(N, Np, ds, D, *cargs, nq, _dp(u), _dp(s), *[_dp(o) for o in out], int(nthreads))
+    if rc != 0:
+        raise RuntimeError(f"gpmpc_given_step_diag failed: {rc}")
+    return dict(zip(("mean", "var", "A_mean", "A_var", "A_exp"), out))
+
+
+def given_step_full(pb, beta, W, u, S, prec="ld", nthreads=0):
+    """nq full-covariance steps on given constants: u (nq, D), S (nq, D, D) -> dict(mean, A_mean (nq, ds), cov, A_cov (nq, ds, ds))."""
+    (N, Np, ds), cargs, keep = _given_args(pb, beta, W)
+    D = pb["ds"] + pb["da"]
+    u, S = _dbl(u).reshape(-1, D), _dbl(S).reshape(-1, D, D)
+    nq = u.shape[0]
+    mean, A_mean, cov, A_cov = np.zeros((nq, ds)), np.zeros((nq, ds)), np.zeros((nq, ds, ds)), np.zeros((nq, ds, ds))
+    rc = _given_fn("gpmpc_given_step_full", prec)(N, Np, ds, D, *cargs, nq, _dp(u), _dp(S), _dp(mean), _dp(cov), _dp(A_mean), _dp(A_cov), int(nthreads))
+    if rc != 0:
+        raise RuntimeError(f"gpmpc_given_step_full failed: {rc}")
+    return {"mean": mean, "cov": cov, "A_mean": A_mean, "A_cov": A_cov}
+
+
+def given_rollout(pb, beta, W, gamma, x0=None, U=None, full=False, prec="ld", nthreads=0):
+    """Whole trajectories on given constants with the cost of src/mpc.py:179-198.  prec "d" / "ld": dict(means, vars or covs, cost);
+    prec "cd" / "cld": dict(cost, grad), the gradient by the complex step, one run per entry of U (small H da only)."""
+    (N, Np, ds), cargs, keep = _given_args(pb, beta, W)
+    da = pb["da"]
+    x0 = _dbl(pb["x0"] if x0 is None else x0).reshape(-1, ds)
+    U = _dbl(pb["U"] if U is None else U)
+    U = U.reshape(-1, U.shape[-2], da)
+    B, H = U.shape[0], U.shape[1]
+    Q, R, xr, ur = _dbl(pb["Q"]), _dbl(pb["R"]), _dbl(pb["x_ref"]), _dbl(pb["u_ref"])
+    means, covs = np.zeros((B, H + 1, ds)), np.zeros((B, H + 1, ds, ds) if full else (B, H + 1, ds))
+    cost, grad = np.zeros(B), np.zeros((B, H, da))
+    rc = _given_fn("gpmpc_given_rollout", prec)(int(bool(full)), N, Np, ds, da, H, B, *cargs, _dp(x0), _dp(U), ctypes.c_double(gamma), _dp(Q), _dp(R),
+                                                _dp(xr), _dp(ur), _dp(means), _dp(covs), _dp(cost), _dp(grad), int(nthreads))
+    if rc != 0:
+        raise RuntimeError(f"gpmpc_given_rollout failed: {rc}")
+    if prec in ("cd", "cld"):
+        return {"cost": cost, "grad": grad}
+    return {"means": means, "covs" if full else "vars": covs, "cost": cost}

@@ -35,6 +35,15 @@ FULLCOV_CASES = [(11,   110, 2, 1, False),
 FULLCOV_H, FULLCOV_B = 3, 2
 
 
+# The rounding-error budget (tests/test_gpu_accuracy.py, tests/test_host_accuracy.py): K = max |error| / (2^-53 x sum of absolute terms) per step.
+# One number per quantity for all forms: twice the worst K measured on an MI355X (means 0.88, variances 0.342, covariances 0.30; the table in
+# tests/test_gpu_accuracy.py), rounded up to one significant digit.  Whole trajectory, against the long double complex step: relative error
+# of the cost (worst 9.5e-10) and of the gradient in norm (worst 7.4e-10), both at N = 520, the worst-conditioned problem of the tables.
+BUDGET_K = {"mean": 2.0, "var": 0.7, "cov": 0.6}
+BUDGET_TRAJ = {"cost": 2e-9, "grad": 2e-9}
+EXCESS_FACTOR = 10.0                                     # a form further than this above K_ref (the floor) on the same case is traced, not absorbed
+
+
 def seed_of(config_id):
     return 77 + config_id
 
@@ -164,3 +173,99 @@ def gpu_rollout_shapes():
     for tag, (cfg, N, ds, da, H, shared, gamma) in JAC_CASES.items():
         out.append(("jacobian " + tag, (cfg, N, ds, da, H, 2, shared), [0, 1], gamma, False))
     return out
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# The step tables of tests/test_gpu_offgrid.py (parity with the C ports at the project tolerances) and tests/test_gpu_accuracy.py (the
+# rounding-error budget): which batch, under which GPMPC_* overrides, reaches which kernel form.  Both modules iterate these.
+# ------------------------------------------------------------------------------------------------------------------------------
+NO_PERSIST = {"GPMPC_PERSIST": "0"}        # (a small training set in a large batch is planned as the whole-horizon kernel: the step-per-launch forms are asked for)
+LADDER_EXPECTED = {("fused_staged", "64x64", "quarter columns"), ("fused_staged", "64x64", "whole tiles"), ("head+pair_sb", "256x64", "tb1"),
+                   ("fused_sb", "256x64", ""), ("fused_sb", "256x32", ""), ("fused_sb", "256x16", ""), ("persist", "", "16 waves"),
+                   ("persist", "", "8 waves"), ("head+pair_sb", "256x256", "big"), ("head+pair_staged", "64x64", "")}
+
+
+def ladder_steps(ds):
+    """The diagonal form ladder at N = LADDER_N: (B, overrides, form, tiling, tag, how the kernel name shows it)."""
+    bs = ladder_batches(ds)
+    narrow = {"GPMPC_FUSED_SB": "1", "GPMPC_PAIR_SB": "1"}
+    return [(bs["small"],       {},                                         "fused_staged",     "64x64",   "quarter columns", ",4,1>"),
+            (bs["one"],         {},                                         "fused_staged",     "64x64",   "quarter columns", ",4,1>"),
+            (bs["whole_tiles"], {},                                         "fused_staged",     "64x64",   "whole tiles",     ",1,1>"),
+            (bs["mid"],         NO_PERSIST,                                 "head+pair_sb",     "256x64",  "tb1",             ""),
+            (bs["mid"],         {"GPMPC_FUSED_SB": "1"},                    "fused_sb",         "256x64",  "",                ",0,1>"),
+            (5,                 dict(narrow, GPMPC_TILING="5"),             "fused_sb",         "256x32",  "",                ",32,1>"),
+            (4,                 dict(narrow, GPMPC_TILING="6"),             "fused_sb",         "256x16",  "",                ",16,1>"),
+            (7,                 {"GPMPC_PERSIST": "16"},                    "persist",          "",        "16 waves",        "x16waves"),
+            (6,                 {"GPMPC_PERSIST": "8"},                     "persist",          "",        "8 waves",         "x8waves"),
+            (bs["big"],         NO_PERSIST,                                 "head+pair_sb",     "256x256", "big",             ""),
+            (5,                 {"GPMPC_PAIR_SB": "0", "GPMPC_FUSED": "0"}, "head+pair_staged", "64x64",   "",                "")]
+
+
+def assert_ladder_plan(plan, step, D):
+    """The plan of a ladder step is the form the step is meant for."""
+    B, env, form, tiling, tag, kern = step
+    assert plan["form"] == form and (not tiling or plan["tiling"] == tiling) and kern in plan["kernel"], (B, env, plan)
+    if tag == "big":                              # two trajectories per wave up to D = 5: the odd batch leaves the last wave half empty
+        assert plan["tb"] == (2 if D <= 5 else 1) and B % 2 == 1, plan
+    if tag == "tb1":
+        assert plan["tb"] == 1, plan
+
+
+def wide_step(tag):
+    """(overrides, assertion on the plan) of a WIDE_CASES entry."""
+    if tag == "256x128":
+        def check(plan):
+            assert plan["form"] == "head+pair_sb" and plan["tiling"] == "256x128" and plan["tb"] == 2, plan
+        return {"GPMPC_PAIR_SB": "1", "GPMPC_TILING": "4"}, check
+
+    def check(plan):
+        assert plan["form"] == "fused_sb" and plan["tiling"] == "256x256" and ",256,1>" in plan["kernel"] and plan["launches_per_step"] == 1, plan
+    return {}, check
+
+
+def shared_steps(ds):
+    """The one-lambda forms at N = LADDER_N, da = 1: (B, overrides, form, tiling, how the kernel name shows it)."""
+    bs = shared_batches(ds)
+    group = {2: 2, 3: 3, 4: 4, 5: 3}[ds]                      # gpmpc_sbs_group at da = 1
+    all_in_one = ds in (3, 4)
+    fsb = {"GPMPC_FUSED_SB": "1"}
+    steps = [(bs["mid"],     NO_PERSIST,               "head+pair_sbs",   "256x64",  ",%d,%d," % (group, ds)),
+             (bs["big"],     NO_PERSIST,               "head+pair_sbs",   "256x256", ",%d,%d," % (group, ds)),
+             (bs["mid"],     fsb,                      "fused_sb_shared", "256x64",  ",0,%d>" % (2 if ds == 4 else group)),      # ds = 4: the 2 + 2 split list
+             (bs["persist"], {"GPMPC_PERSIST": "16"},  "persist",         "",        ",%d>x16waves" % (ds if all_in_one else 2)),
+             (bs["persist"], {"GPMPC_PERSIST": "8"},   "persist",         "",        ",2>x8waves")]
+    if ds == 4:
+        steps.insert(3, (bs["groups"], fsb,            "fused_sb_shared", "256x64",  ",0,4>"))                                   # >= 4200 tile workgroups: all four GPs
+    return steps
+
+
+def assert_shared_plan(plan, step):
+    B, env, form, tiling, kern = step
+    assert plan["form"] == form and (not tiling or plan["tiling"] == tiling) and kern in plan["kernel"].replace(" ", ""), (B, env, plan)
+
+
+def fullcov_steps(ds, shared):
+    """The full-covariance forms: (B, overrides, form).  The two-launch form on each of its tilings, the four-launch form at a small and a
+    large batch; with one lambda, the cross-unit kernel forced on (ds <= 4; its per-unit fallback at ds = 5)."""
+    b_big = fullcov_big_batch(ds)
+    two = {"GPMPC_FC_FORM": "1"}
+    cases = [(3, {}, "two_launch"), (b_big, {}, "two_launch"), (3, dict(two, GPMPC_FC_TILING="4"), "two_launch"), (2, dict(two, GPMPC_FC_TILING="0"), "two_launch"),
+             (1, dict(two, GPMPC_FC_TILING="2"), "two_launch"), (3, {"GPMPC_FC_FORM": "0"}, "four_launch"), (b_big, {"GPMPC_FC_FORM": "0"}, "four_launch")]
+    if shared:
+        forced = {"GPMPC_FC_SHARED": "1"}
+        cases += [(1, forced, "two_launch"), (3, forced, "two_launch"), (5, dict(forced, GPMPC_FC_TILING="4"), "two_launch"),
+                  (2, dict(forced, GPMPC_FC_TILING="0"), "two_launch")]
+    return cases
+
+
+def assert_fullcov_plan(plan, step, ds):
+    """The plan of a full-covariance step; returns a word on the cross units for the label."""
+    B, env, form = step
+    assert plan["form"] == form, (env, plan)
+    if "GPMPC_FC_SHARED" in env:
+        assert plan["shared_cross_units"] == (1 if ds <= 4 else 0), plan
+        return " cross units %s" % ("pair_kernel_sbfx.h" if plan["shared_cross_units"] else "per unit")
+    if form == "two_launch" and B <= 5:
+        assert plan["shared_cross_units"] == 0, plan           # (the shared cross-unit kernel is planned from B Np^2 pairs >= 3.5e7)
+    return ""

@@ -19,6 +19,7 @@ Observed on an MI355X, worst deviation per form as a fraction of its tolerance (
     full covariance two- / four-launch 3e-5 | 1.4e-2 | 3e-4 | 1e-5        cross-unit kernel 1e-5 | 9e-5 | 4e-6 | 1e-6        nominal 2e-4 | 3e-3 | 2e-4 | 1e-5
     constraints 8e-4, dense Jacobian 4e-5        moment_match 1e-5 | 3e-5        class path 4e-4 | 1e-3 | 1e-4 | 2e-6
 No form deviates by more than 1.4 % of a tolerance: no kernel was found wrong.
+(What these fractions mean in units of rounding error, form by form: tests/test_gpu_accuracy.py.  The step tables live in tests/offgrid_problems.py.)
 """
 import contextlib
 import ctypes
@@ -35,7 +36,7 @@ from nominal_reference import assert_reference_is_sane, nominal_rollout, synth_n
 pytestmark = pytest.mark.gpu
 
 MEAN_RTOL, VAR_RTOL, COST_RTOL, GRAD_RTOL = OG.GPU_MEAN_RTOL, OG.GPU_VAR_RTOL, OG.GPU_COST_RTOL, OG.GPU_GRAD_RTOL
-NO_PERSIST = {"GPMPC_PERSIST": "0"}        # (a small training set in a large batch is planned as the whole-horizon kernel: the step-per-launch forms are asked for)
+NO_PERSIST = OG.NO_PERSIST
 _refs = {}
 
 
@@ -168,9 +169,7 @@ def _run_diag(G, pack, pb, cost, B, args, gamma, what, graph=False):
 # ------------------------------------------------------------------------------------------------------------------------------
 # 1. the diagonal form ladder
 # ------------------------------------------------------------------------------------------------------------------------------
-LADDER_EXPECTED = {("fused_staged", "64x64", "quarter columns"), ("fused_staged", "64x64", "whole tiles"), ("head+pair_sb", "256x64", "tb1"),
-                   ("fused_sb", "256x64", ""), ("fused_sb", "256x32", ""), ("fused_sb", "256x16", ""), ("persist", "", "16 waves"),
-                   ("persist", "", "8 waves"), ("head+pair_sb", "256x256", "big"), ("head+pair_staged", "64x64", "")}
+LADDER_EXPECTED = OG.LADDER_EXPECTED
 
 
 @pytest.mark.parametrize("ds,da", OG.LADDER_DIMS)
@@ -184,28 +183,12 @@ def test_diag_form_ladder_vs_cport(G, ds, da):
     pb, kinv = OG.problem(*args)
     H = pb["H"]
     pack, cost = _pack(G, pb, kinv), _cost(G, pb)
-    narrow = {"GPMPC_FUSED_SB": "1", "GPMPC_PAIR_SB": "1"}
-    #        B                  overrides                                   form                tiling     tag                how the kernel name shows it
-    steps = [(bs["small"],       {},                                         "fused_staged",     "64x64",   "quarter columns", ",4,1>"),
-             (bs["one"],         {},                                         "fused_staged",     "64x64",   "quarter columns", ",4,1>"),
-             (bs["whole_tiles"], {},                                         "fused_staged",     "64x64",   "whole tiles",     ",1,1>"),
-             (bs["mid"],         NO_PERSIST,                                 "head+pair_sb",     "256x64",  "tb1",             ""),
-             (bs["mid"],         {"GPMPC_FUSED_SB": "1"},                    "fused_sb",         "256x64",  "",                ",0,1>"),
-             (5,                 dict(narrow, GPMPC_TILING="5"),             "fused_sb",         "256x32",  "",                ",32,1>"),
-             (4,                 dict(narrow, GPMPC_TILING="6"),             "fused_sb",         "256x16",  "",                ",16,1>"),
-             (7,                 {"GPMPC_PERSIST": "16"},                    "persist",          "",        "16 waves",        "x16waves"),
-             (6,                 {"GPMPC_PERSIST": "8"},                     "persist",          "",        "8 waves",         "x8waves"),
-             (bs["big"],         NO_PERSIST,                                 "head+pair_sb",     "256x256", "big",             ""),
-             (5,                 {"GPMPC_PAIR_SB": "0", "GPMPC_FUSED": "0"}, "head+pair_staged", "64x64",   "",                "")]
+    steps = OG.ladder_steps(ds)                              # (B, overrides, form, tiling, tag, how the kernel name shows it)
     reached = set()
     for B, env, form, tiling, tag, kern in steps:
         with _tuning(pack, env):
             plan = pack.plan(B, H)
-            assert plan["form"] == form and (not tiling or plan["tiling"] == tiling) and kern in plan["kernel"], (B, env, plan)
-            if tag == "big":                          # two trajectories per wave up to D = 5: the odd batch leaves the last wave half empty
-                assert plan["tb"] == (2 if D <= 5 else 1) and B % 2 == 1, plan
-            if tag == "tb1":
-                assert plan["tb"] == 1, plan
+            OG.assert_ladder_plan(plan, (B, env, form, tiling, tag, kern), D)
             assert pack.plan(B, H, want_grad=False)["form"] == form
             _run_diag(G, pack, pb, cost, B, args, -1.0, "ds=%d da=%d B=%d %s %s %s" % (ds, da, B, form, tiling, tag))
             if tag == "tb1":                          # the captured graph of this dimension: head + pair kernel in concurrent sub-batches
@@ -229,13 +212,10 @@ def test_wide_tilings_vs_cport(G, tag):
     args = (cfg, N, ds, da, H, B, False)
     pb, kinv = OG.problem(*args)
     pack, cost = _pack(G, pb, kinv), _cost(G, pb)
-    env = {"GPMPC_PAIR_SB": "1", "GPMPC_TILING": "4"} if tag == "256x128" else {}
+    env, assert_plan = OG.wide_step(tag)
     with _tuning(pack, env):
         plan = pack.plan(B, H)
-        if tag == "256x128":
-            assert plan["form"] == "head+pair_sb" and plan["tiling"] == "256x128" and plan["tb"] == 2, plan
-        else:
-            assert plan["form"] == "fused_sb" and plan["tiling"] == "256x256" and ",256,1>" in plan["kernel"] and plan["launches_per_step"] == 1, plan
+        assert_plan(plan)
         _run_diag(G, pack, pb, cost, B, args, -1.0, "%s N=%d ds=%d B=%d %s" % (tag, N, ds, B, plan["form"]))
     del pack
     torch.cuda.empty_cache()
@@ -268,22 +248,13 @@ def test_shared_lambda_forms_with_distinct_sigma_f(G, ds, da):
     lam = pb["lambdas"].copy()
     lam[ds - 1, 0] = np.nextafter(lam[ds - 1, 0], 10.0)
     assert not G.GPPack(pb["X"], pb["Y"], kinv, lam, pb["sigma_f"]).shared_lambda
-    group = {2: 2, 3: 3, 4: 4, 5: 3}[ds]                      # gpmpc_sbs_group at da = 1
-    all_in_one = ds in (3, 4)
-    fsb = {"GPMPC_FUSED_SB": "1"}
-    steps = [(bs["mid"],     NO_PERSIST,               "head+pair_sbs",   "256x64",  ",%d,%d," % (group, ds)),
-             (bs["big"],     NO_PERSIST,               "head+pair_sbs",   "256x256", ",%d,%d," % (group, ds)),
-             (bs["mid"],     fsb,                      "fused_sb_shared", "256x64",  ",0,%d>" % (2 if ds == 4 else group)),      # ds = 4: the 2 + 2 split list
-             (bs["persist"], {"GPMPC_PERSIST": "16"},  "persist",         "",        ",%d>x16waves" % (ds if all_in_one else 2)),
-             (bs["persist"], {"GPMPC_PERSIST": "8"},   "persist",         "",        ",2>x8waves")]
-    if ds == 4:
-        steps.insert(3, (bs["groups"], fsb,            "fused_sb_shared", "256x64",  ",0,4>"))                                   # >= 4200 tile workgroups: all four GPs
+    steps = OG.shared_steps(ds)                              # (B, overrides, form, tiling, how the kernel name shows it)
     reached = set()
     for B, env, form, tiling, kern in steps:
         what = "shared ds=%d da=%d B=%d %s %s %s" % (ds, da, B, form, tiling, kern)
         with _tuning(pack, env):
             plan = pack.plan(B, H)
-            assert plan["form"] == form and (not tiling or plan["tiling"] == tiling) and kern in plan["kernel"].replace(" ", ""), (B, env, plan)
+            OG.assert_shared_plan(plan, (B, env, form, tiling, kern))
             r = _run_diag(G, pack, pb, cost, B, args, -1.0, what)
         with _tuning(pack, dict(env, GPMPC_SHARED="0")):
             plan0 = pack.plan(B, H)
@@ -312,14 +283,9 @@ def test_fullcov_rollout_vs_cport(G, case):
     pb, kinv = OG.problem(*args)
     pack, cost = _pack(G, pb, kinv), _cost(G, pb)
     pack.enable_fullcov()
-    two = {"GPMPC_FC_FORM": "1"}
-    cases = [(3, {}, "two_launch"), (b_big, {}, "two_launch"), (3, dict(two, GPMPC_FC_TILING="4"), "two_launch"), (2, dict(two, GPMPC_FC_TILING="0"), "two_launch"),
-             (1, dict(two, GPMPC_FC_TILING="2"), "two_launch"), (3, {"GPMPC_FC_FORM": "0"}, "four_launch"), (b_big, {"GPMPC_FC_FORM": "0"}, "four_launch")]
+    cases = OG.fullcov_steps(ds, shared)                     # (B, overrides, form)
     if shared:
         assert pack.shared_lambda
-        forced = {"GPMPC_FC_SHARED": "1"}
-        cases += [(1, forced, "two_launch"), (3, forced, "two_launch"), (5, dict(forced, GPMPC_FC_TILING="4"), "two_launch"),
-                  (2, dict(forced, GPMPC_FC_TILING="0"), "two_launch")]
     res = {}
     for B, env, form in cases:
         what = "fullcov ds=%d da=%d N=%d B=%d %s" % (ds, da, N, B, env or "default")
@@ -327,12 +293,7 @@ def test_fullcov_rollout_vs_cport(G, case):
         ref = _ref_fullcov(args, pick)
         with _tuning(pack, env):
             plan = pack.plan_fullcov(B, H)
-            assert plan["form"] == form, (env, plan)
-            if "GPMPC_FC_SHARED" in env:
-                assert plan["shared_cross_units"] == (1 if ds <= 4 else 0), plan
-                what += " cross units %s" % ("pair_kernel_sbfx.h" if plan["shared_cross_units"] else "per unit")
-            elif form == "two_launch" and B <= 5:
-                assert plan["shared_cross_units"] == 0, plan       # (the shared cross-unit kernel is planned from B Np^2 pairs >= 3.5e7)
+            what += OG.assert_fullcov_plan(plan, (B, env, form), ds)
             r = G.rollout_fullcov(pack, pb["x0"][:B], pb["U"][:B], cost)
             f = G.rollout_fullcov(pack, pb["x0"][:B], pb["U"][:B], cost, want_grad=False)
         _check_fullcov(r, ref, pick, what)
