@@ -193,9 +193,10 @@ def given_step_full(pb, beta, W, u, S, prec="ld", nthreads=0):
     return {"mean": mean, "cov": cov, "A_mean": A_mean, "A_cov": A_cov}
 
 
-def given_rollout(pb, beta, W, gamma, x0=None, U=None, full=False, prec="ld", nthreads=0):
+def given_rollout(pb, beta, W, gamma, x0=None, U=None, full=False, prec="ld", nthreads=0, init_cov=None, action_var=None, process_var=None):
     """Whole trajectories on given constants with the cost of src/mpc.py:179-198.  prec "d" / "ld": dict(means, vars or covs, cost);
-    prec "cd" / "cld": dict(cost, grad), the gradient by the complex step, one run per entry of U (small H da only)."""
+    prec "cd" / "cld": dict(cost, grad), the gradient by the complex step, one run per entry of U (small H da only).
+    init_cov (ds, ds), action_var (da,), process_var (ds,): the noise model of the pack, each None = the reference's constants."""
     (N, Np, ds), cargs, keep = _given_args(pb, beta, W)
     da = pb["da"]
     x0 = _dbl(pb["x0"] if x0 is None else x0).reshape(-1, ds)
@@ -205,8 +206,10 @@ def given_rollout(pb, beta, W, gamma, x0=None, U=None, full=False, prec="ld", nt
     Q, R, xr, ur = _dbl(pb["Q"]), _dbl(pb["R"]), _dbl(pb["x_ref"]), _dbl(pb["u_ref"])
     means, covs = np.zeros((B, H + 1, ds)), np.zeros((B, H + 1, ds, ds) if full else (B, H + 1, ds))
     cost, grad = np.zeros(B), np.zeros((B, H, da))
+    noise = [None if a is None else _dbl(a).reshape(shape) for a, shape in ((init_cov, (ds, ds)), (action_var, (da,)), (process_var, (ds,)))]
     rc = _given_fn("gpmpc_given_rollout", prec)(int(bool(full)), N, Np, ds, da, H, B, *cargs, _dp(x0), _dp(U), ctypes.c_double(gamma), _dp(Q), _dp(R),
-                                                _dp(xr), _dp(ur), _dp(means), _dp(covs), _dp(cost), _dp(grad), int(nthreads))
+                                                _dp(xr), _dp(ur), _dp(means), _dp(covs), _dp(cost), _dp(grad), int(nthreads),
+                                                *[None if a is None else _dp(a) for a in noise])
     if rc != 0:
         raise RuntimeError(f"gpmpc_given_rollout failed: {rc}")
     if prec in ("cd", "cld"):

@@ -83,6 +83,7 @@ typedef struct {
     const void *beta, *M;    /* [ds][N] and [ds][Np][Np], double (cld = 0) or long double */
     int cld;
     double gamma; const double *Q, *R, *xref, *uref;
+    const double *init_cov, *action_var, *process_var;    /* noise model, each NULL = the constants below */
 } ctx_t;
 
 static inline real FN(cb)(const ctx_t* c, int a, int i) {
@@ -249,10 +250,18 @@ static void FN(step_full)(const ctx_t* c, const num* u, const num* S, num* mt, n
 }
 
 /* One trajectory: means [H+1][ds], covs [H+1][ds][ds] (diagonal rollout: off-diagonal zeros); returns the cost of
- * src/mpc.py:179-198.  Start and action noise as src/dynamics.py:145-163: Sigma_0 = 1e-3 I, action variance float32(1e-3). */
+ * src/mpc.py:179-198.  Start and action noise as src/dynamics.py:145-163: Sigma_0 = 1e-3 I, action variance float32(1e-3), unless the
+ * noise model of the pack is given: init_cov [ds][ds] (the diagonal rollout takes its diagonal), action_var [da], process_var [ds] added
+ * to the predicted variance of every step t >= 1.  NULL keeps the constants and the bits. */
 static num FN(rollout_one)(const ctx_t* c, int full, const double* x0, const num* U, num* means, num* covs) {
     const int N = c->N, ds = c->ds, da = c->da, D = c->D, H = c->H;
-    for (int k = 0; k < ds; ++k) { means[k] = (real)x0[k]; for (int l = 0; l < ds; ++l) covs[k * ds + l] = (k == l) ? (real)1e-3 : (real)0.0; }
+    for (int k = 0; k < ds; ++k) {
+        means[k] = (real)x0[k];
+        for (int l = 0; l < ds; ++l) {
+            if (!c->init_cov) covs[k * ds + l] = (k == l) ? (real)1e-3 : (real)0.0;
+            else covs[k * ds + l] = (full || k == l) ? (real)c->init_cov[k * ds + l] : (real)0.0;
+        }
+    }
     num* V = (num*)malloc(sizeof(num) * (size_t)N * D);
     num* AV = (num*)malloc(sizeof(num) * (size_t)N * D);
     num* gq = (num*)malloc(sizeof(num) * (size_t)N * 2);
@@ -265,13 +274,14 @@ static num FN(rollout_one)(const ctx_t* c, int full, const double* x0, const num
         num* ct = covs + (size_t)t * ds * ds;
         for (int k = 0; k < D * D; ++k) S[k] = (real)0.0;
         for (int k = 0; k < ds; ++k) { u[k] = means[(t - 1) * ds + k]; for (int l = 0; l < ds; ++l) S[k * D + l] = covs[((size_t)(t - 1) * ds + k) * ds + l]; }
-        for (int k = 0; k < da; ++k) { u[ds + k] = U[(t - 1) * da + k]; S[(ds + k) * D + ds + k] = act_var; }
+        for (int k = 0; k < da; ++k) { u[ds + k] = U[(t - 1) * da + k]; S[(ds + k) * D + ds + k] = c->action_var ? (real)c->action_var[k] : act_var; }
         if (full) FN(step_full)(c, u, S, means + (size_t)t * ds, ct, 0, 0, V, AV, gq, Z2, rowz, rowa);
         else {
             for (int k = 0; k < D; ++k) s[k] = S[k * D + k];
             FN(step_diag)(c, u, s, means + (size_t)t * ds, vt, 0, 0, 0, rowz, rowa, rowa + N);
             for (int k = 0; k < ds; ++k) for (int l = 0; l < ds; ++l) ct[k * ds + l] = (k == l) ? vt[k] : (num)(real)0.0;
         }
+        if (c->process_var) for (int k = 0; k < ds; ++k) ct[k * ds + k] += (real)c->process_var[k];
     }
     free(V); free(AV); free(gq); free(Z2); free(rowz); free(rowa);
     num total = (real)0.0;
@@ -306,13 +316,14 @@ static int FN(bad_shape)(int N, int Np, int ds, int D) { return D > MAXD || ds <
 int FN(gpmpc_given_rollout)(int full, int N, int Np, int ds, int da, int H, int B, const double* X, const double* lam,
                             const double* sf, const void* beta, const void* M, int cld, const double* x0, const double* U,
                             double gamma, const double* Q, const double* R, const double* xref, const double* uref,
-                            double* means, double* covs, double* cost, double* grad, int nthreads) {
+                            double* means, double* covs, double* cost, double* grad, int nthreads,
+                            const double* init_cov, const double* action_var, const double* process_var) {
     const int D = ds + da, n = H * da;
     if (FN(bad_shape)(N, Np, ds, D) || H < 1) return -1;
 #ifdef _OPENMP
     if (nthreads > 0) omp_set_num_threads(nthreads);
 #endif
-    const ctx_t c = {N, Np, ds, da, D, H, X, lam, sf, beta, M, cld, gamma, Q, R, xref, uref};
+    const ctx_t c = {N, Np, ds, da, D, H, X, lam, sf, beta, M, cld, gamma, Q, R, xref, uref, init_cov, action_var, process_var};
     num* Uc = (num*)malloc(sizeof(num) * (size_t)n);
     num* m = (num*)malloc(sizeof(num) * (size_t)(H + 1) * ds);
     num* s = (num*)malloc(sizeof(num) * (size_t)(H + 1) * ds * ds);
