@@ -21,6 +21,7 @@ LBFGS_MAX_STARTS = 256
 LBFGS_MAX_HISTORY = 16
 WANT_GRAD = 1
 COV_BUG_COMPAT = 2
+DESCRIBE_WANT_COV = 0x100      # gpmpc_moment_match_describe: a call with out_cov
 USE_GRAPH = 4
 FP32_ACCUM = 8
 FP32_ALL = 16
@@ -123,6 +124,7 @@ SIGNATURES = {
     "gpmpc_pack_export": (_i, [_vp, _vp, _vp, _vp]),
     "gpmpc_moment_match_workspace_bytes": (_sz, [_vp, _i]),
     "gpmpc_moment_match": (_i, [_vp, _i, _vp, _vp, _u] + [_vp] * 10 + [_vp, _sz, _vp]),
+    "gpmpc_moment_match_describe": (_i, [_vp, _i, _u, ctypes.c_char_p, _sz]),
     "gpmpc_cost": (_i, [_i, _i, _i, _i, ctypes.POINTER(CostParamsC), _vp, _vp, _vp, _vp, _vp]),
     "gpmpc_cost_grad": (_i, [_i, _i, _i, _i, ctypes.POINTER(CostParamsC)] + [_vp] * 8),
     "gpmpc_cost_schedule_create": (_i, [_i, _i, _i, ctypes.POINTER(_i)]),

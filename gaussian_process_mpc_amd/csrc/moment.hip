@@ -305,6 +305,24 @@ extern "C" size_t gpmpc_moment_match_workspace_bytes(const gpmpc_pack* p, int nq
     return best;
 }
 
+// What gpmpc_moment_match would launch for nq queries with these flags (GPMPC_DESCRIBE_WANT_COV: a call with out_cov): the plan
+// of the call below, in words; nothing is launched.
+extern "C" int gpmpc_moment_match_describe(const gpmpc_pack* p, int nq, unsigned flags, char* out, size_t out_bytes) {
+    if (!p || !out || out_bytes < 128 || nq < 1) return GPMPC_E_ARG;
+    if (!p->built || p->nominal) return GPMPC_E_STATE;
+    const bool grad = (flags & GPMPC_WANT_GRAD) != 0, bug = (flags & GPMPC_COV_BUG_COMPAT) != 0;
+    const bool want_cov = (flags & GPMPC_DESCRIBE_WANT_COV) != 0;
+    const bool pair_cov = want_cov && !bug && p->fullcov && p->npairs > 0;          // as gpmpc_moment_match_ex
+    MomPlan r;
+    plan_mom(p, nq, grad, pair_cov, p->D, &r);
+    const gpmpc_worklist& w = p->wl[r.mode][r.tiling];
+    // (the column-split tiles run the staged kernel with 4 waves; tb is the plan's, which the scalar-broadcast kernel does not read: see run_mom)
+    snprintf(out, out_bytes, "tiling=%dx%d sbf=%d tb=%d waves=%d nunits=%d nwork=%d cross=%s workspace=%zu", w.it, w.jt, r.sbf, r.tb,
+             (!r.sbf && r.tiling == 1) ? 4 : r.waves, r.nunits, r.nwork,
+             pair_cov ? "pair" : ((want_cov && p->ds > 1) ? "direct" : "none"), r.total);
+    return GPMPC_OK;
+}
+
 template <int D>
 static int run_mom(const gpmpc_pack* p, MomArgs& A, const MomPlan& r, bool grad, hipStream_t s, int* pairs_dev) {
     hipLaunchKernelGGL(k_mom_prep<D>, dim3(A.nq, A.nunits), dim3(256), 0, s, A);

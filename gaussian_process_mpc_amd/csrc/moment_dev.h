@@ -443,13 +443,21 @@ __device__ __forceinline__ void mom_finish_unit(const MomArgs& A, const double* 
             if (A.dvar_du) A.dvar_du[((size_t)q * ds + a) * D + k] = dv;
             if (A.dcov_du) A.dcov_du[(((size_t)q * ds + a) * ds + a) * D + k] = dv;
         }
-        for (int e = 0; e < D * D; ++e) {
-            const double dT_dS = -0.5 * T * Bm[e] + 8.0 * c * CZC[e];
-            const double dv = -dT_dS - 2.0 * mu * dmu_dS[e];
-            A.dmean_dS[((size_t)q * ds + a) * D * D + e] = dmu_dS[e];
-            if (A.dvar_dS) A.dvar_dS[((size_t)q * ds + a) * D * D + e] = dv;
-            if (A.dcov_dS) A.dcov_dS[(((size_t)q * ds + a) * ds + a) * D * D + e] = dv;
-        }
+        // d/dS is the SYMMETRISED derivative: [k][l] and [l][k] get the mean of the two evaluations, so they are the same bits (the
+        // inverse by elimination and the products (B S2) B, Cm^T (Z2 Cm) are symmetric only up to rounding); the diagonal is unchanged
+#pragma unroll
+        for (int k = 0; k < D; ++k)
+#pragma unroll
+            for (int l = k; l < D; ++l) {
+                const int e = k * D + l, f = l * D + k;
+                const double dT_e = -0.5 * T * Bm[e] + 8.0 * c * CZC[e], dT_f = -0.5 * T * Bm[f] + 8.0 * c * CZC[f];
+                const double dm = 0.5 * (dmu_dS[e] + dmu_dS[f]);
+                const double dv = 0.5 * ((-dT_e - 2.0 * mu * dmu_dS[e]) + (-dT_f - 2.0 * mu * dmu_dS[f]));
+                double* om = A.dmean_dS + ((size_t)q * ds + a) * D * D;
+                om[e] = dm; om[f] = dm;
+                if (A.dvar_dS) { double* ov = A.dvar_dS + ((size_t)q * ds + a) * D * D; ov[e] = dv; ov[f] = dv; }
+                if (A.dcov_dS) { double* oc = A.dcov_dS + (((size_t)q * ds + a) * ds + a) * D * D; oc[e] = dv; oc[f] = dv; }
+            }
     } else {                                                  // cross unit (a, b): F = c Z0, Cov = F - mu_a mu_b
         const int pr = u - ds, a = A.pair_ab[2 * pr], b = A.pair_ab[2 * pr + 1];
         const double* spa = spbase + ((size_t)q * nunits + a) * A.sps;
@@ -469,11 +477,18 @@ __device__ __forceinline__ void mom_finish_unit(const MomArgs& A, const double* 
             A.dcov_du[(((size_t)q * ds + a) * ds + b) * D + k] = d;
             A.dcov_du[(((size_t)q * ds + b) * ds + a) * D + k] = d;
         }
-        for (int e = 0; e < D * D; ++e) {
-            const double d = -0.5 * F * Bm[e] + 2.0 * c * CZC[e] - mub * da_dS[e] - mua * db_dS[e];
-            A.dcov_dS[(((size_t)q * ds + a) * ds + b) * D * D + e] = d;
-            A.dcov_dS[(((size_t)q * ds + b) * ds + a) * D * D + e] = d;
-        }
+#pragma unroll
+        for (int k = 0; k < D; ++k)                           // symmetrised as above
+#pragma unroll
+            for (int l = k; l < D; ++l) {
+                const int e = k * D + l, f = l * D + k;
+                const double d_e = -0.5 * F * Bm[e] + 2.0 * c * CZC[e] - mub * da_dS[e] - mua * db_dS[e];
+                const double d_f = -0.5 * F * Bm[f] + 2.0 * c * CZC[f] - mub * da_dS[f] - mua * db_dS[f];
+                const double d = 0.5 * (d_e + d_f);
+                double* o1 = A.dcov_dS + (((size_t)q * ds + a) * ds + b) * D * D;
+                double* o2 = A.dcov_dS + (((size_t)q * ds + b) * ds + a) * D * D;
+                o1[e] = d; o1[f] = d; o2[e] = d; o2[f] = d;
+            }
     }
 }
 

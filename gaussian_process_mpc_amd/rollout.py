@@ -419,6 +419,20 @@ class GPPack:
             out[k] = int(v) if v.lstrip("-").isdigit() else v
         return out
 
+    def plan_moment_match(self, nq, want_cov=False, want_grad=False, bug_compatible=False):
+        """What ``moment_match`` launches for nq queries with these options (C ABI ``gpmpc_moment_match_describe``; nothing runs):
+        dict with ``tiling``, ``sbf`` (1: scalar-broadcast pair kernel), ``tb``, ``waves``, ``nunits``, ``nwork``, ``cross``
+        (``pair`` | ``direct`` | ``none``: who evaluates the cross-covariances and their Jacobians) and ``workspace`` (bytes this call needs)."""
+        buf = ctypes.create_string_buffer(256)
+        flags = ((_lib.WANT_GRAD if want_grad else 0) | (_lib.COV_BUG_COMPAT if bug_compatible else 0)
+                 | (_lib.DESCRIBE_WANT_COV if want_cov else 0))
+        check(lib().gpmpc_moment_match_describe(self._h, int(nq), flags, buf, 256), "gpmpc_moment_match_describe")
+        out = {}
+        for kv in buf.value.decode().split():
+            k, v = kv.split("=", 1)
+            out[k] = int(v) if v.lstrip("-").isdigit() else v
+        return out
+
     def autotune(self, B, H, want_grad=True, graph=False):
         """Time the candidate plans of this call shape on this device and keep the fastest for later calls (C ABI
         ``gpmpc_pack_autotune``).  Returns a list of dicts (``name``, ``ms``, ``winner``, plan fields), the default plan first."""
@@ -678,7 +692,7 @@ def moment_match(pack, u, S, want_cov=False, want_grad=False, bug_compatible=Fal
         out.update(dmean_du=e(nq, ds, D), dmean_dS=e(nq, ds, D, D), dvar_du=e(nq, ds, D), dvar_dS=e(nq, ds, D, D))
         if want_cov and ds > 1:
             # pair kernel's cross units when the pack has them (enable_fullcov) and the consistent form is asked for, else the direct
-            # kernel (either form); diagonal (a, a) entries are not written: zero-filled
+            # kernel (either form); the diagonal (a, a) entries are written too (= dvar_du / dvar_dS, by the variance units)
             out.update(dcov_du=torch.zeros((nq, ds, ds, D), dtype=torch.float64, device=dev),
                        dcov_dS=torch.zeros((nq, ds, ds, D, D), dtype=torch.float64, device=dev))
     nbytes = lib().gpmpc_moment_match_workspace_bytes(pack.handle, nq)

@@ -209,9 +209,19 @@ int gpmpc_pack_export(const gpmpc_pack* pack, double* beta_out, double* weights_
  *   with GPMPC_WANT_GRAD (the first four non-NULL):
  *     dmean_du dev [nq][ds][D], dmean_dS dev [nq][ds][D][D] (symmetrised),
  *     dvar_du  dev [nq][ds][D], dvar_dS  dev [nq][ds][D][D] (symmetrised),
- *     dcov_du  dev [nq][ds][ds][D], dcov_dS dev [nq][ds][ds][D][D] or both NULL: Jacobians of the full covariance
- *              (consistent form only; needs gpmpc_pack_enable_fullcov, else GPMPC_E_STATE)
+ *     dcov_du  dev [nq][ds][ds][D], dcov_dS dev [nq][ds][ds][D][D] or both NULL: Jacobians of the full covariance,
+ *              diagonal (a, a) entries (= dvar_du / dvar_dS) included.  On a pack with gpmpc_pack_enable_fullcov and in the
+ *              consistent form the pair kernel's cross units supply the off-diagonal entries; without the cross weights, or
+ *              with GPMPC_COV_BUG_COMPAT, the direct N^2 kernel does (in that form [a][b] != [b][a], both are written).
+ *              GPMPC_E_STATE only without GPMPC_WANT_GRAD or without out_cov; GPMPC_E_ARG if only one of the two is given.
+ * gpmpc_moment_match_describe writes what a call of this shape would launch, as "key=value" words, and launches nothing:
+ *   tiling=IxJ (tile of the pair kernel's work list) sbf=0|1 (scalar-broadcast kernel) tb=1|2 (queries per workgroup)
+ *   waves= nunits= nwork= cross=pair|direct|none (who evaluates the cross-covariances) workspace= (the bytes this very call
+ *   needs: at most gpmpc_moment_match_workspace_bytes, which covers every call of nq queries).  flags as for the call plus
+ *   GPMPC_DESCRIBE_WANT_COV for a call with out_cov.  out_bytes >= 128.
  * ------------------------------------------------------------------------- */
+#define GPMPC_DESCRIBE_WANT_COV 0x100u
+int gpmpc_moment_match_describe(const gpmpc_pack* pack, int nq, unsigned flags, char* out, size_t out_bytes);
 size_t gpmpc_moment_match_workspace_bytes(const gpmpc_pack* pack, int nq);
 int gpmpc_moment_match(const gpmpc_pack* pack, int nq, const double* u_dev, const double* S_dev,
                        unsigned flags, double* out_mean, double* out_var, double* out_cov, double* out_l,

@@ -180,17 +180,42 @@ def given_step_diag(pb, beta, W, u, s, prec="ld", nthreads=0):
     return dict(zip(("mean", "var", "A_mean", "A_var", "A_exp"), out))
 
 
-def given_step_full(pb, beta, W, u, S, prec="ld", nthreads=0):
-    """nq full-covariance steps on given constants: u (nq, D), S (nq, D, D) -> dict(mean, A_mean (nq, ds), cov, A_cov (nq, ds, ds))."""
+def given_step_full(pb, beta, W, u, S, prec="ld", nthreads=0, bug=False, want_l=False):
+    """nq full-covariance steps on given constants: u (nq, D), S (nq, D, D) -> dict(mean, A_mean (nq, ds), cov, A_cov (nq, ds, ds)).
+    S is read as given (the HIP kernels read (S + S^T)/2: pass that).  bug: the reference's transposed cross term (GPMPC_COV_BUG_COMPAT),
+    every ordered pair (a, b) a sum of its own.  want_l: also ``l`` (nq, ds, N), l_i = c_m exp(-1/2 v_i^T B v_i)."""
     (N, Np, ds), cargs, keep = _given_args(pb, beta, W)
     D = pb["ds"] + pb["da"]
     u, S = _dbl(u).reshape(-1, D), _dbl(S).reshape(-1, D, D)
     nq = u.shape[0]
     mean, A_mean, cov, A_cov = np.zeros((nq, ds)), np.zeros((nq, ds)), np.zeros((nq, ds, ds)), np.zeros((nq, ds, ds))
-    rc = _given_fn("gpmpc_given_step_full", prec)(N, Np, ds, D, *cargs, nq, _dp(u), _dp(S), _dp(mean), _dp(cov), _dp(A_mean), _dp(A_cov), int(nthreads))
+    l = np.zeros((nq, ds, N)) if want_l else None
+    rc = _given_fn("gpmpc_given_step_full", prec)(N, Np, ds, D, *cargs, nq, _dp(u), _dp(S), _dp(mean), _dp(cov), _dp(A_mean), _dp(A_cov), int(nthreads),
+                                                  int(bool(bug)), None if l is None else _dp(l))
     if rc != 0:
         raise RuntimeError(f"gpmpc_given_step_full failed: {rc}")
-    return {"mean": mean, "cov": cov, "A_mean": A_mean, "A_cov": A_cov}
+    out = {"mean": mean, "cov": cov, "A_mean": A_mean, "A_cov": A_cov}
+    if want_l:
+        out["l"] = l
+    return out
+
+
+def given_step_full_jac(pb, beta, W, u, S, prec="cld", nthreads=0, bug=False):
+    """Jacobians of nq full-covariance steps by the complex step, at (S + S^T)/2 and symmetrised in S: dict(dmean_du (nq, ds, D),
+    dmean_dS (nq, ds, D, D), dcov_du (nq, ds, ds, D), dcov_dS (nq, ds, ds, D, D)); the diagonal of dcov is the variance Jacobian.
+    prec "cd" | "cld".  D + D (D + 1) / 2 runs of the step per query."""
+    assert prec in ("cd", "cld")
+    (N, Np, ds), cargs, keep = _given_args(pb, beta, W)
+    D = pb["ds"] + pb["da"]
+    u, S = _dbl(u).reshape(-1, D), _dbl(S).reshape(-1, D, D)
+    nq = u.shape[0]
+    out = {"dmean_du": np.zeros((nq, ds, D)), "dmean_dS": np.zeros((nq, ds, D, D)),
+           "dcov_du": np.zeros((nq, ds, ds, D)), "dcov_dS": np.zeros((nq, ds, ds, D, D))}
+    rc = _given_fn("gpmpc_given_step_full_jac", prec)(N, Np, ds, D, *cargs, nq, _dp(u), _dp(S), int(bool(bug)), _dp(out["dmean_du"]),
+                                                      _dp(out["dmean_dS"]), _dp(out["dcov_du"]), _dp(out["dcov_dS"]), int(nthreads))
+    if rc != 0:
+        raise RuntimeError(f"gpmpc_given_step_full_jac failed: {rc}")
+    return out
 
 
 def given_rollout(pb, beta, W, gamma, x0=None, U=None, full=False, prec="ld", nthreads=0, init_cov=None, action_var=None, process_var=None):

@@ -167,8 +167,12 @@ static num FN(inv_det)(int n, const num* Min, num* inv) {
 
 /* Full-covariance step for the input N(u, S): gpmpc_cpu_fullcov.c step(), with the folded weights read instead of
  * built and every operation in ``num``.  mt [ds], ct [ds][ds]; Amn [ds] and Ac [ds][ds] may be NULL.  V, AV, Z2: N x D scratch;
- * gq: 2N; rowz, rowa: N. */
-static void FN(step_full)(const ctx_t* c, const num* u, const num* S, num* mt, num* ct, real* Amn, real* Ac, num* V, num* AV, num* gq, num* Z2, num* rowz, real* rowa) {
+ * gq: 2N; rowz, rowa: N.  S is read as given (no symmetrisation: the HIP kernels read (S + S^T)/2, so their callers pass that).
+ * bug != 0: the cross term of the reference's line :446, z2_i^T Am z1_j instead of z1_i^T Am z2_j (GPMPC_COV_BUG_COMPAT;
+ * oracle/gpmpc_oracle.py::covariance_prop(bug_compatible=True)), evaluated for every ORDERED pair (a, b) as the HIP kernel does, so
+ * ct[a][b] and ct[b][a] are two sums of their own; 0 keeps every bit of the consistent form.
+ * Lout [ds][N] (real builds, may be NULL): l_i = c_m exp(-1/2 v_i^T B v_i), the second return value of mean_prop_torch (:335-336). */
+static void FN(step_full)(const ctx_t* c, const num* u, const num* S, int bug, num* mt, num* ct, real* Amn, real* Ac, real* Lout, num* V, num* AV, num* gq, num* Z2, num* rowz, real* rowa) {
     const int N = c->N, ds = c->ds, D = c->D;
     for (int i = 0; i < N; ++i) for (int k = 0; k < D; ++k) V[(size_t)i * D + k] = u[k] - (real)c->X[(size_t)i * D + k];
     num mu[MAXD];
@@ -184,6 +188,9 @@ static void FN(step_full)(const ctx_t* c, const num* u, const num* S, num* mt, n
             for (int r = 0; r < D; ++r) { num t = (real)0.0; for (int q = 0; q < D; ++q) t += Bm[r * D + q] * v[q]; quad += v[r] * t; }
             const num l = N_EXP((real)-0.5 * quad);
             S0 += FN(cb)(c, a, i) * l; A0 += R_ABS(FN(cb)(c, a, i)) * E_ABS(l);
+#ifndef CPLX
+            if (Lout) Lout[(size_t)a * N + i] = sf2 / N_SQRT(detm) * l;
+#endif
         }
         mu[a] = sf2 / N_SQRT(detm) * S0;
         if (Amn) Amn[a] = N_ABS(sf2 / N_SQRT(detm)) * A0;
@@ -215,7 +222,8 @@ static void FN(step_full)(const ctx_t* c, const num* u, const num* S, num* mt, n
     }
     /* cross-covariances, consistent form (src/tools/uncertainty_prop.py:187-237; :402-465 with z1^T A z2) */
     for (int a = 0; a < ds; ++a)
-        for (int b = a + 1; b < ds; ++b) {
+        for (int b = bug ? 0 : a + 1; b < ds; ++b) {
+            if (b == a) continue;
             const double* la = c->lam + a * D; const double* lb = c->lam + b * D;
             num Rm[MAXD * MAXD], Ri[MAXD * MAXD], Am[MAXD * MAXD];
             for (int r = 0; r < D; ++r) for (int q = 0; q < D; ++q) Rm[r * D + q] = S[r * D + q] * ((real)1.0 / (real)la[q] + (real)1.0 / (real)lb[q]) + (r == q ? (real)1.0 : (real)0.0);
@@ -224,8 +232,9 @@ static void FN(step_full)(const ctx_t* c, const num* u, const num* S, num* mt, n
             for (int i = 0; i < N; ++i) {
                 const num* v = V + (size_t)i * D; num z1[MAXD], z2[MAXD], k1 = (real)0.0, k2 = (real)0.0, q1 = (real)0.0, q2 = (real)0.0;
                 for (int r = 0; r < D; ++r) { z1[r] = -v[r] / (real)la[r]; z2[r] = -v[r] / (real)lb[r]; k1 += v[r] * v[r] / (real)la[r]; k2 += v[r] * v[r] / (real)lb[r]; }
-                for (int q = 0; q < D; ++q) { num t = (real)0.0; for (int r = 0; r < D; ++r) t += z1[r] * Am[r * D + q]; AV[(size_t)i * D + q] = t; }
-                for (int r = 0; r < D; ++r) { num s1 = (real)0.0, s2 = (real)0.0; for (int q = 0; q < D; ++q) { s1 += Am[r * D + q] * z1[q]; s2 += Am[r * D + q] * z2[q]; } q1 += z1[r] * s1; q2 += z2[r] * s2; Z2[(size_t)i * D + r] = z2[r]; }
+                const num* zc = bug ? z2 : z1;     /* the row side of the cross term */
+                for (int q = 0; q < D; ++q) { num t = (real)0.0; for (int r = 0; r < D; ++r) t += zc[r] * Am[r * D + q]; AV[(size_t)i * D + q] = t; }
+                for (int r = 0; r < D; ++r) { num s1 = (real)0.0, s2 = (real)0.0; for (int q = 0; q < D; ++q) { s1 += Am[r * D + q] * z1[q]; s2 += Am[r * D + q] * z2[q]; } q1 += z1[r] * s1; q2 += z2[r] * s2; Z2[(size_t)i * D + r] = bug ? z1[r] : z2[r]; }
                 gq[2 * i] = (real)-0.5 * k1 + (real)0.5 * q1; gq[2 * i + 1] = (real)-0.5 * k2 + (real)0.5 * q2;
             }
 #pragma omp parallel for schedule(static)
@@ -244,8 +253,8 @@ static void FN(step_full)(const ctx_t* c, const num* u, const num* S, num* mt, n
             const real sfab = (real)c->sf[a] * (real)c->sf[a] * (real)c->sf[b] * (real)c->sf[b];
             const num cab = sfab / N_SQRT(detR);
             const num cov = cab * Qs - mu[a] * mu[b];
-            ct[a * ds + b] = cov; ct[b * ds + a] = cov;
-            if (Ac) { const real A = N_ABS(cab) * AQ + N_ABS(mu[a]) * N_ABS(mu[b]); Ac[a * ds + b] = A; Ac[b * ds + a] = A; }
+            ct[a * ds + b] = cov; if (!bug) ct[b * ds + a] = cov;
+            if (Ac) { const real A = N_ABS(cab) * AQ + N_ABS(mu[a]) * N_ABS(mu[b]); Ac[a * ds + b] = A; if (!bug) Ac[b * ds + a] = A; }
         }
 }
 
@@ -275,7 +284,7 @@ static num FN(rollout_one)(const ctx_t* c, int full, const double* x0, const num
         for (int k = 0; k < D * D; ++k) S[k] = (real)0.0;
         for (int k = 0; k < ds; ++k) { u[k] = means[(t - 1) * ds + k]; for (int l = 0; l < ds; ++l) S[k * D + l] = covs[((size_t)(t - 1) * ds + k) * ds + l]; }
         for (int k = 0; k < da; ++k) { u[ds + k] = U[(t - 1) * da + k]; S[(ds + k) * D + ds + k] = c->action_var ? (real)c->action_var[k] : act_var; }
-        if (full) FN(step_full)(c, u, S, means + (size_t)t * ds, ct, 0, 0, V, AV, gq, Z2, rowz, rowa);
+        if (full) FN(step_full)(c, u, S, 0, means + (size_t)t * ds, ct, 0, 0, 0, V, AV, gq, Z2, rowz, rowa);
         else {
             for (int k = 0; k < D; ++k) s[k] = S[k * D + k];
             FN(step_diag)(c, u, s, means + (size_t)t * ds, vt, 0, 0, 0, rowz, rowa, rowa + N);
@@ -380,10 +389,46 @@ int FN(gpmpc_given_step_diag)(int N, int Np, int ds, int D, const double* X, con
     return 0;
 }
 
-/* nq full-covariance steps: u [nq][D], S [nq][D][D] -> mean and Amean [nq][ds], cov and Acov [nq][ds][ds] */
+/* nq full-covariance steps: u [nq][D], S [nq][D][D] -> mean and Amean [nq][ds], cov and Acov [nq][ds][ds]; bug: see step_full;
+ * lout [nq][ds][N] or NULL: the vector l of every GP, rounded to double. */
 int FN(gpmpc_given_step_full)(int N, int Np, int ds, int D, const double* X, const double* lam, const double* sf,
                               const void* beta, const void* M, int cld, int nq, const double* u, const double* S,
-                              double* mean, double* cov, double* Amean, double* Acov, int nthreads) {
+                              double* mean, double* cov, double* Amean, double* Acov, int nthreads, int bug, double* lout) {
+    if (FN(bad_shape)(N, Np, ds, D)) return -1;
+#ifdef _OPENMP
+    if (nthreads > 0) omp_set_num_threads(nthreads);
+#endif
+    const ctx_t c = {N, Np, ds, D - ds, D, 1, X, lam, sf, beta, M, cld, 0.0, 0, 0, 0, 0};
+    num* scr = (num*)malloc(sizeof(num) * (size_t)N * (3 * D + 3));
+    real* rowa = (real*)malloc(sizeof(real) * (size_t)N);
+    real* lbuf = lout ? (real*)malloc(sizeof(real) * (size_t)ds * N) : 0;
+    if (!scr || !rowa || (lout && !lbuf)) { free(scr); free(rowa); free(lbuf); return -2; }
+    const size_t nd = (size_t)N * D;
+    for (int q = 0; q < nq; ++q) {
+        num uu[MAXD], SS[MAXD * MAXD], mt[MAXD], ct[MAXD * MAXD]; real Am[MAXD], Ac[MAXD * MAXD];
+        for (int k = 0; k < D; ++k) uu[k] = (real)u[(size_t)q * D + k];
+        for (int k = 0; k < D * D; ++k) SS[k] = (real)S[(size_t)q * D * D + k];
+        FN(step_full)(&c, uu, SS, bug, mt, ct, Am, Ac, lbuf, scr, scr + nd, scr + 2 * nd, scr + 2 * nd + 2 * (size_t)N, scr + 3 * nd + 2 * (size_t)N, rowa);
+        if (lout) for (size_t k = 0; k < (size_t)ds * N; ++k) lout[(size_t)q * ds * N + k] = (double)lbuf[k];
+        for (int a = 0; a < ds; ++a) {
+            mean[(size_t)q * ds + a] = (double)mt[a]; Amean[(size_t)q * ds + a] = (double)Am[a];
+            for (int b = 0; b < ds; ++b) { cov[((size_t)q * ds + a) * ds + b] = (double)ct[a * ds + b]; Acov[((size_t)q * ds + a) * ds + b] = (double)Ac[a * ds + b]; }
+        }
+    }
+    free(scr); free(rowa); free(lbuf);
+    return 0;
+}
+#endif
+
+#ifdef CPLX
+/* Jacobians of nq full-covariance steps by the complex step (h = 1e-20: no subtraction, exact to rounding), at sym(S) = (S + S^T)/2:
+ *   dmean_du [nq][ds][D], dmean_dS [nq][ds][D][D], dcov_du [nq][ds][ds][D], dcov_dS [nq][ds][ds][D][D];
+ * one run per u_k, and one per pair k <= l along the SYMMETRIC direction (E_kl + E_lk)/2, written to [k][l] and [l][k]: the
+ * symmetrised derivative include/gpmpc.h promises and sym(autograd) gives.  The diagonal (a, a) of dcov is the variance Jacobian.
+ * bug: see step_full (both [a][b] and [b][a] are then derivatives of sums of their own). */
+int FN(gpmpc_given_step_full_jac)(int N, int Np, int ds, int D, const double* X, const double* lam, const double* sf,
+                                  const void* beta, const void* M, int cld, int nq, const double* u, const double* S, int bug,
+                                  double* dmean_du, double* dmean_dS, double* dcov_du, double* dcov_dS, int nthreads) {
     if (FN(bad_shape)(N, Np, ds, D)) return -1;
 #ifdef _OPENMP
     if (nthreads > 0) omp_set_num_threads(nthreads);
@@ -393,15 +438,34 @@ int FN(gpmpc_given_step_full)(int N, int Np, int ds, int D, const double* X, con
     real* rowa = (real*)malloc(sizeof(real) * (size_t)N);
     if (!scr || !rowa) { free(scr); free(rowa); return -2; }
     const size_t nd = (size_t)N * D;
+    const real h = (real)1e-20;
     for (int q = 0; q < nq; ++q) {
-        num uu[MAXD], SS[MAXD * MAXD], mt[MAXD], ct[MAXD * MAXD]; real Am[MAXD], Ac[MAXD * MAXD];
-        for (int k = 0; k < D; ++k) uu[k] = (real)u[(size_t)q * D + k];
-        for (int k = 0; k < D * D; ++k) SS[k] = (real)S[(size_t)q * D * D + k];
-        FN(step_full)(&c, uu, SS, mt, ct, Am, Ac, scr, scr + nd, scr + 2 * nd, scr + 2 * nd + 2 * (size_t)N, scr + 3 * nd + 2 * (size_t)N, rowa);
-        for (int a = 0; a < ds; ++a) {
-            mean[(size_t)q * ds + a] = (double)mt[a]; Amean[(size_t)q * ds + a] = (double)Am[a];
-            for (int b = 0; b < ds; ++b) { cov[((size_t)q * ds + a) * ds + b] = (double)ct[a * ds + b]; Acov[((size_t)q * ds + a) * ds + b] = (double)Ac[a * ds + b]; }
+        num uu[MAXD], SS[MAXD * MAXD], mt[MAXD], ct[MAXD * MAXD];
+        for (int k = 0; k < D; ++k) {
+                for (int m = 0; m < D; ++m) uu[m] = (real)u[(size_t)q * D + m] + (m == k ? h : (real)0.0) * I;
+                for (int r = 0; r < D; ++r) for (int m = 0; m < D; ++m) SS[r * D + m] = (real)0.5 * ((real)S[((size_t)q * D + r) * D + m] + (real)S[((size_t)q * D + m) * D + r]);
+                FN(step_full)(&c, uu, SS, bug, mt, ct, 0, 0, 0, scr, scr + nd, scr + 2 * nd, scr + 2 * nd + 2 * (size_t)N, scr + 3 * nd + 2 * (size_t)N, rowa);
+                for (int a = 0; a < ds; ++a) {
+                    dmean_du[((size_t)q * ds + a) * D + k] = (double)(__imag__ mt[a] / h);
+                    for (int b = 0; b < ds; ++b) dcov_du[(((size_t)q * ds + a) * ds + b) * D + k] = (double)(__imag__ ct[a * ds + b] / h);
+                }
         }
+        for (int k = 0; k < D; ++k)
+            for (int l = k; l < D; ++l) {
+                for (int m = 0; m < D; ++m) uu[m] = (real)u[(size_t)q * D + m];
+                for (int r = 0; r < D; ++r) for (int m = 0; m < D; ++m) SS[r * D + m] = (real)0.5 * ((real)S[((size_t)q * D + r) * D + m] + (real)S[((size_t)q * D + m) * D + r]);
+                if (k == l) SS[k * D + k] += h * I;
+                else { SS[k * D + l] += (real)0.5 * h * I; SS[l * D + k] += (real)0.5 * h * I; }
+                FN(step_full)(&c, uu, SS, bug, mt, ct, 0, 0, 0, scr, scr + nd, scr + 2 * nd, scr + 2 * nd + 2 * (size_t)N, scr + 3 * nd + 2 * (size_t)N, rowa);
+                for (int a = 0; a < ds; ++a) {
+                    const double dm = (double)(__imag__ mt[a] / h);
+                    dmean_dS[(((size_t)q * ds + a) * D + k) * D + l] = dm; dmean_dS[(((size_t)q * ds + a) * D + l) * D + k] = dm;
+                    for (int b = 0; b < ds; ++b) {
+                        const double dc = (double)(__imag__ ct[a * ds + b] / h);
+                        dcov_dS[((((size_t)q * ds + a) * ds + b) * D + k) * D + l] = dc; dcov_dS[((((size_t)q * ds + a) * ds + b) * D + l) * D + k] = dc;
+                    }
+                }
+            }
     }
     free(scr); free(rowa);
     return 0;
