@@ -31,6 +31,7 @@ struct gpmpc_worklist {
     int jt;         // column extent of a tile (multiple of 64)
     int nunits, nwork;
     int contiguous;     // items of a unit are contiguous (ustart valid); 0: XCD-sorted order, look the unit up per item
+    // (the three device arrays are sections of the pack's index arena, gpmpc_pack::index_dev; null: the list is not built)
     int* work_dev;      // [nwork][4]
     int* perm_dev;      // [nwork] item indices grouped by unit (XCD-sorted lists only, else null): unit u owns perm[ustart[u] .. ustart[u+1])
     int* ustart_dev;    // [nunits + 1]
@@ -73,10 +74,14 @@ struct gpmpc_pack {
     int npairs;     // ds (ds - 1) / 2 cross-covariance units (a < b, lexicographic)
     int fullcov;    // cross-covariance weight matrices are allocated and kept up to date
     int pair_a[GPMPC_MAX_PAIRS > 0 ? GPMPC_MAX_PAIRS : 1], pair_b[GPMPC_MAX_PAIRS > 0 ? GPMPC_MAX_PAIRS : 1];
+    // ALL integer device data of the pack -- the work lists of wl / wl_sh, pair_ab_dev, ncol_dev, the fcs_* tables -- is one allocation, laid out
+    // and uploaded once by gpmpc_pack_create (pack.hip; sections aligned to 256 bytes).  The fields below point into it.
+    int* index_dev;
     int* pair_ab_dev;   // [npairs][2]
-    // one lambda for all GPs, full-covariance rollout (pair_kernel_sbfx.h): constant column rows [Np][fcs_rw] (refreshed by every build while
-    // `fullcov`), and per tri-unit tiling k of wl[1][k] the unit offsets into a trajectory's partial-sum slots: tri units as in that work list,
-    // cross unit pr at fcs_base[k] + pr * fcs_ntile
+    // one lambda for all GPs, full-covariance rollout (pair_kernel_sbfx.h): constant column rows [Np][fcs_rw] (allocated by the first build or
+    // enable_fullcov that serves that path, refreshed by every build while `fullcov`), and -- from creation on, for every shape that can take the
+    // path (gpmpc_fcs_shape) -- per tri-unit tiling k of wl[1][k] the unit offsets into a trajectory's partial-sum slots: tri units as in that
+    // work list, cross unit pr at fcs_base[k] + pr * fcs_ntile
     double* fcs_rows; int fcs_rw, fcs_tj;
     // (two tile widths: 64 columns per wave for launches that fill the chip, 16 for small ones -- four times the waves, each a quarter as long)
     int fcs_ntile[3];                                  // tiles per trajectory: [0] 64 x 64, [1] 64 x 16, [2] 64 x (up to) 256 (listed in fcs_tiles256_dev)
@@ -100,7 +105,7 @@ struct gpmpc_pack {
     void* lock;                // host lock of the pack's own streams / events / caches (std::recursive_mutex, runtime.hip; rollout.h::PackGuard)
     // [0: variance units only | 1: + cross units][0: 256x256 tiles | 1: 64x64 | 2: 256x64 | 3: 64x128 | 4: 256x128 | 5: 256x32 | 6: 256x16
     //  (4...6: mode 0 only)]
-    gpmpc_worklist wl[2][8];   // [7] (diagonal rollout only, D >= 6): balanced runs of up to 256 columns, one workgroup generation per trajectory (pack.hip)
+    gpmpc_worklist wl[2][8];   // [7] (diagonal rollout only, D >= 6): balanced runs of up to 256 columns, one workgroup generation per trajectory (worklist.h)
     // shared-lambda path (pair_kernel_sbs.h): every GP has bit-identical length-scales (detected at gpmpc_pack_build)
     int shared_lambda;
     int sh_ng;                 // GPs per workgroup
@@ -142,7 +147,7 @@ struct PairArgs {
 
 // Arguments of the scalar-broadcast pair kernel (pair_kernel_sb.h): rollout hot path, variance units only.
 struct PairSbArgs {
-    const double* M;      // [ds][Np][Np] upper-triangular, weight 2 off the diagonal (pack.hip)
+    const double* M;      // [ds][Np][Np] upper-triangular, weight 2 off the diagonal (pack_build.hip)
     const double* XT;     // [D][Np]
     const double* pp;     // [B][ds][pps]: cvec[D] = sc o u, sc[D]
     const double* G;      // [B][ds][Np][GW] column rows [h_j (D) | q_j | h_j^2 (NS2) | pad]
@@ -186,6 +191,8 @@ struct PairSbfxArgs {
 };
 template <int D> int gpmpc_launch_pair_sbfx_D(bool grad, int ns2, const PairSbfxArgs& a, hipStream_t s);
 int gpmpc_launch_pair_sbfx(int D, bool grad, int ns2, const PairSbfxArgs& a, hipStream_t s);
+// shapes whose full-covariance rollout can run the cross units through pair_kernel_sbfx.h when all GPs have one lambda
+static inline bool gpmpc_fcs_shape(int ds, int da) { return ds >= 2 && ds <= 4 && da >= 1 && da <= 2; }
 static inline int gpmpc_sbf_gw(int D, int ns2) { return (D + 1 + ns2 * (ns2 + 1) / 2 + 1) & ~1; }
 int gpmpc_launch_pair_sbf(int D, bool grad, int ns2, int waves, const PairSbfArgs& a, hipStream_t s);
 template <int D> int gpmpc_launch_pair_sbf_D(bool grad, int ns2, int waves, const PairSbfArgs& a, hipStream_t s);

@@ -7,7 +7,7 @@
 // and, for the input-gradients, the moments  Z1_k = sum P m_k,  Z2_kl = sum P m_k m_l  with  m = p_i + q_j,
 // P = M_ij exp(-|m|^2).  Two kinds of unit share the code:
 //   * variance unit a (unit < ntri): the trace term of variance_prop_torch (src/tools/uncertainty_prop.py:372-399),
-//       T = c Z0,  M = sym(Ky_inv - beta beta^T) o exp(-1/4 d^2_Lambda) sf^4 (pack.hip),  rows and columns use the same
+//       T = c Z0,  M = sym(Ky_inv - beta beta^T) o exp(-1/4 d^2_Lambda) sf^4 (pack_build.hip),  rows and columns use the same
 //       transform h = Cm (u - x), Cm^T Cm = (Lambda/2 + S)^-1 / 8, so exp(-1/8 (G_ii + 2 G_ij + G_jj)) = exp(-|h_i + h_j|^2)
 //       (:389).  M is stored upper-triangular with weight 2 off the diagonal: only i <= j is visited.
 //   * cross-covariance unit (a, b) (unit >= ntri): beta_a^T Qt beta_b of covariance_prop_torch (:402-465) written as a

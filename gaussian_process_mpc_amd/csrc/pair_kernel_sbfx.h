@@ -1,6 +1,6 @@
 // Cross-covariance units of the full-covariance rollout when ALL GPs SHARE their length-scales (round 5): every cross unit (a, b),
 // a < b, of pair_kernel_sbf.h then has the same row transform p_i, the same column rows q_j and -- up to beta_a,i beta_b,j sf_a^2 sf_b^2 --
-// the same weight matrix (pack.hip::k_pack_cross: E_ij = exp(-1/2 sum_k (x_ik - x_jk)^2 / (lambda_ak + lambda_bk)), here lambda_a + lambda_b =
+// the same weight matrix (pack_build.hip::k_pack_cross: E_ij = exp(-1/2 sum_k (x_ik - x_jk)^2 / (lambda_ak + lambda_bk)), here lambda_a + lambda_b =
 // 2 lambda for every pair).  Instead of ds (ds - 1) / 2 streamed N x N weight matrices and as many exp per pair (201 MB and six at C5's
 // sizes), ONE pass over the pairs evaluates
 //     Q_ij = exp(-(1/4 sum_k (x_ik - x_jk)^2 / lambda_k + |p_i + q_j|^2))                 (one exponent: two quadratic forms, one table exp)

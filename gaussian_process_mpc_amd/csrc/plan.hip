@@ -194,7 +194,7 @@ RollShape gpmpc_choose_shape(const gpmpc_pack* p, int B, int H, bool grad, bool 
         r->rgroup = r->sh_list != 1 ? ((tn.rgroup >= 1 && tn.rgroup <= 16) ? tn.rgroup : 4) : 1;
     }
     // One trajectory (or a few) of a training set whose 256x64 tiles would take several workgroup generations: balanced runs of up to 256
-    // columns, ONE generation per trajectory (pack.hip, work list 7; step_fused.h, Q = 256)
+    // columns, ONE generation per trajectory (worklist.h, work list 7; step_fused.h, Q = 256)
     if (r->fused == 2 && r->tiling == 2 && !r->shared && tn.tiling < 0 && p->wl[0][7].work_dev) {
         r->tiling = 7;
         r->nwork = p->wl[0][7].nwork;

@@ -32,7 +32,7 @@
 #include "gpmpc_internal.h"
 #include "fast_exp.h"
 
-// Item q of the 64x64 upper-triangular list of one unit (pack.hip::build_worklist: row tile r, then column tile c >= r;
+// Item q of the 64x64 upper-triangular list of one unit (worklist.h::gpmpc_build_tile_list: row tile r, then column tile c >= r;
 // T tiles per side): r is the largest row with start(r) = r T - r (r - 1) / 2 <= q.  Saves the dependent load of the item.
 __device__ __forceinline__ void gpmpc_tri_decode(int q, int T, int* r_out, int* c_out) {
     const float tt = 2.0f * T + 1.0f;

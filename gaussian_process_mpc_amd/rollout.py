@@ -215,11 +215,12 @@ class GPPack:
     GaussianProcessRegression hold, src/dynamics.py:33-37, src/gpr.py:24-36) folded into
     the per-data-update constants of the rollout (beta, weight matrices)."""
 
-    def __init__(self, X, Y, Ky_inv, lambdas, sigma_f, device=None, y_is_beta=False, nominal=None):
+    def __init__(self, X, Y, Ky_inv, lambdas, sigma_f, device=None, y_is_beta=False, nominal=None, fullcov=False):
         """Y: (N, ds) targets, or the beta vectors themselves when ``y_is_beta`` (then Ky_inv may be
         None: only means and cross-covariances are meaningful).
         nominal: (W (ds, D), b (ds,) or scalar) of a linear nominal model m_a(z) = W[a] . z + b[a], z = (x, u): Y stays the RAW targets, the
-        library forms beta from Y - X W^T - b and the rollout adds the model back exactly (with ``y_is_beta`` beta is taken as given)."""
+        library forms beta from Y - X W^T - b and the rollout adds the model back exactly (with ``y_is_beta`` beta is taken as given).
+        fullcov: the cross-covariance weights exist from creation on (``enable_fullcov`` BEFORE the first build, which then fills them)."""
         self.device = device if device is not None else require_gpu()
         self._h = None
         self.generation = 0          # bumped by every (re)build: caches keyed on the pack object include it
@@ -227,7 +228,7 @@ class GPPack:
         self._graph_bufs = {}
         self.fullcov = False
         self._nominal = None
-        self._fill(X, Y, Ky_inv, lambdas, sigma_f, y_is_beta, nominal)
+        self._fill(X, Y, Ky_inv, lambdas, sigma_f, y_is_beta, nominal, fullcov)
 
     def _set_nominal(self, nominal):
         """Hand a changed model to the library (switching it on or off re-plans the pack: scratch sizes change)."""
@@ -291,7 +292,7 @@ class GPPack:
     def noise_is_default(self):
         return lib().gpmpc_pack_get_noise(self._h, None, None, None) == 0
 
-    def _fill(self, X, Y, Ky_inv, lambdas, sigma_f, y_is_beta, nominal=None):
+    def _fill(self, X, Y, Ky_inv, lambdas, sigma_f, y_is_beta, nominal=None, fullcov_first=False):
         self.X = _dev(X, self.device)
         Y = _dev(Y, self.device)
         self.Y = Y.reshape(self.X.shape[0], -1)
@@ -318,6 +319,8 @@ class GPPack:
             with torch.cuda.device(self.device):       # the pack's HBM buffers belong to THIS device, whatever is current
                 check(lib().gpmpc_pack_create(ctypes.byref(h), self.N, self.ds, self.da), "gpmpc_pack_create")
             self._h = h
+            if fullcov_first:
+                self.enable_fullcov()
         self._set_nominal(nominal)
         _, lp = host_doubles(self.lambdas)
         _, sp = host_doubles(self.sigma_f)

@@ -665,9 +665,22 @@ int gpmpc_pair_kernel_time_class(int kernel_class, double* total_ms, long long* 
  *   {GP, first row, first column, end column}; n_padded = N rounded up to 64; slots = workgroup slots of the device minus the
  *   2 state_dim role workgroups).  *n_items = 0 when the plain 256x64 list is within 1.1 generations.  items_out holds 4 * capacity ints
  *   (capacity = 0: count only).
+ * gpmpc_debug_work_list: a tile work list exactly as a pack holds it -- units x row tiles x column tiles, the first n_tri_units keeping only
+ *   the tiles that reach the diagonal; items {unit, first row, first column, end column} (tile_slot: the tile's index within its unit instead
+ *   of the end column), XCD re-ordered when xcd_sort is set and the list has 16 items or more.  Same convention as gpmpc_debug_run_list; with
+ *   capacity > 0 also ustart_out [units + 1] and, for a re-ordered list only (it is left untouched otherwise: a pack keeps none), perm_out
+ *   [*n_items], the item positions grouped by unit.
+ * gpmpc_debug_fcs_tables: the tile tables of the one-lambda full-covariance form for the variance-unit tiling 256 x cols_per_tile:
+ *   ntile_out [3] tiles per trajectory and pair in the three widths, tiles_out [*n_tiles][3] = {64-row block, first column, columns} of the
+ *   widest (capacity in tiles, 0: counts only), ustart_out [3][units + 1] the unit offsets per width (last entry: slots per trajectory).
  * gpmpc_debug_xcd_order: (trajectory, grid column) that workgroup `linear_id` of a (grid_x, n_traj) grid with n_tile tile columns runs in
- *   the XCD-aware dispatch order. */
+ *   the XCD-aware dispatch order.
+ * All: GPMPC_E_ARG on sizes that are no padded size / tile size / unit count of a pack, or a capacity below the count. */
 int gpmpc_debug_run_list(int n_padded, int state_dim, int slots, int* items_out, int capacity, int* n_items);
+int gpmpc_debug_work_list(int n_padded, int rows_per_tile, int cols_per_tile, int n_tri_units, int n_cross_units, int xcd_sort, int tile_slot,
+                          int* items_out, int capacity, int* n_items, int* perm_out, int* ustart_out);
+int gpmpc_debug_fcs_tables(int n_padded, int state_dim, int cols_per_tile, int* ntile_out, int* tiles_out, int capacity, int* n_tiles,
+                           int* ustart_out);
 int gpmpc_debug_xcd_order(int linear_id, int grid_x, int n_tile, int n_traj, int* traj, int* column);
 
 /* ---------------------------------------------------------------------------

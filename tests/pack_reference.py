@@ -1,4 +1,4 @@
-"""Extended-precision restatement of the PACK BUILD (csrc/pack.hip: k_pack_beta, k_pack_residual, k_pack_weights), the link between the
+"""Extended-precision restatement of the PACK BUILD (csrc/pack_build.hip: k_pack_beta, k_pack_residual, k_pack_weights), the link between the
 training data and the constants every rollout kernel reads.  TEST INFRASTRUCTURE ONLY.
 
 Plain numpy in the working precision of tests/gpstate_reference.py (``np.longdouble``, object arrays of ``mpmath.mpf`` on request or where

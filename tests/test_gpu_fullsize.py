@@ -239,7 +239,7 @@ def test_c4_full_horizon_against_cport(G):
 
 @pytest.mark.parametrize("N,ds,da,H", [(2500, 6, 1, 4), (3011, 5, 1, 3), (2700, 5, 2, 3), (4096, 6, 2, 2)])
 def test_one_trajectory_on_balanced_runs_against_cport(G, N, ds, da, H):
-    """Work list 7 (pack.hip::build_worklist_runs; step_fused.h, Q = 256): ONE trajectory of a training set whose 256x64 tiles would take
+    """Work list 7 (worklist.h::gpmpc_build_run_list; step_fused.h, Q = 256): ONE trajectory of a training set whose 256x64 tiles would take
     several workgroup generations runs on balanced runs of up to 256 columns.  Sizes that are no multiple of 64 / 256 (clipped and ragged
     last runs, waves that enter a run at their diagonal block), D = 6 ... 8, objective + gradient and objective only, eager and as a graph,
     held to the C port; and to the same library on the plain 256x64 list."""

@@ -1,5 +1,5 @@
 """Every rollout kernel form OFF the grid the other GPU tests sit on: per-GP amplitudes sigma_f in [0.6, 1.8] (distinct), non-zero x_ref / u_ref,
-a coupled Q (tests/offgrid_problems.py).  Each form has its own amplitude code -- pack.hip folds sf^4 into the pair weights, step.hip forms
+a coupled Q (tests/offgrid_problems.py).  Each form has its own amplitude code -- pack_build.hip folds sf^4 into the pair weights, step.hip forms
 sf^2 / sqrt(det) and var = sf^2 - T - mu^2 (and again in its nominal twin), step_fused.h, traj_persist.h and fullcov.hip keep their own copies, the
 cross-unit weights carry sf_a^2 sf_b^2, the shared-lambda forms share one exponent over a group of GPs but not one amplitude -- and every one of
 those factors is 1 in the other rollout tests.

@@ -31,7 +31,7 @@ or two fmas differ from numpy's multiply and add by a rounding (0.955 against 0.
 elementwise operations, sf^4 formed as (sf^2)^2 and the device's exp.
 The caps (tests/pack_reference.py::CAP_K), twice the worst measured value rounded up to two digits: beta 4.3, nominal beta 4.2, M 5.8.
 
-Checked once on scratch copies of csrc/pack.hip (not committed): `kij` for `0.5 * (kij + kji)`, `sf2` for `sf4`, and `j * ld + row` for
+Checked once on scratch copies of csrc/pack_build.hip (not committed): `kij` for `0.5 * (kij + kji)`, `sf2` for `sf4`, and `j * ld + row` for
 `row * ld + j` in k_pack_beta each make this module fail while test_pack_constants still passes.
 """
 import ctypes
@@ -418,6 +418,46 @@ def test_resize_into_the_same_padded_size(G, full):
     assert _L().gpmpc_pack_resize(pack.handle, 129) == E_ARG and _L().gpmpc_pack_resize(pack.handle, 0) == E_ARG
     b3, W3 = _export(pack.handle, 128, RESIZE_DS)
     assert _same(b3, beta) and _same(W3, W)
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# lifecycle order
+# ------------------------------------------------------------------------------------------------------------------------------
+def _fullcov_rollout(G, pack):
+    """(cost, grad, means, covs) of one full-covariance rollout, B = 2, H = 3."""
+    rng = np.random.default_rng(11)
+    cost = G.CostParams(-1.0, 0.01 * np.eye(pack.ds), 0.001 * np.eye(pack.da))
+    r = G.rollout_fullcov(pack, rng.uniform(-0.5, 0.5, (2, pack.ds)), rng.uniform(-0.5, 0.5, (2, 3, pack.da)), cost, want_grad=True)
+    torch.cuda.synchronize()
+    assert all(torch.isfinite(r[k]).all() for k in r)
+    return [r[k].clone() for k in ("cost", "grad", "means", "covs")]
+
+
+@pytest.mark.parametrize("D,ds,shared", [(3, 2, True), (4, 3, False)], ids=["one-lambda", "distinct-no-tables"])
+def test_fullcov_rollout_does_not_depend_on_the_order_of_build_and_enable(G, monkeypatch, D, ds, shared):
+    """N = 100 (Np = 128), da = 1: the full-covariance rollout after (a) build, then enable_fullcov, (b) enable_fullcov on a fresh pack, then
+    the build, (c) as (a), then a rebuild for 101 points and one back to the 100: bit for bit the same.  GPMPC_FC_SHARED=1 (read at pack
+    creation) makes the one-lambda pack run its cross unit through pair_kernel_sbfx.h at this small size -- the default plan takes that path
+    from B Np^2 pairs >= 3.5e7 --, i.e. from the one-lambda tables of the pack's index data and the column rows that (a) enable_fullcov,
+    (b) the first build, (c) the first enable_fullcov allocates and every later build refreshes; the plan of EACH pack is asserted to say so,
+    so that a table or an allocation that is missing cannot pass as a quiet change of path.  ds = 3 with distinct lambdas has neither and must
+    plan the per-unit kernels.  (The commit before the index data became one allocation, dcfe28d, showed the same equality in all three
+    orders under the same forced plan, and the same bits.)"""
+    monkeypatch.setenv("GPMPC_FC_SHARED", "1")
+    pr, other = P.problem(100, D, ds, shared=shared), P.problem(101, D, ds, shared=shared)
+    first = _gppack(G, pr, fullcov=True)
+    assert first.fullcov
+    back = _gppack(G, pr).enable_fullcov()
+    for q in (other, pr):
+        assert back.rebuild(_dev(q["X"]), _dev(q["Y"]), _dev(q["Kinv"]), np.array(q["lam"]), np.array(q["sf"]))
+    out = []
+    for pack in (_gppack(G, pr).enable_fullcov(), first, back):
+        plan = pack.plan_fullcov(2, 3)
+        assert plan["shared_cross_units"] == (1 if shared else 0), plan
+        out.append(_fullcov_rollout(G, pack))
+    for name, x, y, z in zip(("cost", "grad", "means", "covs"), *out):
+        assert torch.equal(x, y), ("enable before the first build", name)
+        assert torch.equal(x, z), ("101 points and back", name)
 
 
 # ------------------------------------------------------------------------------------------------------------------------------

@@ -110,6 +110,28 @@ int main() {
         EXPECT_NEG(gpmpc_debug_run_list(100, 4, 1016, nullptr, 0, &n_items));
         EXPECT_NEG(gpmpc_debug_run_list(4096, 0, 1012, nullptr, 0, &n_items));
         EXPECT_NEG(gpmpc_debug_run_list(4096, 6, 1012, nullptr, 0, nullptr));
+        // the tile lists and one-lambda tables of a pack (csrc/worklist.h): a re-ordered list whose XCD queues run dry, a ragged one with tile slots
+        for (int slot = 0; slot < 2; ++slot) {
+            const int np = slot ? 320 : 1024, units = slot ? 2 : 4, jt = slot ? 128 : 256;
+            EXPECT_ZERO(gpmpc_debug_work_list(np, 256, jt, units, 0, 1, slot, nullptr, 0, &n_items, nullptr, nullptr));
+            std::vector<int> items(4 * (size_t)n_items), perm(n_items, -1), ust(units + 1);
+            EXPECT_ZERO(gpmpc_debug_work_list(np, 256, jt, units, 0, 1, slot, items.data(), n_items, &n_items, perm.data(), ust.data()));
+            if (ust[units] != n_items) { printf("FAIL gpmpc_debug_work_list: ustart ends at %d of %d items\n", ust[units], n_items); ++failures; }
+        }
+        {
+            int ntile[3], n_tiles = -1;
+            EXPECT_ZERO(gpmpc_debug_fcs_tables(320, 3, 64, ntile, nullptr, 0, &n_tiles, nullptr));
+            std::vector<int> tiles(3 * (size_t)n_tiles), ust(3 * (3 + 3 + 1));
+            EXPECT_ZERO(gpmpc_debug_fcs_tables(320, 3, 64, ntile, tiles.data(), n_tiles, &n_tiles, ust.data()));
+            EXPECT_NEG(gpmpc_debug_fcs_tables(320, 3, 64, ntile, tiles.data(), n_tiles - 1, &n_tiles, ust.data()));
+            EXPECT_NEG(gpmpc_debug_fcs_tables(320, 5, 64, ntile, nullptr, 0, &n_tiles, nullptr));
+            EXPECT_NEG(gpmpc_debug_fcs_tables(320, 3, 64, nullptr, nullptr, 0, &n_tiles, nullptr));
+        }
+        EXPECT_NEG(gpmpc_debug_work_list(100, 256, 64, 2, 0, 1, 0, nullptr, 0, &n_items, nullptr, nullptr));
+        EXPECT_NEG(gpmpc_debug_work_list(128, 256, 64, 0, 0, 1, 0, nullptr, 0, &n_items, nullptr, nullptr));
+        EXPECT_NEG(gpmpc_debug_work_list(128, 256, 64, GPMPC_MAX_DS + 1, 0, 1, 0, nullptr, 0, &n_items, nullptr, nullptr));
+        EXPECT_NEG(gpmpc_debug_work_list(128, 256, 64, 2, 0, 1, 0, nullptr, 0, nullptr, nullptr, nullptr));
+        EXPECT_NEG(gpmpc_debug_work_list(128, 256, 64, 2, 0, 1, 0, &traj, 1, &n_items, &traj, nullptr));
         for (int L = 0; L < (24 + 8) * 5; ++L) EXPECT_ZERO(gpmpc_debug_xcd_order(L, 24 + 8, 24, 5, &traj, &col));
         EXPECT_NEG(gpmpc_debug_xcd_order(-1, 32, 24, 5, &traj, &col));
         EXPECT_NEG(gpmpc_debug_xcd_order(0, 32, 33, 5, &traj, &col));
