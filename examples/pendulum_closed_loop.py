@@ -6,7 +6,7 @@ src/experiments/pretrain_uncertainty.py: pre-train the GP on random transitions,
     python examples/pendulum_closed_loop.py [--pretrain 200] [--steps 25] [--horizon 10] [--window N] [--nominal identity]
                                             [--max-speed V [--prob P]] [--solver mppi [--samples K] [--iters I]] [--solver lbfgs [--starts K]]
                                             [--max-speed V --solver auglag [--starts K]] [--track AMPLITUDE,PERIOD [--terminal W]]
-                                            [--obs-var V [--process-var sigma_n]]
+                                            [--obs-var V [--process-var sigma_n]] [--inducing M [--inducing-select farthest|random]]
 
 --window N: fixed-size training window -- once the model holds N points every new observation replaces the oldest one (first-in
 first-out), so the cost of the data update and the memory stay constant however long the loop runs (what the solver makes of a model
@@ -40,6 +40,11 @@ told so: V I is the covariance of the start state of every prediction (RiskSensi
 covariance goes there, before every solve; the values live in device memory, the callback graph is captured once).  --process-var sigma_n
 adds each GP's noise variance to its predicted variance at every step: the spread of the next STATE, not of the latent function.
 
+--inducing M [--inducing-select farthest|random]: sparse GP dynamics (RiskSensitiveMPC.use_inducing_points, sparse.py): M inducing points
+chosen among the pre-training inputs summarise ALL observations (FITC); every new observation is an O(M^2) rank-one update on the device
+and the rollout's cost depends on M only, so neither grows with the loop (printed: the data-update time of the first and the last
+quarter of the steps, and the one pack handle / callback capture of the whole loop).  Not with --window (nothing is forgotten).
+
 Needs an MI355X and the built library; no gym, no cyipopt (the stand-in solver is scipy's L-BFGS-B on the same
 objective / gradient callbacks, so the trajectories are NOT the reference's Ipopt trajectories)."""
 import argparse
@@ -50,7 +55,7 @@ import time
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from gaussian_process_mpc_amd import LinearNominalModel, PendulumPlant, RiskSensitiveMPC, Simulator   # noqa: E402
+from gaussian_process_mpc_amd import LinearNominalModel, PendulumPlant, RiskSensitiveMPC, Simulator, select_inducing   # noqa: E402
 
 
 class NoisyObservation(object):
@@ -92,7 +97,11 @@ def main():
     ap.add_argument("--terminal", type=float, default=None, help="terminal weight W Q on the last predicted state (mpc.Q_terminal)")
     ap.add_argument("--obs-var", type=float, default=None, metavar="V", help="measurement-noise variance on what the controller sees; V I is its initial covariance")
     ap.add_argument("--process-var", choices=("sigma_n",), default=None, help="sigma_n: add each GP's noise variance to its predicted variance")
+    ap.add_argument("--inducing", type=int, default=None, metavar="M", help="sparse GP dynamics on M inducing points (FITC), chosen among the pre-training inputs")
+    ap.add_argument("--inducing-select", choices=("farthest", "random"), default="farthest", help="how --inducing picks its points")
     args = ap.parse_args()
+    if args.inducing is not None and args.window is not None:
+        ap.error("--inducing and --window exclude each other: the inducing points bound the cost, nothing is forgotten")
 
     rng = np.random.default_rng(0)
     plant = PendulumPlant()
@@ -111,6 +120,10 @@ def main():
     for i in range(args.pretrain):
         plant.state = S[i].copy()
         NS[i] = plant.step(A[i])[0]
+    if args.inducing is not None:
+        if not 1 <= args.inducing <= args.pretrain:
+            ap.error("--inducing must lie in 1...--pretrain")
+        mpc.use_inducing_points(select_inducing(np.column_stack((S, A)), args.inducing, np.array([0.5, 0.5, 0.5]), method=args.inducing_select))
     mpc.dynamics.append_train_data(S, A, NS)
     mpc.set_lb([-2.0]); mpc.set_ub([2.0])
     mpc.set_xref(np.zeros(2))
@@ -155,6 +168,20 @@ def main():
             env = NoisyObservation(plant, args.obs_var, np.random.default_rng(1))
             mpc.set_initial_covariance(args.obs_var * np.eye(2))      # (constant here; an estimator would hand in its P before every solve)
 
+    data_ms = []
+    if args.inducing is not None:                        # time every data update of the loop (synchronised: the update is asynchronous)
+        import torch
+        feed, handle0 = mpc.dynamics.append_train_data, mpc.dynamics.pack().handle
+
+        def timed(*a, **kw):
+            torch.cuda.synchronize()
+            t = time.perf_counter()
+            feed(*a, **kw)
+            mpc.dynamics.pack()
+            torch.cuda.synchronize()
+            data_ms.append((time.perf_counter() - t) * 1e3)
+        mpc.dynamics.append_train_data = timed
+
     sim = Simulator(mpc, env, num_iters=args.steps, incremental=True, refresh=args.refresh, max_train=args.window)
     t0 = time.perf_counter()
     hist = sim.run()
@@ -164,6 +191,14 @@ def main():
           f"training set {args.pretrain} -> {mpc.dynamics.gpr_err[0].num_train} points"
           + (f" (window of {args.window}, next slot {mpc.dynamics.window_slot})" if args.window else "")
           + (f"; nominal model: {args.nominal}" if nominal else ""))
+    if args.inducing is not None:
+        from gaussian_process_mpc_amd import lib
+        q = max(1, len(data_ms) // 4)
+        st = mpc.dynamics._groups[0][1]
+        print(f"sparse GP: {args.inducing} inducing points ({args.inducing_select}) for {mpc.dynamics.num_train} observations, min Lambda {st.min_lambda:.3e}; "
+              f"data update + pack refill {np.mean(data_ms[:q]):.3f} ms per step over the first {q} steps, {np.mean(data_ms[-q:]):.3f} ms over the last {q}; "
+              f"pack handle kept: {mpc.dynamics.pack().handle is handle0}, "
+              f"gpmpc_pack_callback_captures = {lib().gpmpc_pack_callback_captures(mpc.dynamics.pack().handle)}")
     if args.max_speed is not None:
         sp = np.array([abs(h[0][1]) for h in hist])
         print(f"|theta_dot| <= {args.max_speed} with probability {args.prob}: largest visited {sp.max():.3f}; "

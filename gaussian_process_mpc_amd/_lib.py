@@ -183,6 +183,13 @@ SIGNATURES = {
     "gpmpc_predict": (_i, [_i, _i, _vp, _dp, _d, _vp, _vp, _d, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "gpmpc_ml_grad_workspace_bytes": (_sz, [_i, _i]),
     "gpmpc_ml_grad": (_i, [_i, _i, _vp, _vp, _vp, _vp, _dp, _d, _d, _vp, _vp, _sz, _vp]),
+    "gpmpc_sparse_set_form": (_i, [_i]),
+    "gpmpc_sparse_accumulate_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
+    "gpmpc_sparse_accumulate": (_i, [_i, _i, _i, _i, _vp, _vp, _sz, _vp, _vp, _sz, _dp, _d, _d, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "gpmpc_sparse_finish_workspace_bytes": (_sz, [_i, _i]),
+    "gpmpc_sparse_finish": (_i, [_i, _i, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "gpmpc_sparse_append_workspace_bytes": (_sz, [_i, _i]),
+    "gpmpc_sparse_append": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _sz, _dp, _d, _d, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
 }
 
 _lib = None
@@ -215,7 +222,7 @@ def lib():
 def check(rc, what):
     if rc != 0:
         detail = lib().gpmpc_last_error().decode() if rc == -3 else ""
-        if rc == -1 and ("mppi" in what or "lbfgs" in what or "auglag" in what):    # the planners' refusals say which parameter
+        if rc == -1 and ("mppi" in what or "lbfgs" in what or "auglag" in what or "sparse" in what):    # these refusals say which parameter
             detail = lib().gpmpc_last_error().decode()
         if rc == -1 and not detail:        # refusals of a cost schedule say which and why
             why = lib().gpmpc_last_error().decode()

@@ -338,10 +338,11 @@ class GPPack:
         self.Np = npad.value
         self.generation += 1
 
-    def rebuild(self, X, Y, Ky_inv, lambdas, sigma_f, nominal="keep"):
+    def rebuild(self, X, Y, Ky_inv, lambdas, sigma_f, nominal="keep", y_is_beta=False):
         """Refill THIS pack for new data / hyper-parameters when its allocation fits (same device, dimensions and padded
         size): no allocation, the library handle survives.  Returns False (pack untouched) when it does not fit.
-        nominal: as in the constructor; None clears the model, the default keeps the one the pack has."""
+        nominal: as in the constructor; None clears the model, the default keeps the one the pack has.
+        y_is_beta: as in the constructor (a sparse GP refills its pack with (Z, alpha, Q) after every data update)."""
         Xs = X.shape
         n, D = int(Xs[0]), int(Xs[1])
         ds = int(Y.shape[1]) if len(Y.shape) > 1 else 1
@@ -350,7 +351,7 @@ class GPPack:
         with torch.cuda.device(self.device):
             if n != self.N:
                 check(lib().gpmpc_pack_resize(self._h, n), "gpmpc_pack_resize")
-        self._fill(X, Y, Ky_inv, lambdas, sigma_f, False,      # (cross-covariance weights, if enabled, follow every build)
+        self._fill(X, Y, Ky_inv, lambdas, sigma_f, bool(y_is_beta),      # (cross-covariance weights, if enabled, follow every build)
                    self._nominal if isinstance(nominal, str) and nominal == "keep" else nominal)
         return True
 

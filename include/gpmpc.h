@@ -755,6 +755,58 @@ int gpmpc_ml_grad(int n, int D, const double* X_dev, const double* Ky_inv_dev, c
                   const double* resid_dev, const double* lambdas_host, double sigma_f, double noise_var,
                   double* out_dev, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---------------------------------------------------------------------------
+ * Sparse GP: FITC inducing points in the WHITENED form (no reference counterpart).  M pseudo-inputs Z [M][D] summarise n observations
+ * for a group of GPs with identical hyper-parameters (lambda, sigma_f, sigma_n); the GPs' targets are the columns of Y.  With
+ *     Kmm = k(Z, Z) + jitter I     L = chol(Kmm)     W = L^-1  (lower triangular, M x M; from the caller)
+ *     v_n = W k(Z, x_n)            Lambda_n = sigma_f^2 + noise_var - |v_n|^2      (no clamp: a NaN or a negative value is passed on)
+ *     G = sum_n v_n v_n^T / Lambda_n          r = sum_n v_n y_n^T / Lambda_n  [M][n_targets]
+ *     B = I + G                    Binv = B^-1  (SYMMETRIC, from the caller: only its lower triangle is read)
+ *     alpha = W^T Binv r  [M][n_targets]      Q = W^T (I - Binv) W  [M][M]
+ * the posterior of GP a is mean k_*^T alpha[:, a], variance sigma_f^2 - k_*^T Q k_*: exactly what gpmpc_pack_build_beta takes as
+ * (X := Z, beta := alpha^T, Ky_inv := Q) and gpmpc_predict as (X := Z, beta := alpha[:, a], Ky_inv := Q).  The textbook form
+ * (Kmm + Kmn Lambda^-1 Knm)^-1 is NOT used: its condition number reaches 1e14.
+ * All matrices row-major and dense ([M][M]) unless a row stride is named; k(z, x) = sigma_f^2 exp(-1/2 sum_d (z_d - x_d)^2 / lambda_d).
+ * No atomics, fixed summation orders, launch geometry from the sizes only: two identical calls agree bit for bit; G and Q are exactly
+ * symmetric; G does not depend on n_targets nor a column of r on the others.  Common refusals (GPMPC_E_ARG with a text in gpmpc_last_error,
+ * before any launch): M < 1 or M > GPMPC_SPARSE_MAX_M, D outside 1...GPMPC_MAX_D, n_targets outside 1...GPMPC_MAX_DS, a row stride below
+ * its row length, a NULL pointer.  A workspace below *_workspace_bytes: GPMPC_E_WORKSPACE.
+ *
+ * gpmpc_sparse_accumulate: G, r and stats [2] = {rows accumulated, min Lambda_n} over the n rows of X [n][D], Y [n][ld_y] (first n_targets
+ *   columns).  Rows are taken in chunks of `chunk` (a multiple of 64; 0: the default, 4096): V_c = W k(Z, X_c) into the workspace ([M][chunk],
+ *   kernel values generated on the fly, the triangle of W used), Lambda_c, then G += V_c Lambda_c^-1 V_c^T, r += V_c Lambda_c^-1 Y_c; chunks are
+ *   added in call order.  accumulate 0: outputs overwritten (they may hold anything); 1: added to what G, r, stats hold.  A call over rows
+ *   [0, n) equals one over [0, s) followed by accumulate = 1 over [s, n) bit for bit when s is a multiple of chunk; the result may depend on
+ *   chunk and on nothing else.  The workspace size depends on (M, chunk) only.  Also refused: n < 1, chunk negative or no multiple of 64.
+ *   The two N M^2 products exist in two forms, scalar fp64 FMA on 4 x 4 register tiles and v_mfma_f64_16x16x4_f64; gpmpc_sparse_set_form
+ *   chooses between them for the whole process (GPMPC_SPARSE_FORM_FMA | GPMPC_SPARSE_FORM_MFMA; -1 only asks) and returns the form that was
+ *   set before; anything else is GPMPC_E_ARG.  Every property above holds within a form; the two forms agree to rounding, not bit for bit.
+ * gpmpc_sparse_finish: alpha and Q from W, Binv, r.  M^3-class, no pass over the data.
+ * gpmpc_sparse_append: ONE observation x_new dev [D], y_new dev [n_targets], O(M^2) whatever n is:
+ *     v = W k(Z, x); Lambda = sigma_f^2 + noise_var - |v|^2; t = Binv v; den = Lambda + v . t; u = W^T t
+ *     G += v v^T / Lambda; r += v y^T / Lambda; Binv -= t t^T / den; Q += u u^T / den; alpha = W^T (Binv r); stats += {1, min}
+ *   in place.  Six dependent launches (v | t | u | the M x M streams and r | Binv r | alpha), no allocation, no host round trip; G, Binv
+ *   and Q stay exactly symmetric.
+ * ------------------------------------------------------------------------- */
+#define GPMPC_SPARSE_MAX_M 8192
+#define GPMPC_SPARSE_FORM_FMA  0
+#define GPMPC_SPARSE_FORM_MFMA 1
+#define GPMPC_SPARSE_FORM_DEFAULT GPMPC_SPARSE_FORM_MFMA  /* the measured choice (0.80-0.83 of the FMA form's time): DESIGN.md section 3h */
+int gpmpc_sparse_set_form(int form);
+size_t gpmpc_sparse_accumulate_workspace_bytes(int n, int D, int M, int n_targets, int chunk);
+int gpmpc_sparse_accumulate(int n, int D, int M, int n_targets, const double* X_dev, const double* Y_dev, size_t ld_y,
+                            const double* Z_dev, const double* W_dev, size_t ld_w, const double* lambdas_host, double sigma_f,
+                            double noise_var, int chunk, int accumulate, double* G_dev, double* r_dev, double* stats_dev,
+                            void* workspace, size_t workspace_bytes, void* stream);
+size_t gpmpc_sparse_finish_workspace_bytes(int M, int n_targets);
+int gpmpc_sparse_finish(int M, int n_targets, const double* W_dev, size_t ld_w, const double* Binv_dev, const double* r_dev,
+                        double* alpha_dev, double* Q_dev, void* workspace, size_t workspace_bytes, void* stream);
+size_t gpmpc_sparse_append_workspace_bytes(int M, int n_targets);
+int gpmpc_sparse_append(int D, int M, int n_targets, const double* x_new_dev, const double* y_new_dev, const double* Z_dev,
+                        const double* W_dev, size_t ld_w, const double* lambdas_host, double sigma_f, double noise_var,
+                        double* G_dev, double* r_dev, double* Binv_dev, double* Q_dev, double* alpha_dev, double* stats_dev,
+                        void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
