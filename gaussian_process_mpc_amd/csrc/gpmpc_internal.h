@@ -351,6 +351,9 @@ __device__ __forceinline__ double wave_row_sum(double v) {
     return v;
 }
 
+// Fixed-order combine of the four row sums of one wave, stored s doubles apart: (row 0 + row 1) + (row 2 + row 3)
+__device__ __forceinline__ double gpmpc_rows4(const double* r, int s) { return (r[0] + r[s]) + (r[2 * s] + r[3 * s]); }
+
 // The same for workgroups of exactly 4 waves (256 threads), with the cheaper row sums: scratch >= 16*NV doubles
 // ([wave][row of 16 lanes][value]); fixed summation order.
 template <int NV>
@@ -365,8 +368,7 @@ __device__ __forceinline__ void block_sum4_rows(const double (&v)[NV], double* s
     if (threadIdx.x < NV) {
         double s = 0;
         for (int ww = 0; ww < 4; ++ww) {
-            const double* r4 = &scratch[ww * 4 * NV + threadIdx.x];
-            s += (r4[0] + r4[NV]) + (r4[2 * NV] + r4[3 * NV]);
+            s += gpmpc_rows4(&scratch[ww * 4 * NV + threadIdx.x], NV);
         }
         out[threadIdx.x] = s;
     }

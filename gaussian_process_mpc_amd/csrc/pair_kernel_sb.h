@@ -21,6 +21,7 @@
 #pragma once
 #include "gpmpc_internal.h"
 #include "fast_exp.h"
+#include "pair_sb_dev.h"
 #include <cstdlib>
 
 // Columns per iteration of the column loop.  ONE is fastest: the plain load / wait / evaluate loop (43 instructions,
@@ -52,11 +53,6 @@ static __device__ unsigned long long g_sb_stamps[8192 * GPMPC_SB_NSTAMP];
 #else
 #define GPMPC_SBST(slot, val) do { } while (0)
 #endif
-
-template <int D, int NS2>
-struct PairSbTraits {
-    static constexpr int GW = (D + 1 + NS2 + 1) & ~1;     // doubles per G row (even: rows stay 16-byte aligned)
-};
 
 // GRAD = false: objective only (Z0), NM = 1.  (A two-rows-per-lane shape was measured 15 % slower: occupancy wins.)
 // FIRST: horizon step 1, whose state inputs (x0, Sigma_0) are constants: only the derivatives w.r.t. the action dimensions
@@ -227,8 +223,7 @@ __global__ __launch_bounds__(256, (TB == 2 && D <= 5) ? GPMPC_SB_TB2_WAVES : 1) 
         if (b < A.B) {
             double s = 0.0;                       // fixed order: waves, each as (row 0 + row 1) + (row 2 + row 3)
             for (int ww = 0; ww < (int)(blockDim.x >> 6); ++ww) {
-                const double* r4 = &s_red[(ww * 4 * TB + tb) * NM + m];
-                s += (r4[0] + r4[TB * NM]) + (r4[2 * TB * NM] + r4[3 * TB * NM]);
+                s += gpmpc_rows4(&s_red[(ww * 4 * TB + tb) * NM + m], TB * NM);
             }
             A.part[((size_t)b * A.nwork + wi) * A.nm + m] = s;
         }

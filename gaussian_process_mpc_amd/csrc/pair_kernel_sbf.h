@@ -170,10 +170,7 @@ __global__ __launch_bounds__(256, (CU == 2 && GRAD && D <= 5) ? GPMPC_SBF_MINWG 
     __syncthreads();
     for (int m = tid; m < NM; m += blockDim.x) {
         double s = 0.0;
-        for (int ww = 0; ww < (int)(blockDim.x >> 6); ++ww) {
-            const double* r4 = &s_red[ww * 4 * NM + m];
-            s += (r4[0] + r4[NM]) + (r4[2 * NM] + r4[3 * NM]);
-        }
+        for (int ww = 0; ww < (int)(blockDim.x >> 6); ++ww) s += gpmpc_rows4(&s_red[ww * 4 * NM + m], NM);
         const size_t stride = A.pstride > 0 ? A.pstride : A.nwork;        // (slots per trajectory: more than this launch's items with one lambda)
         A.part[((size_t)b * stride + wi) * A.nm + m] = s;
         if (m == 0 && A.part0) A.part0[(size_t)b * stride + wi] = s;

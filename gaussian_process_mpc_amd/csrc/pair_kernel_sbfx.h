@@ -166,7 +166,7 @@ __global__ __launch_bounds__(256, 2) void gpmpc_pair_kernel_sbfx(PairSbfxArgs A)
             if (k < NS2 && l < NS2) ma = 1 + D + (k * NS2 - k * (k - 1) / 2 + (l - k));
         }
         double sum = 0.0;
-        if (ma >= 0) { const int q = pr * NA + ma; sum = (s_red[q] + s_red[NP * NA + q]) + (s_red[2 * NP * NA + q] + s_red[3 * NP * NA + q]); }
+        if (ma >= 0) sum = gpmpc_rows4(&s_red[pr * NA + ma], NP * NA);
         const int a = A.pair_ab[2 * pr], c = A.pair_ab[2 * pr + 1];
         const double s2 = A.sf[a] * A.sf[a] * A.sf[c] * A.sf[c];
         const size_t wi = (size_t)A.base + (size_t)pr * A.ntile + tile;

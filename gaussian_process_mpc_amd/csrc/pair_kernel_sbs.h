@@ -21,11 +21,7 @@
 #pragma once
 #include "gpmpc_internal.h"
 #include "fast_exp.h"
-
-template <int D, int NS2>
-struct PairSbsTraits {
-    static constexpr int GW = (D + 1 + NS2 + 1) & ~1;     // doubles per G row, as PairSbTraits
-};
+#include "pair_sb_dev.h"
 
 // waves per SIMD the instance is compiled for: 2 VGPRs per accumulator + ~48 for everything else, out of 512
 constexpr int gpmpc_sbs_waves(int NG, int NA) {
@@ -41,7 +37,7 @@ constexpr int gpmpc_sbs_waves(int NG, int NA) {
 template <int D, int NG, int NS2, bool GRAD, bool FIRST = false>
 __global__ __launch_bounds__(256, gpmpc_sbs_waves(NG, GRAD ? (FIRST ? 1 + D - NS2 : 1 + D + NS2) : 1))
 void gpmpc_pair_kernel_sbs(PairSbsArgs A) {
-    constexpr int GW = PairSbsTraits<D, NS2>::GW;
+    constexpr int GW = PairSbTraits<D, NS2>::GW;
     constexpr int NM = GRAD ? 1 + 2 * D : 1, NA = GRAD ? 1 + D + NS2 : 1;
     __shared__ double s_red[16 * NG * NM];        // [wave][row of 16 lanes][GP of the group][moment]
     __shared__ double s_tab[GPMPC_EXP_N];
@@ -100,19 +96,9 @@ void gpmpc_pair_kernel_sbs(PairSbsArgs A) {
             Mrs[g] = __builtin_amdgcn_make_buffer_rsrc(const_cast<double*>(A.M + ((size_t)a * Np + jstart) * Np + iw0), 0, 0x7fffffff, 0x00020000);
         }
         const int lane8 = lane * 8;
-#ifndef GPMPC_SBS_CU
-#define GPMPC_SBS_CU 1       /* columns per loop iteration (A/B knob; 1 measured best, see profiles/r03/ab_shared_columns.txt) */
-#endif
-        constexpr int CU = GPMPC_SBS_CU;
-#ifndef GPMPC_SBS_PREFETCH
-#define GPMPC_SBS_PREFETCH 0     /* 1: the NG weights of column jc + 1 are requested before column jc is evaluated (register double buffer, 124 instead of
-                                    114 VGPRs, still 4 waves per SIMD).  Measured -2...-4 % (C3 sizes with one lambda, B = 256: 26.5 -> 27.4 ms per batch;
-                                    N = 1024, B = 256: 7.31 -> 7.60 ms; profiles/r04/ab_shared_prefetch.txt): A/B build only */
-#endif
-#ifndef GPMPC_SBS_STAGED
-#define GPMPC_SBS_STAGED 1       /* round 5: columns in batches of two with the stages pinned (see below); 0: the one-column loop */
-#endif
-        if constexpr (GPMPC_SBS_STAGED && GRAD && !FIRST) {
+        // Tried and lost, removed (see git history): two columns per iteration of the one-column loop (profiles/r03/ab_shared_columns.txt), and
+        // the weights of column jc + 1 requested before column jc is evaluated, 2-4 % slower (profiles/r04/ab_shared_prefetch.txt).
+        if constexpr (GRAD && !FIRST) {
             // Round 5 (as traj_persist.h / step_fused.h).  At 3-4 waves per SIMD a wave of the one-column loop -- weights requested, G row
             // requested, both waited for, exponent, table read, waited for, ~57 instructions of arithmetic -- leaves its SIMD to the others
             // for ~900 cycles per column, and they have 750 of arithmetic to fill them with: VALU issue 0.61 of its bound at C3 sizes with
@@ -130,34 +116,7 @@ void gpmpc_pair_kernel_sbs(PairSbsArgs A) {
                     for (int k = 0; k < D + 1 + NS2; ++k) gr[c][k] = gp[k];
                 }
                 __builtin_amdgcn_sched_barrier(0);
-                double fr[KC], Tv[KC];
-                int ni[KC];
-#pragma unroll
-                for (int c = 0; c < KC; ++c) {
-                    double sx = qi + gr[c][D];
-#pragma unroll
-                    for (int k = 0; k < D; ++k) sx = fma(hi2[k], gr[c][k], sx);
-                    const double ax = __builtin_fabs(sx);          // gpmpc_exp_neg_scaled (fast_exp.h), split around the table read
-                    ni[c] = (int)(-ax);
-                    fr[c] = __builtin_amdgcn_fract(ax);
-                    Tv[c] = s_tab[ni[c] & (GPMPC_EXP_N - 1)];
-                }
-                __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                for (int c = 0; c < KC; ++c) {
-                    const double pq = fma(fr[c], fma(fr[c], GPMPC_EXP_A3, GPMPC_EXP_A2), GPMPC_EXP_A1);
-                    const double e = ldexp(fma(Tv[c] * fr[c], pq, Tv[c]), ni[c] >> GPMPC_EXP_BITS);
-#pragma unroll
-                    for (int q = 0; q < NG; ++q) {
-                        const double P = mij[c][q] * e;
-                        acc[q][0] += P;
-#pragma unroll
-                        for (int k = 0; k < D; ++k) acc[q][1 + k] = fma(P, gr[c][k], acc[q][1 + k]);
-#pragma unroll
-                        for (int k = 0; k < NS2; ++k) acc[q][1 + D + k] = fma(P, gr[c][D + 1 + k], acc[q][1 + D + k]);
-                    }
-                }
-                __builtin_amdgcn_sched_barrier(0);
+                gpmpc_sb_batch<D, NS2, GRAD, NG, KC, false>(gr, mij, hi2, qi, s_tab, acc);
             };
             auto wload = [&](double (*m)[NG], int jrel) {
 #pragma unroll
@@ -187,54 +146,38 @@ void gpmpc_pair_kernel_sbs(PairSbsArgs A) {
                 }
             }
         } else {
-        constexpr bool PRE = GPMPC_SBS_PREFETCH && CU == 1;
-        double mnext[NG];
-        if (PRE) {
+            // objective only, and horizon step 1: the one-column loop, in the generic form of pair_kernel_sb.h (see the note there: a
+            // hand-simplified body with the same arithmetic is scheduled differently)
+            constexpr int CU = 1;
+            for (int jc = jstart; jc < j1; jc += CU) {
+                double mij[CU][NG];
 #pragma unroll
-            for (int g = 0; g < NG; ++g) mnext[g] = __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(Mrs[g], lane8, 0, 0));
-        }
-        for (int jc = jstart; jc < j1; jc += CU) {
-            double mij[CU][NG];
-            if (PRE) {
-                // this kernel runs 3-4 waves per SIMD (NG x (1 + D + ds) accumulators): a wave that issues its NG loads, waits for
-                // them and only then evaluates the column leaves its SIMD to 2-3 others for a whole L2 round trip -- VALU-busy 0.81
-                // against 0.88-0.95 of the distinct-lambda kernels (profiles/r03/pmc_C3_shared.json).  One column ahead costs 2 NG
-                // registers.  The last iteration re-requests its own column (in bounds, unused).
-                const int jn = jc + 1 < j1 ? jc + 1 : jc;
+                for (int c = 0; c < CU; ++c)
 #pragma unroll
-                for (int g = 0; g < NG; ++g) {
-                    mij[0][g] = mnext[g];
-                    mnext[g] = __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(Mrs[g], lane8, (jn - jstart) * Np * 8, 0));
-                }
-            } else {
+                    for (int g = 0; g < NG; ++g)
+                        mij[c][g] = __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(Mrs[g], lane8, (jc - jstart + c) * Np * 8, 0));
+                __builtin_amdgcn_sched_barrier(0);            // loads stay at the top of the iteration (pair_kernel_sb.h)
 #pragma unroll
-            for (int c = 0; c < CU; ++c)
+                for (int c = 0; c < CU; ++c) {
+                    typedef const double __attribute__((address_space(4))) gpmpc_cdouble;      // constant for the launch: scalar loads
+                    const gpmpc_cdouble* __restrict__ g = (const gpmpc_cdouble*)(Gt + (size_t)(jc + c) * GW);
+                    double s = qi + g[D];
 #pragma unroll
-                for (int g = 0; g < NG; ++g)
-                    mij[c][g] = __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(Mrs[g], lane8, (jc - jstart + c) * Np * 8, 0));
-            }
-            __builtin_amdgcn_sched_barrier(0);            // loads stay at the top of the iteration (pair_kernel_sb.h)
+                    for (int k = 0; k < D; ++k) s = fma(hi2[k], g[k], s);
+                    const double e = gpmpc_exp_neg_scaled(s, s_tab);
 #pragma unroll
-            for (int c = 0; c < CU; ++c) {
-                typedef const double __attribute__((address_space(4))) gpmpc_cdouble;      // constant for the launch: scalar loads
-                const gpmpc_cdouble* __restrict__ g = (const gpmpc_cdouble*)(Gt + (size_t)(jc + c) * GW);
-                double s = qi + g[D];
+                    for (int q = 0; q < NG; ++q) {
+                        const double P = mij[c][q] * e;
+                        acc[q][0] += P;
+                        if (GRAD) {
 #pragma unroll
-                for (int k = 0; k < D; ++k) s = fma(hi2[k], g[k], s);
-                const double e = gpmpc_exp_neg_scaled(s, s_tab);
+                            for (int k = 0; k < D; ++k) if (!FIRST || k >= NS2) acc[q][1 + k] = fma(P, g[k], acc[q][1 + k]);
 #pragma unroll
-                for (int q = 0; q < NG; ++q) {
-                    const double P = mij[c][q] * e;
-                    acc[q][0] += P;
-                    if (GRAD) {
-#pragma unroll
-                        for (int k = 0; k < D; ++k) if (!FIRST || k >= NS2) acc[q][1 + k] = fma(P, g[k], acc[q][1 + k]);
-#pragma unroll
-                        for (int k = 0; k < NS2; ++k) if (!FIRST) acc[q][1 + D + k] = fma(P, g[D + 1 + k], acc[q][1 + D + k]);
+                            for (int k = 0; k < NS2; ++k) if (!FIRST) acc[q][1 + D + k] = fma(P, g[D + 1 + k], acc[q][1 + D + k]);
+                        }
                     }
                 }
             }
-        }
         }
     }
 
@@ -267,8 +210,7 @@ void gpmpc_pair_kernel_sbs(PairSbsArgs A) {
         if (a < A.ds) {
             double s = 0.0;                       // fixed order: waves, each as (row 0 + row 1) + (row 2 + row 3)
             for (int ww = 0; ww < (int)(blockDim.x >> 6); ++ww) {
-                const double* r4 = &s_red[(ww * 4 * NG + q) * NM + m];
-                s += (r4[0] + r4[NG * NM]) + (r4[2 * NG * NM] + r4[3 * NG * NM]);
+                s += gpmpc_rows4(&s_red[(ww * 4 * NG + q) * NM + m], NG * NM);
             }
             A.part[((size_t)b * A.ds * A.tiles + (size_t)a * A.tiles + tile) * A.nm + m] = s;
         }

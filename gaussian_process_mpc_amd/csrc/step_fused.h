@@ -31,6 +31,7 @@
 #pragma once
 #include "gpmpc_internal.h"
 #include "fast_exp.h"
+#include "pair_sb_dev.h"
 
 // Item q of the 64x64 upper-triangular list of one unit (worklist.h::gpmpc_build_tile_list: row tile r, then column tile c >= r;
 // T tiles per side): r is the largest row with start(r) = r T - r (r - 1) / 2 <= q.  Saves the dependent load of the item.
@@ -63,12 +64,8 @@ static __device__ unsigned long long g_fused_wg[2 * 8192];         // [start | e
 #define GPMPC_STAMP_WG(which) do { } while (0)
 #endif
 
-// The tile pieces of this kernel evaluate 4..16 columns per wave: copying the 16 KB exp table into LDS per workgroup (7 MB
-// per launch at N = 512, most of the burst every workgroup opens with) costs more than the ~12 extra fp64 instructions per
-// pair of the table-free exp.  GPMPC_FUSED_TABLE=1 restores the table (A/B).
-#ifndef GPMPC_FUSED_TABLE
-#define GPMPC_FUSED_TABLE 0
-#endif
+// The tile pieces of the 64-row forms evaluate 4..16 columns per wave with the table-free exp: copying the 16 KB exp table into LDS per
+// workgroup (7 MB per launch at N = 512) cost more than the ~12 extra fp64 instructions per pair.  (The table variant was removed; see git history.)
 #ifndef GPMPC_FUSED_UNROLL
 // Columns of the evaluation loop in flight per wave.  Fully unrolled (16 for a whole tile's share) three instantiations were
 // compiled to 256 VGPRs; 2 / 4 / 8 avoid that and differ little, 2 gives the pendulum shape <3, 2> a fourth wave per SIMD
@@ -79,40 +76,16 @@ static __device__ unsigned long long g_fused_wg[2 * 8192];         // [start | e
 #ifndef GPMPC_FUSED_PZ_SB
 #define GPMPC_FUSED_PZ_SB 6     // ... of the 256-row forms: 384 per GP in the first round trip (N = 2048 on 256x32 tiles has 288), the rest 4 at a time
 #endif
-#ifndef GPMPC_FUSED_XCDMAP
-#define GPMPC_FUSED_XCDMAP 1      // XCD-aware dispatch order of the 256-row forms for several trajectories (A/B: profiles/r05/ab19_xcdmap.txt)
-#endif
-#ifndef GPMPC_FUSED_PIPE_EARLY
-#define GPMPC_FUSED_PIPE_EARLY 1    // first group requested in phase 0 (1) or when the column loop starts (0)
-#endif
-#ifndef GPMPC_FUSED_PIPE_ILP
-#define GPMPC_FUSED_PIPE_ILP 2      // columns whose dependency chains the scheduler may interleave (4 held ~20 more registers: spills at the 96 of 5 waves)
-#endif
 #ifndef GPMPC_FUSED_MEAN_UNROLL
 #define GPMPC_FUSED_MEAN_UNROLL 2   // points per round trip of the mean-sum workgroups of the 256-row forms
-#endif
-#ifndef GPMPC_FUSED_STAGED
-#define GPMPC_FUSED_STAGED 1      // the 256-row forms' column loop in staged batches with the next weight group in flight (round 5); 0: the four-column body
 #endif
 #ifndef GPMPC_FUSED_MGS
 #define GPMPC_FUSED_MGS 2         // columns per group of weight loads of the staged loop (two groups in flight)
 #endif
-#ifndef GPMPC_FUSED_PIPE
-// 256-row forms (Q = 0 / 32 / 16, one GP per tile workgroup): the weight stream M_ij is software-pipelined -- the first group of
-// columns is requested in phase 0, behind every load the prologue waits for (vector-memory results return in order, so the prologue's
-// counted waits do not include it), and group g + 1 is requested before group g is evaluated.  One or a few trajectories of a large
-// training set stream M from HBM / Infinity Cache with a handful of waves per SIMD: a wave that issues its loads, waits, and only then
-// evaluates has nothing in flight half of the time (N = 2048, B = 1: 3.2 TB/s of the 67 MB per step; N = 4096, ds = 6: 3.3 TB/s).
-// Same sums in the same order: results are bit-identical to the unpipelined loop.
-// MEASURED (round 4, profiles/r04/ab_fused_pipeline.txt): it LOSES 4-20 % everywhere it applies, with the first group requested in
-// phase 0 or at the loop, two or four columns interleaved -- N = 2048, B = 1: 0.485 -> 0.509 ms per rollout; N = 4096, ds = 6, B = 1:
-// 3.59 -> 3.90 ms; N = 1024, B = 16: 0.98 -> 1.07 ms.  The in-kernel timeline (tools/fused_stamps.py, profiles/r04/fused_stamps_*.txt)
-// says why: at N = 2048, B = 1 the 4.5 waves per SIMD of the single workgroup generation already saturate VALU issue in the column loop
-// (2170 cycles per four columns = 4.5 waves x 4 x 27 instructions x 4.4 cycles), the launch is prologue + loop + reduction in lock-step;
-// at N = 4096, ds = 6 a column costs a wave 834 cycles against 145 of issue because its G row (28 SGPRs) is fetched by scalar loads one
-// column at a time -- the SGPR file holds two of them -- and neither is a matter of weight loads in flight.  Kept as an A/B build (1).
-#define GPMPC_FUSED_PIPE 0
-#endif
+// Tried and lost, removed (see git history): the weight stream of the 256-row forms software-pipelined from phase 0 on (first group requested
+// behind the prologue's loads, group g + 1 before group g is evaluated) was 4-20 % slower everywhere it applied -- the column loop is bound by VALU
+// issue or by the scalar loads of the G rows, not by weight loads in flight (profiles/r04/ab_fused_pipeline.txt).  The staged batches of the
+// column loop below replaced the four-column body they were measured against (+2 ... +7 %).
 
 // Q = 0: the MID-SIZE form (round 3).  The tile workgroups take 256 x 64 tiles (work list 2) and run the SCALAR-BROADCAST column
 // loop of pair_kernel_sb.h (four columns in flight, table exp) instead of the staged one: a batch of B = 4...32 trajectories of
@@ -141,10 +114,8 @@ void k_step_fused(FusedArgs A, int t) {
     constexpr int QQ = SB ? 1 : Q;
     constexpr int DS = NS2, DA = D - NS2, NM = GRAD ? 1 + 2 * D : 1, DP = (D + 1) & ~1;
     constexpr int NV = 1 + 2 * D, NT = 256, CW = 16 / QQ, NCOL = 64 / QQ;          // NCOL columns of a chunk per workgroup
-    constexpr int TABN = GPMPC_EXP_N / NT; (void)TABN;
-    constexpr bool TABLE = SB || GPMPC_FUSED_TABLE;
-    constexpr int GW = (D + 1 + NS2 + 1) & ~1;                                     // doubles per G row, as PairSbTraits
-    __shared__ double s_tab[TABLE ? GPMPC_EXP_N : 1];
+    constexpr int GW = PairSbTraits<D, NS2>::GW;                                   // doubles per G row
+    __shared__ double s_tab[SB ? GPMPC_EXP_N : 1];
     __shared__ __attribute__((aligned(16))) double s_hj[SB ? 2 : NCOL * DP];
     __shared__ double s_red[16 * NV * NG];
     __shared__ double s_out[NV];
@@ -153,9 +124,6 @@ void k_step_fused(FusedArgs A, int t) {
     __shared__ double s_spp[4 * D];
     __shared__ double s_uin[D], s_sin[D], s_sck[D], s_cv[D];     // input moments of step t and the pair transform h = sc (u - x)
     const int tid = threadIdx.x, lane = tid & 63;
-#if !GPMPC_FUSED_XCDMAP
-    const int b = blockIdx.y; unsigned bx = blockIdx.x;
-#else
     int b = blockIdx.y; unsigned bx = blockIdx.x;
     // XCD-aware order for several trajectories (256-row forms): workgroups go to the 8 XCDs round-robin in dispatch order (x fastest), each
     // XCD with its own L2.  In the natural order trajectory b + 1 visits a tile ntile + 2 ds workgroups after trajectory b -- another XCD as
@@ -166,7 +134,6 @@ void k_step_fused(FusedArgs A, int t) {
         const int gx = gridDim.x;
         gpmpc_xcd_remap((int)blockIdx.y * gx + (int)blockIdx.x, gx, A.ntile, A.B, &b, &bx);
     }
-#endif
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int role = ((int)bx >= A.ntile) + ((int)bx >= A.ntile + DS);     // 0 tile | 1 mean sums | 2 finish  (as a sum of comparisons: the select form of the same value costs the D = 5 instances 13 VGPR spills -- block placement)
     const int Np = A.Np, pprev = (t - 1) & 1, pcur = t & 1;
@@ -210,7 +177,6 @@ void k_step_fused(FusedArgs A, int t) {
     //      followed by its own s_waitcnt, which serialises the round trips. ---------------------------------------------------
     int unit = 0, i0 = 0, j0 = 0, j1 = 0, jq = 0;
     double xrow[D], xcol[D], mpre[CW];
-    double tabreg[(TABLE && !SB) ? TABN : 1];
     if (role == 0) {
         const int item = (int)bx / QQ;
         jq = ((int)bx - item * QQ) * NCOL;                                    // this workgroup's columns of every chunk
@@ -304,27 +270,11 @@ void k_step_fused(FusedArgs A, int t) {
             const int e = ((w * 4 + r) * 64 + lane) * 2;
             __builtin_amdgcn_global_load_lds((gvoid*)(gpmpc_exp2_table + e), (lvoid*)(s_tab + e), 16, 0, 0);
         }
-    } else if (TABLE && role == 0) {
-#pragma unroll
-        for (int r = 0; r < TABN; ++r) tabreg[r] = gpmpc_exp2_table[tid + r * NT];   // LDS write deferred: see below
     }
-    // 256-row forms: the first group of weight columns of this wave, requested LAST in phase 0 (see GPMPC_FUSED_PIPE above)
-    constexpr bool PIPE = SB && !SH && GPMPC_FUSED_PIPE;
-    constexpr bool EARLY = PIPE && GPMPC_FUSED_PIPE_EARLY;
-    constexpr int MG = 4;                                           // columns per group (two groups in flight)
-    double mga[PIPE ? MG : 1];
     const int iw0_t = i0 + 64 * w;
     const bool wave_on = role == 0 && iw0_t < Np && (NC > 64 ? j1 > iw0_t : j0 >= iw0_t);    // tiles left of the wave's diagonal block carry no weight (wave-uniform; runs, NC = 256: a run that ENDS left of it)
     __amdgpu_buffer_rsrc_t Mrs_t = __builtin_amdgcn_make_buffer_rsrc(
         const_cast<double*>(A.M + (size_t)unit * Np * Np + (size_t)j0 * Np + (wave_on ? iw0_t : 0)), 0, 0x7fffffff, 0x00020000);
-    if constexpr (EARLY) {
-        if (wave_on) {
-#pragma unroll
-            for (int q = 0; q < MG; ++q)
-                mga[q] = __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(Mrs_t, lane * 8, q * Np * 8, 0));
-        }
-        __builtin_amdgcn_sched_barrier(0);                          // ... and not moved in front of the loads above
-    }
     // mean sums: this thread's first points (the loop below loads the ones beyond)
     constexpr int PF = SB ? 1 : 2;                                  // (mid-size form: registers; N >= 1024 loops anyway)
     double xpt[PF][D], bpt[PF], sf_a = 0.0;
@@ -401,10 +351,6 @@ void k_step_fused(FusedArgs A, int t) {
         const double sc = rsqrt(8.0 * (0.5 * lam_k + sk));
         s_sck[k] = sc;
         s_cv[k] = sc * uk;
-    }
-    if (TABLE && !SB && role == 0) {
-#pragma unroll
-        for (int r = 0; r < TABN; ++r) s_tab[tid + r * NT] = tabreg[r];
     }
     __syncthreads();
     GPMPC_STAMP(3);
@@ -530,8 +476,7 @@ void k_step_fused(FusedArgs A, int t) {
                 if (a < DS) {
                     double sum = 0.0;                                    // fixed order: waves, each as (row 0 + row 1) + (row 2 + row 3)
                     for (int ww = 0; ww < 4; ++ww) {
-                        const double* r4 = &s_red[(ww * 4 * NG + q) * NM + m];
-                        sum += (r4[0] + r4[NG * NM]) + (r4[2 * NG * NM] + r4[3 * NG * NM]);
+                        sum += gpmpc_rows4(&s_red[(ww * 4 * NG + q) * NM + m], NG * NM);
                     }
                     const size_t o = ((size_t)pcur * A.B + b) * A.nwork + (size_t)a * A.tiles + tile;
                     A.part[o * A.nm + m] = sum;
@@ -540,9 +485,9 @@ void k_step_fused(FusedArgs A, int t) {
             }
             return;
         }
-        double acc[NA];
+        double acc[1][NA];                                               // (one GP: the batch helper takes [GP][sum])
 #pragma unroll
-        for (int m = 0; m < NA; ++m) acc[m] = 0.0;
+        for (int m = 0; m < NA; ++m) acc[0][m] = 0.0;
         __syncthreads();                                                 // G rows and exp table ready
         GPMPC_STAMP(4);
         // (runs, NC = 256: a run may START left of this wave's diagonal block -- the wave enters at the block's first column, jst)
@@ -555,59 +500,9 @@ void k_step_fused(FusedArgs A, int t) {
             const __amdgpu_buffer_rsrc_t Mrs = Mrs_t;
             const int lane8 = lane * 8;
             typedef const double __attribute__((address_space(4))) gpmpc_cdouble;
-            // one column: exponent from the wave-uniform row G[j] (scalar loads), table exp, weight, moments (pair_kernel_sb.h)
-            auto column = [&](int j, double mij) {
-                const gpmpc_cdouble* __restrict__ g = (const gpmpc_cdouble*)(Gl + (size_t)j * GW);
-                double sx = qi + g[D];
-#pragma unroll
-                for (int k = 0; k < D; ++k) sx = fma(hi2[k], g[k], sx);
-                const double P = mij * gpmpc_exp_neg_scaled(sx, s_tab);
-                acc[0] += P;
-                if (GRAD) {
-#pragma unroll
-                    for (int k = 0; k < D; ++k) acc[GRAD ? 1 + k : 0] = fma(P, g[k], acc[GRAD ? 1 + k : 0]);
-#pragma unroll
-                    for (int k = 0; k < NS2; ++k) acc[GRAD ? 1 + D + k : 0] = fma(P, g[D + 1 + k], acc[GRAD ? 1 + D + k : 0]);
-                }
-            };
-            if constexpr (PIPE) {
-                if constexpr (!EARLY) {
-#pragma unroll
-                    for (int q = 0; q < MG; ++q)
-                        mga[q] = __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(Mrs, lane8, q * Np * 8, 0));
-                }
-                static_assert(NC % (2 * MG) == 0, "two groups of columns per iteration");
-                constexpr int PAIRW = GPMPC_FUSED_PIPE_ILP;
-                double mgb[MG];
-                for (int jc = 0; jc < NC; jc += 2 * MG) {
-#pragma unroll
-                    for (int q = 0; q < MG; ++q)                         // group jc + MG: in flight while group jc is evaluated
-                        mgb[q] = __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(Mrs, lane8, (jc + MG + q) * Np * 8, 0));
-                    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                    for (int q = 0; q < MG; ++q) {
-                        column(jc + q, mga[q]);
-                        if (q % PAIRW == PAIRW - 1) __builtin_amdgcn_sched_barrier(0);      // PAIRW columns' dependency chains interleaved at a time
-                    }
-                    {   // group jc + 2 MG; UNCONDITIONAL (the last iteration re-requests its own first group, unused): under a
-                        // branch the compiler's wait counts merge both paths and every wait below becomes "all loads done"
-                        const int jn = jc + 2 * MG < NC ? jc + 2 * MG : jc;
-#pragma unroll
-                        for (int q = 0; q < MG; ++q)
-                            mga[q] = __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(Mrs, lane8, (jn + q) * Np * 8, 0));
-                    }
-                    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                    for (int q = 0; q < MG; ++q) {
-                        column(jc + MG + q, mgb[q]);
-                        if (q % PAIRW == PAIRW - 1) __builtin_amdgcn_sched_barrier(0);
-                    }
-                }
-            } else {
             const int ncw = __builtin_amdgcn_readfirstlane(ncw_v);
             const int nct = j1 - j0 < NC ? j1 - j0 : NC;                      // (work list 7: the last tiles of the list are 16 columns wide)
             const int ncl = ncw - j0 < nct ? ncw - j0 : nct;                  // columns of this tile that carry weight (a multiple of 8, or <= 0)
-#if GPMPC_FUSED_STAGED
             // Round 5 (as traj_persist.h): a wave of this loop is bound by its own latency chain, not by issue -- the compiler's schedule
             // of the four-column body waited for the G rows twice, for the exp table four times and for the weights of the SAME
             // iteration (no load in flight across iterations) per four columns; at D = 7 (C4, one trajectory: 834 cycles per column
@@ -616,10 +511,10 @@ void k_step_fused(FusedArgs A, int t) {
             // loads of the next group of columns are in flight (unconditional refill, two register sets in alternation).
             constexpr int MGS = GPMPC_FUSED_MGS, KC = (D >= 8 || (MGS > 2 && D >= 7)) ? 1 : 2;     // (MGS = 4: an A/B option, more weight loads in flight)
             static_assert(8 % (2 * MGS) == 0 && MGS % KC == 0, "tiles carry multiples of 8 columns");
-            double wa[MGS], wb[MGS];
+            double wa[MGS][1], wb[MGS][1];
 #pragma unroll
-            for (int q = 0; q < MGS; ++q) wa[q] = __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(Mrs, lane8, (jst + q) * Np * 8, 0));
-            auto batch = [&](int j, const double* mw) {
+            for (int q = 0; q < MGS; ++q) wa[q][0] = __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(Mrs, lane8, (jst + q) * Np * 8, 0));
+            auto batch = [&](int j, const double (*mw)[1]) {
                 double g[KC][GW];
 #pragma unroll
                 for (int c = 0; c < KC; ++c) {
@@ -628,37 +523,12 @@ void k_step_fused(FusedArgs A, int t) {
                     for (int k = 0; k < D + 1 + NS2; ++k) g[c][k] = gp[k];
                 }
                 __builtin_amdgcn_sched_barrier(0);
-                double fr[KC], pq[KC], Tv[KC];
-                int ni[KC];
-#pragma unroll
-                for (int c = 0; c < KC; ++c) {
-                    double sx = qi + g[c][D];
-#pragma unroll
-                    for (int k = 0; k < D; ++k) sx = fma(hi2[k], g[c][k], sx);
-                    const double ax = __builtin_fabs(sx);            // gpmpc_exp_neg_scaled (fast_exp.h), split around the table read
-                    ni[c] = (int)(-ax);
-                    fr[c] = __builtin_amdgcn_fract(ax);
-                    Tv[c] = s_tab[ni[c] & (GPMPC_EXP_N - 1)];
-                    pq[c] = fma(fr[c], fma(fr[c], GPMPC_EXP_A3, GPMPC_EXP_A2), GPMPC_EXP_A1);
-                }
-                __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                for (int c = 0; c < KC; ++c) {
-                    const double P = mw[c] * ldexp(fma(Tv[c] * fr[c], pq[c], Tv[c]), ni[c] >> GPMPC_EXP_BITS);
-                    acc[0] += P;
-                    if (GRAD) {
-#pragma unroll
-                        for (int k = 0; k < D; ++k) acc[GRAD ? 1 + k : 0] = fma(P, g[c][k], acc[GRAD ? 1 + k : 0]);
-#pragma unroll
-                        for (int k = 0; k < NS2; ++k) acc[GRAD ? 1 + D + k : 0] = fma(P, g[c][D + 1 + k], acc[GRAD ? 1 + D + k : 0]);
-                    }
-                }
-                __builtin_amdgcn_sched_barrier(0);
+                gpmpc_sb_batch<D, NS2, GRAD, 1, KC, true>(g, mw, hi2, qi, s_tab, acc);
             };
             for (int jc = jst; jc < ncl; jc += 2 * MGS) {
 #pragma unroll
                 for (int q = 0; q < MGS; ++q)
-                    wb[q] = __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(Mrs, lane8, (jc + MGS + q) * Np * 8, 0));
+                    wb[q][0] = __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(Mrs, lane8, (jc + MGS + q) * Np * 8, 0));
                 __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
                 for (int q = 0; q < MGS; q += KC) batch(jc + q, &wa[q]);
@@ -666,24 +536,11 @@ void k_step_fused(FusedArgs A, int t) {
                     const int jn = jc + 2 * MGS < ncl ? jc + 2 * MGS : jc;
 #pragma unroll
                     for (int q = 0; q < MGS; ++q)
-                        wa[q] = __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(Mrs, lane8, (jn + q) * Np * 8, 0));
+                        wa[q][0] = __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(Mrs, lane8, (jn + q) * Np * 8, 0));
                 }
                 __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
                 for (int q = 0; q < MGS; q += KC) batch(jc + MGS + q, &wb[q]);
-            }
-#else
-            constexpr int CU = 4;
-            for (int jc = jst; jc < ncl; jc += CU) {
-                double mij[CU];
-#pragma unroll
-                for (int q = 0; q < CU; ++q)
-                    mij[q] = __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(Mrs, lane8, (jc + q) * Np * 8, 0));
-                __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                for (int q = 0; q < CU; ++q) column(jc + q, mij[q]);
-            }
-#endif
             }
         }
         GPMPC_STAMP(5);
@@ -691,14 +548,14 @@ void k_step_fused(FusedArgs A, int t) {
             double z[NM];
 #pragma unroll
             for (int m = 0; m < NM; ++m) z[m] = 0.0;
-            const double rs = acc[0];
+            const double rs = acc[0][0];
             z[0] = rs;
             if (GRAD) {
 #pragma unroll
                 for (int k = 0; k < D; ++k) {
-                    const double h = (0.5 / GPMPC_EXP_NEG_INV_C) * hi2[k], v = acc[GRAD ? 1 + k : 0];
+                    const double h = (0.5 / GPMPC_EXP_NEG_INV_C) * hi2[k], v = acc[0][GRAD ? 1 + k : 0];
                     z[GRAD ? 1 + k : 0] = fma(h, rs, v);
-                    if (k < NS2) z[GRAD ? 1 + D + k : 0] = fma(h * h, rs, fma(2.0 * h, v, acc[GRAD ? 1 + D + (k < NS2 ? k : 0) : 0]));
+                    if (k < NS2) z[GRAD ? 1 + D + k : 0] = fma(h * h, rs, fma(2.0 * h, v, acc[0][GRAD ? 1 + D + (k < NS2 ? k : 0) : 0]));
                 }
             }
 #pragma unroll
@@ -712,8 +569,7 @@ void k_step_fused(FusedArgs A, int t) {
         if (tid < NM) {
             double sum = 0.0;                                            // fixed order: waves, each as (row 0 + row 1) + (row 2 + row 3)
             for (int ww = 0; ww < 4; ++ww) {
-                const double* r4 = &s_red[ww * 4 * NM + tid];
-                sum += (r4[0] + r4[NM]) + (r4[2 * NM] + r4[3 * NM]);
+                sum += gpmpc_rows4(&s_red[ww * 4 * NM + tid], NM);
             }
             A.part[(((size_t)pcur * A.B + b) * A.nwork + bx) * A.nm + tid] = sum;
             if (tid == 0) A.partz[((size_t)pcur * A.B + b) * A.nwork + bx] = sum;
@@ -762,7 +618,7 @@ void k_step_fused(FusedArgs A, int t) {
                 double s = sq[0];
 #pragma unroll
                 for (int k = 1; k < D; ++k) s += sq[k];
-                const double P = mpre[q] * (GPMPC_FUSED_TABLE ? gpmpc_exp_neg(s, s_tab) : exp(-s));
+                const double P = mpre[q] * exp(-s);
                 acc[0] += P;
                 if (GRAD) {
 #pragma unroll
@@ -784,8 +640,7 @@ void k_step_fused(FusedArgs A, int t) {
         if (tid < NM) {
             double s = 0.0;
             for (int ww = 0; ww < 4; ++ww) {
-                const double* r4 = &s_red[ww * 4 * NM + tid];
-                s += (r4[0] + r4[NM]) + (r4[2 * NM] + r4[3 * NM]);
+                s += gpmpc_rows4(&s_red[ww * 4 * NM + tid], NM);
             }
             A.part[(((size_t)pcur * A.B + b) * A.nwork + bx) * A.nm + tid] = s;
             if (tid == 0) A.partz[((size_t)pcur * A.B + b) * A.nwork + bx] = s;

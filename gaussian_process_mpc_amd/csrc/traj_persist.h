@@ -26,6 +26,7 @@
 #pragma once
 #include "gpmpc_internal.h"
 #include "fast_exp.h"
+#include "pair_sb_dev.h"
 #include <type_traits>
 
 
@@ -49,28 +50,15 @@ static __device__ unsigned long long g_persist_stamps[64];
 // this kernel that put the write latency of the step's Jacobian rows -- read by nobody before the kernel ends -- and of the weight /
 // beta prefetches in front of every barrier (6.7 us of an 84 us step in the in-kernel timeline).  Where waves exchange data through
 // GLOBAL memory (the column rows) the drain is explicit.
-#ifdef GPMPC_PERSIST_SYNCTHREADS
-#define GPMPC_LDS_BARRIER() __syncthreads()
-#else
 #define GPMPC_LDS_BARRIER() do { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); __builtin_amdgcn_s_barrier(); asm volatile("" ::: "memory"); } while (0)
-#endif
 #ifndef GPMPC_PERSIST_CSEG
 #define GPMPC_PERSIST_CSEG 16       // overhead of one (unit, row block) segment of a wave's range, in columns (range balancing)
 #endif
 #ifndef GPMPC_PERSIST_KC3
 #define GPMPC_PERSIST_KC3 1         // batches of three columns where the rows fit the SGPR file (see KC)
 #endif
-#ifndef GPMPC_PERSIST_TOUCH
-#define GPMPC_PERSIST_TOUCH 0       // 1: request the next batch's G-row cache lines with this batch's rows (scalar-cache warm-up; A/B)
-#endif
 #ifndef GPMPC_PERSIST_AGEW
 #define GPMPC_PERSIST_AGEW 4        // range weights by wave age, per cent per age group (see the range table)
-#endif
-#ifndef GPMPC_PERSIST_PRIO_SHIFT
-#define GPMPC_PERSIST_PRIO_SHIFT 5  // the issue priority rotates every 2^shift columns
-#endif
-#ifndef GPMPC_PERSIST_ROTPRIO
-#define GPMPC_PERSIST_ROTPRIO 2     // 0: none; 1: by the wave's column count; 2: by the shader clock
 #endif
 #ifndef GPMPC_PERSIST_CLK_SHIFT
 #define GPMPC_PERSIST_CLK_SHIFT 14  // the issue priority rotates every 2^shift cycles (measured: 12 x1.19, 14 x1.23-1.28 over the round-4 kernel at N = 300, ds = 4)
@@ -89,7 +77,7 @@ template <int D, int NS2, bool GRAD, int NG = 1>
 __global__ __launch_bounds__(1024, 4) void k_traj_persist(PersistArgs A) {
     constexpr bool SH = NG > 1;
     constexpr int DS = NS2, DA = D - NS2, NM = GRAD ? 1 + 2 * D : 1, NA = GRAD ? 1 + D + NS2 : 1, NV = 1 + 2 * D;
-    constexpr int GW = (D + 1 + NS2 + 1) & ~1;     // doubles per G row, as PairSbTraits
+    constexpr int GW = PairSbTraits<D, NS2>::GW;   // doubles per G row
     // columns per batch of the column loop (KC (D + 1 + ds) doubles of G rows in SGPRs, KC sets of exp temporaries in VGPRs) and per group of
     // weight loads (two groups in flight): what fits the 128 registers of four waves per SIMD WITHOUT a spill (tools/spill_guard.py).
     // Range boundaries fall on multiples of GR = 2 MGc columns (the loop's step): 8 for NG = 1, down to 2 for units of four GPs, whose
@@ -124,11 +112,7 @@ __global__ __launch_bounds__(1024, 4) void k_traj_persist(PersistArgs A) {
     // training-set sizes of the reference's experiments that is much of the loop (N = 200: Np = 256, 224 of 640 column steps per GP; N = 300: 8 %;
     // N = 400: 19 %).  Nc is read from the pack (device memory, refreshed by every pack build: a captured launch stays valid when the
     // training set grows within its padded size).  start(r) = sum_{r' < r} (Nc - 64 r') = r Nc - 32 r (r - 1).
-#if defined(GPMPC_PERSIST_NO_CLIP)
-    const int Nc = Np;                             // A/B: the padded column space of the first version
-#else
     const int Nc = __builtin_amdgcn_readfirstlane(*A.ncol);
-#endif
     const int per_gp = T * Nc - 32 * T * (T - 1);  // columns of one GP
     const int total = ((DS + NG - 1) / NG) * per_gp;
     double* __restrict__ s_X = s_dyn;
@@ -273,8 +257,7 @@ __global__ __launch_bounds__(1024, 4) void k_traj_persist(PersistArgs A) {
                 if ((ln & 15) == 0) s_mred[(w * 4 + (ln >> 4)) * NV + m] = sr;
             }
             if (MW == 1 && ln < NV) {                              // (a wave's LDS operations execute in order)
-                const double* r4 = &s_mred[w * 4 * NV + ln];
-                s_ms[a * NV + ln] = (r4[0] + r4[NV]) + (r4[2 * NV] + r4[3 * NV]);
+                s_ms[a * NV + ln] = gpmpc_rows4(&s_mred[w * 4 * NV + ln], NV);
             }
         } else if constexpr (!GPAIR) {
             // row-major rows (batches of three columns read 3 GW contiguous doubles): written THROUGH LDS -- a lane's row goes to the wave's
@@ -337,8 +320,7 @@ __global__ __launch_bounds__(1024, 4) void k_traj_persist(PersistArgs A) {
         if (MW == 2 && tiz < DS * NV) {                            // two waves per GP: their row sums in fixed order (read in phase 4, two barriers on)
             const int a = tiz / NV, m = tiz - a * NV;
             const double* r0 = &s_mred[(2 * a) * 4 * NV + m];
-            const double* r1 = r0 + 4 * NV;
-            s_ms[tiz] = ((r0[0] + r0[NV]) + (r0[2 * NV] + r0[3 * NV])) + ((r1[0] + r1[NV]) + (r1[2 * NV] + r1[3 * NV]));
+            s_ms[tiz] = gpmpc_rows4(r0, NV) + gpmpc_rows4(r0 + 4 * NV, NV);
         }
         GPMPC_PST(6);
         GPMPC_PSTW(16);
@@ -401,19 +383,8 @@ __global__ __launch_bounds__(1024, 4) void k_traj_persist(PersistArgs A) {
                 auto batch = [&](auto kc_tag, int j, const double (*mw)[NG]) {
                     constexpr int KC = decltype(kc_tag)::value;     // (shadows the kernel's: the tail of a KC = 3 loop runs batches of two)
                     double g[KC][GW];
-#if GPMPC_PERSIST_TOUCH   /* (pair layout only; measured SLOWER: profiles/r05/persist_stamps_touch.txt) */
-                    // Scalar-cache warm-up: one dword of every 64-byte line of the NEXT batch's rows is requested together with this batch's
-                    // rows (same wait), so that the next batch's loads hit the scalar cache (~90 cycles) instead of the L2 (~550: the
-                    // latency four waves per SIMD do not hide, tools/ubench/latency_probe.hip).  Within the segment only (the last batch
-                    // touches itself): nothing is read beyond the trajectory's rows.
-                    unsigned touch[(KC * GW * 8 + 63) / 64];
-                    {
-                        const double* gn = Ga + (size_t)((j + KC < n ? j + KC : j) >> 1) * (2 * GW) + ((j + KC) & 1) * 2;
-                        asm volatile("" : "+s"(gn));
-#pragma unroll
-                        for (int q = 0; q < (KC * GW * 8 + 63) / 64; ++q) touch[q] = ((const unsigned __attribute__((address_space(4)))*)gn)[16 * q];
-                    }
-#endif
+                    // (tried and lost, removed -- see git history: requesting the next batch's G-row cache lines with this batch's rows as a
+                    // scalar-cache warm-up was slower, profiles/r05/persist_stamps_touch.txt)
                     // (the base goes through an opaque asm per batch: left to see that consecutive batches are adjacent in memory the
                     // compiler merges their loads into 64-byte ones -- 80 SGPRs of rows, the loop's other scalars spilled to VGPR lanes
                     // and read back with 18 v_readlane per iteration)
@@ -425,68 +396,27 @@ __global__ __launch_bounds__(1024, 4) void k_traj_persist(PersistArgs A) {
                         for (int c = 0; c < KC; ++c)
                             g[c][k] = GPAIR ? ((const gpmpc_cdouble*)(gb + (size_t)(k >> 1) * 4 + c * 2))[k & 1] : ((const gpmpc_cdouble*)(gb + (size_t)c * GW))[k];
                     __builtin_amdgcn_sched_barrier(0);
-#if GPMPC_PERSIST_TOUCH
-#pragma unroll
-                    for (int q = 0; q < (KC * GW * 8 + 63) / 64; ++q) asm volatile("" :: "s"(touch[q]));
-#endif
-                    double fr[KC], pq[KC], Tv[KC];
-                    int ni[KC];
-#pragma unroll
-                    for (int c = 0; c < KC; ++c) {
-                        double sx = qi + g[c][D];
-#pragma unroll
-                        for (int k = 0; k < D; ++k) sx = fma(hi2[k], g[c][k], sx);
-                        const double ax = __builtin_fabs(sx);      // gpmpc_exp_neg_scaled (fast_exp.h), split around the table read
-                        ni[c] = (int)(-ax);
-                        fr[c] = __builtin_amdgcn_fract(ax);
-                        Tv[c] = s_tab[ni[c] & (GPMPC_EXP_N - 1)];
-                        if (NG == 1) pq[c] = fma(fr[c], fma(fr[c], GPMPC_EXP_A3, GPMPC_EXP_A2), GPMPC_EXP_A1);   // in the shadow of the table read
-                    }
-                    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                    for (int c = 0; c < KC; ++c) {
-                        if (NG > 1) pq[c] = fma(fr[c], fma(fr[c], GPMPC_EXP_A3, GPMPC_EXP_A2), GPMPC_EXP_A1);    // (two GPs' sums: registers are short)
-                        const double e = ldexp(fma(Tv[c] * fr[c], pq[c], Tv[c]), ni[c] >> GPMPC_EXP_BITS);
-#pragma unroll
-                        for (int q = 0; q < NG; ++q) {
-                            const double P = mw[c][q] * e;
-                            acc[q][0] += P;
-                            if (GRAD) {
-#pragma unroll
-                                for (int k = 0; k < D; ++k) acc[q][GRAD ? 1 + k : 0] = fma(P, g[c][k], acc[q][GRAD ? 1 + k : 0]);
-#pragma unroll
-                                for (int k = 0; k < NS2; ++k) acc[q][GRAD ? 1 + D + k : 0] = fma(P, g[c][D + 1 + k], acc[q][GRAD ? 1 + D + k : 0]);
-                            }
-                        }
-                    }
-                    __builtin_amdgcn_sched_barrier(0);
+                    gpmpc_sb_batch<D, NS2, GRAD, NG, KC, NG == 1>(g, mw, hi2, qi, s_tab, acc);     // (pq beside the table read for one GP, after it for several: registers are short)
                 };
-#if GPMPC_PERSIST_ROTPRIO == 2
                 unsigned long long clk = __builtin_amdgcn_s_memtime();
-#endif
                 int jc = 0;
                 for (; jc + 2 * MGc <= n; jc += 2 * MGc) {         // n is a multiple of GR (= 2 MGc, or 2 with a tail below)
-#if GPMPC_PERSIST_ROTPRIO
                     // The four waves a SIMD holds of this workgroup are arbitrated by age: left alone the oldest runs ahead and the
                     // youngest finishes 40 % later, the SIMD half empty at the end (stamps: wave 2 109 k cycles, wave 15 165 k for
                     // equal ranges).  Rotating the issue priority lets them advance together.  Round 5: the rotation follows the
                     // shader CLOCK, not the wave's own column count -- positions within segments differ from wave to wave, priorities
                     // then coincide and ties go to the older wave again (waves 12-15 finished 15-20 % after the others); with a common
                     // clock the four waves of a SIMD hold four distinct priorities at every instant.  The counter read is issued one
-                    // iteration ahead (a scalar memory instruction: consumed after waits that happen anyway).
-#if GPMPC_PERSIST_ROTPRIO == 2
+                    // iteration ahead (a scalar memory instruction: consumed after waits that happen anyway).  (No rotation, and rotation by
+                    // the wave's own column count, were the variants this replaced: removed, see git history.)
                     const unsigned tick = (unsigned)(clk >> GPMPC_PERSIST_CLK_SHIFT);
                     clk = __builtin_amdgcn_s_memtime();
                     switch ((tick + (w >> 2)) & 3) {
-#else
-                    switch (((jc >> GPMPC_PERSIST_PRIO_SHIFT) + (w >> 2)) & 3) {
-#endif
                         case 0: __builtin_amdgcn_s_setprio(0); break;
                         case 1: __builtin_amdgcn_s_setprio(1); break;
                         case 2: __builtin_amdgcn_s_setprio(2); break;
                         default: __builtin_amdgcn_s_setprio(3); break;
                     }
-#endif
 #pragma unroll
                     for (int c = 0; c < MGc; ++c)
 #pragma unroll
@@ -548,9 +478,7 @@ __global__ __launch_bounds__(1024, 4) void k_traj_persist(PersistArgs A) {
                 }
             }
             GPMPC_PSTW(32);
-#if GPMPC_PERSIST_ROTPRIO
             __builtin_amdgcn_s_setprio(0);
-#endif
             GPMPC_PSTW(48);
         }
         GPMPC_PST(7);
@@ -579,7 +507,7 @@ __global__ __launch_bounds__(1024, 4) void k_traj_persist(PersistArgs A) {
                 const int un = a / NG, qn = a - un * NG;           // unit of GP a and its place in it
                 if (lo < hi && (un == a0 || (un == a0 + 1 && hi > (a0 + 1) * per_gp))) {
                     const double* r4 = &s_part[(((ww * 2 + (un - a0)) * NG + qn) * 4) * NM + m];
-                    v = (r4[0] + r4[NM]) + (r4[2 * NM] + r4[3 * NM]);
+                    v = (r4[0] + r4[NM]) + (r4[2 * NM] + r4[3 * NM]);     // (written out, not gpmpc_rows4: with the helper this phase's address arithmetic is scheduled differently)
                 }
             }
             v = wave_row_sum(v);
@@ -629,7 +557,7 @@ __global__ __launch_bounds__(1024, 4) void k_traj_persist(PersistArgs A) {
 template <int D, int NS2, bool GRAD, int NG = 1>
 static int launch_persist_one(const PersistArgs& a, int waves, hipStream_t s) {
     // dynamic LDS: X, the actions, and -- instances whose column loop runs batches of three (row-major rows) -- the row writers' staging blocks
-    constexpr int DSh = NS2, GWh = (D + 1 + NS2 + 1) & ~1;
+    constexpr int DSh = NS2, GWh = PairSbTraits<D, NS2>::GW;
     constexpr bool kc3 = !(D >= 7 || (NG > 1 && D >= 6) || NG >= 4 || (NG == 3 && D >= 5)) && NG == 1 && D <= 5 && GPMPC_PERSIST_KC3;
     const int mw = (waves >= 16 && 2 * DSh <= waves / 2) ? 2 : 1;
     const size_t lds = sizeof(double) * ((size_t)D * a.Np + (size_t)((a.H * (D - NS2) + 1) & ~1) + (kc3 ? (size_t)(waves - mw * DSh) * 64 * GWh : 0));
