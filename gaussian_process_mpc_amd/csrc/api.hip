@@ -4,70 +4,25 @@
 
 int gpmpc_launch_pair(int D, bool diag, bool grad, int tb, int waves, const PairArgs& a, hipStream_t s) {
     if (waves < 1 || waves > 4) return GPMPC_E_ARG;
-    switch (D) {
-        case 1: return gpmpc_launch_pair_D<1>(diag, grad, tb, waves, a, s);
-        case 2: return gpmpc_launch_pair_D<2>(diag, grad, tb, waves, a, s);
-        case 3: return gpmpc_launch_pair_D<3>(diag, grad, tb, waves, a, s);
-        case 4: return gpmpc_launch_pair_D<4>(diag, grad, tb, waves, a, s);
-        case 5: return gpmpc_launch_pair_D<5>(diag, grad, tb, waves, a, s);
-        case 6: return gpmpc_launch_pair_D<6>(diag, grad, tb, waves, a, s);
-        case 7: return gpmpc_launch_pair_D<7>(diag, grad, tb, waves, a, s);
-        case 8: return gpmpc_launch_pair_D<8>(diag, grad, tb, waves, a, s);
-    }
-    return GPMPC_E_ARG;
+    return gpmpc_dispatch_dim<1>(D, [&](auto d) { return gpmpc_launch_pair_D<decltype(d)::value>(diag, grad, tb, waves, a, s); });
 }
 
 int gpmpc_launch_pair_sb(int D, bool grad, int tb, int ns2, int waves, const PairSbArgs& a, hipStream_t s) {
     if (waves < 1 || waves > 4) return GPMPC_E_ARG;
-    switch (D) {
-        case 1: return gpmpc_launch_pair_sb_D<1>(grad, tb, ns2, waves, a, s);
-        case 2: return gpmpc_launch_pair_sb_D<2>(grad, tb, ns2, waves, a, s);
-        case 3: return gpmpc_launch_pair_sb_D<3>(grad, tb, ns2, waves, a, s);
-        case 4: return gpmpc_launch_pair_sb_D<4>(grad, tb, ns2, waves, a, s);
-        case 5: return gpmpc_launch_pair_sb_D<5>(grad, tb, ns2, waves, a, s);
-        case 6: return gpmpc_launch_pair_sb_D<6>(grad, tb, ns2, waves, a, s);
-        case 7: return gpmpc_launch_pair_sb_D<7>(grad, tb, ns2, waves, a, s);
-        case 8: return gpmpc_launch_pair_sb_D<8>(grad, tb, ns2, waves, a, s);
-    }
-    return GPMPC_E_ARG;
+    return gpmpc_dispatch_dim<1>(D, [&](auto d) { return gpmpc_launch_pair_sb_D<decltype(d)::value>(grad, tb, ns2, waves, a, s); });
 }
 
 int gpmpc_launch_pair_sbs(int D, bool grad, int ng, int ns2, const PairSbsArgs& a, hipStream_t s) {
-    switch (D) {
-        case 2: return gpmpc_launch_pair_sbs_D<2>(grad, ng, ns2, a, s);
-        case 3: return gpmpc_launch_pair_sbs_D<3>(grad, ng, ns2, a, s);
-        case 4: return gpmpc_launch_pair_sbs_D<4>(grad, ng, ns2, a, s);
-        case 5: return gpmpc_launch_pair_sbs_D<5>(grad, ng, ns2, a, s);
-        case 6: return gpmpc_launch_pair_sbs_D<6>(grad, ng, ns2, a, s);
-        case 7: return gpmpc_launch_pair_sbs_D<7>(grad, ng, ns2, a, s);
-        case 8: return gpmpc_launch_pair_sbs_D<8>(grad, ng, ns2, a, s);
-    }
-    return GPMPC_E_ARG;
+    return gpmpc_dispatch_dim<2>(D, [&](auto d) { return gpmpc_launch_pair_sbs_D<decltype(d)::value>(grad, ng, ns2, a, s); });
 }
 
 int gpmpc_launch_pair_sbf(int D, bool grad, int ns2, int waves, const PairSbfArgs& a, hipStream_t s) {
     if (waves < 1 || waves > 4) return GPMPC_E_ARG;
-    switch (D) {
-        case 1: return gpmpc_launch_pair_sbf_D<1>(grad, ns2, waves, a, s);
-        case 2: return gpmpc_launch_pair_sbf_D<2>(grad, ns2, waves, a, s);
-        case 3: return gpmpc_launch_pair_sbf_D<3>(grad, ns2, waves, a, s);
-        case 4: return gpmpc_launch_pair_sbf_D<4>(grad, ns2, waves, a, s);
-        case 5: return gpmpc_launch_pair_sbf_D<5>(grad, ns2, waves, a, s);
-        case 6: return gpmpc_launch_pair_sbf_D<6>(grad, ns2, waves, a, s);
-        case 7: return gpmpc_launch_pair_sbf_D<7>(grad, ns2, waves, a, s);
-        case 8: return gpmpc_launch_pair_sbf_D<8>(grad, ns2, waves, a, s);
-    }
-    return GPMPC_E_ARG;
+    return gpmpc_dispatch_dim<1>(D, [&](auto d) { return gpmpc_launch_pair_sbf_D<decltype(d)::value>(grad, ns2, waves, a, s); });
 }
 
 int gpmpc_launch_pair_sbfx(int D, bool grad, int ns2, const PairSbfxArgs& a, hipStream_t s) {
-    switch (D) {
-        case 3: return gpmpc_launch_pair_sbfx_D<3>(grad, ns2, a, s);
-        case 4: return gpmpc_launch_pair_sbfx_D<4>(grad, ns2, a, s);
-        case 5: return gpmpc_launch_pair_sbfx_D<5>(grad, ns2, a, s);
-        case 6: return gpmpc_launch_pair_sbfx_D<6>(grad, ns2, a, s);
-    }
-    return GPMPC_E_ARG;
+    return gpmpc_dispatch_dim<3, 6>(D, [&](auto d) { return gpmpc_launch_pair_sbfx_D<decltype(d)::value>(grad, ns2, a, s); });
 }
 
 // K*[r][i] = sf^2 exp(-1/2 sum_k (xp_rk - x_ik)^2 / lambda_k)      (src/gpr.py:266-283)
@@ -159,7 +114,7 @@ extern "C" int gpmpc_matvec(int rows, int cols, const double* A_dev, const doubl
 
 extern "C" size_t gpmpc_predict_workspace_bytes(int n, int D, int np) {
     if (n < 1 || np < 1 || D < 1) return 0;
-    return 2 * ((sizeof(double) * (size_t)np * n + 255) & ~(size_t)255) + 256;
+    return 2 * gpmpc_align256(sizeof(double) * (size_t)np * n) + 256;
 }
 
 extern "C" int gpmpc_predict(int n, int D, const double* X, const double* lambdas_host, double sigma_f,
@@ -170,7 +125,7 @@ extern "C" int gpmpc_predict(int n, int D, const double* X, const double* lambda
     if ((out_mean && !beta) || (out_cov && !Kinv)) return GPMPC_E_ARG;
     if (workspace_bytes < gpmpc_predict_workspace_bytes(n, D, np)) return GPMPC_E_WORKSPACE;
     hipStream_t s = (hipStream_t)stream;
-    const size_t slab = (sizeof(double) * (size_t)np * n + 255) & ~(size_t)255;
+    const size_t slab = gpmpc_align256(sizeof(double) * (size_t)np * n);
     double* K = out_K ? out_K : (double*)workspace;
     double* W = (double*)((char*)workspace + slab);
     double* lam = (double*)((char*)workspace + 2 * slab);

@@ -22,20 +22,14 @@ struct AlLayout { long sum, plan, rho, vprev, v, f, incv, incf, alive, settled, 
 
 static AlLayout al_layout(int K, long n, long R) {
     AlLayout L;
-    long o = 0;
-    L.sum = o; o += 32;
-    L.plan = o; o += lbfgs_r(n);
-    L.rho = o; o += lbfgs_r(K);
-    L.vprev = o; o += lbfgs_r(K);
-    L.v = o; o += lbfgs_r(K);
-    L.f = o; o += lbfgs_r(K);
-    L.incv = o; o += lbfgs_r(K);
-    L.incf = o; o += lbfgs_r(K);
-    L.alive = o; o += lbfgs_r(K);
-    L.settled = o; o += lbfgs_r(K);
-    L.lam = o; o += lbfgs_r(K * R);
-    L.incx = o; o += lbfgs_r(K * n);
-    L.total = o;
+    lbfgs_carver c;
+    L.sum = c.take(32);
+    L.plan = c.take(n);
+    L.rho = c.take(K); L.vprev = c.take(K); L.v = c.take(K); L.f = c.take(K); L.incv = c.take(K); L.incf = c.take(K);
+    L.alive = c.take(K); L.settled = c.take(K);
+    L.lam = c.take(K * R);
+    L.incx = c.take(K * n);
+    L.total = c.total();
     return L;
 }
 
@@ -212,27 +206,26 @@ __global__ __launch_bounds__(256) void k_al_finish(int K, int n, int R, AlLayout
 // host entries
 // ---------------------------------------------------------------------------
 static int al_check_scalars(const gpmpc_auglag_params* P, const char* who) {
-    char text[120];
     if (!P) return GPMPC_E_ARG;
     if (int rc = lbfgs_check_scalars(&P->inner, who)) return rc;
     const double pos[3] = {P->rho0, P->growth, P->rho_max};
     const char* pos_name[3] = {"rho0", "growth", "rho_max"};
     for (int i = 0; i < 3; ++i)
-        if (!(pos[i] > 0.0)) { snprintf(text, sizeof(text), "%s = %g is not positive", pos_name[i], pos[i]); return lbfgs_refuse(who, text); }
-    if (!(P->growth >= 1.0)) { snprintf(text, sizeof(text), "growth = %g is less than 1", P->growth); return lbfgs_refuse(who, text); }
-    if (!(P->shrink > 0.0 && P->shrink <= 1.0)) { snprintf(text, sizeof(text), "shrink = %g outside (0, 1]", P->shrink); return lbfgs_refuse(who, text); }
+        if (!(pos[i] > 0.0)) return gpmpc_refuse(who, "%s = %g is not positive", pos_name[i], pos[i]);
+    if (!(P->growth >= 1.0)) return gpmpc_refuse(who, "growth = %g is less than 1", P->growth);
+    if (!(P->shrink > 0.0 && P->shrink <= 1.0)) return gpmpc_refuse(who, "shrink = %g outside (0, 1]", P->shrink);
     const double nn[2] = {P->feas_tol, P->lam_max};
     const char* nn_name[2] = {"feas_tol", "lam_max"};
     for (int i = 0; i < 2; ++i)
-        if (!(nn[i] >= 0.0)) { snprintf(text, sizeof(text), "%s = %g is negative or NaN", nn_name[i], nn[i]); return lbfgs_refuse(who, text); }
-    if (P->inner_ticks < 1) { snprintf(text, sizeof(text), "inner_ticks = %d is less than 1", P->inner_ticks); return lbfgs_refuse(who, text); }
+        if (!(nn[i] >= 0.0)) return gpmpc_refuse(who, "%s = %g is negative or NaN", nn_name[i], nn[i]);
+    if (P->inner_ticks < 1) return gpmpc_refuse(who, "inner_ticks = %d is less than 1", P->inner_ticks);
     return GPMPC_OK;
 }
 
 static int al_rows_ok(int n_rows) { return n_rows >= 1 && n_rows <= GPMPC_MAX_CONS; }
 
 extern "C" size_t gpmpc_auglag_state_bytes(int K, int H, int da, int n_rows) {
-    if (K < 1 || K > GPMPC_LBFGS_MAX_STARTS || !al_rows_ok(n_rows) || !lbfgs_dims_ok(H, 0, da)) return 0;
+    if (K < 1 || K > GPMPC_LBFGS_MAX_STARTS || !al_rows_ok(n_rows) || !gpmpc_solver_dims_ok(H, 0, da)) return 0;
     return sizeof(double) * (size_t)al_layout(K, (long)H * da, (long)H * n_rows).total;
 }
 
@@ -256,7 +249,7 @@ static int al_launch_finish(int K, int n, int R, const AlLayout& L, const double
 
 extern "C" int gpmpc_auglag_merit(int K, int H, int da, int n_rows, const double* f, const double* grad, const double* g, const double* gjac,
                                   const double* lam, const double* rho, double* out_M, double* out_grad, void* stream) {
-    if (!f || !grad || !g || !gjac || !lam || !rho || !out_M || !out_grad || K < 1 || !al_rows_ok(n_rows) || !lbfgs_dims_ok(H, 0, da))
+    if (!f || !grad || !g || !gjac || !lam || !rho || !out_M || !out_grad || K < 1 || !al_rows_ok(n_rows) || !gpmpc_solver_dims_ok(H, 0, da))
         return GPMPC_E_ARG;
     return al_launch_merit(K, H * da, H * n_rows, f, grad, g, gjac, lam, rho, out_M, out_grad, (hipStream_t)stream);
 }
@@ -264,7 +257,7 @@ extern "C" int gpmpc_auglag_merit(int K, int H, int da, int n_rows, const double
 extern "C" int gpmpc_auglag_outer(int H, int da, int n_rows, const gpmpc_auglag_params* P, int update, const double* f, const double* g,
                                   const double* X, const double* conv, const double* alive, void* state, size_t state_bytes, void* stream) {
     const char* who = "gpmpc_auglag_outer";
-    if (!P || !f || !g || !X || !state || !al_rows_ok(n_rows) || !lbfgs_dims_ok(H, 0, da)) return GPMPC_E_ARG;
+    if (!P || !f || !g || !X || !state || !al_rows_ok(n_rows) || !gpmpc_solver_dims_ok(H, 0, da)) return GPMPC_E_ARG;
     if (int rc = al_check_scalars(P, who)) return rc;
     const int K = P->inner.n_starts, n = H * da, R = H * n_rows;
     const AlLayout L = al_layout(K, n, R);
@@ -276,23 +269,23 @@ extern "C" int gpmpc_auglag_outer(int H, int da, int n_rows, const gpmpc_auglag_
 // workspace of a solve: state | the inner search's state | x0 [K][ds] | cost [K] | grad [K][n] | g [K][R] | g_jac [K][R][n] | M [K] |
 // merit gradient [K][n] | copy of X [K][n] | the rollout's own workspace
 struct AlWorkspace { size_t off_lb, off_x0, off_cost, off_grad, off_g, off_gjac, off_M, off_gM, off_copy, off_roll, roll_bytes, total; };
-static size_t al_align(size_t b) { return (b + 255) & ~(size_t)255; }
 static AlWorkspace al_workspace(const gpmpc_pack* p, int H, int K, int n_rows, const AlLayout& L, const LbfgsLayout& LB) {
     AlWorkspace W;
     const size_t n = (size_t)H * p->da, R = (size_t)H * n_rows, d = sizeof(double);
-    size_t o = al_align(d * (size_t)L.total);
-    W.off_lb = o; o += al_align(d * (size_t)LB.total);
-    W.off_x0 = o; o += al_align(d * K * p->ds);
-    W.off_cost = o; o += al_align(d * K);
-    W.off_grad = o; o += al_align(d * K * n);
-    W.off_g = o; o += al_align(d * K * R);
-    W.off_gjac = o; o += al_align(d * K * R * n);
-    W.off_M = o; o += al_align(d * K);
-    W.off_gM = o; o += al_align(d * K * n);
-    W.off_copy = o; o += al_align(d * K * n);
-    W.off_roll = o;
+    gpmpc_carver c;
+    c.take(d * (size_t)L.total);
+    W.off_lb = c.take(d * (size_t)LB.total);
+    W.off_x0 = c.take(d * K * p->ds);
+    W.off_cost = c.take(d * K);
+    W.off_grad = c.take(d * K * n);
+    W.off_g = c.take(d * K * R);
+    W.off_gjac = c.take(d * K * R * n);
+    W.off_M = c.take(d * K);
+    W.off_gM = c.take(d * K * n);
+    W.off_copy = c.take(d * K * n);
     W.roll_bytes = gpmpc_rollout_constrained_workspace_bytes(p, K, H, GPMPC_WANT_GRAD);
-    W.total = o + al_align(W.roll_bytes);
+    W.off_roll = c.take(W.roll_bytes);
+    W.total = c.total();
     return W;
 }
 
@@ -300,7 +293,7 @@ extern "C" size_t gpmpc_auglag_solve_workspace_bytes(const gpmpc_pack* p, int H,
                                                      const gpmpc_auglag_params* P) {
     if (!p || !P || !cons || !al_rows_ok(cons->n_rows)) return 0;
     const int K = P->inner.n_starts, m = P->inner.history;
-    if (K < 1 || K > GPMPC_LBFGS_MAX_STARTS || m < 1 || m > GPMPC_LBFGS_MAX_HISTORY || !lbfgs_dims_ok(H, p->ds, p->da)) return 0;
+    if (K < 1 || K > GPMPC_LBFGS_MAX_STARTS || m < 1 || m > GPMPC_LBFGS_MAX_HISTORY || !gpmpc_solver_dims_ok(H, p->ds, p->da)) return 0;
     const long n = (long)H * p->da;
     return al_workspace(p, H, K, cons->n_rows, al_layout(K, n, (long)H * cons->n_rows), lbfgs_layout(K, n, m)).total;
 }
@@ -311,17 +304,10 @@ extern "C" int gpmpc_auglag_solve(const gpmpc_pack* p, int H, const double* x0, 
     const char* who = "gpmpc_auglag_solve";
     if (!p || !x0 || !cost || !cons || !P || !workspace || H < 1 || (first_outer == 0 && !X0)) return GPMPC_E_ARG;
     if (int rc = al_check_scalars(P, who)) return rc;                    // (before the pack is looked at)
-    if (first_outer < 0) return lbfgs_refuse(who, "first_outer is negative");
-    if (n_outer < 0) return lbfgs_refuse(who, "n_outer is negative");
-    if (int rc = gpmpc_check_constraints(cons, who)) return rc;
-    if (int rc_dev = gpmpc_check_device(p)) return rc_dev;
-    if (!lbfgs_dims_ok(H, p->ds, p->da)) return GPMPC_E_ARG;
-    if (int rc = lbfgs_check_inputs(&P->inner, p->da, who)) return rc;
-    if (!p->built) return GPMPC_E_STATE;
-    {   // the rollouts below would refuse a bad cost schedule too, but only after the first kernels of this solve
-        gpmpc_sched_ref sched;
-        if (int rcs = gpmpc_schedule_resolve(cost, p->ds, p->da, H, "gpmpc_auglag_solve", &sched)) return rcs;
-    }
+    if (first_outer < 0) return gpmpc_refuse(who, "first_outer is negative");
+    if (n_outer < 0) return gpmpc_refuse(who, "n_outer is negative");
+    if (int rc = gpmpc_solver_enter(p, H, cost, cons, who, [&](int da) { return gpmpc_check_bounds(P->inner.lb, P->inner.ub, da, who); }))
+        return rc;
     const gpmpc_lbfgs_params& PI = P->inner;
     const int K = PI.n_starts, n = H * p->da, R = H * cons->n_rows, ds = p->ds, da = p->da;
     const AlLayout L = al_layout(K, n, R);

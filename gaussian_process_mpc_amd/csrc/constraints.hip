@@ -91,29 +91,21 @@ __global__ __launch_bounds__(64) void k_rollout_constraints(int H, int da, gpmpc
 }
 
 template <int DS>
-static void launch_constraints(int B, int H, int da, const gpmpc_state_constraints& C, const double* means, const double* vars,
-                               const double* jac, double* out_g, double* out_gjac, hipStream_t s) {
+static int launch_constraints(int B, int H, int da, const gpmpc_state_constraints& C, const double* means, const double* vars,
+                              const double* jac, double* out_g, double* out_gjac, hipStream_t s) {
     if (out_gjac)
         hipLaunchKernelGGL((k_rollout_constraints<DS, true>), dim3(B, (H * da + 63) / 64), dim3(64), 0, s, H, da, C, means, vars, jac,
                            out_g, out_gjac);
     else
         hipLaunchKernelGGL((k_rollout_constraints<DS, false>), dim3(B, 1), dim3(64), 0, s, H, da, C, means, vars, jac, out_g, out_gjac);
+    return GPMPC_OK;
 }
 
 int gpmpc_check_constraints(const gpmpc_state_constraints* C, const char* who) {
-    char text[200];
     if (!C) return GPMPC_E_ARG;
-    if (C->n_rows < 1 || C->n_rows > GPMPC_MAX_CONS) {
-        snprintf(text, sizeof(text), "%s: n_rows = %d outside 1..%d", who, C->n_rows, GPMPC_MAX_CONS);
-        gpmpc_set_error_text(text);
-        return GPMPC_E_ARG;
-    }
+    if (C->n_rows < 1 || C->n_rows > GPMPC_MAX_CONS) return gpmpc_refuse(who, "n_rows = %d outside 1..%d", C->n_rows, GPMPC_MAX_CONS);
     for (int r = 0; r < C->n_rows; ++r)
-        if (!(C->kappa[r] >= 0.0)) {                        // negative or NaN
-            snprintf(text, sizeof(text), "%s: kappa[%d] = %g is negative or NaN", who, r, C->kappa[r]);
-            gpmpc_set_error_text(text);
-            return GPMPC_E_ARG;
-        }
+        if (!(C->kappa[r] >= 0.0)) return gpmpc_refuse(who, "kappa[%d] = %g is negative or NaN", r, C->kappa[r]);
     return GPMPC_OK;
 }
 
@@ -124,17 +116,10 @@ extern "C" int gpmpc_rollout_constraints(int B, int H, int ds, int da, const gpm
         return GPMPC_E_ARG;
     if (int rc = gpmpc_check_constraints(C, "gpmpc_rollout_constraints")) return rc;
     hipStream_t s = (hipStream_t)stream;
-    switch (ds) {
-        case 1: launch_constraints<1>(B, H, da, *C, means, vars, jac, out_g, out_gjac, s); break;
-        case 2: launch_constraints<2>(B, H, da, *C, means, vars, jac, out_g, out_gjac, s); break;
-        case 3: launch_constraints<3>(B, H, da, *C, means, vars, jac, out_g, out_gjac, s); break;
-        case 4: launch_constraints<4>(B, H, da, *C, means, vars, jac, out_g, out_gjac, s); break;
-        case 5: launch_constraints<5>(B, H, da, *C, means, vars, jac, out_g, out_gjac, s); break;
-        case 6: launch_constraints<6>(B, H, da, *C, means, vars, jac, out_g, out_gjac, s); break;
-        case 7: launch_constraints<7>(B, H, da, *C, means, vars, jac, out_g, out_gjac, s); break;
-        case 8: launch_constraints<8>(B, H, da, *C, means, vars, jac, out_g, out_gjac, s); break;
-        default: return GPMPC_E_ARG;
-    }
+    if (int rc = gpmpc_dispatch_dim<1>(ds, [&](auto d) {
+            return launch_constraints<decltype(d)::value>(B, H, da, *C, means, vars, jac, out_g, out_gjac, s);
+        }))
+        return rc;
     GPMPC_HIP(hipGetLastError());
     return GPMPC_OK;
 }

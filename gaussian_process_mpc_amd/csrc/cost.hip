@@ -294,17 +294,12 @@ extern "C" int gpmpc_cost_grad(int B, int H, int ds, int da, const gpmpc_cost_pa
     gpmpc_sched_ref sched;
     if (int rcs = gpmpc_schedule_resolve(cost, ds, da, H, "gpmpc_cost", &sched)) return rcs;
     if (sched.dev) {
-#define GPMPC_COST_SCHED(DSV)                                                                                                        \
-    case DSV:                                                                                                                        \
-        hipLaunchKernelGGL(k_cost_sched<DSV>, dim3((B + 63) / 64), dim3(64), 0, (hipStream_t)stream, B, H, da, *cost, sched.dev,     \
-                           sched.H_max, means, covs, U, out_cost, d_means, d_covs, d_U);                                             \
-        break;
-        switch (ds) {
-            GPMPC_COST_SCHED(1) GPMPC_COST_SCHED(2) GPMPC_COST_SCHED(3) GPMPC_COST_SCHED(4)
-            GPMPC_COST_SCHED(5) GPMPC_COST_SCHED(6) GPMPC_COST_SCHED(7) GPMPC_COST_SCHED(8)
-            default: return GPMPC_E_ARG;
-        }
-#undef GPMPC_COST_SCHED
+        if (int rc = gpmpc_dispatch_dim<1>(ds, [&](auto d) {
+                hipLaunchKernelGGL(k_cost_sched<decltype(d)::value>, dim3((B + 63) / 64), dim3(64), 0, (hipStream_t)stream, B, H, da, *cost,
+                                   sched.dev, sched.H_max, means, covs, U, out_cost, d_means, d_covs, d_U);
+                return GPMPC_OK;
+            }))
+            return rc;
         GPMPC_HIP(hipGetLastError());
         return GPMPC_OK;
     }

@@ -507,15 +507,15 @@ static int plan_fc2(const gpmpc_pack* p, int B, int H, bool grad, FcPlan2* r) {
         if (p->tune.fc_cu == 1 || p->tune.fc_cu == 2 || p->tune.fc_cu == 4) r->cu = p->tune.fc_cu;
     }
     r->pps = 2 * (p->D + p->D * p->D); r->sps = msps_of(p->D); r->gw = gpmpc_sbf_gw(p->D, p->ds);
-    size_t off = 0;
-    auto take = [&](size_t n) { size_t o = off; off += (n * sizeof(double) + 255) & ~(size_t)255; return o; };
+    gpmpc_carver c;
+    auto take = [&](size_t n) { return c.take(n * sizeof(double)); };
     r->off_pp = take((size_t)B * r->nunits * r->pps);
     r->off_sp0 = take((size_t)B * r->nunits * r->sps); r->off_sp1 = take((size_t)B * r->nunits * r->sps);
     r->off_part = take((size_t)B * r->nwork * r->nm); r->off_part0 = take((size_t)B * r->nwork);
     r->off_G = take((size_t)B * r->nunits * p->Np * r->gw);
     r->off_dmu = take(HB * ds * D); r->off_dmS = take(HB * ds * D * D);
     r->off_dcu = take(HB * ds * ds * D); r->off_dcS = take(HB * ds * ds * D * D);
-    r->total = off;
+    r->total = c.total();
     return 1;
 }
 
@@ -574,24 +574,13 @@ static int run_fc2(const gpmpc_pack* p, const FcPlan2& r, FcArgs& T, bool grad, 
 }
 
 static int launch_fc_tail(const FcArgs& A, int B, size_t lds, hipStream_t s) {
-    if (A.sched) switch (A.ds) {
-        case 1: hipLaunchKernelGGL((k_fc_tail<1, true>), dim3(B), dim3(256), lds, s, A); break;
-        case 2: hipLaunchKernelGGL((k_fc_tail<2, true>), dim3(B), dim3(256), lds, s, A); break;
-        case 3: hipLaunchKernelGGL((k_fc_tail<3, true>), dim3(B), dim3(256), lds, s, A); break;
-        case 4: hipLaunchKernelGGL((k_fc_tail<4, true>), dim3(B), dim3(256), lds, s, A); break;
-        case 5: hipLaunchKernelGGL((k_fc_tail<5, true>), dim3(B), dim3(256), lds, s, A); break;
-        case 6: hipLaunchKernelGGL((k_fc_tail<6, true>), dim3(B), dim3(256), lds, s, A); break;
-        default: return GPMPC_E_ARG;
-    }
-    else switch (A.ds) {
-        case 1: hipLaunchKernelGGL(k_fc_tail<1>, dim3(B), dim3(256), lds, s, A); break;
-        case 2: hipLaunchKernelGGL(k_fc_tail<2>, dim3(B), dim3(256), lds, s, A); break;
-        case 3: hipLaunchKernelGGL(k_fc_tail<3>, dim3(B), dim3(256), lds, s, A); break;
-        case 4: hipLaunchKernelGGL(k_fc_tail<4>, dim3(B), dim3(256), lds, s, A); break;
-        case 5: hipLaunchKernelGGL(k_fc_tail<5>, dim3(B), dim3(256), lds, s, A); break;
-        case 6: hipLaunchKernelGGL(k_fc_tail<6>, dim3(B), dim3(256), lds, s, A); break;
-        default: return GPMPC_E_ARG;
-    }
+    auto launch = [&](auto sched) {
+        return gpmpc_dispatch_dim<1, 6>(A.ds, [&](auto d) {
+            hipLaunchKernelGGL((k_fc_tail<decltype(d)::value, decltype(sched)::value>), dim3(B), dim3(256), lds, s, A);
+            return GPMPC_OK;
+        });
+    };
+    if (int rc = A.sched ? launch(std::true_type{}) : launch(std::false_type{})) return rc;
     GPMPC_HIP(hipGetLastError());
     return GPMPC_OK;
 }
@@ -600,16 +589,16 @@ struct FcPlan { size_t off_u, off_S, off_mean, off_cov, off_var, off_dvu, off_dv
 
 static void plan_fc(const gpmpc_pack* p, int B, int H, bool grad, FcPlan* r) {
     const size_t ds = p->ds, D = p->D, HB = (size_t)(grad ? H : 1) * B;
-    size_t off = 0;
-    auto take = [&](size_t n) { size_t o = off; off += (n * sizeof(double) + 255) & ~(size_t)255; return o; };
+    gpmpc_carver c;
+    auto take = [&](size_t n) { return c.take(n * sizeof(double)); };
     r->off_u = take((size_t)B * D); r->off_S = take((size_t)B * D * D);
     r->off_mean = take((size_t)B * ds); r->off_cov = take((size_t)B * ds * ds); r->off_var = take((size_t)B * ds);
     r->off_dvu = take((size_t)B * ds * D); r->off_dvS = take((size_t)B * ds * D * D);
     r->off_dmu = take(HB * ds * D); r->off_dmS = take(HB * ds * D * D);
     r->off_dcu = take(HB * ds * ds * D); r->off_dcS = take(HB * ds * ds * D * D);
     r->mm_bytes = gpmpc_moment_match_workspace_bytes(p, B);
-    r->off_mm = off; off += (r->mm_bytes + 255) & ~(size_t)255;
-    r->total = off;
+    r->off_mm = c.take(r->mm_bytes);
+    r->total = c.total();
 }
 
 extern "C" size_t gpmpc_rollout_fullcov_workspace_bytes(const gpmpc_pack* p, int B, int H, unsigned flags) {
@@ -672,16 +661,7 @@ extern "C" int gpmpc_rollout_fullcov(const gpmpc_pack* p, int B, int H, const do
     if (lds > 60 * 1024) return GPMPC_E_ARG;
     if (two) {
         A.out_means = out_means; A.out_covs = out_covs; A.out_cost = out_cost; A.out_grad = out_grad; A.cost = *cost;
-        int rc = GPMPC_E_ARG;
-        switch (p->D) {
-            case 2: rc = run_fc2<2>(p, r2, A, grad, ws, s); break;
-            case 3: rc = run_fc2<3>(p, r2, A, grad, ws, s); break;
-            case 4: rc = run_fc2<4>(p, r2, A, grad, ws, s); break;
-            case 5: rc = run_fc2<5>(p, r2, A, grad, ws, s); break;
-            case 6: rc = run_fc2<6>(p, r2, A, grad, ws, s); break;
-            case 7: rc = run_fc2<7>(p, r2, A, grad, ws, s); break;
-            case 8: rc = run_fc2<8>(p, r2, A, grad, ws, s); break;
-        }
+        const int rc = gpmpc_dispatch_dim<2>(p->D, [&](auto d) { return run_fc2<decltype(d)::value>(p, r2, A, grad, ws, s); });
         if (rc != GPMPC_OK) return rc;
         return launch_fc_tail(A, B, lds, s);
     }

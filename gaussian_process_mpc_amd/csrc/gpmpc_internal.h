@@ -1,9 +1,11 @@
-// Internal declarations shared by the HIP translation units of libgpmpc_hip.so.
+// Internal declarations shared by the HIP translation units of libgpmpc_hip.so: the pack, the kernel argument structs, the host
+// plumbing every unit writes the same way (dimension dispatch, workspace carving, refusals) and the device reduction helpers.
 // gfx950 (MI355X) only: 64-wide wavefronts are assumed throughout.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstring>
+#include <type_traits>
 #include "../../include/gpmpc.h"
 
 #define GPMPC_WAVE 64
@@ -274,6 +276,24 @@ template <int D> int gpmpc_launch_pair_D(bool diag, bool grad, int tb, int waves
 
 void gpmpc_set_error(const char* what, hipError_t e);
 void gpmpc_set_error_text(const char* text);      // gpmpc_last_error for refusals that are not HIP errors
+// The refusal of an argument: "<who>: <formatted>" into gpmpc_last_error, returns GPMPC_E_ARG (runtime.hip).  Refusals with another code
+// set the text with gpmpc_set_error_text and return their own.
+int gpmpc_refuse(const char* who, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
+
+// A run-time dimension in [LO, HI] as a compile-time one: f(std::integral_constant<int, d>), or GPMPC_E_ARG outside the range.
+template <int LO, int HI = 8, class F>
+static inline int gpmpc_dispatch_dim(int d, F&& f) {
+    if constexpr (LO > HI) return GPMPC_E_ARG;
+    else return d == LO ? f(std::integral_constant<int, LO>{}) : gpmpc_dispatch_dim<LO + 1, HI>(d, f);
+}
+
+// Workspace carving: sections start on 256-byte boundaries.  take() returns the offset of the next section and moves past it.
+static inline size_t gpmpc_align256(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
+struct gpmpc_carver {
+    size_t off = 0;
+    size_t take(size_t bytes) { const size_t o = off; off += gpmpc_align256(bytes); return o; }
+    size_t total() const { return off; }
+};
 // GPMPC_OK, or GPMPC_E_ARG with the reason in gpmpc_last_error: n_rows outside 1..GPMPC_MAX_CONS, a negative or NaN kappa (constraints.hip)
 int gpmpc_check_constraints(const gpmpc_state_constraints* cons, const char* who);
 // Cost schedules (schedule.hip; layout in include/gpmpc.h): offsets, in doubles, of the parts behind x_ref, from the dimensions the

@@ -362,7 +362,7 @@ extern "C" int gpmpc_rollout(const gpmpc_pack* p, int B, int H, const double* x0
 // Differentiable propagation: trajectory + step Jacobians, and their vector-Jacobian product
 // ---------------------------------------------------------------------------
 static inline size_t jac_scratch_bytes(const gpmpc_pack* p, int B, int H) {     // [cost | grad] of the (zero-cost) tail kernel
-    return (sizeof(double) * (size_t)B * (1 + (size_t)H * p->da) + 255) & ~(size_t)255;
+    return gpmpc_align256(sizeof(double) * (size_t)B * (1 + (size_t)H * p->da));
 }
 extern "C" size_t gpmpc_rollout_jac_workspace_bytes(const gpmpc_pack* p, int B, int H) {
     if (!p || B < 1 || H < 1) return 0;

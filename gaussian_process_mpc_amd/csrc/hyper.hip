@@ -77,12 +77,6 @@ extern "C" size_t gpmpc_ml_grad_workspace_bytes(int n, int D) {
     return sizeof(double) * (nblocks * (D + 1) + GPMPC_MAX_D);
 }
 
-template <int D>
-static void launch_ml_partial(int n, int nblocks, const double* X, const double* Kinv, const double* alpha, const double* lam,
-                              double sf2, double* part, hipStream_t s) {
-    hipLaunchKernelGGL(k_ml_partial<D>, dim3(nblocks), dim3(256), 0, s, n, X, Kinv, alpha, lam, sf2, part);
-}
-
 extern "C" int gpmpc_ml_grad(int n, int D, const double* X_dev, const double* Ky_inv_dev, const double* alpha_dev,
                              const double* resid_dev, const double* lambdas_host, double sigma_f, double noise_var,
                              double* out_dev, void* workspace, size_t workspace_bytes, void* stream) {
@@ -97,17 +91,11 @@ extern "C" int gpmpc_ml_grad(int n, int D, const double* X_dev, const double* Ky
     double* lam = part + (size_t)nblocks * (D + 1);
     if (int rcu = gpmpc_upload_small(lam, lambdas_host, sizeof(double) * D, s)) return rcu;
     const double sf2 = sigma_f * sigma_f;
-    switch (D) {
-        case 1: launch_ml_partial<1>(n, nblocks, X_dev, Ky_inv_dev, alpha_dev, lam, sf2, part, s); break;
-        case 2: launch_ml_partial<2>(n, nblocks, X_dev, Ky_inv_dev, alpha_dev, lam, sf2, part, s); break;
-        case 3: launch_ml_partial<3>(n, nblocks, X_dev, Ky_inv_dev, alpha_dev, lam, sf2, part, s); break;
-        case 4: launch_ml_partial<4>(n, nblocks, X_dev, Ky_inv_dev, alpha_dev, lam, sf2, part, s); break;
-        case 5: launch_ml_partial<5>(n, nblocks, X_dev, Ky_inv_dev, alpha_dev, lam, sf2, part, s); break;
-        case 6: launch_ml_partial<6>(n, nblocks, X_dev, Ky_inv_dev, alpha_dev, lam, sf2, part, s); break;
-        case 7: launch_ml_partial<7>(n, nblocks, X_dev, Ky_inv_dev, alpha_dev, lam, sf2, part, s); break;
-        case 8: launch_ml_partial<8>(n, nblocks, X_dev, Ky_inv_dev, alpha_dev, lam, sf2, part, s); break;
-        default: return GPMPC_E_ARG;
-    }
+    if (int rc = gpmpc_dispatch_dim<1>(D, [&](auto d) {
+            hipLaunchKernelGGL(k_ml_partial<decltype(d)::value>, dim3(nblocks), dim3(256), 0, s, n, X_dev, Ky_inv_dev, alpha_dev, lam, sf2, part);
+            return GPMPC_OK;
+        }))
+        return rc;
     hipLaunchKernelGGL(k_ml_finish, dim3(1), dim3(256), 0, s, n, D, nblocks, part, Ky_inv_dev, alpha_dev, resid_dev, noise_var, out_dev);
     GPMPC_HIP(hipGetLastError());
     return GPMPC_OK;

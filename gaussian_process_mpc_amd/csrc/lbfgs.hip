@@ -270,48 +270,22 @@ __global__ __launch_bounds__(256) void k_lbfgs_finish(int K, int n, int m, Lbfgs
 // ---------------------------------------------------------------------------
 // host entries
 // ---------------------------------------------------------------------------
-int lbfgs_refuse(const char* who, const char* what) {
-    char text[200];
-    snprintf(text, sizeof(text), "%s: %s", who, what);
-    gpmpc_set_error_text(text);
-    return GPMPC_E_ARG;
-}
-
 // the part of the parameters that needs no dimension
 int lbfgs_check_scalars(const gpmpc_lbfgs_params* P, const char* who) {
-    char text[120];
     if (!P) return GPMPC_E_ARG;
-    if (P->n_starts < 1 || P->n_starts > GPMPC_LBFGS_MAX_STARTS) {
-        snprintf(text, sizeof(text), "n_starts = %d outside 1..%d", P->n_starts, GPMPC_LBFGS_MAX_STARTS);
-        return lbfgs_refuse(who, text);
-    }
-    if (P->history < 1 || P->history > GPMPC_LBFGS_MAX_HISTORY) {
-        snprintf(text, sizeof(text), "history = %d outside 1..%d", P->history, GPMPC_LBFGS_MAX_HISTORY);
-        return lbfgs_refuse(who, text);
-    }
+    if (P->n_starts < 1 || P->n_starts > GPMPC_LBFGS_MAX_STARTS)
+        return gpmpc_refuse(who, "n_starts = %d outside 1..%d", P->n_starts, GPMPC_LBFGS_MAX_STARTS);
+    if (P->history < 1 || P->history > GPMPC_LBFGS_MAX_HISTORY)
+        return gpmpc_refuse(who, "history = %d outside 1..%d", P->history, GPMPC_LBFGS_MAX_HISTORY);
     const double v[4] = {P->gtol, P->ftol, P->c1, P->min_step};
     const char* name[4] = {"gtol", "ftol", "c1", "min_step"};
     for (int i = 0; i < 4; ++i)
-        if (!(v[i] >= 0.0)) { snprintf(text, sizeof(text), "%s = %g is negative or NaN", name[i], v[i]); return lbfgs_refuse(who, text); }
+        if (!(v[i] >= 0.0)) return gpmpc_refuse(who, "%s = %g is negative or NaN", name[i], v[i]);
     return GPMPC_OK;
-}
-
-int lbfgs_check_inputs(const gpmpc_lbfgs_params* P, int da, const char* who) {
-    char text[120];
-    for (int j = 0; j < da; ++j)
-        if (!(P->lb[j] <= P->ub[j])) {                      // lb > ub, or a NaN bound
-            snprintf(text, sizeof(text), "lb[%d] = %g exceeds ub[%d] = %g", j, P->lb[j], j, P->ub[j]);
-            return lbfgs_refuse(who, text);
-        }
-    return GPMPC_OK;
-}
-
-int lbfgs_dims_ok(int H, int ds, int da) {
-    return H >= 1 && da >= 1 && da <= GPMPC_MAX_D && ds >= 0 && ds <= GPMPC_MAX_DS && (long)H * da <= 64L * 65535;      // (n as in constraints.hip)
 }
 
 extern "C" size_t gpmpc_lbfgs_state_bytes(int K, int H, int da, int m) {
-    if (K < 1 || K > GPMPC_LBFGS_MAX_STARTS || m < 1 || m > GPMPC_LBFGS_MAX_HISTORY || !lbfgs_dims_ok(H, 0, da)) return 0;
+    if (K < 1 || K > GPMPC_LBFGS_MAX_STARTS || m < 1 || m > GPMPC_LBFGS_MAX_HISTORY || !gpmpc_solver_dims_ok(H, 0, da)) return 0;
     return sizeof(double) * (size_t)lbfgs_layout(K, (long)H * da, m).total;
 }
 
@@ -336,10 +310,10 @@ int lbfgs_launch_tick(int n, int da, const gpmpc_lbfgs_params& P, const LbfgsLay
 extern "C" int gpmpc_lbfgs_start(int H, int ds, int da, const gpmpc_lbfgs_params* P, const double* X0, const double* cost, const double* grad,
                                  const double* x0, double* out_x0_batch, void* state, size_t state_bytes, void* stream) {
     const char* who = "gpmpc_lbfgs_start";
-    if (!P || !X0 || !state || (cost != nullptr) != (grad != nullptr) || !lbfgs_dims_ok(H, ds, da) || (out_x0_batch && (!x0 || ds < 1)))
+    if (!P || !X0 || !state || (cost != nullptr) != (grad != nullptr) || !gpmpc_solver_dims_ok(H, ds, da) || (out_x0_batch && (!x0 || ds < 1)))
         return GPMPC_E_ARG;
     if (int rc = lbfgs_check_scalars(P, who)) return rc;
-    if (int rc = lbfgs_check_inputs(P, da, who)) return rc;
+    if (int rc = gpmpc_check_bounds(P->lb, P->ub, da, who)) return rc;
     const int n = H * da;
     const LbfgsLayout L = lbfgs_layout(P->n_starts, n, P->history);
     if (state_bytes < sizeof(double) * (size_t)L.total) return GPMPC_E_WORKSPACE;
@@ -350,9 +324,9 @@ extern "C" int gpmpc_lbfgs_start(int H, int ds, int da, const gpmpc_lbfgs_params
 extern "C" int gpmpc_lbfgs_tick(int H, int da, const gpmpc_lbfgs_params* P, const double* cost, const double* grad, void* state,
                                 size_t state_bytes, void* stream) {
     const char* who = "gpmpc_lbfgs_tick";
-    if (!P || !cost || !grad || !state || !lbfgs_dims_ok(H, 0, da)) return GPMPC_E_ARG;
+    if (!P || !cost || !grad || !state || !gpmpc_solver_dims_ok(H, 0, da)) return GPMPC_E_ARG;
     if (int rc = lbfgs_check_scalars(P, who)) return rc;
-    if (int rc = lbfgs_check_inputs(P, da, who)) return rc;
+    if (int rc = gpmpc_check_bounds(P->lb, P->ub, da, who)) return rc;
     const int n = H * da;
     const LbfgsLayout L = lbfgs_layout(P->n_starts, n, P->history);
     if (state_bytes < sizeof(double) * (size_t)L.total) return GPMPC_E_WORKSPACE;
@@ -362,23 +336,23 @@ extern "C" int gpmpc_lbfgs_tick(int H, int da, const gpmpc_lbfgs_params* P, cons
 
 // workspace of a solve: state | x0 [K][ds] | cost [K] | grad [K][n] | the rollout's own workspace
 struct LbfgsWorkspace { size_t off_x0, off_cost, off_grad, off_roll, roll_bytes, total; };
-static size_t lbfgs_align(size_t b) { return (b + 255) & ~(size_t)255; }
 static LbfgsWorkspace lbfgs_workspace(const gpmpc_pack* p, int H, int K, const LbfgsLayout& L) {
     LbfgsWorkspace W;
     const size_t n = (size_t)H * p->da, d = sizeof(double);
-    size_t o = lbfgs_align(d * (size_t)L.total);
-    W.off_x0 = o; o += lbfgs_align(d * K * p->ds);
-    W.off_cost = o; o += lbfgs_align(d * K);
-    W.off_grad = o; o += lbfgs_align(d * K * n);
-    W.off_roll = o;
+    gpmpc_carver c;
+    c.take(d * (size_t)L.total);
+    W.off_x0 = c.take(d * K * p->ds);
+    W.off_cost = c.take(d * K);
+    W.off_grad = c.take(d * K * n);
     W.roll_bytes = gpmpc_rollout_workspace_bytes(p, K, H, GPMPC_WANT_GRAD);
-    W.total = o + lbfgs_align(W.roll_bytes);
+    W.off_roll = c.take(W.roll_bytes);
+    W.total = c.total();
     return W;
 }
 
 extern "C" size_t gpmpc_lbfgs_solve_workspace_bytes(const gpmpc_pack* p, int H, const gpmpc_lbfgs_params* P) {
     if (!p || !P || P->n_starts < 1 || P->n_starts > GPMPC_LBFGS_MAX_STARTS || P->history < 1 || P->history > GPMPC_LBFGS_MAX_HISTORY) return 0;
-    if (!lbfgs_dims_ok(H, p->ds, p->da)) return 0;
+    if (!gpmpc_solver_dims_ok(H, p->ds, p->da)) return 0;
     return lbfgs_workspace(p, H, P->n_starts, lbfgs_layout(P->n_starts, (long)H * p->da, P->history)).total;
 }
 
@@ -388,16 +362,9 @@ extern "C" int gpmpc_lbfgs_solve(const gpmpc_pack* p, int H, const double* x0, c
     const char* who = "gpmpc_lbfgs_solve";
     if (!p || !x0 || !cost || !P || !workspace || H < 1 || (first_tick == 0 && !X0)) return GPMPC_E_ARG;
     if (int rc = lbfgs_check_scalars(P, who)) return rc;                 // (before the pack is looked at)
-    if (first_tick < 0) return lbfgs_refuse(who, "first_tick is negative");
-    if (n_ticks < 0) return lbfgs_refuse(who, "n_ticks is negative");
-    if (int rc_dev = gpmpc_check_device(p)) return rc_dev;
-    if (!lbfgs_dims_ok(H, p->ds, p->da)) return GPMPC_E_ARG;
-    if (int rc = lbfgs_check_inputs(P, p->da, who)) return rc;
-    if (!p->built) return GPMPC_E_STATE;
-    {   // the rollouts below would refuse a bad cost schedule too, but only after the first kernels of this solve
-        gpmpc_sched_ref sched;
-        if (int rcs = gpmpc_schedule_resolve(cost, p->ds, p->da, H, "gpmpc_lbfgs_solve", &sched)) return rcs;
-    }
+    if (first_tick < 0) return gpmpc_refuse(who, "first_tick is negative");
+    if (n_ticks < 0) return gpmpc_refuse(who, "n_ticks is negative");
+    if (int rc = gpmpc_solver_enter(p, H, cost, nullptr, who, [&](int da) { return gpmpc_check_bounds(P->lb, P->ub, da, who); })) return rc;
     const int K = P->n_starts, n = H * p->da;
     const LbfgsLayout L = lbfgs_layout(K, n, P->history);
     const LbfgsWorkspace W = lbfgs_workspace(p, H, K, L);

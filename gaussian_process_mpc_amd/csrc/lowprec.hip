@@ -57,25 +57,16 @@ __global__ __launch_bounds__(256) void k_pair_lowprec(PairArgs A) {
 }
 
 template <int D>
-static void launch_lp(int mode, const PairArgs& a, hipStream_t s) {
+static int launch_lp(int mode, const PairArgs& a, hipStream_t s) {
     if (mode == 1) hipLaunchKernelGGL((k_pair_lowprec<D, 1>), dim3(a.B * a.nwork), dim3(256), 0, s, a);
     else hipLaunchKernelGGL((k_pair_lowprec<D, 2>), dim3(a.B * a.nwork), dim3(256), 0, s, a);
+    return GPMPC_OK;
 }
 
 // a: the 256x256 work list of the variance units, nm == 1 (objective only)
 int gpmpc_launch_pair_lowprec(int D, int mode, const PairArgs& a, hipStream_t s) {
     if ((mode != 1 && mode != 2) || a.nm != 1) return GPMPC_E_ARG;
-    switch (D) {
-        case 1: launch_lp<1>(mode, a, s); break;
-        case 2: launch_lp<2>(mode, a, s); break;
-        case 3: launch_lp<3>(mode, a, s); break;
-        case 4: launch_lp<4>(mode, a, s); break;
-        case 5: launch_lp<5>(mode, a, s); break;
-        case 6: launch_lp<6>(mode, a, s); break;
-        case 7: launch_lp<7>(mode, a, s); break;
-        case 8: launch_lp<8>(mode, a, s); break;
-        default: return GPMPC_E_ARG;
-    }
+    if (int rc = gpmpc_dispatch_dim<1>(D, [&](auto d) { return launch_lp<decltype(d)::value>(mode, a, s); })) return rc;
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) { gpmpc_set_error("reduced-precision pair kernel launch", e); return GPMPC_E_LAUNCH; }
     return GPMPC_OK;

@@ -281,14 +281,13 @@ static void plan_mom(const gpmpc_pack* p, int nq, bool grad, bool pair_cov, int 
     r->nm = gpmpc_num_moments(D, false, grad);
     r->pps = 2 * (D + D * D);
     r->sps = msps_of(D);
-    size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; };
-    r->off_pp = take(sizeof(double) * (size_t)nq * r->nunits * r->pps);
-    r->off_sp = take(sizeof(double) * (size_t)nq * r->nunits * r->sps);
-    r->off_part = take(sizeof(double) * (size_t)nq * r->nwork * r->nm);
-    r->off_pairs = take(sizeof(int) * 2 * GPMPC_MAX_DS * GPMPC_MAX_DS);
-    r->off_G = take(r->sbf ? sizeof(double) * (size_t)nq * r->nunits * p->Np * r->gw : 0);
-    r->total = off;
+    gpmpc_carver c;
+    r->off_pp = c.take(sizeof(double) * (size_t)nq * r->nunits * r->pps);
+    r->off_sp = c.take(sizeof(double) * (size_t)nq * r->nunits * r->sps);
+    r->off_part = c.take(sizeof(double) * (size_t)nq * r->nwork * r->nm);
+    r->off_pairs = c.take(sizeof(int) * 2 * GPMPC_MAX_DS * GPMPC_MAX_DS);
+    r->off_G = c.take(r->sbf ? sizeof(double) * (size_t)nq * r->nunits * p->Np * r->gw : 0);
+    r->total = c.total();
 }
 
 extern "C" size_t gpmpc_moment_match_workspace_bytes(const gpmpc_pack* p, int nq) {
@@ -393,17 +392,7 @@ int gpmpc_moment_match_ex(const gpmpc_pack* p, int nq, const double* u, const do
     A.flags = flags;
     hipStream_t s = (hipStream_t)stream;
     int* pairs_dev = (int*)(ws + r.off_pairs);
-    switch (p->D) {
-        case 1: return run_mom<1>(p, A, r, grad, s, pairs_dev);
-        case 2: return run_mom<2>(p, A, r, grad, s, pairs_dev);
-        case 3: return run_mom<3>(p, A, r, grad, s, pairs_dev);
-        case 4: return run_mom<4>(p, A, r, grad, s, pairs_dev);
-        case 5: return run_mom<5>(p, A, r, grad, s, pairs_dev);
-        case 6: return run_mom<6>(p, A, r, grad, s, pairs_dev);
-        case 7: return run_mom<7>(p, A, r, grad, s, pairs_dev);
-        case 8: return run_mom<8>(p, A, r, grad, s, pairs_dev);
-    }
-    return GPMPC_E_ARG;
+    return gpmpc_dispatch_dim<1>(p->D, [&](auto d) { return run_mom<decltype(d)::value>(p, A, r, grad, s, pairs_dev); });
 }
 
 extern "C" int gpmpc_moment_match(const gpmpc_pack* p, int nq, const double* u, const double* S, unsigned flags,

@@ -16,7 +16,7 @@
 //             then the 256 partial sums are folded in halves, p[i] <- p[i] + p[i + h], h = 128, 64, ... 1
 //   mean[c]   wave w adds w_k U[k][c] over its quarter of the samples in ascending k (zero weights skipped), the four are added in wave
 //             order, one division by the sum of the weights
-#include "gpmpc_internal.h"
+#include "solver_frame.h"
 #include <cmath>
 
 #define MPPI_THREADS 256
@@ -216,41 +216,24 @@ __global__ __launch_bounds__(MPPI_THREADS) void k_mppi_update(int K, int n, int 
 // ---------------------------------------------------------------------------
 // host entries
 // ---------------------------------------------------------------------------
-static int mppi_refuse(const char* who, const char* what) {
-    char text[200];
-    snprintf(text, sizeof(text), "%s: %s", who, what);
-    gpmpc_set_error_text(text);
-    return GPMPC_E_ARG;
-}
-
 // the part of the parameters that needs no dimension
 static int mppi_check_scalars(const gpmpc_mppi_params* P, const char* who) {
-    char text[120];
     if (!P) return GPMPC_E_ARG;
-    if (P->n_samples < 1 || P->n_samples > GPMPC_MPPI_MAX_SAMPLES) {
-        snprintf(text, sizeof(text), "n_samples = %d outside 1..%d", P->n_samples, GPMPC_MPPI_MAX_SAMPLES);
-        return mppi_refuse(who, text);
-    }
-    if (P->iterations < 1) { snprintf(text, sizeof(text), "iterations = %d is less than 1", P->iterations); return mppi_refuse(who, text); }
-    if (!(P->sigma_decay > 0.0)) { snprintf(text, sizeof(text), "sigma_decay = %g is not positive", P->sigma_decay); return mppi_refuse(who, text); }
-    if (!(P->beta > 0.0)) { snprintf(text, sizeof(text), "beta = %g is not positive", P->beta); return mppi_refuse(who, text); }
+    if (P->n_samples < 1 || P->n_samples > GPMPC_MPPI_MAX_SAMPLES)
+        return gpmpc_refuse(who, "n_samples = %d outside 1..%d", P->n_samples, GPMPC_MPPI_MAX_SAMPLES);
+    if (P->iterations < 1) return gpmpc_refuse(who, "iterations = %d is less than 1", P->iterations);
+    if (!(P->sigma_decay > 0.0)) return gpmpc_refuse(who, "sigma_decay = %g is not positive", P->sigma_decay);
+    if (!(P->beta > 0.0)) return gpmpc_refuse(who, "beta = %g is not positive", P->beta);
     return GPMPC_OK;
 }
 
+// sigma and the bounds of input j are checked together, input by input
 static int mppi_check_inputs(const gpmpc_mppi_params* P, int da, const char* who) {
-    char text[120];
     for (int j = 0; j < da; ++j) {
-        if (!(P->sigma[j] > 0.0)) { snprintf(text, sizeof(text), "sigma[%d] = %g is not positive", j, P->sigma[j]); return mppi_refuse(who, text); }
-        if (!(P->lb[j] <= P->ub[j])) {                      // lb > ub, or a NaN bound
-            snprintf(text, sizeof(text), "lb[%d] = %g exceeds ub[%d] = %g", j, P->lb[j], j, P->ub[j]);
-            return mppi_refuse(who, text);
-        }
+        if (!(P->sigma[j] > 0.0)) return gpmpc_refuse(who, "sigma[%d] = %g is not positive", j, P->sigma[j]);
+        if (!(P->lb[j] <= P->ub[j])) return gpmpc_refuse(who, "lb[%d] = %g exceeds ub[%d] = %g", j, P->lb[j], j, P->ub[j]);      // lb > ub, or NaN
     }
     return GPMPC_OK;
-}
-
-static int mppi_dims_ok(int H, int ds, int da) {
-    return H >= 1 && da >= 1 && da <= GPMPC_MAX_D && ds >= 0 && ds <= GPMPC_MAX_DS && (long)H * da <= 64L * 65535;      // (n as in constraints.hip)
 }
 
 static int mppi_launch_sample(int H, int ds, int da, const gpmpc_mppi_params& P, int iteration, const double* mean, const double* x0,
@@ -266,7 +249,7 @@ static int mppi_launch_sample(int H, int ds, int da, const gpmpc_mppi_params& P,
 
 extern "C" int gpmpc_mppi_sample(int H, int ds, int da, const gpmpc_mppi_params* P, int iteration, const double* mean, const double* x0,
                                  double* out_U, double* out_x0_batch, void* stream) {
-    if (!P || !mean || !out_U || iteration < 0 || !mppi_dims_ok(H, ds, da) || (out_x0_batch && (!x0 || ds < 1))) return GPMPC_E_ARG;
+    if (!P || !mean || !out_U || iteration < 0 || !gpmpc_solver_dims_ok(H, ds, da) || (out_x0_batch && (!x0 || ds < 1))) return GPMPC_E_ARG;
     if (int rc = mppi_check_scalars(P, "gpmpc_mppi_sample")) return rc;
     if (int rc = mppi_check_inputs(P, da, "gpmpc_mppi_sample")) return rc;
     return mppi_launch_sample(H, ds, da, *P, iteration, mean, x0, out_U, out_x0_batch, (hipStream_t)stream);
@@ -274,12 +257,12 @@ extern "C" int gpmpc_mppi_sample(int H, int ds, int da, const gpmpc_mppi_params*
 
 extern "C" int gpmpc_mppi_update(int K, int H, int da, int n_rows, double beta, const double* U, const double* cost, const double* g,
                                  double* mean, const double* best_in, double* best_out, double* out_trace, void* stream) {
-    if (!U || !cost || !mean || !best_in || !best_out || !out_trace || !mppi_dims_ok(H, 0, da)) return GPMPC_E_ARG;
-    if (K < 1 || K > GPMPC_MPPI_MAX_SAMPLES) return mppi_refuse("gpmpc_mppi_update", "the number of samples is outside 1..GPMPC_MPPI_MAX_SAMPLES");
-    if (!(beta > 0.0)) return mppi_refuse("gpmpc_mppi_update", "beta is not positive");
-    if (best_in == best_out) return mppi_refuse("gpmpc_mppi_update", "best_in and best_out must be different buffers");
+    if (!U || !cost || !mean || !best_in || !best_out || !out_trace || !gpmpc_solver_dims_ok(H, 0, da)) return GPMPC_E_ARG;
+    if (K < 1 || K > GPMPC_MPPI_MAX_SAMPLES) return gpmpc_refuse("gpmpc_mppi_update", "the number of samples is outside 1..GPMPC_MPPI_MAX_SAMPLES");
+    if (!(beta > 0.0)) return gpmpc_refuse("gpmpc_mppi_update", "beta is not positive");
+    if (best_in == best_out) return gpmpc_refuse("gpmpc_mppi_update", "best_in and best_out must be different buffers");
     if (n_rows < 0 || n_rows > GPMPC_MAX_CONS || (g != nullptr) != (n_rows > 0))
-        return mppi_refuse("gpmpc_mppi_update", "constraint values and n_rows in 1..GPMPC_MAX_CONS are given together (NULL and 0 without constraints)");
+        return gpmpc_refuse("gpmpc_mppi_update", "constraint values and n_rows in 1..GPMPC_MAX_CONS are given together (NULL and 0 without constraints)");
     const int n = H * da;
     hipLaunchKernelGGL(k_mppi_update, dim3((n + 63) / 64), dim3(MPPI_THREADS), 0, (hipStream_t)stream, K, n, H * n_rows, beta, U, cost, g, mean,
                        best_in, best_out, out_trace);
@@ -289,28 +272,27 @@ extern "C" int gpmpc_mppi_update(int K, int H, int da, int n_rows, double beta, 
 
 // workspace of a solve: U [K][n] | x0 [K][ds] | cost [K] | g [K][H m_c] | mean [n] | best x 2 [2 + n] | the rollout's own workspace
 struct MppiLayout { size_t off_U, off_x0, off_cost, off_g, off_mean, off_best[2], off_roll, roll_bytes, total; };
-static size_t mppi_align(size_t b) { return (b + 255) & ~(size_t)255; }
 static MppiLayout mppi_layout(const gpmpc_pack* p, int H, int K, int m_c) {
     MppiLayout L;
     const size_t n = (size_t)H * p->da, d = sizeof(double);
-    size_t o = 0;
-    L.off_U = o; o += mppi_align(d * K * n);
-    L.off_x0 = o; o += mppi_align(d * K * p->ds);
-    L.off_cost = o; o += mppi_align(d * K);
-    L.off_g = o; o += mppi_align(d * K * H * m_c);
-    L.off_mean = o; o += mppi_align(d * n);
-    L.off_best[0] = o; o += mppi_align(d * (2 + n));
-    L.off_best[1] = o; o += mppi_align(d * (2 + n));
-    L.off_roll = o;
+    gpmpc_carver c;
+    L.off_U = c.take(d * K * n);
+    L.off_x0 = c.take(d * K * p->ds);
+    L.off_cost = c.take(d * K);
+    L.off_g = c.take(d * K * H * m_c);
+    L.off_mean = c.take(d * n);
+    L.off_best[0] = c.take(d * (2 + n));
+    L.off_best[1] = c.take(d * (2 + n));
     L.roll_bytes = m_c ? gpmpc_rollout_constrained_workspace_bytes(p, K, H, 0) : gpmpc_rollout_workspace_bytes(p, K, H, 0);
-    L.total = o + mppi_align(L.roll_bytes);
+    L.off_roll = c.take(L.roll_bytes);
+    L.total = c.total();
     return L;
 }
 
 extern "C" size_t gpmpc_mppi_solve_workspace_bytes(const gpmpc_pack* p, int H, const gpmpc_mppi_params* P, const gpmpc_state_constraints* cons) {
     if (!p || !P || P->n_samples < 1 || P->n_samples > GPMPC_MPPI_MAX_SAMPLES) return 0;
     if (cons && (cons->n_rows < 1 || cons->n_rows > GPMPC_MAX_CONS)) return 0;
-    if (!mppi_dims_ok(H, p->ds, p->da)) return 0;
+    if (!gpmpc_solver_dims_ok(H, p->ds, p->da)) return 0;
     return mppi_layout(p, H, P->n_samples, cons ? cons->n_rows : 0).total;
 }
 
@@ -320,15 +302,7 @@ extern "C" int gpmpc_mppi_solve(const gpmpc_pack* p, int H, const double* x0, co
     const char* who = "gpmpc_mppi_solve";
     if (!p || !x0 || !start || !cost || !P || !out_U || !out_best || !out_trace || !workspace || H < 1) return GPMPC_E_ARG;
     if (int rc = mppi_check_scalars(P, who)) return rc;                  // (before the pack is looked at)
-    if (cons) if (int rc = gpmpc_check_constraints(cons, who)) return rc;
-    if (int rc_dev = gpmpc_check_device(p)) return rc_dev;
-    if (!mppi_dims_ok(H, p->ds, p->da)) return GPMPC_E_ARG;
-    if (int rc = mppi_check_inputs(P, p->da, who)) return rc;
-    if (!p->built) return GPMPC_E_STATE;
-    {   // the rollouts below would refuse a bad cost schedule too, but only after the first kernels of this solve
-        gpmpc_sched_ref sched;
-        if (int rcs = gpmpc_schedule_resolve(cost, p->ds, p->da, H, "gpmpc_mppi_solve", &sched)) return rcs;
-    }
+    if (int rc = gpmpc_solver_enter(p, H, cost, cons, who, [&](int da) { return mppi_check_inputs(P, da, who); })) return rc;
     const int K = P->n_samples, n = H * p->da, m_c = cons ? cons->n_rows : 0;
     const MppiLayout L = mppi_layout(p, H, K, m_c);
     if (workspace_bytes < L.total) return GPMPC_E_WORKSPACE;

@@ -317,19 +317,19 @@ extern "C" int gpmpc_pack_set_noise(gpmpc_pack* p, const double* init_cov_host, 
     double img[GPMPC_NOISE_MAX];
     memset(img, 0, sizeof(img));
     noise_defaults(ds, da, img, !init_cov_host, !action_var_host, !process_var_host);
-    char msg[160];
+    const char* who = "gpmpc_pack_set_noise";
     if (init_cov_host) {
         double pmax = 0.0;
         for (int e = 0; e < ds * ds; ++e) {
             const double v = init_cov_host[e];
-            if (!(v - v == 0.0)) { snprintf(msg, sizeof(msg), "gpmpc_pack_set_noise: init_cov[%d][%d] is not finite", e / ds, e % ds); gpmpc_set_error_text(msg); return GPMPC_E_ARG; }
+            if (!(v - v == 0.0)) return gpmpc_refuse(who, "init_cov[%d][%d] is not finite", e / ds, e % ds);
             if (fabs(v) > pmax) pmax = fabs(v);
         }
         for (int k = 0; k < ds; ++k) {
-            if (init_cov_host[k * ds + k] < 0.0) { snprintf(msg, sizeof(msg), "gpmpc_pack_set_noise: init_cov[%d][%d] is negative", k, k); gpmpc_set_error_text(msg); return GPMPC_E_ARG; }
+            if (init_cov_host[k * ds + k] < 0.0) return gpmpc_refuse(who, "init_cov[%d][%d] is negative", k, k);
             for (int l = 0; l < ds; ++l) {
                 const double a = init_cov_host[k * ds + l], b = init_cov_host[l * ds + k];
-                if (fabs(a - b) > 1e-12 * pmax) { snprintf(msg, sizeof(msg), "gpmpc_pack_set_noise: init_cov is not symmetric at [%d][%d]", k, l); gpmpc_set_error_text(msg); return GPMPC_E_ARG; }
+                if (fabs(a - b) > 1e-12 * pmax) return gpmpc_refuse(who, "init_cov is not symmetric at [%d][%d]", k, l);
                 img[k * ds + l] = k == l ? a : 0.5 * (a + b);          // the mean of each off-diagonal pair
             }
         }
@@ -340,11 +340,8 @@ extern "C" int gpmpc_pack_set_noise(gpmpc_pack* p, const double* init_cov_host, 
         if (!src) continue;
         for (int j = 0; j < cnt; ++j) {
             const double v = src[j];
-            if (!(v - v == 0.0) || v < 0.0) {
-                snprintf(msg, sizeof(msg), "gpmpc_pack_set_noise: %s[%d] is %s", part ? "process_var" : "action_var", j, v < 0.0 ? "negative" : "not finite");
-                gpmpc_set_error_text(msg);
-                return GPMPC_E_ARG;
-            }
+            if (!(v - v == 0.0) || v < 0.0)
+                return gpmpc_refuse(who, "%s[%d] is %s", part ? "process_var" : "action_var", j, v < 0.0 ? "negative" : "not finite");
             img[off + j] = v;
         }
     }

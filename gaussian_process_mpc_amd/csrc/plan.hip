@@ -291,8 +291,8 @@ RollLayout gpmpc_layout_for(const gpmpc_pack* p, const RollShape& r, int B, int 
     L.nm = gpmpc_num_moments(D, true, grad);
     L.pps = D + D * D;
     L.sps = p->nominal ? sps_nominal(D) : sps_of(D);
-    size_t off = 0;
-    auto take = [&](size_t n) { size_t o = off; off += (n * sizeof(double) + 255) & ~(size_t)255; return o; };
+    gpmpc_carver c;
+    auto take = [&](size_t n) { return c.take(n * sizeof(double)); };
     L.off_pp = take((size_t)B * p->ds * L.pps);
     L.off_sp = take((size_t)2 * B * p->ds * L.sps);
     L.off_part = take((size_t)(r.fused ? 2 * r.fq : 1) * B * r.nwork * L.nm);     // fused: double-buffered by step parity
@@ -305,7 +305,7 @@ RollLayout gpmpc_layout_for(const gpmpc_pack* p, const RollShape& r, int B, int 
                                 : (r.sb ? (size_t)B * (r.shared ? 1 : p->ds) * p->Np * L.gw : 0));
     L.off_means = take((size_t)B * (H + 1) * p->ds);
     L.off_vars = take((size_t)B * (H + 1) * p->ds);
-    L.total = off;
+    L.total = c.total();
     return L;
 }
 

@@ -1,10 +1,10 @@
 // Host side of the diagonal rollout, shared by step.hip (kernels + enqueue), graph.hip (graph cache, split launch, callback cache, the
 // rollout entry points), autotune.hip and runtime.hip (error text, timing record, per-pack lock).  Host only: no device code here.
+// (gpmpc_dispatch_dim, which the timed launchers use, lives in gpmpc_internal.h with the rest of the plumbing every unit shares.)
 #pragma once
 #include "gpmpc_internal.h"
 #include "plan.h"
 #include <mutex>
-#include <type_traits>
 
 // One rollout call: what the entry points, the split launch, the graph capture and the autotuner hand to the enqueue.
 struct RollCall {
@@ -62,11 +62,4 @@ static int gpmpc_capture(hipStream_t s, Enqueue&& enqueue, hipGraphExec_t* out) 
     }
     if (graph) (void)hipGraphDestroy(graph);
     return rc != GPMPC_OK ? rc : (e == hipSuccess ? GPMPC_OK : GPMPC_E_LAUNCH);
-}
-
-// A run-time dimension in [LO, 8] as a compile-time one: f(std::integral_constant<int, d>), or GPMPC_E_ARG outside the range.
-template <int LO, class F>
-static inline int gpmpc_dispatch_dim(int d, F&& f) {
-    if constexpr (LO > 8) return GPMPC_E_ARG;
-    else return d == LO ? f(std::integral_constant<int, LO>{}) : gpmpc_dispatch_dim<LO + 1>(d, f);
 }

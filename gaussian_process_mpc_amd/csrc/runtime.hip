@@ -1,6 +1,7 @@
 // Process-wide state of the library that is not a kernel: the error text of the calling thread, version / device count, the opt-in
 // timing record of the pair kernels with the timed launchers of every kernel form, and the per-pack host lock.
 #include "rollout.h"
+#include <cstdarg>
 #include <new>
 #include <vector>
 
@@ -9,6 +10,14 @@ void gpmpc_set_error(const char* what, hipError_t e) {
     snprintf(g_err, sizeof(g_err), "%s: %s", what, hipGetErrorString(e));
 }
 void gpmpc_set_error_text(const char* text) { snprintf(g_err, sizeof(g_err), "%s", text); }
+int gpmpc_refuse(const char* who, const char* fmt, ...) {
+    const int n = snprintf(g_err, sizeof(g_err), "%s: ", who);
+    va_list ap;
+    va_start(ap, fmt);
+    if (n >= 0 && n < (int)sizeof(g_err)) vsnprintf(g_err + n, sizeof(g_err) - n, fmt, ap);
+    va_end(ap);
+    return GPMPC_E_ARG;
+}
 extern "C" const char* gpmpc_last_error(void) { return g_err; }
 extern "C" const char* gpmpc_version(void) { return "gpmpc-hip 0.1 (gfx950)"; }
 extern "C" int gpmpc_device_count(void) {

@@ -22,12 +22,6 @@ Schedule* find_locked(int id) {
 }
 size_t total_doubles(const Schedule& s) { return gpmpc_sched_off_flags(s.H_max, s.ds, s.da) + 2; }
 
-int refuse(const char* fmt, const char* who, int a = 0, int b = 0, int c = 0, int d = 0) {
-    char text[256];
-    snprintf(text, sizeof(text), fmt, who, a, b, c, d);
-    gpmpc_set_error_text(text);
-    return GPMPC_E_ARG;
-}
 bool all_finite(const double* v, size_t n) {
     for (size_t i = 0; i < n; ++i) if (!std::isfinite(v[i])) return false;
     return true;
@@ -59,10 +53,10 @@ int gpmpc_schedule_resolve(const gpmpc_cost_params* cost, int ds, int da, int H,
     if (!cost || cost->schedule_id == 0) return GPMPC_OK;
     std::lock_guard<std::mutex> lock(g_mu);
     const Schedule* s = find_locked(cost->schedule_id);
-    if (!s) return refuse("%s: cost schedule %d is unknown or destroyed", who, cost->schedule_id);
+    if (!s) return gpmpc_refuse(who, "cost schedule %d is unknown or destroyed", cost->schedule_id);
     if (s->ds != ds || s->da != da)
-        return refuse("%s: cost schedule of state_dim %d, action_dim %d in a call of state_dim %d, action_dim %d", who, s->ds, s->da, ds, da);
-    if (H > s->H) return refuse("%s: horizon %d exceeds the horizon %d the cost schedule was last set for", who, H, s->H);
+        return gpmpc_refuse(who, "cost schedule of state_dim %d, action_dim %d in a call of state_dim %d, action_dim %d", s->ds, s->da, ds, da);
+    if (H > s->H) return gpmpc_refuse(who, "horizon %d exceeds the horizon %d the cost schedule was last set for", H, s->H);
     int dev = -1;
     if (hipGetDevice(&dev) != hipSuccess) return GPMPC_E_LAUNCH;
     if (dev != s->device) return GPMPC_E_DEVICE;
@@ -93,7 +87,7 @@ extern "C" int gpmpc_cost_schedule_destroy(int id) {
     {
         std::lock_guard<std::mutex> lock(g_mu);
         Schedule* s = find_locked(id);
-        if (!s) return refuse("%s: cost schedule %d is unknown or destroyed", "gpmpc_cost_schedule_destroy", id);
+        if (!s) return gpmpc_refuse("gpmpc_cost_schedule_destroy", "cost schedule %d is unknown or destroyed", id);
         int cur = -1;
         if (hipGetDevice(&cur) != hipSuccess) return GPMPC_E_LAUNCH;
         if (cur != s->device) return GPMPC_E_DEVICE;         // (the wait below must be for the device the buffer lives on)
@@ -109,16 +103,16 @@ extern "C" int gpmpc_cost_schedule_destroy(int id) {
 // interleave, and the table takes the new H / has_Qf only after the last launch was enqueued -- a refused or failed set leaves the table
 // as it was.  upload: host values as kernel arguments (sched_upload); else device arrays (sched_write).
 static int sched_set(int id, int H, const double* x_ref, const double* u_ref, const double* Qf, bool upload, hipStream_t st, const char* who) {
-    if (!x_ref) return refuse("%s: cost schedule: x_ref is NULL", who);
+    if (!x_ref) return gpmpc_refuse(who, "cost schedule: x_ref is NULL");
     std::lock_guard<std::mutex> lock(g_mu);
     Schedule* s = find_locked(id);
-    if (!s) return refuse("%s: cost schedule %d is unknown or destroyed", who, id);
-    if (H < 1 || H > s->H_max) return refuse("%s: cost schedule: horizon %d outside 1..H_max = %d", who, H, s->H_max);
+    if (!s) return gpmpc_refuse(who, "cost schedule %d is unknown or destroyed", id);
+    if (H < 1 || H > s->H_max) return gpmpc_refuse(who, "cost schedule: horizon %d outside 1..H_max = %d", H, s->H_max);
     const size_t nx = (size_t)(H + 1) * s->ds, nu = (size_t)H * s->da, nq = (size_t)s->ds * s->ds;
     if (upload) {
-        if (!all_finite(x_ref, nx)) return refuse("%s: cost schedule: x_ref has a non-finite value", who);
-        if (u_ref && !all_finite(u_ref, nu)) return refuse("%s: cost schedule: u_ref has a non-finite value", who);
-        if (Qf && !all_finite(Qf, nq)) return refuse("%s: cost schedule: Q_terminal has a non-finite value", who);
+        if (!all_finite(x_ref, nx)) return gpmpc_refuse(who, "cost schedule: x_ref has a non-finite value");
+        if (u_ref && !all_finite(u_ref, nu)) return gpmpc_refuse(who, "cost schedule: u_ref has a non-finite value");
+        if (Qf && !all_finite(Qf, nq)) return gpmpc_refuse(who, "cost schedule: Q_terminal has a non-finite value");
     }
     int dev = -1;
     if (hipGetDevice(&dev) != hipSuccess) return GPMPC_E_LAUNCH;
@@ -144,7 +138,7 @@ extern "C" int gpmpc_cost_schedule_set_dev(int id, int H, const double* x_ref, c
 extern "C" int gpmpc_cost_schedule_get(int id, int* H_max, int* ds, int* da, int* H, int* has_Qf, const double** dev_out) {
     std::lock_guard<std::mutex> lock(g_mu);
     const Schedule* s = find_locked(id);
-    if (!s) return refuse("%s: cost schedule %d is unknown or destroyed", "gpmpc_cost_schedule_get", id);
+    if (!s) return gpmpc_refuse("gpmpc_cost_schedule_get", "cost schedule %d is unknown or destroyed", id);
     if (H_max) *H_max = s->H_max;
     if (ds) *ds = s->ds;
     if (da) *da = s->da;

@@ -229,19 +229,14 @@ __global__ __launch_bounds__(256) void k_sparse_gr(int cn, int cnp, int M, int n
     }
 }
 
-static size_t sp_align(size_t b) { return (b + 255) & ~(size_t)255; }
 static int sp_chunk(int chunk) { return chunk == 0 ? SP_DEFAULT_CHUNK : chunk; }
-static int sp_refuse(const char* text) { gpmpc_set_error_text(text); return GPMPC_E_ARG; }
 
 static int sp_check_dims(const char* who, int D, int M, int nt) {
-    static thread_local char buf[160];
     const char* why = nullptr;
     if (M < 1 || M > GPMPC_SPARSE_MAX_M) why = "M (inducing points) outside 1...GPMPC_SPARSE_MAX_M";
     else if (D < 1 || D > GPMPC_MAX_D) why = "D outside 1...GPMPC_MAX_D";
     else if (nt < 1 || nt > GPMPC_MAX_DS) why = "n_targets outside 1...GPMPC_MAX_DS";
-    if (!why) return GPMPC_OK;
-    snprintf(buf, sizeof(buf), "%s: %s", who, why);
-    return sp_refuse(buf);
+    return why ? gpmpc_refuse(who, "%s", why) : GPMPC_OK;
 }
 
 static void sp_hyp(SparseHyp* h, int D, const double* lambdas_host, double sigma_f, double noise_var) {
@@ -257,7 +252,7 @@ static std::atomic<int> g_sparse_form{GPMPC_SPARSE_FORM_DEFAULT};
 extern "C" int gpmpc_sparse_set_form(int form) {
     if (form != GPMPC_SPARSE_FORM_FMA && form != GPMPC_SPARSE_FORM_MFMA) {
         if (form == -1) return g_sparse_form.load();
-        return sp_refuse("gpmpc_sparse_set_form: form must be GPMPC_SPARSE_FORM_FMA, GPMPC_SPARSE_FORM_MFMA or -1 (query)");
+        return gpmpc_refuse("gpmpc_sparse_set_form", "form must be GPMPC_SPARSE_FORM_FMA, GPMPC_SPARSE_FORM_MFMA or -1 (query)");
     }
     return g_sparse_form.exchange(form);
 }
@@ -266,26 +261,26 @@ extern "C" size_t gpmpc_sparse_accumulate_workspace_bytes(int n, int D, int M, i
     (void)n; (void)D; (void)n_targets;
     if (M < 1 || M > GPMPC_SPARSE_MAX_M || chunk < 0 || chunk % 64) return 0;
     const size_t c = (size_t)sp_chunk(chunk), nbi = (size_t)(M + SP_T - 1) / SP_T;
-    return sp_align(sizeof(double) * M * c) + sp_align(sizeof(double) * nbi * c) + sp_align(sizeof(double) * c);
+    return gpmpc_align256(sizeof(double) * M * c) + gpmpc_align256(sizeof(double) * nbi * c) + gpmpc_align256(sizeof(double) * c);
 }
 
 extern "C" int gpmpc_sparse_accumulate(int n, int D, int M, int n_targets, const double* X_dev, const double* Y_dev, size_t ld_y,
                                        const double* Z_dev, const double* W_dev, size_t ld_w, const double* lambdas_host, double sigma_f,
                                        double noise_var, int chunk, int accumulate, double* G_dev, double* r_dev, double* stats_dev,
                                        void* workspace, size_t workspace_bytes, void* stream) {
-    if (n < 1) return sp_refuse("gpmpc_sparse_accumulate: n < 1");
+    if (n < 1) return gpmpc_refuse("gpmpc_sparse_accumulate", "n < 1");
     if (int rc = sp_check_dims("gpmpc_sparse_accumulate", D, M, n_targets)) return rc;
-    if (chunk < 0 || chunk % 64) return sp_refuse("gpmpc_sparse_accumulate: chunk must be 0 or a positive multiple of 64");
-    if (ld_y < (size_t)n_targets) return sp_refuse("gpmpc_sparse_accumulate: ld_y < n_targets");
-    if (ld_w < (size_t)M) return sp_refuse("gpmpc_sparse_accumulate: ld_w < M");
+    if (chunk < 0 || chunk % 64) return gpmpc_refuse("gpmpc_sparse_accumulate", "chunk must be 0 or a positive multiple of 64");
+    if (ld_y < (size_t)n_targets) return gpmpc_refuse("gpmpc_sparse_accumulate", "ld_y < n_targets");
+    if (ld_w < (size_t)M) return gpmpc_refuse("gpmpc_sparse_accumulate", "ld_w < M");
     if (!X_dev || !Y_dev || !Z_dev || !W_dev || !lambdas_host || !G_dev || !r_dev || !stats_dev || !workspace)
-        return sp_refuse("gpmpc_sparse_accumulate: NULL pointer");
+        return gpmpc_refuse("gpmpc_sparse_accumulate", "NULL pointer");
     if (workspace_bytes < gpmpc_sparse_accumulate_workspace_bytes(n, D, M, n_targets, chunk)) return GPMPC_E_WORKSPACE;
     hipStream_t s = (hipStream_t)stream;
     const int c = sp_chunk(chunk), nbi = (M + SP_T - 1) / SP_T, ntri = nbi * (nbi + 1) / 2;
     double* V = (double*)workspace;
-    double* sq = (double*)((char*)workspace + sp_align(sizeof(double) * (size_t)M * c));
-    double* winv = (double*)((char*)sq + sp_align(sizeof(double) * (size_t)nbi * c));
+    double* sq = (double*)((char*)workspace + gpmpc_align256(sizeof(double) * (size_t)M * c));
+    double* winv = (double*)((char*)sq + gpmpc_align256(sizeof(double) * (size_t)nbi * c));
     SparseHyp hyp;
     sp_hyp(&hyp, D, lambdas_host, sigma_f, noise_var);
     const bool mfma = g_sparse_form.load() == GPMPC_SPARSE_FORM_MFMA;
@@ -404,19 +399,19 @@ __global__ __launch_bounds__(256) void k_sparse_alpha(int M, int nt, const doubl
 
 extern "C" size_t gpmpc_sparse_finish_workspace_bytes(int M, int n_targets) {
     if (M < 1 || M > GPMPC_SPARSE_MAX_M || n_targets < 1 || n_targets > GPMPC_MAX_DS) return 0;
-    return sp_align(sizeof(double) * (size_t)M * M) + sp_align(sizeof(double) * (size_t)M * n_targets);
+    return gpmpc_align256(sizeof(double) * (size_t)M * M) + gpmpc_align256(sizeof(double) * (size_t)M * n_targets);
 }
 
 extern "C" int gpmpc_sparse_finish(int M, int n_targets, const double* W_dev, size_t ld_w, const double* Binv_dev, const double* r_dev,
                                    double* alpha_dev, double* Q_dev, void* workspace, size_t workspace_bytes, void* stream) {
     if (int rc = sp_check_dims("gpmpc_sparse_finish", 1, M, n_targets)) return rc;
-    if (ld_w < (size_t)M) return sp_refuse("gpmpc_sparse_finish: ld_w < M");
-    if (!W_dev || !Binv_dev || !r_dev || !alpha_dev || !Q_dev || !workspace) return sp_refuse("gpmpc_sparse_finish: NULL pointer");
+    if (ld_w < (size_t)M) return gpmpc_refuse("gpmpc_sparse_finish", "ld_w < M");
+    if (!W_dev || !Binv_dev || !r_dev || !alpha_dev || !Q_dev || !workspace) return gpmpc_refuse("gpmpc_sparse_finish", "NULL pointer");
     if (workspace_bytes < gpmpc_sparse_finish_workspace_bytes(M, n_targets)) return GPMPC_E_WORKSPACE;
     hipStream_t s = (hipStream_t)stream;
     const int nb = (M + SP_T - 1) / SP_T;
     double* C = (double*)workspace;
-    double* T = (double*)((char*)workspace + sp_align(sizeof(double) * (size_t)M * M));
+    double* T = (double*)((char*)workspace + gpmpc_align256(sizeof(double) * (size_t)M * M));
     hipLaunchKernelGGL(k_sparse_c, dim3(nb, nb), dim3(256), 0, s, M, Binv_dev, W_dev, ld_w, C);
     hipLaunchKernelGGL(k_sparse_q, dim3(nb * (nb + 1) / 2), dim3(256), 0, s, M, W_dev, ld_w, (const double*)C, Q_dev);
     hipLaunchKernelGGL(k_sparse_t, dim3(M), dim3(256), 0, s, M, n_targets, Binv_dev, r_dev, T);
@@ -486,7 +481,7 @@ __global__ __launch_bounds__(256) void k_sparse_app_fill(int M, int nt, const do
 
 extern "C" size_t gpmpc_sparse_append_workspace_bytes(int M, int n_targets) {
     if (M < 1 || M > GPMPC_SPARSE_MAX_M || n_targets < 1 || n_targets > GPMPC_MAX_DS) return 0;
-    return sp_align(sizeof(double) * 3 * (size_t)M) + sp_align(sizeof(double) * (size_t)M * n_targets);
+    return gpmpc_align256(sizeof(double) * 3 * (size_t)M) + gpmpc_align256(sizeof(double) * (size_t)M * n_targets);
 }
 
 extern "C" int gpmpc_sparse_append(int D, int M, int n_targets, const double* x_new_dev, const double* y_new_dev, const double* Z_dev,
@@ -494,14 +489,14 @@ extern "C" int gpmpc_sparse_append(int D, int M, int n_targets, const double* x_
                                    double* G_dev, double* r_dev, double* Binv_dev, double* Q_dev, double* alpha_dev, double* stats_dev,
                                    void* workspace, size_t workspace_bytes, void* stream) {
     if (int rc = sp_check_dims("gpmpc_sparse_append", D, M, n_targets)) return rc;
-    if (ld_w < (size_t)M) return sp_refuse("gpmpc_sparse_append: ld_w < M");
+    if (ld_w < (size_t)M) return gpmpc_refuse("gpmpc_sparse_append", "ld_w < M");
     if (!x_new_dev || !y_new_dev || !Z_dev || !W_dev || !lambdas_host || !G_dev || !r_dev || !Binv_dev || !Q_dev || !alpha_dev || !stats_dev ||
         !workspace)
-        return sp_refuse("gpmpc_sparse_append: NULL pointer");
+        return gpmpc_refuse("gpmpc_sparse_append", "NULL pointer");
     if (workspace_bytes < gpmpc_sparse_append_workspace_bytes(M, n_targets)) return GPMPC_E_WORKSPACE;
     hipStream_t s = (hipStream_t)stream;
     double* v = (double*)workspace; double* tv = v + M; double* u = tv + M;
-    double* T = (double*)((char*)workspace + sp_align(sizeof(double) * 3 * (size_t)M));
+    double* T = (double*)((char*)workspace + gpmpc_align256(sizeof(double) * 3 * (size_t)M));
     SparseHyp hyp;
     sp_hyp(&hyp, D, lambdas_host, sigma_f, noise_var);
     hipLaunchKernelGGL(k_sparse_app_v, dim3(M), dim3(256), 0, s, D, M, x_new_dev, Z_dev, W_dev, ld_w, hyp, v);

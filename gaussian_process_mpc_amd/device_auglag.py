@@ -15,6 +15,7 @@ import torch
 from . import _lib
 from ._lib import AuglagParamsC, check, lib, ptr, require_gpu, stream_ptr
 from .device_lbfgs import lbfgs_params, lbfgs_state_layout
+from ._solver import enqueue_chunks, per_input, solver_problem, state_layout
 from .rollout import _dev
 
 SCALARS = ("rho", "V_prev", "v", "f", "inc_v", "inc_f", "alive", "settled")
@@ -32,14 +33,7 @@ def auglag_params(n_starts, da, lb=None, ub=None, inner_ticks=25, rho0=10.0, gro
 
 def auglag_state_layout(K, n, R):
     """Offsets (in doubles) of every field of the state buffer, and ``total``: the arithmetic of include/gpmpc.h."""
-    r = lambda x: (x + 31) & ~31                               # noqa: E731
-    sizes = [("summary", 32), ("plan", r(n))] + [(f, r(K)) for f in SCALARS] + [("lam", r(K * R)), ("inc_x", r(K * n))]
-    L, o = {}, 0
-    for name, size in sizes:
-        L[name] = o
-        o += size
-    L["total"] = o
-    return L
+    return state_layout([("summary", 32), ("plan", n)] + [(f, K) for f in SCALARS] + [("lam", K * R), ("inc_x", K * n)])
 
 
 def auglag_state_view(state, K, H, da, m_c):
@@ -78,9 +72,8 @@ def auglag_state_new(X0, rho0, m_c, lb=None, ub=None):
     K, H, da = X0.shape
     state = torch.zeros(auglag_state_layout(K, H * da, H * m_c)["total"], dtype=torch.float64, device=X0.device)
     v = auglag_state_view(state, K, H, da, m_c)
-    per_input = lambda b, d: torch.as_tensor(np.broadcast_to(np.asarray(d if b is None else b, dtype=np.float64).reshape(-1), (da,)).copy(),  # noqa: E731
-                                             device=X0.device)
-    v["inc_x"].copy_(torch.minimum(torch.maximum(X0, per_input(lb, -np.inf)), per_input(ub, np.inf)).reshape(K, -1))
+    bound = lambda b, d: torch.as_tensor(per_input(b, d, da).copy(), device=X0.device)  # noqa: E731
+    v["inc_x"].copy_(torch.minimum(torch.maximum(X0, bound(lb, -np.inf)), bound(ub, np.inf)).reshape(K, -1))
     v["rho"].fill_(float(rho0))
     for f in ("V_prev", "v", "f", "inc_v", "inc_f"):
         v[f].fill_(float("inf"))
@@ -142,14 +135,9 @@ def auglag_solve(pack, x0, X0, cost, constraints, lb=None, ub=None, outer=8, inn
     Returns (U (H, da) numpy: the incumbent of the best start, its cost, info): info holds per start f and violation (the incumbent's cost and
     max(g, 0), 0 where feasible), feasible, x (the incumbents), rho, lam, alive, settled, and best, outer, evaluations."""
     dev = pack.device
-    X0 = _dev(X0, dev)
-    if X0.dim() != 3 or X0.shape[2] != pack.da:
-        raise ValueError("X0 must have shape (K, H, da)")
+    x0, X0 = solver_problem(pack, x0, X0, cost, "X0", "(K, H, da)")
     K, H, da = X0.shape
     n = H * da
-    x0 = _dev(x0, dev).reshape(-1)
-    if x0.shape[0] != pack.ds or cost.ds != pack.ds or cost.da != pack.da:
-        raise ValueError("shape mismatch between pack, x0, X0 and cost parameters")
     if constraints is None:
         raise ValueError("auglag_solve needs state constraints: the unconstrained multi-start is device_lbfgs.lbfgs_solve")
     if constraints.ds != pack.ds:
@@ -166,21 +154,14 @@ def auglag_solve(pack, x0, X0, cost, constraints, lb=None, ub=None, outer=8, inn
     L = auglag_state_layout(K, n, R)
     inner_total = lbfgs_state_layout(K, n, P.inner.history)["total"] if 1 <= P.inner.history <= _lib.LBFGS_MAX_HISTORY else 0
     ws[:min(L["total"] + inner_total, ws.numel())].zero_()    # (the padding between the fields is never written by a kernel)
-    chunk = check_outer if check_outer > 0 else max(outer, 0)
-    done, first, calls = 0, True, 0
+
+    def enqueue(first_outer, n_outer):
+        check(lib().gpmpc_auglag_solve(pack.handle, H, ptr(x0), ptr(X0), ctypes.byref(cost.c), ctypes.byref(constraints.c),
+                                       ctypes.byref(P), first_outer, n_outer, ctypes.c_void_p(ws.data_ptr()), ws.numel() * 8, stream_ptr()),
+              "gpmpc_auglag_solve")
+
     with torch.cuda.device(dev):
-        while first or done < outer:
-            no = outer if outer < 0 else min(chunk, outer - done)          # (a negative budget is the library's to refuse)
-            check(lib().gpmpc_auglag_solve(pack.handle, H, ptr(x0), ptr(X0), ctypes.byref(cost.c), ctypes.byref(constraints.c),
-                                           ctypes.byref(P), done, no, ctypes.c_void_p(ws.data_ptr()), ws.numel() * 8, stream_ptr()),
-                  "gpmpc_auglag_solve")
-            first = False
-            done += no
-            calls += 1
-            if callback is not None:
-                callback(done, ws, L["total"])
-            if done >= outer or ws[0].item() == 0.0:
-                break
+        done, calls = enqueue_chunks(outer, check_outer, enqueue, ws, None if callback is None else lambda d: callback(d, ws, L["total"]))
     s = auglag_state_fields(ws, K, H, da, m_c)
     info = {"f": s["inc_f"], "violation": s["inc_v"], "feasible": s["inc_v"] == 0.0, "x": s["inc_x"], "best": s["best"], "rho": s["rho"],
             "lam": s["lam"], "outer": done, "evaluations": done * (1 + int(inner_ticks)) + calls, "settled": s["settled"], "alive": s["alive"],

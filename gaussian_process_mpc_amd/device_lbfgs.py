@@ -13,6 +13,7 @@ import torch
 
 from . import _lib
 from ._lib import LbfgsParamsC, check, lib, ptr, require_gpu, stream_ptr
+from ._solver import enqueue_chunks, per_input, solver_problem, state_layout
 from .rollout import _dev
 
 SCALARS = ("F", "converged", "alive", "iters", "ticks", "done", "A", "cnt", "head")
@@ -22,26 +23,18 @@ def lbfgs_params(n_starts, da, lb=None, ub=None, history=8, gtol=1e-4, ftol=1e-1
     """The C struct ``gpmpc_lbfgs_params``.  lb, ub: a scalar or one value per input; missing bounds are infinite."""
     if not 1 <= da <= _lib.MAX_D:
         raise ValueError("input dimension exceeds the library limits")
-    per_input = lambda v, d: np.broadcast_to(np.asarray(d if v is None else v, dtype=np.float64).reshape(-1), (da,))  # noqa: E731
     c = LbfgsParamsC()
     c.n_starts, c.history = int(n_starts), int(history)
     c.gtol, c.ftol, c.c1, c.min_step = float(gtol), float(ftol), float(c1), float(min_step)
-    c.lb[:da] = per_input(lb, -np.inf).tolist()
-    c.ub[:da] = per_input(ub, np.inf).tolist()
+    c.lb[:da] = per_input(lb, -np.inf, da).tolist()
+    c.ub[:da] = per_input(ub, np.inf, da).tolist()
     return c
 
 
 def lbfgs_state_layout(K, n, m):
     """Offsets (in doubles) of every field of the state buffer, and ``total``: the arithmetic of include/gpmpc.h."""
-    r = lambda x: (x + 31) & ~31                               # noqa: E731
-    sizes = [("summary", 32), ("plan", r(n))] + [(f, r(K)) for f in SCALARS] + [("rho", r(K * m))]
-    sizes += [(f, r(K * n)) for f in ("X", "G", "D", "U")] + [(f, r(K * m * n)) for f in ("S", "Y")]
-    L, o = {}, 0
-    for name, size in sizes:
-        L[name] = o
-        o += size
-    L["total"] = o
-    return L
+    return state_layout([("summary", 32), ("plan", n)] + [(f, K) for f in SCALARS] + [("rho", K * m)]
+                        + [(f, K * n) for f in ("X", "G", "D", "U")] + [(f, K * m * n) for f in ("S", "Y")])
 
 
 def lbfgs_state_view(state, K, H, da, m):
@@ -163,14 +156,9 @@ def lbfgs_solve(pack, x0, X0, cost, lb=None, ub=None, max_ticks=150, history=8, 
     ``callback(ticks_enqueued, state)`` (optional) is called after every chunk with the state buffer (``lbfgs_state_view``).
     Returns (U (H, da) numpy: the best plan, its cost, info) with the keys of ``multistart.lockstep_lbfgs``'s info."""
     dev = pack.device
-    X0 = _dev(X0, dev)
-    if X0.dim() != 3 or X0.shape[2] != pack.da:
-        raise ValueError("X0 must have shape (K, H, da)")
+    x0, X0 = solver_problem(pack, x0, X0, cost, "X0", "(K, H, da)")
     K, H, da = X0.shape
     n = H * da
-    x0 = _dev(x0, dev).reshape(-1)
-    if x0.shape[0] != pack.ds or cost.ds != pack.ds or cost.da != pack.da:
-        raise ValueError("shape mismatch between pack, x0, X0 and cost parameters")
     max_ticks, check_every = int(max_ticks), int(check_every)
     if check_every < 0:
         raise ValueError("check_every must be 0 (one chunk) or positive")
@@ -180,19 +168,13 @@ def lbfgs_solve(pack, x0, X0, cost, lb=None, ub=None, max_ticks=150, history=8, 
     ws = torch.empty(max(nbytes // 8, 32), dtype=torch.float64, device=dev)
     L = lbfgs_state_layout(K, n, P.history)
     ws[:L["total"]].zero_()                                  # (the padding between the fields is never written by a kernel)
-    chunk = check_every if check_every > 0 else max(max_ticks, 0)
-    done_ticks, first = 0, True
+
+    def enqueue(first_tick, n_ticks):
+        check(lib().gpmpc_lbfgs_solve(pack.handle, H, ptr(x0), ptr(X0), ctypes.byref(cost.c), ctypes.byref(P), first_tick, n_ticks,
+                                      ctypes.c_void_p(ws.data_ptr()), ws.numel() * 8, stream_ptr()), "gpmpc_lbfgs_solve")
+
     with torch.cuda.device(dev):
-        while first or done_ticks < max_ticks:
-            nt = max_ticks if max_ticks < 0 else min(chunk, max_ticks - done_ticks)        # (a negative budget is the library's to refuse)
-            check(lib().gpmpc_lbfgs_solve(pack.handle, H, ptr(x0), ptr(X0), ctypes.byref(cost.c), ctypes.byref(P), done_ticks, nt,
-                                          ctypes.c_void_p(ws.data_ptr()), ws.numel() * 8, stream_ptr()), "gpmpc_lbfgs_solve")
-            first = False
-            done_ticks += nt
-            if callback is not None:
-                callback(done_ticks, ws)
-            if done_ticks >= max_ticks or ws[0].item() == 0.0:
-                break
+        done_ticks, _ = enqueue_chunks(max_ticks, check_every, enqueue, ws, None if callback is None else lambda done: callback(done, ws))
     host = ws[:L["G"]].cpu().numpy()                                      # one copy: everything before G is what a caller reads
     col = lambda f: host[L[f]:L[f] + K]                                   # noqa: E731
     ticks = int(col("ticks").max())

@@ -398,17 +398,11 @@ class RiskSensitiveMPC:
         K = self.n_starts if n_starts is None else n_starts
         sc = self.state_constraints
         if solver == "mppi":
-            x = self._solve_mppi()
-            self.last_traj = x
-            return np.reshape(x, (self.horizon, self.input_dim))
+            return self._keep_plan(self._solve_mppi())
         if solver == "auglag":
-            x = self._solve_device_auglag(max(int(K), 1), lb, ub)
-            self.last_traj = x
-            return np.reshape(x, (self.horizon, self.input_dim))
+            return self._keep_plan(self._solve_device_auglag(max(int(K), 1), lb, ub))
         if solver == "lbfgs":
-            x = self._solve_device_lbfgs(max(int(K), 1), lb, ub)
-            self.last_traj = x
-            return np.reshape(x, (self.horizon, self.input_dim))
+            return self._keep_plan(self._solve_device_lbfgs(max(int(K), 1), lb, ub))
         if sc is not None and self.full_covariance:
             raise NotImplementedError("state constraints under the full-covariance rollout are not implemented "
                                       "(q = a^T Sigma_t a and that path's Jacobian layout: a follow-up)")
@@ -416,9 +410,7 @@ class RiskSensitiveMPC:
             raise NotImplementedError("the lock-step multi-start solve is unconstrained: use n_starts = 1 with state constraints "
                                       "(a constrained multi-start, e.g. an augmented Lagrangian over the batched evaluation, is a follow-up)")
         if K > 1:
-            x = self._solve_multistart(K, lb, ub)
-            self.last_traj = x
-            return np.reshape(x, (self.horizon, self.input_dim))
+            return self._keep_plan(self._solve_multistart(K, lb, ub))
         if HAVE_CYIPOPT:
             if sc is None:
                 nlp = cyipopt.Problem(n=len(x0), m=0, problem_obj=self, lb=lb, ub=ub, cl=[0], cu=[0])
@@ -434,8 +426,25 @@ class RiskSensitiveMPC:
             self.solver_used = "ipopt"
         else:
             x = self._solve_without_ipopt(x0, lb, ub)
+        return self._keep_plan(x)
+
+    def _keep_plan(self, x):
+        """The end of every solve: the flat plan is kept for the next warm start and returned as (H, da)."""
         self.last_traj = x
         return np.reshape(x, (self.horizon, self.input_dim))
+
+    def _starts(self, K, lb, ub, opt):
+        """The K start points (K, H da) of a multi-start solve (multistart.make_starts): with ``opt["warm"]`` and a previous plan, that plan
+        shifted by one step with its last input repeated; drawn from default_rng([opt["seed"], solve count]), and the solve is counted."""
+        from .multistart import make_starts
+        H, da = self.horizon, self.input_dim
+        warm = None
+        if opt.get("warm", True) and self.solver_used is not None:
+            prev = np.asarray(self.last_traj, dtype=np.float64).reshape(H, da)
+            warm = np.concatenate((prev[1:], prev[-1:]), axis=0).reshape(-1)
+        rng = np.random.default_rng([int(opt.get("seed", 0)), self._solve_count])
+        self._solve_count += 1
+        return make_starts(K, H * da, lb, ub, rng, warm=warm, spread=float(opt.get("spread", 1.0)))
 
     def _solve_without_ipopt(self, x0, lb, ub):
         """Stand-in driver when cyipopt is not installed: bounded L-BFGS (scipy) on the same
@@ -491,16 +500,9 @@ class RiskSensitiveMPC:
         """The lock-step multi-start search on the device (device_lbfgs.lbfgs_solve): the starts, the seed and the solve count are those of
         ``_solve_multistart``; the ticks run as enqueues of ``check_every`` (rollout, tick kernel) pairs without the host in between."""
         from .device_lbfgs import lbfgs_solve
-        from .multistart import make_starts
         opt = self.multistart_options
-        n, H, da = self.horizon * self.input_dim, self.horizon, self.input_dim
-        warm = None
-        if opt.get("warm", True) and self.solver_used is not None:        # the previous plan shifted by one step, last input repeated
-            prev = np.asarray(self.last_traj, dtype=np.float64).reshape(H, da)
-            warm = np.concatenate((prev[1:], prev[-1:]), axis=0).reshape(-1)
-        rng = np.random.default_rng([int(opt.get("seed", 0)), self._solve_count])
-        self._solve_count += 1
-        X0 = make_starts(K, n, lb, ub, rng, warm=warm, spread=float(opt.get("spread", 1.0)))
+        H, da = self.horizon, self.input_dim
+        X0 = self._starts(K, lb, ub, opt)
         U, cost, info = lbfgs_solve(self.dynamics.pack(), self.curr_state, X0.reshape(K, H, da), self._cost_params(),
                                     lb=np.asarray(self.lb, dtype=np.float64), ub=np.asarray(self.ub, dtype=np.float64),
                                     max_ticks=int(opt.get("max_ticks", 150)), history=int(opt.get("history", 8)),
@@ -517,18 +519,11 @@ class RiskSensitiveMPC:
         """The constrained multi-start on the device (device_auglag.auglag_solve): the starts, the seed and the solve count are those of
         ``_solve_device_lbfgs`` (``spread``, ``seed``, ``warm`` from ``multistart_options``); everything else from ``auglag_options``."""
         from .device_auglag import auglag_solve
-        from .multistart import make_starts
-        opt, ms = self.auglag_options, self.multistart_options
-        n, H, da = self.horizon * self.input_dim, self.horizon, self.input_dim
-        warm = None
-        if ms.get("warm", True) and self.solver_used is not None:         # the previous plan shifted by one step, last input repeated
-            prev = np.asarray(self.last_traj, dtype=np.float64).reshape(H, da)
-            warm = np.concatenate((prev[1:], prev[-1:]), axis=0).reshape(-1)
-        rng = np.random.default_rng([int(ms.get("seed", 0)), self._solve_count])
-        self._solve_count += 1
-        X0 = make_starts(K, n, lb, ub, rng, warm=warm, spread=float(ms.get("spread", 1.0)))
+        H, da = self.horizon, self.input_dim
+        X0 = self._starts(K, lb, ub, self.multistart_options)
         U, cost, info = auglag_solve(self.dynamics.pack(), self.curr_state, X0.reshape(K, H, da), self._cost_params(), self.state_constraints,
-                                     lb=np.asarray(self.lb, dtype=np.float64), ub=np.asarray(self.ub, dtype=np.float64), **opt)
+                                     lb=np.asarray(self.lb, dtype=np.float64), ub=np.asarray(self.ub, dtype=np.float64),
+                                     **self.auglag_options)
         best = info["best"]
         info["starts"] = K
         info["success"] = bool(info["feasible"][best])
@@ -542,17 +537,11 @@ class RiskSensitiveMPC:
         """K starts advanced together (multistart.lockstep_lbfgs): one batched rollout of K plans per solver iteration, replayed as
         one hipGraph; with torch.distributed initialised the K plans are sharded over the ranks (parallel.sharded_rollout) and every
         rank takes the same decisions from the same gathered [cost | grad].  Optimiser results unpinned, like the Ipopt stand-in."""
-        from .multistart import lockstep_lbfgs, make_starts
+        from .multistart import lockstep_lbfgs
         opt = self.multistart_options
         n, H, da = self.horizon * self.input_dim, self.horizon, self.input_dim
         pack, cp, cs = self.dynamics.pack(), self._cost_params(), self.curr_state
-        warm = None
-        if opt.get("warm", True) and self.solver_used is not None:        # the previous plan shifted by one step, last input repeated
-            prev = np.asarray(self.last_traj, dtype=np.float64).reshape(H, da)
-            warm = np.concatenate((prev[1:], prev[-1:]), axis=0).reshape(-1)
-        rng = np.random.default_rng([int(opt.get("seed", 0)), self._solve_count])
-        self._solve_count += 1
-        X0 = make_starts(K, n, lb, ub, rng, warm=warm, spread=float(opt.get("spread", 1.0)))
+        X0 = self._starts(K, lb, ub, opt)
         dist = None
         if torch.distributed.is_available() and torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1:
             dist = torch.distributed

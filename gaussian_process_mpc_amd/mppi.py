@@ -12,6 +12,7 @@ import torch
 
 from . import _lib
 from ._lib import MppiParamsC, check, lib, ptr, require_gpu, stream_ptr
+from ._solver import per_input, solver_problem
 from .rollout import _dev
 
 DEFAULTS = {"samples": 64, "iterations": 30, "sigma": None, "decay": 0.9, "beta": 0.1, "seed": 0}
@@ -21,12 +22,11 @@ def mppi_params(samples, da, sigma, lb=None, ub=None, iterations=1, decay=1.0, b
     """The C struct ``gpmpc_mppi_params``.  sigma, lb, ub: a scalar or one value per input; missing bounds are infinite."""
     if not 1 <= da <= _lib.MAX_D:
         raise ValueError("input dimension exceeds the library limits")
-    per_input = lambda v, d: np.broadcast_to(np.asarray(d if v is None else v, dtype=np.float64).reshape(-1), (da,))  # noqa: E731
     c = MppiParamsC()
     c.n_samples, c.iterations = int(samples), int(iterations)
-    c.sigma[:da] = per_input(sigma, 1.0).tolist()
-    c.lb[:da] = per_input(lb, -np.inf).tolist()
-    c.ub[:da] = per_input(ub, np.inf).tolist()
+    c.sigma[:da] = per_input(sigma, 1.0, da).tolist()
+    c.lb[:da] = per_input(lb, -np.inf, da).tolist()
+    c.ub[:da] = per_input(ub, np.inf, da).tolist()
     c.sigma_decay, c.beta = float(decay), float(beta)
     c.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
     c.call_index = int(call_index) & 0xFFFFFFFF
@@ -99,13 +99,8 @@ def mppi_solve(pack, x0, U0, cost, constraints=None, samples=64, iterations=30, 
     one device-to-host copy at the end.  x0 (ds,), U0 (H, da) the plan the search starts from.
     Returns dict(U (H, da) numpy: the best plan seen, cost, violation, feasible, trace (iterations, 6) numpy, columns TRACE_FIELDS)."""
     dev = pack.device
-    U0 = _dev(U0, dev)
-    if U0.dim() != 2 or U0.shape[1] != pack.da:
-        raise ValueError("U0 must have shape (H, da)")
+    x0, U0 = solver_problem(pack, x0, U0, cost, "U0", "(H, da)")
     H, da = U0.shape
-    x0 = _dev(x0, dev).reshape(-1)
-    if x0.shape[0] != pack.ds or cost.ds != pack.ds or cost.da != pack.da:
-        raise ValueError("shape mismatch between pack, x0, U0 and cost parameters")
     if constraints is not None and constraints.ds != pack.ds:
         raise ValueError("the constraint rows have %d state coefficients, the pack has %d states" % (constraints.ds, pack.ds))
     P = mppi_params(samples, da, sigma, lb, ub, iterations=iterations, decay=decay, beta=beta, seed=seed, call_index=call_index)

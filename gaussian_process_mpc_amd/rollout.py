@@ -5,6 +5,7 @@ arithmetic lives in csrc/*.hip.  Tensors are float64 CUDA tensors; numpy inputs 
 copied to the current device.
 """
 import ctypes
+import functools
 
 import numpy as np
 import torch
@@ -17,6 +18,34 @@ def _dev(a, device):
     if isinstance(a, torch.Tensor):
         return a.detach().to(device=device, dtype=torch.float64).contiguous()
     return torch.as_tensor(np.ascontiguousarray(np.asarray(a, dtype=np.float64)), device=device)
+
+
+def _empty(device, *shape):
+    return torch.empty(shape, dtype=torch.float64, device=device)
+
+
+def _problem(pack, x0, U, cost):
+    """What every rollout does to its inputs: U (a device tensor, or the float64 host array of the graph path) to (B, H, da), x0 to a
+    device tensor (B, ds) -- one start state serves all trajectories --, both checked against the pack and the cost.
+    Returns (x0, U, B, H, da)."""
+    if U.ndim == 2:
+        U = U[None]
+    B, H, da = U.shape
+    x0 = _dev(x0, pack.device).reshape(-1, pack.ds)
+    if x0.shape[0] == 1 and B > 1:
+        x0 = x0.expand(B, pack.ds).contiguous()
+    if da != pack.da or x0.shape[0] != B or cost.ds != pack.ds or cost.da != pack.da:
+        raise ValueError("shape mismatch between pack, x0, U and cost parameters")
+    return x0, U, B, H, da
+
+
+def _describe(buf):
+    """The ``key=value`` words of a ``*_describe`` entry as a dict (integers as int)."""
+    out = {}
+    for kv in buf.value.decode().split():
+        k, v = kv.split("=", 1)
+        out[k] = int(v) if v.lstrip("-").isdigit() else v
+    return out
 
 
 class CostSchedule:
@@ -224,11 +253,15 @@ class GPPack:
         self.device = device if device is not None else require_gpu()
         self._h = None
         self.generation = 0          # bumped by every (re)build: caches keyed on the pack object include it
-        self._ws = {}
-        self._graph_bufs = {}
+        self._drop_caches()
         self.fullcov = False
         self._nominal = None
         self._fill(X, Y, Ky_inv, lambdas, sigma_f, y_is_beta, nominal, fullcov)
+
+    def _drop_caches(self):
+        """Forget the per-stream workspaces and the buffers of the graph path: the plans they were sized for are gone."""
+        self._graph_bufs = {}
+        self._ws = {}
 
     def _set_nominal(self, nominal):
         """Hand a changed model to the library (switching it on or off re-plans the pack: scratch sizes change)."""
@@ -249,8 +282,7 @@ class GPPack:
                 check(lib().gpmpc_pack_set_nominal(self._h, host_doubles(nominal[0])[1], host_doubles(nominal[1])[1], stream_ptr()),
                       "gpmpc_pack_set_nominal")
         if (nominal is None) != (old is None):
-            self._graph_bufs = {}
-            self._ws = {}
+            self._drop_caches()
         self._nominal = nominal
 
     @property
@@ -395,8 +427,7 @@ class GPPack:
         with torch.cuda.device(self.device):
             torch.cuda.synchronize(self.device)
             check(lib().gpmpc_pack_reload_tuning(self._h), "gpmpc_pack_reload_tuning")
-        self._graph_bufs = {}
-        self._ws = {}
+        self._drop_caches()
         return self
 
     def plan(self, B, H, want_grad=True, graph=False):
@@ -405,11 +436,7 @@ class GPPack:
         buf = ctypes.create_string_buffer(512)
         flags = (_lib.WANT_GRAD if want_grad else 0) | (_lib.USE_GRAPH if graph else 0)
         check(lib().gpmpc_plan_describe(self._h, int(B), int(H), flags, buf, 512), "gpmpc_plan_describe")
-        out = {}
-        for kv in buf.value.decode().split():
-            k, v = kv.split("=", 1)
-            out[k] = int(v) if v.lstrip("-").isdigit() else v
-        return out
+        return _describe(buf)
 
     def plan_fullcov(self, B, H, want_grad=True):
         """What ``rollout_fullcov`` launches for this call shape (C ABI ``gpmpc_rollout_fullcov_describe``): dict with ``form``
@@ -417,11 +444,7 @@ class GPPack:
         buf = ctypes.create_string_buffer(512)
         check(lib().gpmpc_rollout_fullcov_describe(self._h, int(B), int(H), _lib.WANT_GRAD if want_grad else 0, buf, 512),
               "gpmpc_rollout_fullcov_describe")
-        out = {}
-        for kv in buf.value.decode().split():
-            k, v = kv.split("=", 1)
-            out[k] = int(v) if v.lstrip("-").isdigit() else v
-        return out
+        return _describe(buf)
 
     def plan_moment_match(self, nq, want_cov=False, want_grad=False, bug_compatible=False):
         """What ``moment_match`` launches for nq queries with these options (C ABI ``gpmpc_moment_match_describe``; nothing runs):
@@ -431,11 +454,7 @@ class GPPack:
         flags = ((_lib.WANT_GRAD if want_grad else 0) | (_lib.COV_BUG_COMPAT if bug_compatible else 0)
                  | (_lib.DESCRIBE_WANT_COV if want_cov else 0))
         check(lib().gpmpc_moment_match_describe(self._h, int(nq), flags, buf, 256), "gpmpc_moment_match_describe")
-        out = {}
-        for kv in buf.value.decode().split():
-            k, v = kv.split("=", 1)
-            out[k] = int(v) if v.lstrip("-").isdigit() else v
-        return out
+        return _describe(buf)
 
     def autotune(self, B, H, want_grad=True, graph=False):
         """Time the candidate plans of this call shape on this device and keep the fastest for later calls (C ABI
@@ -447,8 +466,7 @@ class GPPack:
             rc = lib().gpmpc_pack_autotune(self._h, int(B), int(H), flags, buf, 8192)
         if rc < 0:
             check(rc, "gpmpc_pack_autotune")
-        self._graph_bufs = {}
-        self._ws = {}
+        self._drop_caches()
         out = []
         for item in buf.value.decode().split(";"):
             name, fields, ms = item.split(":")
@@ -461,8 +479,7 @@ class GPPack:
 
     def autotune_clear(self):
         check(lib().gpmpc_pack_autotune_clear(self._h), "gpmpc_pack_autotune_clear")
-        self._graph_bufs = {}
-        self._ws = {}
+        self._drop_caches()
 
     @property
     def shared_lambda(self):
@@ -527,26 +544,15 @@ def rollout(pack, x0, U, cost, want_grad=True, want_traj=True, graph=False, prec
     dev = pack.device
     U_host = None
     if graph and not isinstance(U, torch.Tensor):          # solver callbacks hand numpy: stage through pinned memory
-        U_host = np.ascontiguousarray(np.asarray(U, dtype=np.float64))
-        if U_host.ndim == 2:
-            U_host = U_host[None]
-        B, H, da = U_host.shape
+        x0, U_host, B, H, da = _problem(pack, x0, np.ascontiguousarray(np.asarray(U, dtype=np.float64)), cost)
     else:
-        U = _dev(U, dev)
-        if U.dim() == 2:
-            U = U.unsqueeze(0)
-        B, H, da = U.shape
-    x0 = _dev(x0, dev).reshape(-1, pack.ds)
-    if x0.shape[0] == 1 and B > 1:
-        x0 = x0.expand(B, pack.ds).contiguous()
-    if da != pack.da or x0.shape[0] != B or cost.ds != pack.ds or cost.da != pack.da:
-        raise ValueError("shape mismatch between pack, x0, U and cost parameters")
+        x0, U, B, H, da = _problem(pack, x0, _dev(U, dev), cost)
     prec = {"fp64": 0, "fp32acc": _lib.FP32_ACCUM, "fp32": _lib.FP32_ALL}[precision]
     if prec and want_grad:
         raise ValueError("the reduced-precision sweep modes are objective only: pass want_grad=False")
     flags = (_lib.WANT_GRAD if want_grad else 0) | (_lib.USE_GRAPH if graph else 0) | prec
     nbytes = lib().gpmpc_rollout_workspace_bytes(pack.handle, B, H, flags)
-    e = lambda *shape: torch.empty(shape, dtype=torch.float64, device=dev)  # noqa: E731
+    e = functools.partial(_empty, dev)
     if graph:
         key = (B, H, bool(want_grad), bool(want_traj))
         buf = pack._graph_bufs.get(key)
@@ -592,19 +598,11 @@ def rollout(pack, x0, U, cost, want_grad=True, want_traj=True, graph=False, prec
 
 def _rollout_constrained(pack, x0, U, cost, sc, want_grad, want_traj):
     dev = pack.device
-    U = _dev(U, dev)
-    if U.dim() == 2:
-        U = U.unsqueeze(0)
-    B, H, da = U.shape
-    x0 = _dev(x0, dev).reshape(-1, pack.ds)
-    if x0.shape[0] == 1 and B > 1:
-        x0 = x0.expand(B, pack.ds).contiguous()
-    if da != pack.da or x0.shape[0] != B or cost.ds != pack.ds or cost.da != pack.da:
-        raise ValueError("shape mismatch between pack, x0, U and cost parameters")
+    x0, U, B, H, da = _problem(pack, x0, _dev(U, dev), cost)
     if sc.ds != pack.ds:
         raise ValueError("the constraint rows have %d state coefficients, the pack has %d states" % (sc.ds, pack.ds))
     flags = _lib.WANT_GRAD if want_grad else 0
-    e = lambda *shape: torch.empty(shape, dtype=torch.float64, device=dev)  # noqa: E731
+    e = functools.partial(_empty, dev)
     out = {"cost": e(B), "g": e(B, H, sc.m)}
     if want_grad:
         out["grad"], out["g_jac"] = e(B, H, da), e(B, H * sc.m, H * da)
@@ -650,17 +648,9 @@ def rollout_fullcov(pack, x0, U, cost, want_grad=True):
                                   "(its cross-covariances with the linear part are not implemented)")
     if not pack.fullcov:
         pack.enable_fullcov()
-    U = _dev(U, dev)
-    if U.dim() == 2:
-        U = U.unsqueeze(0)
-    B, H, da = U.shape
-    x0 = _dev(x0, dev).reshape(-1, pack.ds)
-    if x0.shape[0] == 1 and B > 1:
-        x0 = x0.expand(B, pack.ds).contiguous()
-    if da != pack.da or x0.shape[0] != B or cost.ds != pack.ds or cost.da != pack.da:
-        raise ValueError("shape mismatch between pack, x0, U and cost parameters")
+    x0, U, B, H, da = _problem(pack, x0, _dev(U, dev), cost)
     flags = _lib.WANT_GRAD if want_grad else 0
-    e = lambda *shape: torch.empty(shape, dtype=torch.float64, device=dev)  # noqa: E731
+    e = functools.partial(_empty, dev)
     out = {"cost": e(B), "means": e(B, H + 1, pack.ds), "covs": e(B, H + 1, pack.ds, pack.ds)}
     if want_grad:
         out["grad"] = e(B, H, da)
@@ -686,7 +676,7 @@ def moment_match(pack, u, S, want_cov=False, want_grad=False, bug_compatible=Fal
     S = _dev(S, dev).reshape(nq, pack.D, pack.D)
     flags = (_lib.WANT_GRAD if want_grad else 0) | (_lib.COV_BUG_COMPAT if bug_compatible else 0)
     ds, D = pack.ds, pack.D
-    e = lambda *shape: torch.empty(shape, dtype=torch.float64, device=dev)  # noqa: E731
+    e = functools.partial(_empty, dev)
     out = {"mean": e(nq, ds), "var": e(nq, ds)}
     if want_cov:
         out["cov"] = e(nq, ds, ds)
