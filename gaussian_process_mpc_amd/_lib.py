@@ -95,8 +95,31 @@ class AuglagParamsC(ctypes.Structure):
                 ("reserved", ctypes.c_int)]
 
 
+class GPModelC(ctypes.Structure):
+    _fields_ = [("n", ctypes.c_int),
+                ("state_dim", ctypes.c_int),
+                ("action_dim", ctypes.c_int),
+                ("has_nominal", ctypes.c_int),
+                ("has_noise", ctypes.c_int),
+                ("reserved", ctypes.c_int),
+                ("X", ctypes.c_void_p),
+                ("beta", ctypes.c_void_p),
+                ("Kinv", ctypes.c_void_p),
+                ("ld", ctypes.c_size_t),
+                ("gp_stride", ctypes.c_size_t),
+                ("lambdas", ctypes.c_double * (MAX_DS * MAX_D)),
+                ("sigma_f", ctypes.c_double * MAX_DS),
+                ("nom_w", ctypes.c_double * (MAX_DS * MAX_D)),
+                ("nom_b", ctypes.c_double * MAX_DS),
+                ("init_cov", ctypes.c_double * (MAX_DS * MAX_DS)),
+                ("action_var", ctypes.c_double * MAX_D),
+                ("process_var", ctypes.c_double * MAX_DS)]
+
+
 _vp, _i, _d, _sz, _u = ctypes.c_void_p, ctypes.c_int, ctypes.c_double, ctypes.c_size_t, ctypes.c_uint
 _dp = ctypes.POINTER(ctypes.c_double)
+_ull = ctypes.c_ulonglong
+_gm, _sc = ctypes.POINTER(GPModelC), ctypes.POINTER(StateConstraintsC)
 
 # name -> (restype, argtypes); every symbol include/gpmpc.h declares
 SIGNATURES = {
@@ -190,6 +213,14 @@ SIGNATURES = {
     "gpmpc_sparse_finish": (_i, [_i, _i, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "gpmpc_sparse_append_workspace_bytes": (_sz, [_i, _i]),
     "gpmpc_sparse_append": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _sz, _dp, _d, _d, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "gpmpc_gp_posterior_workspace_bytes": (_sz, [_gm, _i, _i]),
+    "gpmpc_gp_posterior": (_i, [_gm, _i, _vp, _vp, _vp, _i, _vp, _sz, _vp]),
+    "gpmpc_particle_noise": (_i, [_i, _i, _i, _ull, _u, _vp, _vp]),
+    "gpmpc_particle_step_workspace_bytes": (_sz, [_gm, _i, _i, _i]),
+    "gpmpc_particle_step": (_i, [_gm, _i, _i, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _i, _vp, _sz, _vp]),
+    "gpmpc_particle_stats": (_i, [_i, _i, _i, _i, _vp, _vp, _sc, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "gpmpc_particle_rollout_workspace_bytes": (_sz, [_gm, _i, _i, _i, _i]),
+    "gpmpc_particle_rollout": (_i, [_gm, _i, _i, _i, _vp, _vp, _ull, _u, _sc, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _sz, _vp]),
 }
 
 _lib = None
@@ -222,7 +253,8 @@ def lib():
 def check(rc, what):
     if rc != 0:
         detail = lib().gpmpc_last_error().decode() if rc == -3 else ""
-        if rc == -1 and ("mppi" in what or "lbfgs" in what or "auglag" in what or "sparse" in what):    # these refusals say which parameter
+        if rc == -1 and ("mppi" in what or "lbfgs" in what or "auglag" in what or "sparse" in what or "particle" in what
+                         or "gp_posterior" in what):    # these refusals say which parameter
             detail = lib().gpmpc_last_error().decode()
         if rc == -1 and not detail:        # refusals of a cost schedule say which and why
             why = lib().gpmpc_last_error().decode()

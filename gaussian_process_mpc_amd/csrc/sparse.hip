@@ -10,9 +10,8 @@
 #include <hip/hip_runtime.h>
 #include <atomic>
 #include "gpmpc_internal.h"
+#include "tile_stage.h"    // SP_T, SP_KB, sp_stage<MF>: the 64 x 64 x 16 LDS stage (shared with particles.hip)
 
-#define SP_T   64      // tile edge of every matrix product here (a 256-thread workgroup, 16 results per thread)
-#define SP_KB  16       // depth of one LDS stage
 #define SP_DEFAULT_CHUNK 4096
 
 struct SparseHyp { double ilam[GPMPC_MAX_D]; double sf2; double kappa; };      // 1 / lambda_d, sigma_f^2, sigma_f^2 + noise_var
@@ -30,44 +29,6 @@ static __device__ __forceinline__ void sp_tri(int p, int* ti, int* tj) {
     int t = 0;
     while ((t + 1) * (t + 2) / 2 <= p) ++t;
     *ti = t; *tj = p - t * (t + 1) / 2;
-}
-
-// One stage of a 64 x 64 tile product, out[row][col] += sum_k A[k][row] * B[k][col], in two forms (MF = false | true):
-//   FMA:  a thread owns rows ty + 16 a and columns tx + 16 b, acc[a][b]; k ascending.
-//   MFMA: v_mfma_f64_16x16x4_f64.  Wave w = ty >> 2 owns rows 16 w ... 16 w + 15 as four 16 x 16 blocks b; operands are one double per lane,
-//         A[row = lane & 15][k = lane >> 4] and B[k = lane >> 4][col = lane & 15]; a lane holds column tx = lane & 15 of block b in rows
-//         (lane >> 4) + 4 a: acc[b][a].  Four k per instruction, instructions in ascending k.
-// sp_row / sp_acc say where result (a, b) of a thread sits; its column is tx + 16 b in both forms.
-typedef double sp_d4 __attribute__((ext_vector_type(4)));
-template <bool MF> static __device__ __forceinline__ int sp_row(int ty, int a) { return MF ? 16 * (ty >> 2) + (ty & 3) + 4 * a : ty + 16 * a; }
-template <bool MF> static __device__ __forceinline__ double& sp_acc(double (&acc)[4][4], int a, int b) { return MF ? acc[b][a] : acc[a][b]; }
-
-template <bool MF>
-static __device__ __forceinline__ void sp_stage(const double (*A)[SP_T + 1], const double (*B)[SP_T + 1], int tx, int ty, double (&acc)[4][4]) {
-    if (MF) {
-        const int kq = ty & 3, r = 16 * (ty >> 2) + tx;
-#pragma unroll
-        for (int kk = 0; kk < SP_KB / 4; ++kk) {
-            const double a = A[4 * kk + kq][r];
-#pragma unroll
-            for (int b = 0; b < 4; ++b) {
-                sp_d4 c = {acc[b][0], acc[b][1], acc[b][2], acc[b][3]};
-                c = __builtin_amdgcn_mfma_f64_16x16x4f64(a, B[4 * kk + kq][16 * b + tx], c, 0, 0, 0);
-                acc[b][0] = c.x; acc[b][1] = c.y; acc[b][2] = c.z; acc[b][3] = c.w;
-            }
-        }
-        return;
-    }
-#pragma unroll
-    for (int k = 0; k < SP_KB; ++k) {
-        double a[4], b[4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) { a[q] = A[k][ty + 16 * q]; b[q] = B[k][tx + 16 * q]; }
-#pragma unroll
-        for (int qa = 0; qa < 4; ++qa)
-#pragma unroll
-            for (int qb = 0; qb < 4; ++qb) acc[qa][qb] = fma(a[qa], b[qb], acc[qa][qb]);
-    }
 }
 
 // ---------------------------------------------------------------------------

@@ -265,6 +265,13 @@ class Dynamics(object):
             return rollout_fullcov(self.pack(), curr_state, actions, cost, want_grad=want_grad)
         return rollout(self.pack(), curr_state, actions, cost, want_grad=want_grad, want_traj=True)
 
+    def particle_rollout(self, curr_state, actions, particles=1024, seed=0, call_index=0, constraints=None, return_particles=True):
+        """Monte-Carlo rollout through the GPs' pointwise posterior (gaussian_process_mpc_amd.particles.particle_rollout): the check of
+        what ``rollout`` approximates by moment matching.  Reads the GPs' arrays in place; the pack is not touched."""
+        from .particles import particle_rollout
+        return particle_rollout(self, curr_state, actions, particles=particles, seed=seed, call_index=call_index, constraints=constraints,
+                                return_particles=return_particles)
+
     def forward_propagate(self, horizon, curr_state, actions):
         """The reference's numpy rollout (src/dynamics.py:62-124; its slow double-loop oracle, sigma_f = 1 only) with the same
         signature and return types -- numpy (H+1, ds) means and (H+1, ds, ds) diagonal covariances -- evaluated by the HIP

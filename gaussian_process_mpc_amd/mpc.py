@@ -357,6 +357,58 @@ class RiskSensitiveMPC:
         r = self.evaluate_batch(U, curr_state)
         return r["cost"].cpu().numpy(), r["grad"].cpu().numpy()
 
+    # -- Monte-Carlo check of the moment-matched plan (extension)
+    def validate_plan(self, U=None, x0=None, particles=4096, seed=0):
+        """Compare the moment-matched rollout of a plan (the last one by default; diagonal or full by ``self.full_covariance``) with a
+        particle rollout through the same GPs (``particles.particle_rollout``).  Returns a dict of host arrays:
+
+        ``mean_mm``, ``var_mm`` / ``mean_mc``, ``var_mc`` (H+1, ds): both sets of moments (``cov_mm`` / ``cov_mc`` (H+1, ds, ds) too where the
+        rollout is full); ``z_mean``, ``z_var`` (H+1, ds): (Monte-Carlo - moment-matched) in units of the Monte-Carlo standard error,
+        sqrt(var / P) for the mean and sqrt((m4 - var^2) / P) for the variance, both from the particles (0 where the error is 0);
+        ``clamped`` (H,): particles whose latent variance came out negative; ``stage_cost``: the mean over particles of
+        sum_t (x_t - x_ref)^T Q (x_t - x_ref) + sum_t (u_t - u_ref)^T R (u_t - u_ref) (torch, from the particles);
+        with state constraints ``satisfaction`` (H, rows), the fraction of particles with a . x_t <= b at t = 1..H, next to
+        ``requested`` (rows,) = Phi(kappa), and ``joint_satisfaction``, the fraction satisfying every row at every step."""
+        from statistics import NormalDist
+        from .particles import particle_rollout
+        H, ds, da = self.horizon, self.state_dim, self.input_dim
+        U = np.asarray(self.last_traj if U is None else U, dtype=np.float64).reshape(H, da)
+        cs = self.curr_state if x0 is None else x0
+        if cs is None:
+            raise ValueError("no start state: give x0 or solve once")
+        cs = np.asarray(cs.detach().cpu().numpy() if isinstance(cs, torch.Tensor) else cs, dtype=np.float64).reshape(ds)
+        mm = self.dynamics.rollout(cs, U, full_covariance=bool(self.full_covariance))
+        sc = self.state_constraints
+        mc = particle_rollout(self.dynamics, cs, U, particles=particles, seed=seed, constraints=sc)
+        P = int(particles)
+        X = mc["particles"][0]                                            # (P, H+1, ds)
+        out = {"particles": P, "mean_mm": mm["means"][0].cpu().numpy(), "mean_mc": mc["mean"][0].cpu().numpy()}
+        cov_mc = mc["cov"][0]
+        if self.full_covariance:
+            out["cov_mm"], out["cov_mc"] = mm["covs"][0].cpu().numpy(), cov_mc.cpu().numpy()
+            out["var_mm"] = np.diagonal(out["cov_mm"], axis1=1, axis2=2).copy()
+        else:
+            out["var_mm"] = mm["vars"][0].cpu().numpy()
+        out["var_mc"] = torch.diagonal(cov_mc, dim1=1, dim2=2).cpu().numpy().copy()
+        d = X - mc["mean"][0][None]
+        m4 = (d ** 4).mean(dim=0).cpu().numpy()
+        se_mean = np.sqrt(np.maximum(out["var_mc"], 0.0) / P)
+        se_var = np.sqrt(np.maximum(m4 - out["var_mc"] ** 2, 0.0) / P)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            out["z_mean"] = np.where(se_mean > 0, (out["mean_mc"] - out["mean_mm"]) / se_mean, 0.0)
+            out["z_var"] = np.where(se_var > 0, (out["var_mc"] - out["var_mm"]) / se_var, 0.0)
+        out["se_mean"], out["se_var"] = se_mean, se_var
+        out["clamped"] = mc["clamped"][0].cpu().numpy()
+        Ud = torch.as_tensor(U, device=X.device)
+        ex, eu = X - self.x_ref.to(X.device, torch.float64), Ud - self.u_ref.to(X.device, torch.float64)
+        stage = torch.einsum("pti,ij,ptj->p", ex, self.Q_tor.to(X.device), ex) + torch.einsum("ti,ij,tj->", eu, self.R_tor.to(X.device), eu)
+        out["stage_cost"] = float(stage.mean().item())
+        if sc is not None:
+            out["satisfaction"] = 1.0 - mc["violation"][0, 1:].cpu().numpy()
+            out["requested"] = np.array([NormalDist().cdf(float(k)) for k in sc.kappa])
+            out["joint_satisfaction"] = 1.0 - float(mc["joint_violation"][0].item())
+        return out
+
     # -- solve (src/mpc.py:269-330)
     def get_optimal_trajectory(self, curr_state, n_starts=None, solver=None):
         solver = getattr(self, "solver", None) if solver is None else solver

@@ -807,6 +807,92 @@ int gpmpc_sparse_append(int D, int M, int n_targets, const double* x_new_dev, co
                         double* G_dev, double* r_dev, double* Binv_dev, double* Q_dev, double* alpha_dev, double* stats_dev,
                         void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---------------------------------------------------------------------------
+ * Particles: the pointwise posterior of all GPs at many points, and Monte-Carlo rollouts through it (the device counterpart of the
+ * reference's statistical oracles, src/tools/uncertainty_prop.py:47, :139, :239 and src/test/test_dynamics.py:198-268).  DESIGN.md
+ * section 3i.  The model is what gpmpc_pack_build_beta / _strided accept, by raw arrays (a pack cannot serve: its weights carry
+ * exp(-1/4 |x_i - x_j|^2), which underflows for far pairs): a dense GP bundle (X_train, beta, Ky_inv) or a sparse one (Z, alpha, Q).
+ *
+ * For a point z = (x, u) and GP a:
+ *     k_i  = sf_a^2 exp(-1/2 sum_d (X_id - z_d)^2 / lambda_ad)
+ *     m_a  = sum_i beta_ia k_i  [+ W_a . z + b_a with a nominal model]
+ *     q_a  = sum_i sum_j k_i Kinv_a[i][j] k_j         (ALL entries: Kinv comes from LU and is not symmetric)
+ *     s2_a = sf_a^2 - q_a + process_var_a             (latent variance; returned UNCLAMPED)
+ *     x'_a = m_a + sqrt(max(s2_a, 0)) eps_a           (the clamp exists only inside the square root)
+ * A particle rollout of plan b with P particles: x_0^p = x0_b + L eps with L the lower Cholesky factor of init_cov (host; a zero pivot
+ * gives a zero column); for t = 1...H: z = (x_{t-1}^p, U_b[t-1] + sqrt(action_var) eps_u), then x_t^p as above, the GPs drawn
+ * independently given z.  Particle p of plan b is column b P + p of every [B P] array.
+ *
+ * Noise: Philox4x32-10 + Box-Muller, the generator of gpmpc_mppi_sample.  Key (seed low, seed high ^ 0x50415254); counter
+ * (p, j, t, call_index) with p the particle index WITHIN its plan, j the pair index and t the step (0: the initial draw); counter j gives
+ * the normals 2j (cosine) and 2j + 1 (sine).  At t = 0 the normals 0...ds-1 are the initial eps; at t >= 1 the normals 0...da-1 are the
+ * action noise and da...da+ds-1 the GP draws.  Every plan of a batch sees the same noise (common random numbers); a value depends on
+ * (seed, call_index, p, t, element) and on nothing else -- not B, P, chunk or the grid.
+ *
+ * No atomics, fixed summation orders, launch geometry from the sizes only: two identical calls agree bit for bit, and no result
+ * depends on `chunk` (columns are independent).  All refusals are GPMPC_E_ARG with a text in gpmpc_last_error, before any launch:
+ * a NULL pointer, dimensions outside GPMPC_MAX_*, n < 1, nq / P / B / H / T < 1, ld < n, a chunk that is negative or no multiple of 64, a
+ * lambda or sigma_f that is not positive and finite, a non-finite or negative action_var / process_var, an init_cov that is non-finite,
+ * asymmetric (|P_kl - P_lk| > 1e-12 max |P|) or has a negative pivot, constraint rows outside 1...GPMPC_MAX_CONS, more than 2^31 - 1
+ * elements in one array.  A workspace below *_workspace_bytes (which return 0 for arguments that would be refused): GPMPC_E_WORKSPACE.
+ * Not provided: gradients through particles, joint (function-space) sampling across steps, a particle-cost MPPI, multi-GPU sharding,
+ * a form that reads only one triangle of a symmetrised Kinv.
+ * ------------------------------------------------------------------------- */
+typedef struct gpmpc_gp_model {
+    int n, state_dim, action_dim;                     /* training (or inducing) points; D = state_dim + action_dim */
+    int has_nominal;                                  /* nom_w / nom_b are read */
+    int has_noise;                                    /* init_cov / action_var / process_var are read; 0: the defaults of gpmpc_pack_set_noise */
+    int reserved;
+    const double* X;                                  /* dev [n][D] */
+    const double* beta;                               /* dev [n][ds], column a = beta_a */
+    const double* Kinv;                               /* dev: GP a's matrix at Kinv + a gp_stride, row stride ld (doubles) */
+    size_t ld, gp_stride;                             /* ld >= n; gp_stride = 0: ONE matrix for every GP */
+    double lambdas[GPMPC_MAX_DS * GPMPC_MAX_D];       /* [ds][D] row-major in the leading ds*D entries */
+    double sigma_f[GPMPC_MAX_DS];
+    double nom_w[GPMPC_MAX_DS * GPMPC_MAX_D];         /* [ds][D] */
+    double nom_b[GPMPC_MAX_DS];
+    double init_cov[GPMPC_MAX_DS * GPMPC_MAX_DS];     /* [ds][ds] */
+    double action_var[GPMPC_MAX_D];                   /* [da] */
+    double process_var[GPMPC_MAX_DS];                 /* [ds] */
+} gpmpc_gp_model;
+
+/* m and s2 at nq points z dev [nq][D] for all ds GPs: out_mean, out_var dev [nq][ds].  Columns are taken `chunk` at a time (a multiple of
+ * 64; 0: the default, 4096), which bounds the workspace.  Per chunk and per group of GPs with bit-identical (lambda, sigma_f) -- the
+ * check gpmpc_pack_shared_lambda makes --: k_pt_kstar materialises Ks[i][c] (and the partial sums of m), k_pt_quad forms the 64 x 64
+ * tiles of Kinv Ks by v_mfma_f64_16x16x4_f64 and contracts each with the matching rows of Ks in its epilogue (the product is never
+ * written), k_pt_finish adds the row blocks in ascending order.  With gp_stride = 0 and one group the quadratic form is evaluated once
+ * for all GPs. */
+size_t gpmpc_gp_posterior_workspace_bytes(const gpmpc_gp_model* model_host, int nq, int chunk);
+int gpmpc_gp_posterior(const gpmpc_gp_model* model_host, int nq, const double* z_dev, double* out_mean, double* out_var, int chunk,
+                       void* workspace, size_t workspace_bytes, void* stream);
+/* The normals of step t: out_eps dev [P][n_normals], element (p, e) = normal e of counter stream (p, ., t, call_index).  The rollout
+ * uses n_normals = ds at t = 0 and da + ds at t >= 1.  n_normals in 1...GPMPC_MAX_D + GPMPC_MAX_DS, t >= 0. */
+int gpmpc_particle_noise(int P, int n_normals, int t, unsigned long long seed, unsigned call_index, double* out_eps, void* stream);
+/* One step of B plans x P particles: x_prev dev [B P][ds]; U_t dev, input j of plan b at U_t[b u_stride + j] (NULL with da = 0); eps dev
+ * [P][da + ds]; out_next dev [B P][ds]; out_mean / out_var dev [B P][ds] or NULL.  Assembles z, evaluates the posterior, draws. */
+size_t gpmpc_particle_step_workspace_bytes(const gpmpc_gp_model* model_host, int B, int P, int chunk);
+int gpmpc_particle_step(const gpmpc_gp_model* model_host, int B, int P, const double* x_prev, const double* U_t, size_t u_stride,
+                        const double* eps, double* out_next, double* out_mean, double* out_var, int chunk,
+                        void* workspace, size_t workspace_bytes, void* stream);
+/* Statistics of particles dev [T][B P][ds] per plan and step: out_mean dev [B][T][ds] (sum in a fixed order / P), out_cov dev
+ * [B][T][ds][ds] (two-pass, divisor P - 1: NaN for P = 1; exactly symmetric); with var dev [T][B P][ds] (or NULL) out_clamped dev int
+ * [B][T] = particles with some s2 < 0; with cons_host (or NULL; A and b are read, kappa is not) out_viol dev [B][T][n_rows] = fraction of
+ * particles with a_r . x > b_r and out_joint dev [B] = fraction violating any row at any step t >= 1.  Outputs that are not wanted may
+ * be NULL, but for out_viol / out_joint, which are given exactly when cons_host is. */
+int gpmpc_particle_stats(int B, int P, int T, int state_dim, const double* particles, const double* var,
+                         const gpmpc_state_constraints* cons_host, double* out_mean, double* out_cov, int* out_clamped, double* out_viol,
+                         double* out_joint, void* stream);
+/* The rollout: noise(0) -> initial particles -> for t = 1...H: noise(t) -> step, then the statistics; one stream, no host round trip, no
+ * allocation.  x0 dev [B][ds]; U dev [B][H][da]; out_particles dev [H+1][B P][ds]; out_mean dev [B][H+1][ds]; out_cov dev
+ * [B][H+1][ds][ds]; out_clamped dev int [B][H] (steps 1...H, counted from the kept s2, not with atomics); out_viol dev [B][H+1][n_rows]
+ * and out_joint dev [B] exactly when cons_host is given.  The particles are bit for bit those of the chain of gpmpc_particle_noise and
+ * gpmpc_particle_step calls. */
+size_t gpmpc_particle_rollout_workspace_bytes(const gpmpc_gp_model* model_host, int B, int P, int H, int chunk);
+int gpmpc_particle_rollout(const gpmpc_gp_model* model_host, int B, int P, int H, const double* x0, const double* U,
+                           unsigned long long seed, unsigned call_index, const gpmpc_state_constraints* cons_host,
+                           double* out_particles, double* out_mean, double* out_cov, int* out_clamped, double* out_viol,
+                           double* out_joint, int chunk, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
