@@ -43,7 +43,8 @@ adds each GP's noise variance to its predicted variance at every step: the sprea
 --inducing M [--inducing-select farthest|random]: sparse GP dynamics (RiskSensitiveMPC.use_inducing_points, sparse.py): M inducing points
 chosen among the pre-training inputs summarise ALL observations (FITC); every new observation is an O(M^2) rank-one update on the device
 and the rollout's cost depends on M only, so neither grows with the loop (printed: the data-update time of the first and the last
-quarter of the steps, and the one pack handle / callback capture of the whole loop).  Not with --window (nothing is forgotten).
+quarter of the steps, and the one pack handle / callback capture of the whole loop).  With --window N the sparse model holds the newest
+N observations: once full, every observation replaces the oldest one by an O(M^2) rank-one replacement (use_inducing_points(Z, window=N)).
 
 Needs an MI355X and the built library; no gym, no cyipopt (the stand-in solver is scipy's L-BFGS-B on the same
 objective / gradient callbacks, so the trajectories are NOT the reference's Ipopt trajectories)."""
@@ -100,8 +101,8 @@ def main():
     ap.add_argument("--inducing", type=int, default=None, metavar="M", help="sparse GP dynamics on M inducing points (FITC), chosen among the pre-training inputs")
     ap.add_argument("--inducing-select", choices=("farthest", "random"), default="farthest", help="how --inducing picks its points")
     args = ap.parse_args()
-    if args.inducing is not None and args.window is not None:
-        ap.error("--inducing and --window exclude each other: the inducing points bound the cost, nothing is forgotten")
+    if args.window is not None and args.window < 1:
+        ap.error("--window must be >= 1")
 
     rng = np.random.default_rng(0)
     plant = PendulumPlant()
@@ -123,7 +124,8 @@ def main():
     if args.inducing is not None:
         if not 1 <= args.inducing <= args.pretrain:
             ap.error("--inducing must lie in 1...--pretrain")
-        mpc.use_inducing_points(select_inducing(np.column_stack((S, A)), args.inducing, np.array([0.5, 0.5, 0.5]), method=args.inducing_select))
+        mpc.use_inducing_points(select_inducing(np.column_stack((S, A)), args.inducing, np.array([0.5, 0.5, 0.5]), method=args.inducing_select),
+                                window=args.window)                # (the sparse model's own window: max_train is the dense one's)
     mpc.dynamics.append_train_data(S, A, NS)
     mpc.set_lb([-2.0]); mpc.set_ub([2.0])
     mpc.set_xref(np.zeros(2))
@@ -182,7 +184,8 @@ def main():
             data_ms.append((time.perf_counter() - t) * 1e3)
         mpc.dynamics.append_train_data = timed
 
-    sim = Simulator(mpc, env, num_iters=args.steps, incremental=True, refresh=args.refresh, max_train=args.window)
+    sim = Simulator(mpc, env, num_iters=args.steps, incremental=True, refresh=args.refresh,
+                    max_train=None if args.inducing is not None else args.window)
     t0 = time.perf_counter()
     hist = sim.run()
     dt = time.perf_counter() - t0

@@ -213,6 +213,10 @@ SIGNATURES = {
     "gpmpc_sparse_finish": (_i, [_i, _i, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "gpmpc_sparse_append_workspace_bytes": (_sz, [_i, _i]),
     "gpmpc_sparse_append": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _sz, _dp, _d, _d, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "gpmpc_sparse_remove_workspace_bytes": (_sz, [_i, _i]),
+    "gpmpc_sparse_remove": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _sz, _dp, _d, _d, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "gpmpc_sparse_replace_workspace_bytes": (_sz, [_i, _i]),
+    "gpmpc_sparse_replace": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _dp, _d, _d, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "gpmpc_gp_posterior_workspace_bytes": (_sz, [_gm, _i, _i]),
     "gpmpc_gp_posterior": (_i, [_gm, _i, _vp, _vp, _vp, _i, _vp, _sz, _vp]),
     "gpmpc_particle_noise": (_i, [_i, _i, _i, _ull, _u, _vp, _vp]),

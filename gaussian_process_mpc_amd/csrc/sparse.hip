@@ -4,6 +4,7 @@
 //   W = chol(k(Z,Z) + jitter I)^-1 (lower triangular, from the caller)       v_n = W k(Z, x_n)       Lambda_n = sigma_f^2 + noise_var - |v_n|^2
 //   G = sum_n v_n v_n^T / Lambda_n      r = sum_n v_n y_n^T / Lambda_n        B = I + G, Binv = B^-1 (from the caller)
 //   alpha = W^T Binv r                  Q = W^T (I - Binv) W
+// and the O(M^2) rank-one steps of one observation: append, remove and replace (remove + append in one pass over G, Binv, Q).
 //
 // Rules every kernel here keeps: no atomics; every output element is owned by one workgroup, which sums in a fixed order; launch geometry
 // depends on sizes only; symmetric outputs are written once per pair (i, j) and mirrored, so they are symmetric bit for bit.
@@ -465,6 +466,207 @@ extern "C" int gpmpc_sparse_append(int D, int M, int n_targets, const double* x_
     hipLaunchKernelGGL(k_sparse_app_u, dim3(M), dim3(256), 0, s, M, W_dev, ld_w, (const double*)tv, u);
     hipLaunchKernelGGL(k_sparse_app_fill, dim3((M + 255) / 256, M), dim3(256), 0, s, M, n_targets, (const double*)v, (const double*)tv,
                        (const double*)u, y_new_dev, hyp.kappa, G_dev, r_dev, Binv_dev, Q_dev, stats_dev);
+    hipLaunchKernelGGL(k_sparse_t, dim3(M), dim3(256), 0, s, M, n_targets, (const double*)Binv_dev, (const double*)r_dev, T);
+    hipLaunchKernelGGL(k_sparse_alpha, dim3(M), dim3(256), 0, s, M, n_targets, W_dev, ld_w, (const double*)T, alpha_dev);
+    GPMPC_HIP(hipGetLastError());
+    return GPMPC_OK;
+}
+
+// ---------------------------------------------------------------------------
+// removal of ONE observation (x, y) the state holds, O(M^2): the inverse of the append.
+//   v = W k(Z, x); Lambda = kappa - |v|^2; t = Binv v; den = Lambda - v . t; u = W^T t
+//   G -= v v^T / Lambda; r -= v y^T / Lambda; Binv += t t^T / den; Q -= u u^T / den; alpha = W^T (Binv r); stats[0] -= 1
+// den cancels (den / Lambda = 1 - v . t / Lambda is small when the row carries much of what the state knows); nothing is clamped.
+// The launches are the append's with another fill: v | t | u | the M x M streams and r | Binv r | alpha.
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_sparse_rem_fill(int M, int nt, const double* __restrict__ v, const double* __restrict__ tv,
+                                                          const double* __restrict__ u, const double* __restrict__ yold, double kappa,
+                                                          double* __restrict__ G, double* __restrict__ r, double* __restrict__ Binv,
+                                                          double* __restrict__ Q, double* __restrict__ stats) {
+    __shared__ double s_scr[32], s_out[2];
+    double acc[2] = {0.0, 0.0};
+    for (int k = threadIdx.x; k < M; k += blockDim.x) { acc[0] = fma(v[k], v[k], acc[0]); acc[1] = fma(v[k], tv[k], acc[1]); }
+    block_sum<2>(acc, s_scr, s_out);
+    const double lam = kappa - s_out[0], den = lam - s_out[1];
+    const int j = blockIdx.x * blockDim.x + threadIdx.x, i = blockIdx.y;
+    if (blockIdx.x == 0 && (int)threadIdx.x < nt) {
+        const int a = threadIdx.x;
+        r[(size_t)i * nt + a] -= v[i] * yold[a] / lam;
+    }
+    if (blockIdx.x == 0 && i == 0 && threadIdx.x == 0) stats[0] -= 1.0;      // (stats[1] stays: a lower bound on the held rows' Lambda from here on)
+    if (j >= M) return;
+    const size_t o = (size_t)i * M + j;
+    G[o] -= (v[i] * v[j]) / lam;
+    Binv[o] += (tv[i] * tv[j]) / den;
+    Q[o] -= (u[i] * u[j]) / den;
+}
+
+// the argument checks the rank-one entry points share (after sp_check_dims)
+static int sp_check_rank_one(const char* who, int M, size_t ld_w, bool pointers) {
+    if (ld_w < (size_t)M) return gpmpc_refuse(who, "ld_w < M");
+    if (!pointers) return gpmpc_refuse(who, "NULL pointer");
+    return GPMPC_OK;
+}
+
+extern "C" size_t gpmpc_sparse_remove_workspace_bytes(int M, int n_targets) { return gpmpc_sparse_append_workspace_bytes(M, n_targets); }
+
+extern "C" int gpmpc_sparse_remove(int D, int M, int n_targets, const double* x_old_dev, const double* y_old_dev, const double* Z_dev,
+                                   const double* W_dev, size_t ld_w, const double* lambdas_host, double sigma_f, double noise_var,
+                                   double* G_dev, double* r_dev, double* Binv_dev, double* Q_dev, double* alpha_dev, double* stats_dev,
+                                   void* workspace, size_t workspace_bytes, void* stream) {
+    if (int rc = sp_check_dims("gpmpc_sparse_remove", D, M, n_targets)) return rc;
+    if (int rc = sp_check_rank_one("gpmpc_sparse_remove", M, ld_w, x_old_dev && y_old_dev && Z_dev && W_dev && lambdas_host && G_dev && r_dev &&
+                                   Binv_dev && Q_dev && alpha_dev && stats_dev && workspace))
+        return rc;
+    if (workspace_bytes < gpmpc_sparse_remove_workspace_bytes(M, n_targets)) return GPMPC_E_WORKSPACE;
+    hipStream_t s = (hipStream_t)stream;
+    double* v = (double*)workspace; double* tv = v + M; double* u = tv + M;
+    double* T = (double*)((char*)workspace + gpmpc_align256(sizeof(double) * 3 * (size_t)M));
+    SparseHyp hyp;
+    sp_hyp(&hyp, D, lambdas_host, sigma_f, noise_var);
+    hipLaunchKernelGGL(k_sparse_app_v, dim3(M), dim3(256), 0, s, D, M, x_old_dev, Z_dev, W_dev, ld_w, hyp, v);
+    hipLaunchKernelGGL(k_sparse_app_t, dim3(M), dim3(256), 0, s, M, (const double*)Binv_dev, (const double*)v, tv);
+    hipLaunchKernelGGL(k_sparse_app_u, dim3(M), dim3(256), 0, s, M, W_dev, ld_w, (const double*)tv, u);
+    hipLaunchKernelGGL(k_sparse_rem_fill, dim3((M + 255) / 256, M), dim3(256), 0, s, M, n_targets, (const double*)v, (const double*)tv,
+                       (const double*)u, y_old_dev, hyp.kappa, G_dev, r_dev, Binv_dev, Q_dev, stats_dev);
+    hipLaunchKernelGGL(k_sparse_t, dim3(M), dim3(256), 0, s, M, n_targets, (const double*)Binv_dev, (const double*)r_dev, T);
+    hipLaunchKernelGGL(k_sparse_alpha, dim3(M), dim3(256), 0, s, M, n_targets, W_dev, ld_w, (const double*)T, alpha_dev);
+    GPMPC_HIP(hipGetLastError());
+    return GPMPC_OK;
+}
+
+// ---------------------------------------------------------------------------
+// replacement of one held observation (x_o, y_o) by (x_n, y_n) in ONE pass over G, Binv, Q (the hot path of a full window).  The removed
+// state is never formed: with t_o = Binv v_o, s_n = Binv v_n and den_o = Lambda_o - v_o . t_o, the removed state's Binv' v_n is
+//   t_n = s_n + c t_o,  c = (t_o . v_n) / den_o,  den_n = Lambda_n + v_n . t_n,  u_o = W^T t_o,  u_n = W^T t_n
+//   G = (G - v_o v_o^T / Lambda_o) + v_n v_n^T / Lambda_n            r likewise with y_o, y_n
+//   Binv = (Binv + t_o t_o^T / den_o) - t_n t_n^T / den_n            Q = (Q - u_o u_o^T / den_o) + u_n u_n^T / den_n
+// Six dependent launches: v_o, v_n | t_o, s_n (one pass over Binv) | t_n, u_o, u_n (one pass over W) | the streams, r, stats | Binv r | alpha.
+// G and r come out as gpmpc_sparse_remove followed by gpmpc_sparse_append give them, bit for bit: v_o, v_n, Lambda_o, Lambda_n are the
+// same sums in the same order and the two corrections are applied in that order.  Binv, Q and alpha agree with the two calls to rounding.
+// Workspace: v_o | v_n | t_o | s_n | t_n | u_o | u_n, M doubles each, then T [M][n_targets].
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_sparse_rep_v(int D, int M, const double* __restrict__ xold, const double* __restrict__ xnew,
+                                                       const double* __restrict__ Z, const double* __restrict__ W, size_t ld_w, SparseHyp H,
+                                                       double* __restrict__ vo, double* __restrict__ vn) {
+    __shared__ double s_scr[16], s_out[1];
+    const int i = blockIdx.x;
+    const double* __restrict__ x = blockIdx.y ? xnew : xold;
+    double acc[1] = {0.0};
+    for (int l = threadIdx.x; l <= i; l += blockDim.x) acc[0] = fma(W[(size_t)i * ld_w + l], sp_kval(Z + (size_t)l * D, x, D, H), acc[0]);
+    block_sum<1>(acc, s_scr, s_out);
+    if (threadIdx.x == 0) (blockIdx.y ? vn : vo)[i] = s_out[0];
+}
+
+__global__ __launch_bounds__(256) void k_sparse_rep_t(int M, const double* __restrict__ Binv, const double* __restrict__ vo,
+                                                       const double* __restrict__ vn, double* __restrict__ to, double* __restrict__ sn) {
+    __shared__ double s_scr[32], s_out[2];
+    const int i = blockIdx.x;
+    double acc[2] = {0.0, 0.0};
+    for (int k = threadIdx.x; k < M; k += blockDim.x) {
+        const double b = sp_binv(Binv, M, i, k);
+        acc[0] = fma(b, vo[k], acc[0]);
+        acc[1] = fma(b, vn[k], acc[1]);
+    }
+    block_sum<2>(acc, s_scr, s_out);
+    if (threadIdx.x == 0) { to[i] = s_out[0]; sn[i] = s_out[1]; }
+}
+
+// c of the block comment above, from the vectors alone: every workgroup of k_sparse_rep_u evaluates it in this order
+static __device__ __forceinline__ double sp_rep_c(int M, const double* __restrict__ vo, const double* __restrict__ vn,
+                                                   const double* __restrict__ to, double kappa, double* s_scr, double* s_out) {
+    double acc[3] = {0.0, 0.0, 0.0};
+    for (int k = threadIdx.x; k < M; k += blockDim.x) {
+        acc[0] = fma(vo[k], vo[k], acc[0]);
+        acc[1] = fma(vo[k], to[k], acc[1]);
+        acc[2] = fma(to[k], vn[k], acc[2]);
+    }
+    block_sum<3>(acc, s_scr, s_out);
+    const double lam_o = kappa - s_out[0], den_o = lam_o - s_out[1];
+    return s_out[2] / den_o;
+}
+
+// one workgroup per column l of W: u_o[l], u_n[l]; it also owns t_n[l]
+__global__ __launch_bounds__(256) void k_sparse_rep_u(int M, const double* __restrict__ W, size_t ld_w, const double* __restrict__ vo,
+                                                       const double* __restrict__ vn, const double* __restrict__ to,
+                                                       const double* __restrict__ sn, double kappa, double* __restrict__ tn,
+                                                       double* __restrict__ uo, double* __restrict__ un) {
+    __shared__ double s_scr[48], s_out[3];
+    const double c = sp_rep_c(M, vo, vn, to, kappa, s_scr, s_out);
+    __syncthreads();                                     // (s_out is read above by every thread and written again below)
+    const int l = blockIdx.x;
+    double acc[2] = {0.0, 0.0};
+    for (int i = l + threadIdx.x; i < M; i += blockDim.x) {
+        const double w = W[(size_t)i * ld_w + l];
+        acc[0] = fma(w, to[i], acc[0]);
+        acc[1] = fma(w, sn[i] + c * to[i], acc[1]);
+    }
+    block_sum<2>(acc, s_scr, s_out);
+    if (threadIdx.x == 0) { uo[l] = s_out[0]; un[l] = s_out[1]; tn[l] = sn[l] + c * to[l]; }
+}
+
+// grid ((M + 255) / 256, M) as k_sparse_app_fill: row i, columns j; column block 0 of row i owns r[i][:], workgroup (0, 0) the stats
+__global__ __launch_bounds__(256) void k_sparse_rep_fill(int M, int nt, const double* __restrict__ vo, const double* __restrict__ vn,
+                                                          const double* __restrict__ to, const double* __restrict__ tn,
+                                                          const double* __restrict__ uo, const double* __restrict__ un,
+                                                          const double* __restrict__ yold, const double* __restrict__ ynew, double kappa,
+                                                          double* __restrict__ G, double* __restrict__ r, double* __restrict__ Binv,
+                                                          double* __restrict__ Q, double* __restrict__ stats) {
+    __shared__ double s_scr[64], s_out[4];
+    double acc[4] = {0.0, 0.0, 0.0, 0.0};
+    for (int k = threadIdx.x; k < M; k += blockDim.x) {
+        acc[0] = fma(vo[k], vo[k], acc[0]);
+        acc[1] = fma(vo[k], to[k], acc[1]);
+        acc[2] = fma(vn[k], vn[k], acc[2]);
+        acc[3] = fma(vn[k], tn[k], acc[3]);
+    }
+    block_sum<4>(acc, s_scr, s_out);
+    const double lam_o = kappa - s_out[0], den_o = lam_o - s_out[1], lam_n = kappa - s_out[2], den_n = lam_n + s_out[3];
+    const int j = blockIdx.x * blockDim.x + threadIdx.x, i = blockIdx.y;
+    if (blockIdx.x == 0 && (int)threadIdx.x < nt) {
+        const int a = threadIdx.x;
+        const double ra = r[(size_t)i * nt + a] - vo[i] * yold[a] / lam_o;
+        r[(size_t)i * nt + a] = ra + vn[i] * ynew[a] / lam_n;
+    }
+    if (blockIdx.x == 0 && i == 0 && threadIdx.x == 0) stats[1] = sp_min(lam_n, stats[1]);
+    if (j >= M) return;
+    const size_t o = (size_t)i * M + j;
+    const double g = G[o] - (vo[i] * vo[j]) / lam_o;
+    G[o] = g + (vn[i] * vn[j]) / lam_n;
+    const double b = Binv[o] + (to[i] * to[j]) / den_o;
+    Binv[o] = b - (tn[i] * tn[j]) / den_n;
+    const double q = Q[o] - (uo[i] * uo[j]) / den_o;
+    Q[o] = q + (un[i] * un[j]) / den_n;
+}
+
+extern "C" size_t gpmpc_sparse_replace_workspace_bytes(int M, int n_targets) {
+    if (M < 1 || M > GPMPC_SPARSE_MAX_M || n_targets < 1 || n_targets > GPMPC_MAX_DS) return 0;
+    return gpmpc_align256(sizeof(double) * 7 * (size_t)M) + gpmpc_align256(sizeof(double) * (size_t)M * n_targets);
+}
+
+extern "C" int gpmpc_sparse_replace(int D, int M, int n_targets, const double* x_old_dev, const double* y_old_dev, const double* x_new_dev,
+                                    const double* y_new_dev, const double* Z_dev, const double* W_dev, size_t ld_w,
+                                    const double* lambdas_host, double sigma_f, double noise_var, double* G_dev, double* r_dev,
+                                    double* Binv_dev, double* Q_dev, double* alpha_dev, double* stats_dev, void* workspace,
+                                    size_t workspace_bytes, void* stream) {
+    if (int rc = sp_check_dims("gpmpc_sparse_replace", D, M, n_targets)) return rc;
+    if (int rc = sp_check_rank_one("gpmpc_sparse_replace", M, ld_w, x_old_dev && y_old_dev && x_new_dev && y_new_dev && Z_dev && W_dev &&
+                                   lambdas_host && G_dev && r_dev && Binv_dev && Q_dev && alpha_dev && stats_dev && workspace))
+        return rc;
+    if (workspace_bytes < gpmpc_sparse_replace_workspace_bytes(M, n_targets)) return GPMPC_E_WORKSPACE;
+    hipStream_t s = (hipStream_t)stream;
+    double* vo = (double*)workspace; double* vn = vo + M; double* to = vn + M; double* sn = to + M; double* tn = sn + M;
+    double* uo = tn + M; double* un = uo + M;
+    double* T = (double*)((char*)workspace + gpmpc_align256(sizeof(double) * 7 * (size_t)M));
+    SparseHyp hyp;
+    sp_hyp(&hyp, D, lambdas_host, sigma_f, noise_var);
+    hipLaunchKernelGGL(k_sparse_rep_v, dim3(M, 2), dim3(256), 0, s, D, M, x_old_dev, x_new_dev, Z_dev, W_dev, ld_w, hyp, vo, vn);
+    hipLaunchKernelGGL(k_sparse_rep_t, dim3(M), dim3(256), 0, s, M, (const double*)Binv_dev, (const double*)vo, (const double*)vn, to, sn);
+    hipLaunchKernelGGL(k_sparse_rep_u, dim3(M), dim3(256), 0, s, M, W_dev, ld_w, (const double*)vo, (const double*)vn, (const double*)to,
+                       (const double*)sn, hyp.kappa, tn, uo, un);
+    hipLaunchKernelGGL(k_sparse_rep_fill, dim3((M + 255) / 256, M), dim3(256), 0, s, M, n_targets, (const double*)vo, (const double*)vn,
+                       (const double*)to, (const double*)tn, (const double*)uo, (const double*)un, y_old_dev, y_new_dev, hyp.kappa, G_dev,
+                       r_dev, Binv_dev, Q_dev, stats_dev);
     hipLaunchKernelGGL(k_sparse_t, dim3(M), dim3(256), 0, s, M, n_targets, (const double*)Binv_dev, (const double*)r_dev, T);
     hipLaunchKernelGGL(k_sparse_alpha, dim3(M), dim3(256), 0, s, M, n_targets, W_dev, ld_w, (const double*)T, alpha_dev);
     GPMPC_HIP(hipGetLastError());

@@ -151,13 +151,15 @@ class RiskSensitiveMPC:
         return sched
 
     # -- sparse GP dynamics (extension; sparse.py)
-    def use_inducing_points(self, Z, jitter=None, keep_data=True):
+    def use_inducing_points(self, Z, jitter=None, keep_data=True, window=None):
         """Replace ``self.dynamics`` by a :class:`SparseDynamics` on the inducing points Z (M, state_dim + input_dim): FITC sparse GPs whose
         rollout cost depends on M, not on the number of observations.  The hyper-parameters, nominal models and noise model of the
-        current dynamics are taken over; its training data is not (feed the new object).  Returns the new dynamics."""
+        current dynamics are taken over; its training data is not (feed the new object).  ``window``: the model holds the newest
+        ``window`` observations only (``SparseDynamics(window=...)``).  Returns the new dynamics."""
         from .sparse import SparseDynamics
         old = self.dynamics
-        new = SparseDynamics(self.state_dim, self.input_dim, Z, nominal_models=old.nominal_models, jitter=jitter, keep_data=keep_data)
+        new = SparseDynamics(self.state_dim, self.input_dim, Z, nominal_models=old.nominal_models, jitter=jitter, keep_data=keep_data,
+                             window=window)
         for g_new, g_old in zip(new.gpr_err, old.gpr_err):
             g_new.log_lambdas, g_new.log_sigma_f, g_new.log_sigma_n = g_old.log_lambdas, g_old.log_sigma_f, g_old.log_sigma_n
         nm = getattr(old, "_noise", None)

@@ -12,8 +12,8 @@ Everything that touches N is HIP (csrc/sparse.hip).  torch is plumbing, as ``tor
 factor of Kmm, its triangular inverse, the inverse of B and the elementwise residual targets of a linear nominal model.
 
 Out of scope: FITC marginal-likelihood training (train the hyper-parameters on a dense subset with ``update_hyperparams`` and set
-them here), VFE / DTC variants, moving the inducing points along the previous plan, removing observations, a different ``Z`` per GP,
-multi-GPU broadcast of the update.
+them here), VFE / DTC variants, moving the inducing points along the previous plan, a different ``Z`` per GP, multi-GPU broadcast of
+the update.
 """
 import ctypes
 
@@ -69,7 +69,9 @@ class SparseGPState(object):
     ``append(x, y)`` is the O(M^2) rank-one update of one observation and ``refresh()`` recomputes Binv from G by a fresh inverse and
     then alpha and Q: O(M^3) and NO pass over the data.  Every ``refresh_every`` appends (64, the figure of the dense incremental path)
     a refresh bounds the round-off of the rank-one updates.  ``fit``, ``add`` and ``refresh`` synchronise and raise if min Lambda_n is
-    not positive and finite; ``append`` never synchronises."""
+    not positive and finite; ``append`` never synchronises.  ``remove(x, y)`` and ``replace(x_old, y_old, x_new, y_new)`` are the
+    O(M^2) steps of a fixed-size window (each one rank-one step towards ``refresh_every``); ``rebase(X, Y)`` re-accumulates G and r
+    over the rows held, which is what bounds the round-off of a long chain of replacements."""
 
     def __init__(self, Z, lambdas, sigma_f, sigma_n, jitter=None, chunk=0, device=None, noise_var=None):
         self.device = device if device is not None else require_gpu()
@@ -119,12 +121,13 @@ class SparseGPState(object):
         self.stats = torch.tensor([0.0, float("inf")], dtype=torch.float64, device=self.device)
         self._appends = 0
 
-    def _accumulate(self, X, Y, accumulate):
+    def _accumulate(self, X, Y, accumulate, keep=False):
+        """``keep``: overwrite (``accumulate = 0``) into the tensors the state holds instead of fresh ones."""
         X, Y = _dev(X, self.device).reshape(-1, self.D), _dev(Y, self.device)
         Y = Y.reshape(X.shape[0], -1)
         if accumulate and self.n_targets is None:
             accumulate = 0
-        if not accumulate:
+        if not accumulate and not keep:
             self.n_targets = None
         if self.n_targets is None:
             self._alloc(Y.shape[1])
@@ -189,10 +192,53 @@ class SparseGPState(object):
                                             host_doubles(self.lambdas)[1], self.sigma_f, self.noise_var, ptr(self.G), ptr(self.r), ptr(self.Binv),
                                             ptr(self.Q), ptr(self.alpha), ptr(self.stats), ctypes.c_void_p(ws.data_ptr()), nb, stream_ptr()),
                   "gpmpc_sparse_append")
+        self._stepped()
+        return self
+
+    def _stepped(self):
+        """One rank-one step (append, remove or replace) towards the periodic refresh."""
         self._appends += 1
         if self.refresh_every and self._appends >= self.refresh_every:
             self.refresh(check_lambda=False)
+
+    def _rank_one(self, name, rows):
+        """gpmpc_sparse_remove / _replace on device rows [(x, y), ...]; does not synchronise."""
+        if self.n_targets is None:
+            raise RuntimeError("no data: call fit first")
+        ptrs = []
+        for x, y in rows:
+            x, y = _dev(x, self.device).reshape(-1), _dev(y, self.device).reshape(-1)
+            if x.shape[0] != self.D or y.shape[0] != self.n_targets:
+                raise ValueError("%s takes x (%d,) and y (%d,)" % (name, self.D, self.n_targets))
+            ptrs += [x, y]
+        fn = "gpmpc_sparse_" + name
+        nb = getattr(lib(), fn + "_workspace_bytes")(self.M, self.n_targets)
+        ws = self._workspace(name[:3], nb)
+        with torch.cuda.device(self.device):
+            check(getattr(lib(), fn)(self.D, self.M, self.n_targets, *[ptr(t) for t in ptrs], ptr(self.Z), ptr(self.W), self.M,
+                                     host_doubles(self.lambdas)[1], self.sigma_f, self.noise_var, ptr(self.G), ptr(self.r), ptr(self.Binv),
+                                     ptr(self.Q), ptr(self.alpha), ptr(self.stats), ctypes.c_void_p(ws.data_ptr()), nb, stream_ptr()), fn)
+        self._stepped()
         return self
+
+    def remove(self, x, y):
+        """Take out one observation the state holds (the inverse of ``append``, O(M^2), in place, no synchronisation).  Afterwards
+        ``min_lambda`` is a lower bound on the Lambda of the rows held, not their minimum; ``rebase`` restores it."""
+        return self._rank_one("remove", [(x, y)])
+
+    def replace(self, x_old, y_old, x_new, y_new):
+        """``remove(x_old, y_old)`` and ``append(x_new, y_new)`` in one pass over G, Binv and Q (the step of a full window); counts as
+        ONE rank-one step towards ``refresh_every``.  Does not synchronise."""
+        return self._rank_one("replace", [(x_old, y_old), (x_new, y_new)])
+
+    def rebase(self, X, Y):
+        """Re-accumulate G, r and the stats over the rows X (N, D), Y (N, n_targets) the state is meant to hold, into the tensors it
+        has (no reallocation), then ``refresh(check_lambda=False)``: what a chain of replacements has drifted by is gone (a fresh
+        inverse alone does not remove it: the drift sits in G and r).  Bit for bit what ``fit`` gives on the same rows in the same order."""
+        if self.n_targets is None:
+            raise RuntimeError("no data: call fit first")
+        self._accumulate(X, Y, 0, keep=True)
+        return self.refresh(check_lambda=False)
 
     @property
     def num_obs(self):
@@ -232,9 +278,17 @@ class SparseDynamics(Dynamics):
     update: M is constant, so a closed loop keeps one pack handle and one captured callback graph.  Linear nominal models are
     supported (the accumulators see the residual targets, the pack gets the model); other callables are refused.  The observations
     are kept in capacity-doubling device buffers (``keep_data``) so that ``set_inducing`` and hyper-parameter changes can refit; with
-    ``keep_data=False`` those raise.  ``max_train`` and ``async_rebuild=True`` raise ``ValueError``: a window makes no sense here."""
+    ``keep_data=False`` those raise.  ``max_train`` and ``async_rebuild=True`` raise ``ValueError``.
 
-    def __init__(self, state_dim, action_dim, inducing, nominal_models=None, jitter=None, keep_data=True, chunk=0):
+    ``window`` (an int >= 1; needs ``keep_data``) makes the model forget: the observations live in a ring of exactly ``window`` rows,
+    and once it is full a single observation REPLACES the oldest one (``window_slot``) in every hyper-parameter group by the O(M^2)
+    rank-one replacement, the old row read from the ring on the device.  A bulk call that would overflow the window keeps the newest
+    ``window`` rows in chronological order, refits and resets the slot to 0 (the rule of ``Dynamics._trim_to_window``).  After
+    ``rebase_every`` replacements (default ``window``: the amortised cost per step stays O(M^2); 0: never) G and r are re-accumulated
+    from the ring, which bounds the round-off of the chain.  M, the pack handle and the captured callback graph
+    stay what they were."""
+
+    def __init__(self, state_dim, action_dim, inducing, nominal_models=None, jitter=None, keep_data=True, chunk=0, window=None):
         if nominal_models is not None and stack_linear(nominal_models, state_dim, action_dim) is None:
             raise ValueError("SparseDynamics supports LinearNominalModel nominal models only (one per state dimension)")
         Z = _check_inducing(inducing, state_dim + action_dim)
@@ -242,6 +296,11 @@ class SparseDynamics(Dynamics):
             raise ValueError("chunk must be 0 (default) or a positive multiple of 64, got %r" % (chunk,))
         if jitter is not None and not (np.isfinite(jitter) and jitter >= 0):
             raise ValueError("jitter must be finite and non-negative, got %r" % (jitter,))
+        if window is not None:
+            if isinstance(window, bool) or not isinstance(window, (int, np.integer)) or window < 1:
+                raise ValueError("window must be an int >= 1 or None, got %r" % (window,))
+            if not keep_data:
+                raise ValueError("window needs the observations it forgets: SparseDynamics(keep_data=True)")
         super().__init__(state_dim, action_dim, nominal_models)       # (argument errors come first: this needs the device)
         self.D = state_dim + action_dim
         self._Z = Z
@@ -255,6 +314,10 @@ class SparseDynamics(Dynamics):
         self._data_version = 0
         self._z_version = 0
         self._row = None                                 # pinned staging row of one observation
+        self._window = None if window is None else int(window)
+        self.window_slot = 0                             # ring row the next replacement overwrites (the oldest observation)
+        self.rebase_every = 0 if window is None else int(window)
+        self._replacements = 0                           # since the last accumulation from the ring
 
     # -- refused settings ----------------------------------------------------------------------
     @property
@@ -265,6 +328,10 @@ class SparseDynamics(Dynamics):
     def max_train(self, value):
         if value is not None:
             raise ValueError("max_train (fixed-size window) is not supported by SparseDynamics: the inducing points bound the cost")
+
+    @property
+    def window(self):
+        return self._window
 
     @property
     def M(self):
@@ -325,19 +392,30 @@ class SparseDynamics(Dynamics):
             groups.append((cols, st))
         self._groups, self._group_key = groups, key
         if self.num_train:
-            X, Y = self._Xbuf[:self.num_train], self._Ybuf[:self.num_train]
+            X, Y = self._rows()
             R = self._residual(X, Y)
             for cols, st in groups:
                 st.fit(X, R[:, cols].contiguous())
+            self._replacements = 0
         self._data_version += 1
         return groups
 
     # -- data ------------------------------------------------------------------------------------
+    def _rows(self):
+        """The observations held, oldest first (views of the buffers; copies when the ring has wrapped)."""
+        n, s = self.num_train, self.window_slot
+        if s == 0:
+            return self._Xbuf[:n], self._Ybuf[:n]
+        return torch.cat((self._Xbuf[s:n], self._Xbuf[:s])), torch.cat((self._Ybuf[s:n], self._Ybuf[:s]))
+
     def _store(self, X, Y):
         n, k = self.num_train, X.shape[0]
         if not self.keep_data:
             self.num_train = n + k
             return
+        if self._window is not None and self._Xbuf is None:     # the ring: exactly `window` rows, once
+            self._Xbuf = torch.empty((self._window, self.D), dtype=torch.float64, device=self.device)
+            self._Ybuf = torch.empty((self._window, self.state_dim), dtype=torch.float64, device=self.device)
         cap = 0 if self._Xbuf is None else self._Xbuf.shape[0]
         if n + k > cap:
             new = max(256, cap)
@@ -376,6 +454,12 @@ class SparseDynamics(Dynamics):
         groups = self._ensure_groups()                   # (before the new rows are stored: a refit must not see them twice)
         xy = torch.as_tensor(np.concatenate((x, y), axis=1), device=self.device)      # one host-to-device copy
         X, Y = xy[:, :self.D].contiguous(), xy[:, self.D:].contiguous()
+        if self._window is not None and self.num_train + X.shape[0] > self._window:
+            self._window_update(groups, X, Y, single)
+            for g in self.gpr_err:
+                g.num_train = self.num_train
+            self._data_version += 1
+            return
         self._store(X, Y)
         R = self._residual(X, Y)
         for cols, st in groups:
@@ -389,6 +473,42 @@ class SparseDynamics(Dynamics):
         for g in self.gpr_err:
             g.num_train = self.num_train
         self._data_version += 1
+
+    def _window_update(self, groups, X, Y, single):
+        """Rows that do not fit the window any more.  ONE observation into a full window: the rank-one replacement of the oldest row
+        in every group, then the ring row is overwritten (in stream order: the replacement has read it) and the slot advances.  Anything
+        else: the newest `window` rows, oldest first, become the ring and every group is refitted."""
+        w = self._window
+        if single and self.num_train == w:
+            s = self.window_slot
+            xo, yo = self._Xbuf[s:s + 1], self._Ybuf[s:s + 1]
+            Ro, Rn = self._residual(xo, yo), self._residual(X, Y)
+            for cols, st in groups:
+                st.replace(xo[0], Ro[0, cols].contiguous(), X[0], Rn[0, cols].contiguous())
+            self._Xbuf[s].copy_(X[0])
+            self._Ybuf[s].copy_(Y[0])
+            self.window_slot = (s + 1) % w
+            self._replacements += 1
+            if self.rebase_every and self._replacements >= self.rebase_every:
+                Xw, Yw = self._rows()
+                Rw = self._residual(Xw, Yw)
+                for cols, st in groups:
+                    st.rebase(Xw, Rw[:, cols].contiguous())
+                self._replacements = 0
+            return
+        if self.num_train:
+            Xo, Yo = self._rows()
+            X, Y = torch.cat((Xo, X)), torch.cat((Yo, Y))
+        X, Y = X[-w:].contiguous(), Y[-w:].contiguous()
+        if self._Xbuf is None:
+            self.num_train = 0
+            self._store(X[:0], Y[:0])
+        self._Xbuf.copy_(X)
+        self._Ybuf.copy_(Y)
+        self.num_train, self.window_slot, self._replacements = w, 0, 0
+        R = self._residual(X, Y)
+        for cols, st in groups:
+            st.fit(X, R[:, cols].contiguous())
 
     # -- device pack -------------------------------------------------------------------------------
     def _key(self):

@@ -787,6 +787,21 @@ int gpmpc_ml_grad(int n, int D, const double* X_dev, const double* Ky_inv_dev, c
  *     G += v v^T / Lambda; r += v y^T / Lambda; Binv -= t t^T / den; Q += u u^T / den; alpha = W^T (Binv r); stats += {1, min}
  *   in place.  Six dependent launches (v | t | u | the M x M streams and r | Binv r | alpha), no allocation, no host round trip; G, Binv
  *   and Q stay exactly symmetric.
+ * gpmpc_sparse_remove: the inverse of the append for ONE observation x_old dev [D], y_old dev [n_targets] that the state holds:
+ *     v = W k(Z, x); Lambda = sigma_f^2 + noise_var - |v|^2; t = Binv v; den = Lambda - v . t; u = W^T t
+ *     G -= v v^T / Lambda; r -= v y^T / Lambda; Binv += t t^T / den; Q -= u u^T / den; alpha = W^T (Binv r); stats[0] -= 1
+ *   in place, six dependent launches like the append and under the same rules.  den is a cancelling difference (den / Lambda is small
+ *   for a row that carries much of what the state knows); nothing is clamped: a NaN or non-positive den is passed on.  stats[1] is left
+ *   alone: after a removal it is a LOWER BOUND on the Lambda of the rows held, no longer their minimum (a fresh accumulate restores it).
+ *   Removing a row the state does not hold is not detected.  The workspace is the append's.
+ * gpmpc_sparse_replace: x_old, y_old out and x_new, y_new in, in ONE pass over G, Binv and Q (the step of a full window).  The removed
+ *   state is never formed: with t_o = Binv v_o, s_n = Binv v_n, den_o = Lambda_o - v_o . t_o,
+ *     t_n = s_n + t_o (t_o . v_n) / den_o;  den_n = Lambda_n + v_n . t_n;  u_o = W^T t_o;  u_n = W^T t_n
+ *     G = (G - v_o v_o^T / Lambda_o) + v_n v_n^T / Lambda_n;  r likewise;  Binv = (Binv + t_o t_o^T / den_o) - t_n t_n^T / den_n
+ *     Q = (Q - u_o u_o^T / den_o) + u_n u_n^T / den_n;  alpha = W^T (Binv r);  stats[0] unchanged;  stats[1] = min(stats[1], Lambda_n)
+ *   (the NaN-propagating minimum).  Six dependent launches: v_o, v_n | t_o, s_n | t_n, u_o, u_n | the M x M streams, r, stats | Binv r |
+ *   alpha.  G and r equal gpmpc_sparse_remove followed by gpmpc_sparse_append BIT FOR BIT; Binv, Q and alpha agree with the two calls
+ *   to rounding.  G, Binv and Q stay exactly symmetric.  Workspace: 7 M + M n_targets doubles (each part 256-byte aligned).
  * ------------------------------------------------------------------------- */
 #define GPMPC_SPARSE_MAX_M 8192
 #define GPMPC_SPARSE_FORM_FMA  0
@@ -806,6 +821,16 @@ int gpmpc_sparse_append(int D, int M, int n_targets, const double* x_new_dev, co
                         const double* W_dev, size_t ld_w, const double* lambdas_host, double sigma_f, double noise_var,
                         double* G_dev, double* r_dev, double* Binv_dev, double* Q_dev, double* alpha_dev, double* stats_dev,
                         void* workspace, size_t workspace_bytes, void* stream);
+size_t gpmpc_sparse_remove_workspace_bytes(int M, int n_targets);
+int gpmpc_sparse_remove(int D, int M, int n_targets, const double* x_old_dev, const double* y_old_dev, const double* Z_dev,
+                        const double* W_dev, size_t ld_w, const double* lambdas_host, double sigma_f, double noise_var,
+                        double* G_dev, double* r_dev, double* Binv_dev, double* Q_dev, double* alpha_dev, double* stats_dev,
+                        void* workspace, size_t workspace_bytes, void* stream);
+size_t gpmpc_sparse_replace_workspace_bytes(int M, int n_targets);
+int gpmpc_sparse_replace(int D, int M, int n_targets, const double* x_old_dev, const double* y_old_dev, const double* x_new_dev,
+                         const double* y_new_dev, const double* Z_dev, const double* W_dev, size_t ld_w, const double* lambdas_host,
+                         double sigma_f, double noise_var, double* G_dev, double* r_dev, double* Binv_dev, double* Q_dev,
+                         double* alpha_dev, double* stats_dev, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------
  * Particles: the pointwise posterior of all GPs at many points, and Monte-Carlo rollouts through it (the device counterpart of the
