@@ -16,6 +16,10 @@ int gpmpc_launch_pair_sbs(int D, bool grad, int ng, int ns2, const PairSbsArgs& 
     return gpmpc_dispatch_dim<2>(D, [&](auto d) { return gpmpc_launch_pair_sbs_D<decltype(d)::value>(grad, ng, ns2, a, s); });
 }
 
+int gpmpc_launch_pair_q1(int D, int da, const PairQ1Args& a, hipStream_t s) {
+    return gpmpc_dispatch_dim<2>(D, [&](auto d) { return gpmpc_launch_pair_q1_D<decltype(d)::value>(da, a, s); });
+}
+
 int gpmpc_launch_pair_sbf(int D, bool grad, int ns2, int waves, const PairSbfArgs& a, hipStream_t s) {
     if (waves < 1 || waves > 4) return GPMPC_E_ARG;
     return gpmpc_dispatch_dim<1>(D, [&](auto d) { return gpmpc_launch_pair_sbf_D<decltype(d)::value>(grad, ns2, waves, a, s); });

@@ -64,6 +64,8 @@ struct gpmpc_tuning {
     int fc_shared;   // GPMPC_FC_SHARED   full-covariance rollout with one lambda for all GPs: cross units through pair_kernel_sbfx.h 0 off | 1 wherever it can run | -1 unset (by the size of the launch)
     int xcdmap;      // GPMPC_XCDMAP      XCD-aware dispatch order of the one-launch form for several trajectories (step_fused.h): 0 off | 1 on | -1 unset (by the size of the launch)
     int persist;     // GPMPC_PERSIST     whole-horizon kernel, one workgroup per trajectory (traj_persist.h): 0 off | 8 / 16 on with that many waves | -1 unset
+    int step1_quad;  // GPMPC_STEP1_QUAD  horizon step 1 of the two-launch scalar-broadcast form as a quadratic form (pair_kernel_q1.h): 0 off | 1 wherever it can run | -1 unset (by the batch size)
+    int step1_t;     // GPMPC_STEP1_T     trajectories per workgroup of that kernel: 8 | 16 | 0 unset (8)
 };
 void gpmpc_read_tuning(gpmpc_tuning* t);
 
@@ -126,6 +128,16 @@ struct gpmpc_pack {
     // and no kernel instance or plan does either: a set drops nothing.
     double* noise_dev;         // [ds * ds + da + ds]
     double noise_host[GPMPC_NOISE_MAX];
+    // Step-1 weights of the variance units (pair_kernel_q1.h), in the layout of M: M1_ij = M_ij exp(+sum_k sc_k^2 (x_ik - x_jk)^2) with the scales
+    // sc_k of horizon step 1, which depend on lambda and on the pack's noise model only.  Allocated (one allocation, ds Np^2 doubles) and filled by the
+    // first gpmpc_rollout whose plan takes that path (gpmpc_pack_step1_refresh, pack_build.hip); every build and every gpmpc_pack_set_noise marks it
+    // stale, and the next such call refills it in stream order before it launches or replays anything.
+    // The fill runs on the stream of the call that found it missing or stale and is followed by m1_event there: every later call that takes
+    // the path waits for that event on its own stream first, so rollouts stay re-entrant across streams (include/gpmpc.h).
+    // m1_failed: the allocation failed since the last build -- such a pack keeps the FIRST variant and does not try again until the next build.
+    double* M1;
+    int m1_stale, m1_failed;
+    void* m1_event;            // hipEvent_t, created with M1, recorded behind every fill
 };
 
 // Number of pair-kernel output moments per (trajectory, GP, tile).
@@ -164,6 +176,29 @@ struct PairSbArgs {
 static inline int gpmpc_sb_gw(int D, int ns2) { return (D + 1 + ns2 + 1) & ~1; }
 int gpmpc_launch_pair_sb(int D, bool grad, int tb, int ns2, int waves, const PairSbArgs& a, hipStream_t s);
 template <int D> int gpmpc_launch_pair_sb_D(bool grad, int tb, int ns2, int waves, const PairSbArgs& a, hipStream_t s);
+
+// Arguments of the horizon-step-1 kernel (pair_kernel_q1.h): variance units, diagonal S, the scales of step 1 folded into the weights.
+struct PairQ1Args {
+    const double* M1;     // [ds][Np][Np] step-1 weights (gpmpc_pack::M1)
+    const double* XT;     // [D][Np]
+    const double* pp;     // [B][ds][pps]: cvec[D] = sc o u, sc[D]
+    const double* cols;   // [ds][Np][B][1 + da] column values [kappa_j | kappa_j h_jk (k >= ds)] written by the head kernel of step 1
+    double* part;         // [B][nwork][nm]
+    const int* work;      // [nwork][4] = {unit, i0, j0, j1}
+    int Np, B, ds, nwork, pps, nm;
+    int rgroup;           // as PairSbArgs
+    int tblock;           // trajectories per workgroup: 8 | 16
+    const int* ncol;      // as PairSbArgs
+};
+// the shapes the step-1 kernel is instantiated for
+static inline bool gpmpc_q1_shape(int ds, int da) { return da >= 1 && da <= 2 && ds >= 1; }
+int gpmpc_launch_pair_q1(int D, int da, const PairQ1Args& a, hipStream_t s);
+template <int D> int gpmpc_launch_pair_q1_D(int da, const PairQ1Args& a, hipStream_t s);
+// pack_build.hip: allocate (first use) and fill the step-1 weights on s if they are missing or stale, and order s behind a fill that ran on another
+// stream.  Host state of the pack: the caller holds the pack's lock.  GPMPC_OK: a step-1 kernel enqueued on s now reads current weights;
+// GPMPC_E_ALLOC: the pack has no step-1 weights (allocation failed now or earlier since the last build; nothing else changed) -- the caller
+// keeps the FIRST variant; GPMPC_E_LAUNCH.
+int gpmpc_pack_step1_refresh(gpmpc_pack* p, hipStream_t s);
 
 // Arguments of the general scalar-broadcast pair kernel (pair_kernel_sbf.h): full S, variance + cross units.
 struct PairSbfArgs {

@@ -339,7 +339,21 @@ extern "C" int gpmpc_rollout(const gpmpc_pack* p, int B, int H, const double* x0
     }
     const bool graph = (flags & GPMPC_USE_GRAPH) && !gpmpc_timing_on();
     GraphModeGuard mode(graph ? 1 : 0);
-    const RollCall c{p, B, H, x0, U, cost, flags, out_means, out_vars, out_cost, out_grad, workspace, workspace_bytes, (hipStream_t)stream};
+    RollCall c{p, B, H, x0, U, cost, flags, out_means, out_vars, out_cost, out_grad, workspace, workspace_bytes, (hipStream_t)stream};
+    if (p->built && x0 && U && out_cost && workspace && B >= 1 && H >= 1) {
+        // Horizon step 1 as a quadratic form (pair_kernel_q1.h), decided HERE for the whole call: its weights are allocated on first use and
+        // refilled when a build or gpmpc_pack_set_noise has made them stale -- on the caller's stream, ahead of every launch and of every replay
+        // of a graph that was captured with the kernel in it (a replay reads the same buffer; neither event drops a captured graph).  A call on
+        // another stream than the one that filled them waits there for the fill's event: rollouts stay re-entrant across streams.
+        const bool lowprec = (flags & (GPMPC_FP32_ACCUM | GPMPC_FP32_ALL)) != 0;
+        const RollShape whole = gpmpc_choose_shape(p, B, H, (flags & GPMPC_WANT_GRAD) != 0, lowprec);
+        if (gpmpc_step1_quad_plan(p, whole, B, lowprec)) {
+            PackGuard lock(p);
+            const int rc1 = gpmpc_pack_step1_refresh(const_cast<gpmpc_pack*>(p), (hipStream_t)stream);
+            if (rc1 != GPMPC_OK && rc1 != GPMPC_E_ALLOC) return rc1;
+            c.step1_quad = rc1 == GPMPC_OK;                 // (no memory for the weights: the FIRST variant, as before)
+        }
+    }
     if (graph && p->built && x0 && U && out_cost && workspace && B >= 1 && H >= 1) return graph_rollout(const_cast<gpmpc_pack*>(p), c);
     if (p->built && x0 && U && out_cost && workspace && B >= 4 && H >= 1 && !(flags & (GPMPC_FP32_ACCUM | GPMPC_FP32_ALL)) &&
         (!(flags & GPMPC_WANT_GRAD) || out_grad)) {

@@ -79,6 +79,8 @@ void gpmpc_read_tuning(gpmpc_tuning* t) {
     t->fc_tiling = geti("GPMPC_FC_TILING", -1);
     t->fc_rsplit = geti("GPMPC_FC_RSPLIT", 0);
     t->fc_cu = geti("GPMPC_FC_CU", 0);
+    t->step1_quad = geti("GPMPC_STEP1_QUAD", -1);
+    t->step1_t = geti("GPMPC_STEP1_T", 0);
 }
 
 extern "C" int gpmpc_pack_reload_tuning(gpmpc_pack* p) {
@@ -128,17 +130,19 @@ struct IndexImage {
 // Every device buffer a pack owns: the ONE table that creation allocates from and destruction frees by.  bytes 0: allocated on first use
 // (gpmpc_pack_set_nominal; the first build or enable_fullcov that serves the one-lambda full-covariance form, pack_build.hip).
 struct PackBuffer { void** ptr; size_t bytes; const char* name; };
-static std::array<PackBuffer, 11> pack_buffers(gpmpc_pack* p, size_t index_ints = 0) {
+static std::array<PackBuffer, 12> pack_buffers(gpmpc_pack* p, size_t index_ints = 0) {
     const size_t Np = p->Np, ds = p->ds, D = p->D, dbl = sizeof(double);
     return {{{(void**)&p->X, dbl * Np * D, "X"}, {(void**)&p->XT, dbl * Np * D, "XT"}, {(void**)&p->beta, dbl * Np * ds, "beta"},
              {(void**)&p->M, dbl * Np * Np * ds, "the weight matrices"}, {(void**)&p->lam, dbl * ds * D, "lambda"}, {(void**)&p->sf, dbl * ds, "sigma_f"},
              {(void**)&p->noise_dev, dbl * GPMPC_NOISE_MAX, "the noise model"}, {(void**)&p->index_dev, sizeof(int) * index_ints, "the index data"},
-             {(void**)&p->nom_dev, 0, "the nominal model"}, {(void**)&p->resid_dev, 0, "the residual targets"}, {(void**)&p->fcs_rows, 0, "the one-lambda column rows"}}};
+             {(void**)&p->nom_dev, 0, "the nominal model"}, {(void**)&p->resid_dev, 0, "the residual targets"}, {(void**)&p->fcs_rows, 0, "the one-lambda column rows"},
+             {(void**)&p->M1, 0, "the step-1 weights"}}};
 }
 
 extern "C" int gpmpc_pack_destroy(gpmpc_pack* p) {
     if (!p) return GPMPC_OK;
     for (const PackBuffer& b : pack_buffers(p)) if (*b.ptr) (void)hipFree(*b.ptr);
+    if (p->m1_event) (void)hipEventDestroy((hipEvent_t)p->m1_event);
     gpmpc_graph_cache_free(p->graph_cache);
     gpmpc_cb_cache_free(p->cb_cache);
     gpmpc_tuned_free(p->tuned);
@@ -348,12 +352,14 @@ extern "C" int gpmpc_pack_set_noise(gpmpc_pack* p, const double* init_cov_host, 
     if (int rc_dev = gpmpc_check_device(p)) return rc_dev;
     // (pieces of 64 doubles: what one upload carries; ds^2 + da + ds <= 80)
     // (the host mirror follows piece by piece: should a launch fail -- a HIP error, not a refusal --, it still says what the device holds)
+    p->m1_stale = 1;
     for (int o = 0; o < n; o += 64) {
         const int m = n - o < 64 ? n - o : 64;
         if (int rcu = gpmpc_upload_small(p->noise_dev + o, img + o, sizeof(double) * m, (hipStream_t)stream)) return rcu;
         memcpy(p->noise_host + o, img + o, sizeof(double) * m);
     }
     // nothing is dropped: no kernel instance, plan or captured launch depends on the values (the kernels read them from device memory)
+    // (the step-1 weights carry the scales of step 1: marked stale above, refilled by the next call that uses them)
     return GPMPC_OK;
 }
 

@@ -79,6 +79,65 @@ __global__ __launch_bounds__(256) void k_pack_weights(const double* __restrict__
     }
 }
 
+// Step-1 weights (pair_kernel_q1.h).  At horizon step 1 the input variances s_k are those of the pack's noise model, so the scales of the pair
+// transform, sc_k^2 = 1/8 / (lambda_k / 2 + s_k), are constants of the pack, and
+//   M_ij exp(-|h_i + h_j|^2) = M1_ij kappa_i kappa_j,   kappa_i = exp(-2 |h_i|^2),   M1_ij = M_ij exp(+sum_k sc_k^2 (x_ik - x_jk)^2)
+// (|h_i + h_j|^2 = 2 |h_i|^2 + 2 |h_j|^2 - |h_i - h_j|^2, and h_i - h_j = sc o (x_j - x_i) does not depend on the trajectory).  With M's own factor
+// exp(-1/4 sum_k d_k^2 / lambda_k) that leaves M1_ij = bracket_ij exp(-sum_k d_k^2 s_k / (2 lambda_k (lambda_k + 2 s_k))): no decay with the distance
+// when s is small.  The bracket needs Ky_inv, which a pack does not keep, and M1 has to follow a gpmpc_pack_set_noise that brings none: so M1 is
+// formed from M.  What that costs: an entry whose M_ij has underflowed (1/4 sum d^2 / lambda > ~690) is dropped although M1_ij itself would be of
+// the bracket's size -- its term M1_ij kappa_i kappa_j <= |M_ij| < 1e-300 is far below anything the sum resolves --, and exp(e) is taken as
+// exp(e / 2)^2 so that no intermediate overflows while the product is finite.
+__global__ __launch_bounds__(256) void k_pack_weights1(const double* __restrict__ M, const double* __restrict__ XT, const double* __restrict__ lam,
+                                                        const double* __restrict__ noise, int Np, int D, int ds, double* __restrict__ M1) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x, j = blockIdx.y, a = blockIdx.z;
+    if (i >= Np) return;
+    const size_t at = ((size_t)a * Np + j) * Np + i;
+    const double m = M[at];
+    double out = 0.0;
+    if (i <= j && fabs(m) >= 0x1p-1000) {
+        double e = 0.0;
+        for (int k = 0; k < D; ++k) {
+            const double sk = k < ds ? noise[k * (ds + 1)] : noise[gpmpc_noise_off_action(ds) + (k - ds)];
+            const double d = XT[(size_t)k * Np + i] - XT[(size_t)k * Np + j];
+            e = fma(d * d, 0.125 / (0.5 * lam[a * D + k] + sk), e);
+        }
+        const double f = exp(0.5 * e);
+        out = (m * f) * f;
+    }
+    M1[at] = out;
+}
+
+int gpmpc_pack_step1_refresh(gpmpc_pack* p, hipStream_t s) {
+    if (!p || !p->built) return GPMPC_E_STATE;
+    if (p->M1 && !p->m1_stale) {
+        // current, or still being filled on whichever stream found it stale: behind the fill's event (a wait on the stream's own event is free)
+        GPMPC_HIP(hipStreamWaitEvent(s, (hipEvent_t)p->m1_event, 0));
+        return GPMPC_OK;
+    }
+    if (!p->M1) {                                            // weights and event: the pack has both or neither
+        if (p->m1_failed) return GPMPC_E_ALLOC;
+        double* m1 = nullptr; hipEvent_t ev = nullptr;
+        hipError_t e = hipMalloc(&m1, sizeof(double) * (size_t)p->Np * p->Np * p->ds);
+        if (e == hipSuccess) e = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
+        if (e != hipSuccess) {
+            if (m1) (void)hipFree(m1);
+            (void)hipGetLastError();                         // the call goes on with the FIRST variant: no sticky error left behind
+            gpmpc_set_error("gpmpc_rollout: step-1 weights not allocated, horizon step 1 keeps the pair kernel's FIRST variant", e);
+            p->m1_failed = 1;
+            return GPMPC_E_ALLOC;
+        }
+        p->M1 = m1; p->m1_event = ev;
+        p->m1_stale = 1;
+    }
+    hipLaunchKernelGGL(k_pack_weights1, dim3((p->Np + 255) / 256, p->Np, p->ds), dim3(256), 0, s, p->M, p->XT, p->lam, p->noise_dev, p->Np, p->D,
+                       p->ds, p->M1);
+    GPMPC_HIP(hipGetLastError());
+    GPMPC_HIP(hipEventRecord((hipEvent_t)p->m1_event, s));
+    p->m1_stale = 0;
+    return GPMPC_OK;
+}
+
 // Residual targets of a pack with a linear nominal model: R[i][a] = Y[i][a] - sum_k X[i][k] n_ak - c_a (the GPs learn the residual)
 __global__ void k_pack_residual(const double* __restrict__ X, const double* __restrict__ Y, const double* __restrict__ nom,
                                 int N, int D, int ds, double* __restrict__ R) {
@@ -201,6 +260,7 @@ static int pack_build_impl(gpmpc_pack* p, const double* X_dev, const double* Y_d
     for (int a = 1; a < p->ds && shared; ++a)
         if (memcmp(lambdas_host + a * p->D, lambdas_host, sizeof(double) * p->D) != 0) shared = 0;
     if (int rca = fcs_rows_alloc(p, shared)) return rca;     // the one allocation a build can need: before the pack is touched
+    p->m1_stale = 1; p->m1_failed = 0;                       // M, X, lambda and sigma_f change below: the step-1 weights follow on their next use
     for (int a = 0; a < p->ds; ++a) {
         p->sf_host[a] = sigma_f_host[a];
         for (int k = 0; k < p->D; ++k) p->lam_host[a][k] = lambdas_host[a * p->D + k];

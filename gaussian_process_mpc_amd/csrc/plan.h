@@ -34,6 +34,10 @@ RollLayout gpmpc_layout_for(const gpmpc_pack* p, const RollShape& r, int B, int 
 static inline const gpmpc_worklist& gpmpc_fused_shared_list(const gpmpc_pack* p, const RollShape& r) {
     return p->wl_sh[(r.fng == 2 && p->sh_ng != 2) ? 3 : 1];
 }
+// Horizon step 1 as a quadratic form (pair_kernel_q1.h) for a call of B trajectories whose launches are r: the two-launch scalar-broadcast form on
+// 256-row tiles of a pack with distinct lambdas, fp64, da in {1, 2} (with or without a nominal model: that is the head kernel's business), GPMPC_NO_FIRST unset; B from the measured threshold on, or whatever
+// the batch with GPMPC_STEP1_QUAD=1, never with =0.  B = 0 asks about the shape alone (the enqueue of a sub-batch: the whole call's B decided).
+bool gpmpc_step1_quad_plan(const gpmpc_pack* p, const RollShape& r, int B, bool lowprec);
 // equal as far as the LAUNCHES go (the autotuner's de-duplication)
 bool gpmpc_same_shape(const RollShape& a, const RollShape& b);
 

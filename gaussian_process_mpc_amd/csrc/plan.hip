@@ -285,6 +285,24 @@ RollShape gpmpc_choose_shape(const gpmpc_pack* p, int B, int H, bool grad, bool 
     return shape;
 }
 
+// Measured on one MI355X (profiles/step1_quad/threshold.txt; ms of the step-1 pair launch, FIRST variant | this kernel): wherever the plan is the
+// two-launch form the kernel is ahead -- N = 2048, ds = 4: B = 13 0.114 | 0.045, B = 32 0.171 | 0.052, B = 256 1.43 | 0.27; N = 1024: B = 64
+// 0.109 | 0.048; N = 4096, ds = 6: B = 8 0.48 | 0.11, B = 128 5.67 | 0.68 -- so the rule has no crossover of its own: from one full block of 8
+// trajectories, the smallest batch measured.  Blocks of 8 against 16 trajectories: 8 is ahead at every shape but one (N = 2048, B = 96 level).
+#define GPMPC_Q1_MIN_B 8
+bool gpmpc_step1_quad_plan(const gpmpc_pack* p, const RollShape& r, int B, bool lowprec) {
+    const int knob = p->tune.step1_quad;
+    if (knob == 0 || lowprec || p->tune.no_first) return false;
+    if (r.fused || !r.sb || r.shared || !gpmpc_q1_shape(p->ds, p->da)) return false;
+    // A pack with one lambda for all GPs reaches pair_kernel_sb.h only under GPMPC_SHARED=0, the A/B partner of the shared-lambda kernels: those
+    // round the exponent of a pair exactly as the FIRST variant does, and tests/test_gpu_offgrid.py holds the two forms to 1e-9 of each other on
+    // that ground (an agreement ten times tighter than either form's distance from the long double step).  This kernel rounds differently -- as
+    // accurately, profiles/step1_quad/accuracy.txt -- so such a pack keeps the FIRST variant.
+    if (p->shared_lambda) return false;
+    if (p->wl[0][r.tiling].it != 256) return false;
+    return knob == 1 || B == 0 || B >= GPMPC_Q1_MIN_B;
+}
+
 RollLayout gpmpc_layout_for(const gpmpc_pack* p, const RollShape& r, int B, int H, bool grad) {
     const int D = p->D;
     RollLayout L;
@@ -423,9 +441,10 @@ extern "C" int gpmpc_plan_describe(const gpmpc_pack* p, int B, int H, unsigned f
         wgs = (long)((B + r.tb - 1) / r.tb) * r.nwork;
     }
     const int tl = r.shared && r.fused != 2 ? (r.sh_list == 0 ? 0 : (r.sh_list == 1 ? 2 : 4)) : r.tiling;
-    snprintf(out, out_bytes, "form=%s kernel=%s tiling=%dx%d workgroups=%ld launches_per_step=%d split=%d tb=%d shared=%d hchunks=%d workspace=%zu%s",
+    // (step1=quad: what gpmpc_rollout launches at horizon step 1 for this shape; the other entry points keep the FIRST variant)
+    snprintf(out, out_bytes, "form=%s kernel=%s tiling=%dx%d workgroups=%ld launches_per_step=%d split=%d tb=%d shared=%d hchunks=%d workspace=%zu%s%s",
              form, kern, cfg[tl][0], cfg[tl][1], wgs, r.fused == 3 ? 0 : (r.fused ? 1 : 2), S, r.tb, r.shared, r.hchunks, gpmpc_layout_for(p, r, B, H, grad).total,
-             p->nominal ? " nominal=1" : "");
+             p->nominal ? " nominal=1" : "", gpmpc_step1_quad_plan(p, r, B, lowprec) ? " step1=quad" : "");
     return GPMPC_OK;
 }
 

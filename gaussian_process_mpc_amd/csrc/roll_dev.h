@@ -24,7 +24,8 @@ struct RollArgs {
     double* jac;   // [B][H][2ds][2ds+da] or null
     double* G;     // [B][ds][Np][gw] column rows of the scalar-broadcast pair kernel, or null
     int gw;
-    int shared;    // shared-lambda path: G is [B][Np][gw], written by the workgroups of GP 0 only (pair_kernel_sbs.h)
+    double* q1cols; // step-1 kernel (pair_kernel_q1.h): at t = 1 the head kernel writes [ds][Np][B][1 + da] column values HERE (inside the G region) and no G rows; else null
+    int shared;   // shared-lambda path: G is [B][Np][gw], written by the workgroups of GP 0 only (pair_kernel_sbs.h)
     int pps, sps, nwork, nm, grad;
     // Row chunks of the head kernel (small batches of a large N: B ds workgroups walking all N rows are the slowest thing in
     // the step).  hchunks > 1: workgroup (b, a, c) takes rows [c, c+1) * hrows; the O(N) mean sums of step t are left as

@@ -16,6 +16,8 @@ struct RollCall {
     bool full_first = false;            // horizon step 1 keeps the derivatives w.r.t. its state inputs (needed for d/dx0)
     const RollShape* shape = nullptr;   // the launches of a larger batch this one is a sub-batch of, or of a candidate of gpmpc_pack_autotune;
                                         // null: chosen by the enqueue
+    bool step1_quad = false;            // horizon step 1 through pair_kernel_q1.h: set by gpmpc_rollout alone, for the WHOLE call (its sub-batches inherit it), after
+                                        // it has brought the pack's step-1 weights up to date on the caller's stream (gpmpc_step1_quad_plan, plan.h)
 };
 int gpmpc_enqueue_rollout(const RollCall& c);                          // step.hip: validates, plans (unless c.shape), launches on c.stream
 
@@ -37,6 +39,7 @@ bool gpmpc_timing_on();
 int gpmpc_timed_pair(int D, bool diag, bool grad, int tb, int waves, const PairArgs& a, hipStream_t s);
 int gpmpc_timed_pair_sb(int D, bool grad, int tb, int ns2, int waves, const PairSbArgs& a, hipStream_t s);
 int gpmpc_timed_pair_sbs(int D, bool grad, int ng, int ns2, const PairSbsArgs& a, hipStream_t s);
+int gpmpc_timed_pair_q1(int D, int da, const PairQ1Args& a, hipStream_t s);
 int gpmpc_timed_pair_sbf(int D, bool grad, int ns2, int waves, const PairSbfArgs& a, hipStream_t s);
 int gpmpc_timed_persist(int D, bool grad, int ns2, int waves, int ng, const PersistArgs& a, hipStream_t s);
 int gpmpc_timed_step_fused(int D, bool grad, int ns2, int q, int ng, const FusedArgs& a, int t, hipStream_t s);

@@ -94,6 +94,10 @@ int gpmpc_timed_pair_sbs(int D, bool grad, int ng, int ns2, const PairSbsArgs& a
     return timed_launch(a.first_step ? GPMPC_TIME_FIRST : GPMPC_TIME_FULL, s,
                         [&] { return gpmpc_launch_pair_sbs(D, grad, ng, ns2, a, s); });
 }
+// (always horizon step 1: timed in the class of the FIRST variant it replaces)
+int gpmpc_timed_pair_q1(int D, int da, const PairQ1Args& a, hipStream_t s) {
+    return timed_launch(GPMPC_TIME_FIRST, s, [&] { return gpmpc_launch_pair_q1(D, da, a, s); });
+}
 int gpmpc_timed_pair_sbf(int D, bool grad, int ns2, int waves, const PairSbfArgs& a, hipStream_t s) {
     return timed_launch(GPMPC_TIME_FULL, s, [&] { return gpmpc_launch_pair_sbf(D, grad, ns2, waves, a, s); });
 }

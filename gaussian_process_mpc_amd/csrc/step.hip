@@ -85,8 +85,10 @@ __device__ static void prep_step(const RollArgs& A, int b, int t, int a, int chu
         sck[k] = s_sc[k];
         if (NOM == 2) wB[k] = s_wB[k];
     }
-    double* __restrict__ Grow = A.G ? (A.shared ? (a == 0 ? A.G + (size_t)b * A.Np * A.gw : nullptr)
-                                                : A.G + ((size_t)b * ds + a) * A.Np * A.gw) : nullptr;
+    // step 1 through pair_kernel_q1.h: the column values [kappa_j | kappa_j h_jk (k >= ds)] of this (trajectory, GP) instead of G rows
+    double* __restrict__ q1c = (A.q1cols && t == 1) ? A.q1cols + ((size_t)a * A.Np * A.B + b) * (1 + A.da) : nullptr;
+    double* __restrict__ Grow = (A.G && !q1c) ? (A.shared ? (a == 0 ? A.G + (size_t)b * A.Np * A.gw : nullptr)
+                                                          : A.G + ((size_t)b * ds + a) * A.Np * A.gw) : nullptr;
     double v[NV];
 #pragma unroll
     for (int m = 0; m < NV; ++m) v[m] = 0.0;
@@ -124,6 +126,16 @@ __device__ static void prep_step(const RollArgs& A, int b, int t, int a, int chu
                 const double pq = p * qn;
 #pragma unroll
                 for (int k = 0; k < D; ++k) { v[1 + 2 * D + k] = fma(pq, d[k], v[1 + 2 * D + k]); v[1 + 3 * D + k] = fma(pq * d[k], d[k], v[1 + 3 * D + k]); }
+            }
+            if (q1c) {     // h = sc o u - sc o x and |h|^2 as below and in the row side of pair_kernel_q1.h; library exp: O(N) work
+                double hk[D], qh = 0.0;
+#pragma unroll
+                for (int k = 0; k < D; ++k) { hk[k] = fma(-sck[k], xk[k], sck[k] * u[k]); qh = fma(hk[k], hk[k], qh); }
+                const double kap = exp(-2.0 * qh);
+                double* c = q1c + (size_t)i * A.B * (1 + A.da);
+                c[0] = kap;
+#pragma unroll
+                for (int k = 0; k < D; ++k) if (k >= ds) c[1 + k - ds] = kap * hk[k];
             }
             if (Grow) {    // column row of point i: [h (D) | |h|^2 | h_k^2 (k < ds) | pad], h = sc o u - sc o x as in the pair kernel
                 double* g = s_g + threadIdx.x * A.gw;
@@ -293,6 +305,15 @@ int gpmpc_enqueue_rollout(const RollCall& c) {
     A.nom = p->nominal ? p->nom_dev : nullptr;
     A.sched = sched.dev; A.sched_hmax = sched.H_max;
     A.noise = p->noise_dev;
+    // Horizon step 1 as a quadratic form (pair_kernel_q1.h): decided for the whole call by gpmpc_rollout, which has refilled the pack's step-1
+    // weights on this stream; not for d/dx0 (full_first), whose step 1 needs every moment.  The column values take the front of the G region.
+    const bool q1 = c.step1_quad && !c.full_first && p->M1 && gpmpc_step1_quad_plan(p, r, 0, lowprec != 0);
+    const int q1t = p->tune.step1_t == 16 ? 16 : 8;
+    if (q1) {
+        const size_t cols = (size_t)B * p->ds * p->Np * (1 + p->da), room = (size_t)B * p->ds * p->Np * L.gw;
+        if (cols + (size_t)q1t * (1 + p->da) > room) return GPMPC_E_WORKSPACE;      // (never: gw >= D + 2 > 1 + da, and Np >= 64)
+        A.q1cols = A.G;
+    }
     if (A.nom && (r.fused || r.hchunks > 1)) {     // (a plan handed in from outside: the nominal variants exist for the two-launch form only)
         gpmpc_set_error_text("gpmpc_rollout: plan without a nominal variant on a nominal pack");
         return GPMPC_E_STATE;
@@ -361,6 +382,13 @@ int gpmpc_enqueue_rollout(const RollCall& c) {
         if (rc != GPMPC_OK) return rc;
         if (lowprec) {
             rc = gpmpc_launch_pair_lowprec(p->D, lowprec, P, s);
+        } else if (q1 && t == 1) {
+            PairQ1Args Q;
+            Q.M1 = p->M1; Q.XT = p->XT; Q.pp = A.pp; Q.cols = A.q1cols; Q.part = A.part; Q.work = P.work;
+            Q.Np = p->Np; Q.B = B; Q.ds = p->ds; Q.nwork = r.nwork; Q.pps = L.pps; Q.nm = L.nm; Q.rgroup = r.rgroup;
+            Q.tblock = q1t;
+            Q.ncol = p->ncol_dev;
+            rc = gpmpc_timed_pair_q1(p->D, p->da, Q, s);
         } else if (r.shared) {
             const gpmpc_worklist& wl = p->wl_sh[r.sh_list];
             PairSbsArgs Q;

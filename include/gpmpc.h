@@ -22,7 +22,14 @@
  *    rollout, and what a pack OWNS -- its private streams / events (graph replay, the concurrent sub-batches of a mid-size
  *    batch), the captured graphs and the staging buffers of gpmpc_objective_gradient -- is guarded by a per-pack host lock
  *    (lazy creation, a stream capture from begin to end, a fork / join of a split launch, the callback entry are each one
- *    critical section).  Functions that MODIFY a pack (build, resize, enable_fullcov, reload_tuning, autotune, destroy) must
+ *    critical section).  ONE buffer of the pack is written by a rollout: the step-1 weights (ds x Np^2 doubles: 134 MB at N = 2048,
+ *    ds = 4; 805 MB at N = 4096, ds = 6) that gpmpc_rollout allocates the first time a call takes horizon step 1 as a quadratic
+ *    form (two-launch form, distinct lambdas, B >= 8, or GPMPC_STEP1_QUAD=1) and refills, on that call's stream, after a build
+ *    or gpmpc_pack_set_noise.  The fill is followed by an event that every such call on any stream waits for before it launches,
+ *    so the re-entrancy above holds; the build or set that made the weights stale must, as ever, be ordered before the rollouts
+ *    on every stream.  If the allocation fails, the call runs as it did without the weights (the pair kernel's own step-1
+ *    variant; no error is returned, gpmpc_last_error names the failed allocation) and is not retried until the next build.
+ *    Functions that MODIFY a pack (build, resize, enable_fullcov, reload_tuning, autotune, destroy) must
  *    not run concurrently with anything else on that pack.
  *    HOST arrays (hyper-parameters, cost parameters) are consumed before the call
  *    returns -- they travel as kernel arguments --: the caller may free or overwrite
