@@ -100,9 +100,13 @@ def main():
     ap.add_argument("--process-var", choices=("sigma_n",), default=None, help="sigma_n: add each GP's noise variance to its predicted variance")
     ap.add_argument("--inducing", type=int, default=None, metavar="M", help="sparse GP dynamics on M inducing points (FITC), chosen among the pre-training inputs")
     ap.add_argument("--inducing-select", choices=("farthest", "random"), default="farthest", help="how --inducing picks its points")
+    ap.add_argument("--propagation", choices=("moment_matching", "linearised"), default="moment_matching",
+                    help="linearised: first-order propagation mu' = m(z), var' = s2(z) + grad m^T S grad m (mpc.propagation); with the default solver, --starts K or --solver mppi")
     args = ap.parse_args()
     if args.window is not None and args.window < 1:
         ap.error("--window must be >= 1")
+    if args.propagation == "linearised" and args.solver in ("lbfgs", "auglag"):
+        ap.error("--propagation linearised runs with the default solver, --starts K or --solver mppi (the device L-BFGS / augmented Lagrangian: not yet)")
 
     rng = np.random.default_rng(0)
     plant = PendulumPlant()
@@ -130,6 +134,7 @@ def main():
     mpc.set_lb([-2.0]); mpc.set_ub([2.0])
     mpc.set_xref(np.zeros(2))
     mpc.n_starts = args.starts
+    mpc.propagation = args.propagation
     if args.solver == "mppi":
         mpc.solver = "mppi"
         mpc.mppi_options.update(samples=args.samples, iterations=args.iters)

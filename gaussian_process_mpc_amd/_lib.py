@@ -225,6 +225,14 @@ SIGNATURES = {
     "gpmpc_particle_stats": (_i, [_i, _i, _i, _i, _vp, _vp, _sc, _vp, _vp, _vp, _vp, _vp, _vp]),
     "gpmpc_particle_rollout_workspace_bytes": (_sz, [_gm, _i, _i, _i, _i]),
     "gpmpc_particle_rollout": (_i, [_gm, _i, _i, _i, _vp, _vp, _ull, _u, _sc, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _sz, _vp]),
+    "gpmpc_linearised_step_workspace_bytes": (_sz, [_gm, _i, _i, _i]),
+    "gpmpc_linearised_step": (_i, [_gm, _i, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _sz, _i, _vp, _sz, _vp]),
+    "gpmpc_linearised_rollout_workspace_bytes": (_sz, [_gm, _i, _i, _u, _i]),
+    "gpmpc_linearised_rollout": (_i, [_gm, _i, _i, _vp, _vp, ctypes.POINTER(CostParamsC), _sc, _u, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp,
+                                      _sz, _vp]),
+    "gpmpc_mppi_solve_linearised_workspace_bytes": (_sz, [_gm, _i, ctypes.POINTER(MppiParamsC), _sc]),
+    "gpmpc_mppi_solve_linearised": (_i, [_gm, _i, _vp, _vp, ctypes.POINTER(CostParamsC), _sc, ctypes.POINTER(MppiParamsC), _vp, _vp, _vp, _vp,
+                                         _sz, _vp]),
 }
 
 _lib = None
@@ -258,7 +266,7 @@ def check(rc, what):
     if rc != 0:
         detail = lib().gpmpc_last_error().decode() if rc == -3 else ""
         if rc == -1 and ("mppi" in what or "lbfgs" in what or "auglag" in what or "sparse" in what or "particle" in what
-                         or "gp_posterior" in what):    # these refusals say which parameter
+                         or "gp_posterior" in what or "linearised" in what):    # these refusals say which parameter
             detail = lib().gpmpc_last_error().decode()
         if rc == -1 and not detail:        # refusals of a cost schedule say which and why
             why = lib().gpmpc_last_error().decode()

@@ -32,6 +32,12 @@ forced by moving the rollout into one fused HIP call:
   ``x_ref`` under one ``Q``): references that change along the horizon and a terminal weight, through ONE ``rollout.CostSchedule`` owned
   by the controller.  Its rows live in device memory, so the solver-callback graph of the closed loop is captured once however often
   the window moves.  Every callback, batch evaluation, ``cost_torch`` and solver reads it; with none of the three set nothing changes.
+* ``mpc.propagation = "linearised"`` (extension; linearised.py): the first-order propagation mu' = m(z),
+  var' = s2(z) + grad m^T S grad m in the place of exact moment matching -- in the four solver callbacks (one B = 1
+  ``linearised_rollout`` per x), ``evaluate_batch`` (and with it the host lock-step multi-start) and ``solver = "mppi"``
+  (``gpmpc_mppi_solve_linearised``).  ``solver = "lbfgs"``, ``solver = "auglag"`` and ``full_covariance=True`` refuse it (not yet); the
+  lock-step multi-start, which replays its batch as a hipGraph under moment matching, issues plain launches instead (the C entry refuses
+  ``GPMPC_USE_GRAPH``).  ``"moment_matching"`` (the default) is everything above, unchanged.
 """
 import numpy as np
 import torch
@@ -49,6 +55,8 @@ except Exception:                       # pragma: no cover
 
 
 class RiskSensitiveMPC:
+    propagation = "moment_matching"                      # | "linearised" (extension; linearised.py): which rule the rollouts of the solvers use
+
     def __init__(self, gamma, horizon, state_dim, input_dim, Q, R, R_delta=None, full_covariance=False, nominal_models=None):
         # nominal_models (extension; the reference passes None, src/mpc.py:45): one callable per state dimension, handed to Dynamics.  A list
         # of LinearNominalModel is honoured by the rollout, the callbacks and the multi-start solve; other callables by the GPs only.
@@ -275,11 +283,31 @@ class RiskSensitiveMPC:
             return CostFunction.apply(to(xs)[None], to(ss)[None], to(ut)[None], cp)[0]
         return cost_full(cp, xs, ss, ut)[0]
 
+    # -- propagation rule (extension)
+    def _linearised(self):
+        """True under ``propagation = "linearised"``, after the refusals every entry shares."""
+        prop = self.propagation
+        if prop not in ("moment_matching", "linearised"):
+            raise ValueError("propagation must be 'moment_matching' or 'linearised', got %r" % (prop,))
+        if prop == "linearised" and self.full_covariance:
+            raise NotImplementedError("propagation='linearised' is diagonal: a full-covariance linearised rollout is not implemented (not yet)")
+        return prop == "linearised"
+
+    def _linearised_model(self, pack):
+        """The dynamics as a ``particles.GPModel``, rebuilt when the pack or the noise model has changed."""
+        from .particles import GPModel
+        nm = getattr(self.dynamics, "_noise", None)
+        held = getattr(self, "_lin_model", None)
+        if held is None or held[0] is not pack or held[1] != pack.generation or held[2] is not nm:
+            held = self._lin_model = (pack, pack.generation, nm, GPModel.from_dynamics(self.dynamics))
+        return held[3]
+
     # -- cyipopt problem object (src/mpc.py:202-267)
     def _evaluate(self, x):
         x = np.array(x, dtype=np.float64, copy=True).reshape(-1)
         cs, pack, cp = self.curr_state, self.dynamics.pack(), self._cost_params()
-        key = (x.tobytes(), None if cs is None else cs._version, bool(self.full_covariance), pack.generation)
+        lin = self._linearised()
+        key = (x.tobytes(), None if cs is None else cs._version, bool(self.full_covariance), pack.generation, lin)
         held = getattr(self, "_cache_held", (None, None, None))    # kept alive so that `is` cannot alias later objects
         sc = self.state_constraints
         if sc is not None:
@@ -288,7 +316,17 @@ class RiskSensitiveMPC:
                                           "(q = a^T Sigma_t a and that path's Jacobian layout: a follow-up)")
             key = key + (id(sc),)
         if key != self._cache_key or cs is not held[0] or pack is not held[1] or cp is not held[2]:
-            if sc is not None:
+            if lin:
+                # one B = 1 linearised rollout per x: cost, gradient and, with constraints, g and its dense Jacobian from the same pass
+                from .linearised import linearised_rollout
+                r = linearised_rollout(self._linearised_model(pack), cs, x.reshape(1, self.horizon, self.input_dim), cp, want_grad=True,
+                                       want_traj=False, constraints=sc)
+                self.curr_cost = float(r["cost"][0].item())
+                self.curr_grad = r["grad"][0].cpu().numpy()
+                if sc is not None:
+                    self.curr_g = r["g"][0].cpu().numpy().reshape(-1)
+                    self.curr_g_jac = r["g_jac"][0].cpu().numpy()
+            elif sc is not None:
                 # ONE device pass for Ipopt's four callbacks on one x: cost, gradient, g and its dense Jacobian
                 r = rollout(pack, cs, x.reshape(1, self.horizon, self.input_dim), cp, want_grad=True, want_traj=False, constraints=sc)
                 self.curr_cost = float(r["cost"][0].item())
@@ -344,9 +382,14 @@ class RiskSensitiveMPC:
         Returns the rollout dict (device tensors: cost (B,), grad (B,H,da), means, vars).
         constraints=True: also g (B, H, m_c) and, with want_grad, g_jac (B, H m_c, H da) of the state constraints that are set."""
         cs = self.curr_state if curr_state is None else curr_state
+        lin = self._linearised()
+        if constraints and self.state_constraints is None:
+            raise ValueError("no state constraints are set (set_state_constraints / set_state_bounds)")
+        if lin:
+            from .linearised import linearised_rollout
+            return linearised_rollout(self._linearised_model(self.dynamics.pack()), cs, U, self._cost_params(), want_grad=want_grad,
+                                      want_traj=True, constraints=self.state_constraints if constraints else None)
         if constraints:
-            if self.state_constraints is None:
-                raise ValueError("no state constraints are set (set_state_constraints / set_state_bounds)")
             if self.full_covariance:
                 raise NotImplementedError("state constraints under the full-covariance rollout are not implemented")
             return rollout(self.dynamics.pack(), cs, U, self._cost_params(), want_grad=want_grad, want_traj=True,
@@ -360,7 +403,7 @@ class RiskSensitiveMPC:
         return r["cost"].cpu().numpy(), r["grad"].cpu().numpy()
 
     # -- Monte-Carlo check of the moment-matched plan (extension)
-    def validate_plan(self, U=None, x0=None, particles=4096, seed=0):
+    def validate_plan(self, U=None, x0=None, particles=4096, seed=0, linearised=False):
         """Compare the moment-matched rollout of a plan (the last one by default; diagonal or full by ``self.full_covariance``) with a
         particle rollout through the same GPs (``particles.particle_rollout``).  Returns a dict of host arrays:
 
@@ -370,7 +413,9 @@ class RiskSensitiveMPC:
         ``clamped`` (H,): particles whose latent variance came out negative; ``stage_cost``: the mean over particles of
         sum_t (x_t - x_ref)^T Q (x_t - x_ref) + sum_t (u_t - u_ref)^T R (u_t - u_ref) (torch, from the particles);
         with state constraints ``satisfaction`` (H, rows), the fraction of particles with a . x_t <= b at t = 1..H, next to
-        ``requested`` (rows,) = Phi(kappa), and ``joint_satisfaction``, the fraction satisfying every row at every step."""
+        ``requested`` (rows,) = Phi(kappa), and ``joint_satisfaction``, the fraction satisfying every row at every step.
+        linearised=True adds the third column: ``mean_lin``, ``var_lin`` (H+1, ds) of the linearised rollout (linearised.py) and
+        ``z_mean_lin``, ``z_var_lin``, its distance from the particles in the same Monte-Carlo standard errors."""
         from statistics import NormalDist
         from .particles import particle_rollout
         H, ds, da = self.horizon, self.state_dim, self.input_dim
@@ -400,6 +445,13 @@ class RiskSensitiveMPC:
             out["z_mean"] = np.where(se_mean > 0, (out["mean_mc"] - out["mean_mm"]) / se_mean, 0.0)
             out["z_var"] = np.where(se_var > 0, (out["var_mc"] - out["var_mm"]) / se_var, 0.0)
         out["se_mean"], out["se_var"] = se_mean, se_var
+        if linearised:
+            from .linearised import linearised_rollout
+            ln = linearised_rollout(self.dynamics, cs, U, None, want_grad=False)
+            out["mean_lin"], out["var_lin"] = ln["means"][0].cpu().numpy(), ln["vars"][0].cpu().numpy()
+            with np.errstate(divide="ignore", invalid="ignore"):
+                out["z_mean_lin"] = np.where(se_mean > 0, (out["mean_mc"] - out["mean_lin"]) / se_mean, 0.0)
+                out["z_var_lin"] = np.where(se_var > 0, (out["var_mc"] - out["var_lin"]) / se_var, 0.0)
         out["clamped"] = mc["clamped"][0].cpu().numpy()
         Ud = torch.as_tensor(U, device=X.device)
         ex, eu = X - self.x_ref.to(X.device, torch.float64), Ud - self.u_ref.to(X.device, torch.float64)
@@ -416,6 +468,9 @@ class RiskSensitiveMPC:
         solver = getattr(self, "solver", None) if solver is None else solver
         if solver not in (None, "mppi", "lbfgs", "auglag"):
             raise ValueError("solver must be None, 'mppi', 'lbfgs' or 'auglag', got %r" % (solver,))
+        if self._linearised() and solver in ("lbfgs", "auglag"):
+            raise NotImplementedError("propagation='linearised' with solver=%r: the device L-BFGS and augmented-Lagrangian solvers run the "
+                                      "moment-matched rollout (not yet); use solver=None, n_starts > 1 or solver='mppi'" % (solver,))
         if solver == "auglag":
             if getattr(self, "state_constraints", None) is None:
                 raise ValueError("solver='auglag' is the constrained multi-start: without state constraints use solver='lbfgs'")
@@ -527,6 +582,7 @@ class RiskSensitiveMPC:
         """The sampling planner (mppi.mppi_solve) from the previous plan shifted by one step (zeros on the first solve); the call index of
         the noise is the solve count (shared with the multi-start's start sampler), so a loop of solves is reproducible from ``mppi_options["seed"]``."""
         from .mppi import mppi_solve
+        from .linearised import mppi_solve_linearised
         opt = self.mppi_options
         H, da = self.horizon, self.input_dim
         big = 1e15                                                        # (the setters' "no bound", as _solve_without_ipopt reads it)
@@ -539,10 +595,12 @@ class RiskSensitiveMPC:
         if self.solver_used is not None:                                  # (whichever solver made the previous plan)
             prev = np.asarray(self.last_traj, dtype=np.float64).reshape(H, da)
             start = np.clip(np.concatenate((prev[1:], prev[-1:]), axis=0), lb, ub)
-        r = mppi_solve(self.dynamics.pack(), self.curr_state, start, self._cost_params(), constraints=self.state_constraints,
-                       samples=int(opt.get("samples", 64)), iterations=int(opt.get("iterations", 30)), sigma=sigma,
-                       decay=float(opt.get("decay", 0.9)), beta=float(opt.get("beta", 0.1)), seed=int(opt.get("seed", 0)),
-                       call_index=self._solve_count, lb=lb, ub=ub)
+        lin = self._linearised()
+        solve = mppi_solve_linearised if lin else mppi_solve
+        r = solve(self._linearised_model(self.dynamics.pack()) if lin else self.dynamics.pack(), self.curr_state, start, self._cost_params(),
+                  constraints=self.state_constraints, samples=int(opt.get("samples", 64)), iterations=int(opt.get("iterations", 30)), sigma=sigma,
+                  decay=float(opt.get("decay", 0.9)), beta=float(opt.get("beta", 0.1)), seed=int(opt.get("seed", 0)),
+                  call_index=self._solve_count, lb=lb, ub=ub)
         self._solve_count += 1
         self.solver_used = "mppi x%d" % int(opt.get("samples", 64))
         self.last_solve_info = {"cost": r["cost"], "violation": r["violation"], "feasible": r["feasible"], "success": r["feasible"],
@@ -600,7 +658,12 @@ class RiskSensitiveMPC:
         if torch.distributed.is_available() and torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1:
             dist = torch.distributed
 
+        lin = self._linearised()
+
         def run(x0b, Ub, graph):
+            if lin:                                                       # (plain launches: graph replay of the linearised rollout is not provided)
+                from .linearised import linearised_rollout
+                return linearised_rollout(self._linearised_model(pack), x0b, Ub, cp, want_grad=True, want_traj=False)
             if self.full_covariance:
                 return rollout_fullcov(pack, x0b, Ub, cp, want_grad=True)
             return rollout(pack, x0b, Ub, cp, want_grad=True, want_traj=False, graph=graph)

@@ -925,6 +925,72 @@ int gpmpc_particle_rollout(const gpmpc_gp_model* model_host, int B, int P, int H
                            double* out_particles, double* out_mean, double* out_cov, int* out_clamped, double* out_viol,
                            double* out_joint, int chunk, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---------------------------------------------------------------------------
+ * Linearised propagation: the first-order (Taylor, "mean-equivalent") rule of the cautious-MPC literature, beside the exact moment matching
+ * of gpmpc_rollout (no reference counterpart; DESIGN.md section 3j, kernels in csrc/linprop.hip).  The model is a gpmpc_gp_model, dense or
+ * sparse (Z, alpha, Q in the place of X, beta, Kinv), with its nominal and noise model.
+ *
+ * One step.  Inputs: the mean mu (ds), the diagonal variance v (ds), the input u (da).  z = (mu, u), D = ds + da,
+ * S = (v_1 ... v_ds, action_var_1 ... action_var_da).  Step 0 of a rollout is mu_0 = x0, v_0 = diag(init_cov) (the defaults of
+ * gpmpc_pack_set_noise when has_noise = 0).  For GP a, with d_id = (X_id - z_d) / lambda_ad:
+ *     k_i    = sf_a^2 exp(-1/2 sum_d (X_id - z_d)^2 / lambda_ad)
+ *     m_a    = sum_i beta_ia k_i                      [+ W_a . z + b_a with a nominal model]
+ *     g_ad   = d m_a / d z_d = sum_i beta_ia k_i d_id [+ W_ad]
+ *     q_a    = sum_ij k_i Kinv_a[i][j] k_j            (ALL entries: Kinv comes from LU and is not symmetric)
+ *     r_a    = (Kinv_a + Kinv_a^T) k
+ *     d q_a / d z_d = sum_i r_ai k_i d_id
+ *     w_ad   = g_ad S_d
+ *     h_ad   = sum_i beta_ia k_i [ d_id (d_i . w_a) - w_ad / lambda_ad ]     (= sum_l d^2 m_a / d z_l d z_d w_al; the nominal part has no curvature)
+ *     mu'_a  = m_a
+ *     v'_a   = (sf_a^2 - q_a) + sum_d g_ad^2 S_d + process_var_a             (unclamped, as everywhere in this library)
+ * q is evaluated as 1/2 k^T r from the one product r = (Kinv + Kinv^T) k (a staged tile holds Kinv[i][j] + Kinv[j][i]), so q and dq/dz come
+ * from the same numbers.  The step Jacobian has the layout of gpmpc_rollout_jac, [2ds][2ds+da], rows (mu', v'), columns (mu, v, u):
+ *     row mu'_a:  g_ak in the mu columns, 0 in the v columns, g_a,ds+j in the u columns
+ *     row v'_a:   -dq_a/dz_k + 2 h_ak in the mu columns, g_ak^2 in the v columns, -dq_a/dz_{ds+j} + 2 h_a,ds+j in the u columns
+ * The propagation is diagonal, as in gpmpc_rollout: cross-covariances between states are dropped.
+ *
+ * No atomics, fixed summation orders, launch geometry from the sizes only: two identical calls agree bit for bit and no result depends on
+ * `chunk` (columns, i.e. plans, are independent; a multiple of 64, 0: 4096).  B = 1 runs the same tile kernels with padded columns.
+ * All refusals are GPMPC_E_ARG with a text in gpmpc_last_error, before any launch: a NULL pointer, dimensions outside GPMPC_MAX_*, n < 1,
+ * B / H < 1 (or B H above 2^40 Jacobian elements), ld < n, a chunk that is negative or no multiple of 64, a lambda or sigma_f that is not positive
+ * and finite, a non-finite nominal model, a negative or non-finite diagonal entry of init_cov, action_var or process_var, u_stride <
+ * action_dim or jac_stride < 2ds (2ds+da) with B > 1, outputs of a step that alias its inputs, flags other than GPMPC_WANT_GRAD
+ * (GPMPC_USE_GRAPH and the GPMPC_FP32_* modes: not yet / never), out_jac without GPMPC_WANT_GRAD, a cost without out_cost (or without
+ * out_grad under GPMPC_WANT_GRAD), constraint rows without out_g (out_gjac), bad constraint rows, a bad cost schedule, a cost with
+ * action_dim = 0 or with a horizon beyond the cost kernel's LDS (about 48 KiB / (8 (2 + 2ds + da)) steps); in gpmpc_mppi_solve_linearised
+ * also what gpmpc_mppi_solve refuses.  A workspace below *_workspace_bytes (which return 0 for arguments that would be refused):
+ * GPMPC_E_WORKSPACE.
+ * Not provided: a full-covariance linearised rollout, the device L-BFGS / augmented-Lagrangian solvers on this form, graph capture, a
+ * matrix-vector form for B = 1, second-order mean corrections, multi-GPU sharding, gradients w.r.t. hyper-parameters or noise parameters.
+ * ------------------------------------------------------------------------- */
+/* One step of B plans: mu_prev, var_prev dev [B][ds]; U_t dev, input j of plan b at U_t[b u_stride + j] (NULL with da = 0); out_mu, out_var
+ * dev [B][ds]; out_jac dev or NULL, the block of plan b at out_jac + b jac_stride (in doubles: a rollout writes [B][H][2ds][2ds+da] in
+ * place).  Without out_jac neither dq/dz nor h is computed.  want_jac of the size query: whether out_jac will be given. */
+size_t gpmpc_linearised_step_workspace_bytes(const gpmpc_gp_model* model_host, int B, int want_jac, int chunk);
+int gpmpc_linearised_step(const gpmpc_gp_model* model_host, int B, const double* mu_prev, const double* var_prev, const double* U_t,
+                          size_t u_stride, double* out_mu, double* out_var, double* out_jac, size_t jac_stride, int chunk,
+                          void* workspace, size_t workspace_bytes, void* stream);
+/* B rollouts of H steps on one stream, no host round trip, no allocation.  x0 dev [B][ds]; U dev [B][H][da]; out_means, out_vars dev
+ * [B][H+1][ds] or NULL (kept in the workspace); out_jac dev [B][H][2ds][2ds+da] or NULL (GPMPC_WANT_GRAD only).  Means, variances and
+ * Jacobians are bit for bit those of the chain of gpmpc_linearised_step calls.  flags: GPMPC_WANT_GRAD or 0; without it no Jacobian is
+ * computed at all.  cost_host (or NULL: out_cost / out_grad are not touched): out_cost dev [B] and, with GPMPC_WANT_GRAD, out_grad dev
+ * [B][H][da] from the tail kernel of gpmpc_rollout (the risk-sensitive cost on the diagonal covariances and its adjoint sweep over the step
+ * Jacobians; cost schedules are honoured).  cons_host (or NULL): out_g dev [B][H][n_rows] and, with GPMPC_WANT_GRAD, out_gjac dev
+ * [B][H n_rows][H da], bit for bit what gpmpc_rollout_constraints gives on the returned arrays. */
+size_t gpmpc_linearised_rollout_workspace_bytes(const gpmpc_gp_model* model_host, int B, int H, unsigned flags, int chunk);
+int gpmpc_linearised_rollout(const gpmpc_gp_model* model_host, int B, int H, const double* x0, const double* U,
+                             const gpmpc_cost_params* cost_host, const gpmpc_state_constraints* cons_host, unsigned flags,
+                             double* out_means, double* out_vars, double* out_jac, double* out_cost, double* out_grad, double* out_g,
+                             double* out_gjac, int chunk, void* workspace, size_t workspace_bytes, void* stream);
+/* gpmpc_mppi_solve with a gpmpc_gp_model in the place of the pack: per iteration gpmpc_mppi_sample, gpmpc_linearised_rollout objective
+ * only (flags 0, default chunk; with the constraint values when cons_host is given), gpmpc_mppi_update.  Outputs and trace as there. */
+size_t gpmpc_mppi_solve_linearised_workspace_bytes(const gpmpc_gp_model* model_host, int H, const gpmpc_mppi_params* params_host,
+                                                   const gpmpc_state_constraints* cons_host);
+int gpmpc_mppi_solve_linearised(const gpmpc_gp_model* model_host, int H, const double* x0_dev, const double* start_dev,
+                                const gpmpc_cost_params* cost_host, const gpmpc_state_constraints* cons_host,
+                                const gpmpc_mppi_params* params_host, double* out_U, double* out_best, double* out_trace, void* workspace,
+                                size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
