@@ -102,6 +102,8 @@ def main():
     ap.add_argument("--inducing-select", choices=("farthest", "random"), default="farthest", help="how --inducing picks its points")
     ap.add_argument("--propagation", choices=("moment_matching", "linearised"), default="moment_matching",
                     help="linearised: first-order propagation mu' = m(z), var' = s2(z) + grad m^T S grad m (mpc.propagation); with the default solver, --starts K or --solver mppi")
+    ap.add_argument("--linearised-form", choices=("tile", "stream", "auto"), default=None,
+                    help="with --propagation linearised: the form of the linearised step (mpc.linearised_form); stream is the matrix-vector form for B = 1")
     args = ap.parse_args()
     if args.window is not None and args.window < 1:
         ap.error("--window must be >= 1")
@@ -135,6 +137,7 @@ def main():
     mpc.set_xref(np.zeros(2))
     mpc.n_starts = args.starts
     mpc.propagation = args.propagation
+    mpc.linearised_form = args.linearised_form
     if args.solver == "mppi":
         mpc.solver = "mppi"
         mpc.mppi_options.update(samples=args.samples, iterations=args.iters)

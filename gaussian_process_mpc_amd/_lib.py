@@ -25,6 +25,12 @@ DESCRIBE_WANT_COV = 0x100      # gpmpc_moment_match_describe: a call with out_co
 USE_GRAPH = 4
 FP32_ACCUM = 8
 FP32_ALL = 16
+LINPROP_FORM_TILE = 0          # gpmpc_linearised_set_form (include/gpmpc.h, "Linearised propagation")
+LINPROP_FORM_STREAM = 1
+LINPROP_FORM_AUTO = 2
+LINPROP_FORM_DEFAULT = LINPROP_FORM_TILE
+LINPROP_STREAM_COLS = 4
+LINPROP_AUTO_MAX_B = 32        # measured: profiles/linprop/stream_ab.txt
 
 _ERR = {-1: "bad argument", -2: "device allocation failed", -3: "HIP call / kernel launch failed",
         -4: "workspace too small", -5: "pack not built",
@@ -225,6 +231,7 @@ SIGNATURES = {
     "gpmpc_particle_stats": (_i, [_i, _i, _i, _i, _vp, _vp, _sc, _vp, _vp, _vp, _vp, _vp, _vp]),
     "gpmpc_particle_rollout_workspace_bytes": (_sz, [_gm, _i, _i, _i, _i]),
     "gpmpc_particle_rollout": (_i, [_gm, _i, _i, _i, _vp, _vp, _ull, _u, _sc, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _sz, _vp]),
+    "gpmpc_linearised_set_form": (_i, [_i]),
     "gpmpc_linearised_step_workspace_bytes": (_sz, [_gm, _i, _i, _i]),
     "gpmpc_linearised_step": (_i, [_gm, _i, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _sz, _i, _vp, _sz, _vp]),
     "gpmpc_linearised_rollout_workspace_bytes": (_sz, [_gm, _i, _i, _u, _i]),

@@ -19,6 +19,8 @@
 #include "roll_dev.h"        // RollArgs and gpmpc_launch_roll_tail: the cost and the adjoint sweep of the rollout are the existing tail kernel
 #include "solver_frame.h"
 #include "tile_stage.h"
+#include "linprop_internal.h"   // LpTail, LpIn, lp_z, and the STREAM form of the step (linprop_stream.hip)
+#include <atomic>
 
 #define LP_DEFAULT_CHUNK 4096
 
@@ -28,20 +30,6 @@ struct LpGroup {
     int ng;                         // GPs of the group
     int gp[GPMPC_MAX_DS];           // their indices, ascending
 };
-struct LpTail {                     // what the sums / Jacobian kernels need of the model besides the group
-    double nom_w[GPMPC_MAX_DS * GPMPC_MAX_D], nom_b[GPMPC_MAX_DS], process_var[GPMPC_MAX_DS], action_var[GPMPC_MAX_D];
-    double init_var[GPMPC_MAX_DS];  // diag(init_cov): the variance of step 0 (host side only)
-    int has_nominal;
-};
-struct LpIn {                       // the inputs of a step, column c: mu + c xs, var + c xs, U + c us
-    const double* mu; const double* var; const double* U;
-    size_t xs, us;
-};
-
-static __device__ __forceinline__ double lp_z(const LpIn& I, int c, int d, int ds) {
-    return d < ds ? I.mu[(size_t)c * I.xs + d] : I.U[(size_t)c * I.us + (d - ds)];
-}
-
 // ---------------------------------------------------------------------------
 // kernels
 // ---------------------------------------------------------------------------
@@ -267,8 +255,19 @@ __global__ __launch_bounds__(256) void k_lp_init(int B, int ds, size_t stride, c
 }
 
 // ---------------------------------------------------------------------------
-// host: checks
+// host: the form, checks
 // ---------------------------------------------------------------------------
+// which form of the step lp_step launches (process-wide; read once per call, in lp_layout)
+static std::atomic<int> g_lp_form{GPMPC_LINPROP_FORM_DEFAULT};
+
+extern "C" int gpmpc_linearised_set_form(int form) {
+    if (form != GPMPC_LINPROP_FORM_TILE && form != GPMPC_LINPROP_FORM_STREAM && form != GPMPC_LINPROP_FORM_AUTO) {
+        if (form == -1) return g_lp_form.load();
+        return gpmpc_refuse("gpmpc_linearised_set_form", "form must be GPMPC_LINPROP_FORM_TILE, _STREAM, _AUTO or -1 (query)");
+    }
+    return g_lp_form.exchange(form);
+}
+
 static bool lp_finite(double v) { return v - v == 0.0; }
 static int lp_chunk(int chunk) { return chunk == 0 ? LP_DEFAULT_CHUNK : chunk; }
 static unsigned lp_blocks(long threads) { return (unsigned)((threads + 255) / 256); }
@@ -350,9 +349,13 @@ static int lp_groups(const gpmpc_gp_model* m, LpGroup* g) {
 }
 
 // workspace of a step: Ks [np][C] | kpart [nbi][ds][1 + D][C] | part [ds][nbi][nv][C] | with the Jacobian: hpart [nbi][ds][MAX_D][C] | g [C][ds][MAX_D]
-struct LpLayout { size_t off_ks, off_kpart, off_part, off_hpart, off_g, total; int np, nbi, C, nv; };
+// `form`: the process-wide form read ONCE when the layout of a call is made.  Under TILE the offsets and the total are what they always were;
+// STREAM carves its own arrays from `base` on (gpmpc_lps_workspace_bytes); AUTO sizes for the larger of the two.
+struct LpLayout { size_t off_ks, off_kpart, off_part, off_hpart, off_g, total, base; int np, nbi, C, nv, form; };
 static LpLayout lp_layout(const gpmpc_gp_model* m, int chunk, long ncols, bool want_jac, gpmpc_carver& c) {
     LpLayout L;
+    L.form = g_lp_form.load();
+    L.base = c.total();
     const int ds = m->state_dim, D = ds + m->action_dim;
     L.nbi = (m->n + SP_T - 1) / SP_T;
     L.np = L.nbi * SP_T;
@@ -366,12 +369,20 @@ static LpLayout lp_layout(const gpmpc_gp_model* m, int chunk, long ncols, bool w
     L.off_hpart = c.take(want_jac ? d * L.nbi * ds * GPMPC_MAX_D * L.C : 0);
     L.off_g = c.take(want_jac ? d * L.C * ds * GPMPC_MAX_D : 0);
     L.total = c.total();
+    if (L.form != GPMPC_LINPROP_FORM_TILE) {
+        const size_t stream = L.base + gpmpc_lps_workspace_bytes(m, ncols, want_jac);
+        L.total = (L.form == GPMPC_LINPROP_FORM_AUTO && L.total > stream) ? L.total : stream;
+        c.off = L.total;
+    }
     return L;
 }
 
 // One step of B columns.  mu_prev / var_prev: column b at + b xs; U_t: + b us; outputs at + b os; jac (or null): + b js.
+// THE place that picks the form: the step, the rollout and (through the rollout) the MPPI solve all come here.
 static int lp_step(const gpmpc_gp_model* m, const LpTail& tail, int B, const double* mu_prev, const double* var_prev, size_t xs, const double* U_t,
                    size_t us, double* out_mu, double* out_var, size_t os, double* jac, size_t js, const LpLayout& L, char* ws, hipStream_t s) {
+    if (L.form == GPMPC_LINPROP_FORM_STREAM || (L.form == GPMPC_LINPROP_FORM_AUTO && B <= GPMPC_LINPROP_AUTO_MAX_B))
+        return gpmpc_lps_step(m, tail, B, mu_prev, var_prev, xs, U_t, us, out_mu, out_var, os, jac, js, ws + L.base, s);
     const int ds = m->state_dim, da = m->action_dim, D = ds + da;
     LpGroup groups[GPMPC_MAX_DS];
     const int ngroups = lp_groups(m, groups);

@@ -7,7 +7,12 @@ quadratic form per plan, GP and step -- a matrix product on the MFMA pipe, not a
     r = linearised_rollout(dyn, x0, U, cost)                 # what rollout(pack, x0, U, cost) returns, by the other rule
     s = mppi_solve_linearised(model, x0, U0, cost, samples=1024)
 
+Two forms of the step (C ABI ``gpmpc_linearised_set_form``): "tile", the 64-column MFMA kernels and the default; "stream", matrix-vector
+kernels for a few columns (csrc/linprop_stream.hip); "auto", stream up to ``LINPROP_AUTO_MAX_B`` columns.  ``with linearised_form("stream"):``
+selects one for a block; every entry also takes ``form=``.
+
 Plumbing only: the arithmetic is in the kernels.  Every call runs on the current stream of the model's device and returns device tensors."""
+import contextlib
 import ctypes
 
 import torch
@@ -19,9 +24,36 @@ from .particles import GPModel, _dev, _empty, _model, _vp, _workspace
 from .rollout import StateConstraints
 
 
-def linearised_step(model, mu, var, U_t, want_jac=True, chunk=0):
+FORMS = {"tile": _lib.LINPROP_FORM_TILE, "stream": _lib.LINPROP_FORM_STREAM, "auto": _lib.LINPROP_FORM_AUTO}
+
+
+def _form_code(name):
+    if name is not None and name not in FORMS:
+        raise ValueError("form must be None, 'tile', 'stream' or 'auto', got %r" % (name,))
+    return None if name is None else FORMS[name]
+
+
+@contextlib.contextmanager
+def linearised_form(name):
+    """Selects the form of the linearised step for the block -- "tile", "stream" or "auto"; None leaves the process-wide choice alone -- and
+    restores the previous one on the way out, also on an exception.  An unknown name raises ValueError before anything is set.  The library
+    reads the form on the host when a call is ENQUEUED, not when its kernels run, so setting and restoring around asynchronous launches is
+    sound: what was enqueued inside the block keeps the form it was enqueued with.  The choice is process-wide (not per thread)."""
+    code = _form_code(name)
+    if code is None:
+        yield
+        return
+    old = lib().gpmpc_linearised_set_form(code)
+    try:
+        yield
+    finally:
+        lib().gpmpc_linearised_set_form(old)
+
+
+def linearised_step(model, mu, var, U_t, want_jac=True, chunk=0, form=None):
     """One step of B plans: mu, var (B, ds), U_t (B, da) -> (mu', var') or, with ``want_jac``, (mu', var', jac (B, 2ds, 2ds+da)): rows
-    (mu', var'), columns (mu, var, u), the layout of ``gpmpc_rollout_jac``."""
+    (mu', var'), columns (mu, var, u), the layout of ``gpmpc_rollout_jac``.  form: see ``linearised_form``."""
+    _form_code(form)
     model = _model(model)
     ds, da, dev = model.ds, model.da, model.device
     mu = _dev(mu, dev).reshape(-1, ds)
@@ -31,7 +63,7 @@ def linearised_step(model, mu, var, U_t, want_jac=True, chunk=0):
     out_mu, out_var = _empty(dev, B, ds), _empty(dev, B, ds)
     nz, nc = 2 * ds, 2 * ds + da
     jac = _empty(dev, B, nz, nc) if want_jac else None
-    with torch.cuda.device(dev):
+    with torch.cuda.device(dev), linearised_form(form):
         nb = lib().gpmpc_linearised_step_workspace_bytes(ctypes.byref(model.c), B, 1 if want_jac else 0, chunk)
         ws = _workspace(dev, nb)
         check(lib().gpmpc_linearised_step(ctypes.byref(model.c), B, ptr(mu), ptr(var), _vp(U_t) if da else None, da, ptr(out_mu), ptr(out_var),
@@ -39,12 +71,14 @@ def linearised_step(model, mu, var, U_t, want_jac=True, chunk=0):
     return (out_mu, out_var, jac) if want_jac else (out_mu, out_var)
 
 
-def linearised_rollout(model_or_dynamics, x0, U, cost=None, want_grad=True, want_traj=True, want_jac=False, constraints=None, chunk=0):
+def linearised_rollout(model_or_dynamics, x0, U, cost=None, want_grad=True, want_traj=True, want_jac=False, constraints=None, chunk=0,
+                       form=None):
     """B linearised rollouts (+ cost, gradient, chance constraints) in one call (C ABI ``gpmpc_linearised_rollout``): what ``rollout``
     returns for the same arguments -- cost (B,), grad (B, H, da), means / vars (B, H+1, ds), with ``constraints`` g (B, H, m_c) and g_jac
     (B, H m_c, H da) --, plus ``jac`` (B, H, 2ds, 2ds+da) with ``want_jac`` (which needs ``want_grad``: without it no Jacobian is computed).
     model_or_dynamics: a ``GPModel``, a ``Dynamics`` or a ``SparseDynamics``.  x0 (ds,) or (B, ds); U (H, da) or (B, H, da).
-    cost: ``CostParams`` or None (no cost, no grad)."""
+    cost: ``CostParams`` or None (no cost, no grad).  form: see ``linearised_form``."""
+    _form_code(form)
     model = _model(model_or_dynamics)
     ds, da, dev = model.ds, model.da, model.device
     U = _dev(U, dev)
@@ -82,7 +116,7 @@ def linearised_rollout(model_or_dynamics, x0, U, cost=None, want_grad=True, want
         out["means"], out["vars"] = _empty(dev, B, H + 1, ds), _empty(dev, B, H + 1, ds)
     if want_jac:
         out["jac"] = _empty(dev, B, H, 2 * ds, 2 * ds + da)
-    with torch.cuda.device(dev):
+    with torch.cuda.device(dev), linearised_form(form):
         nb = lib().gpmpc_linearised_rollout_workspace_bytes(ctypes.byref(model.c), B, H, flags, chunk)
         ws = _workspace(dev, nb)
         check(lib().gpmpc_linearised_rollout(ctypes.byref(model.c), B, H, ptr(x0), _vp(U) if da else None,
@@ -94,10 +128,11 @@ def linearised_rollout(model_or_dynamics, x0, U, cost=None, want_grad=True, want
 
 
 def mppi_solve_linearised(model, x0, U0, cost, constraints=None, samples=64, iterations=30, sigma=1.0, decay=0.9, beta=0.1, seed=0,
-                          call_index=0, lb=None, ub=None):
+                          call_index=0, lb=None, ub=None, form=None):
     """``mppi.mppi_solve`` over the linearised rollout (C ABI ``gpmpc_mppi_solve_linearised``): per iteration the sample kernel,
     ``gpmpc_linearised_rollout`` objective only over the K samples (with the constraint values when ``constraints`` is given), the update
-    kernel; one device-to-host copy at the end.  Returns what ``mppi_solve`` returns."""
+    kernel; one device-to-host copy at the end.  Returns what ``mppi_solve`` returns.  form: see ``linearised_form``."""
+    _form_code(form)
     model = _model(model)
     dev = model.device
     U0 = _dev(U0, dev)
@@ -113,7 +148,7 @@ def mppi_solve_linearised(model, x0, U0, cost, constraints=None, samples=64, ite
     cons = None if constraints is None else ctypes.byref(constraints.c)
     n = H * da
     res = torch.empty(n + 2 + 6 * max(P.iterations, 1), dtype=torch.float64, device=dev)      # [best plan | key | trace]: one block, one copy
-    with torch.cuda.device(dev):
+    with torch.cuda.device(dev), linearised_form(form):
         nb = lib().gpmpc_mppi_solve_linearised_workspace_bytes(ctypes.byref(model.c), H, ctypes.byref(P), cons)
         ws = _workspace(dev, nb)
         check(lib().gpmpc_mppi_solve_linearised(ctypes.byref(model.c), H, ptr(x0), ptr(U0), ctypes.byref(cost.c), cons, ctypes.byref(P),
@@ -124,4 +159,4 @@ def mppi_solve_linearised(model, x0, U0, cost, constraints=None, samples=64, ite
             "trace": host[n + 2:].reshape(-1, 6).copy()}
 
 
-__all__ = ["GPModel", "linearised_step", "linearised_rollout", "mppi_solve_linearised"]
+__all__ = ["GPModel", "linearised_form", "linearised_step", "linearised_rollout", "mppi_solve_linearised"]

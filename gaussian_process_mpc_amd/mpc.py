@@ -37,7 +37,9 @@ forced by moving the rollout into one fused HIP call:
   ``linearised_rollout`` per x), ``evaluate_batch`` (and with it the host lock-step multi-start) and ``solver = "mppi"``
   (``gpmpc_mppi_solve_linearised``).  ``solver = "lbfgs"``, ``solver = "auglag"`` and ``full_covariance=True`` refuse it (not yet); the
   lock-step multi-start, which replays its batch as a hipGraph under moment matching, issues plain launches instead (the C entry refuses
-  ``GPMPC_USE_GRAPH``).  ``"moment_matching"`` (the default) is everything above, unchanged.
+  ``GPMPC_USE_GRAPH``).  ``"moment_matching"`` (the default) is everything above, unchanged.  ``mpc.linearised_form = "tile" | "stream" |
+  "auto"`` hands every one of these calls its ``form=`` (linearised.py: "stream" is the matrix-vector form for the B = 1 callbacks and the
+  small batches of the multi-start); ``None``, the default, leaves the process-wide choice alone.
 """
 import numpy as np
 import torch
@@ -56,6 +58,7 @@ except Exception:                       # pragma: no cover
 
 class RiskSensitiveMPC:
     propagation = "moment_matching"                      # | "linearised" (extension; linearised.py): which rule the rollouts of the solvers use
+    linearised_form = None                               # | "tile" | "stream" | "auto": the form of the linearised step (None: the process-wide one)
 
     def __init__(self, gamma, horizon, state_dim, input_dim, Q, R, R_delta=None, full_covariance=False, nominal_models=None):
         # nominal_models (extension; the reference passes None, src/mpc.py:45): one callable per state dimension, handed to Dynamics.  A list
@@ -307,7 +310,8 @@ class RiskSensitiveMPC:
         x = np.array(x, dtype=np.float64, copy=True).reshape(-1)
         cs, pack, cp = self.curr_state, self.dynamics.pack(), self._cost_params()
         lin = self._linearised()
-        key = (x.tobytes(), None if cs is None else cs._version, bool(self.full_covariance), pack.generation, lin)
+        key = (x.tobytes(), None if cs is None else cs._version, bool(self.full_covariance), pack.generation, lin,
+               self.linearised_form if lin else None)
         held = getattr(self, "_cache_held", (None, None, None))    # kept alive so that `is` cannot alias later objects
         sc = self.state_constraints
         if sc is not None:
@@ -320,7 +324,7 @@ class RiskSensitiveMPC:
                 # one B = 1 linearised rollout per x: cost, gradient and, with constraints, g and its dense Jacobian from the same pass
                 from .linearised import linearised_rollout
                 r = linearised_rollout(self._linearised_model(pack), cs, x.reshape(1, self.horizon, self.input_dim), cp, want_grad=True,
-                                       want_traj=False, constraints=sc)
+                                       want_traj=False, constraints=sc, form=self.linearised_form)
                 self.curr_cost = float(r["cost"][0].item())
                 self.curr_grad = r["grad"][0].cpu().numpy()
                 if sc is not None:
@@ -388,7 +392,7 @@ class RiskSensitiveMPC:
         if lin:
             from .linearised import linearised_rollout
             return linearised_rollout(self._linearised_model(self.dynamics.pack()), cs, U, self._cost_params(), want_grad=want_grad,
-                                      want_traj=True, constraints=self.state_constraints if constraints else None)
+                                      want_traj=True, constraints=self.state_constraints if constraints else None, form=self.linearised_form)
         if constraints:
             if self.full_covariance:
                 raise NotImplementedError("state constraints under the full-covariance rollout are not implemented")
@@ -447,7 +451,7 @@ class RiskSensitiveMPC:
         out["se_mean"], out["se_var"] = se_mean, se_var
         if linearised:
             from .linearised import linearised_rollout
-            ln = linearised_rollout(self.dynamics, cs, U, None, want_grad=False)
+            ln = linearised_rollout(self.dynamics, cs, U, None, want_grad=False, form=self.linearised_form)
             out["mean_lin"], out["var_lin"] = ln["means"][0].cpu().numpy(), ln["vars"][0].cpu().numpy()
             with np.errstate(divide="ignore", invalid="ignore"):
                 out["z_mean_lin"] = np.where(se_mean > 0, (out["mean_mc"] - out["mean_lin"]) / se_mean, 0.0)
@@ -600,7 +604,7 @@ class RiskSensitiveMPC:
         r = solve(self._linearised_model(self.dynamics.pack()) if lin else self.dynamics.pack(), self.curr_state, start, self._cost_params(),
                   constraints=self.state_constraints, samples=int(opt.get("samples", 64)), iterations=int(opt.get("iterations", 30)), sigma=sigma,
                   decay=float(opt.get("decay", 0.9)), beta=float(opt.get("beta", 0.1)), seed=int(opt.get("seed", 0)),
-                  call_index=self._solve_count, lb=lb, ub=ub)
+                  call_index=self._solve_count, lb=lb, ub=ub, **({"form": self.linearised_form} if lin else {}))
         self._solve_count += 1
         self.solver_used = "mppi x%d" % int(opt.get("samples", 64))
         self.last_solve_info = {"cost": r["cost"], "violation": r["violation"], "feasible": r["feasible"], "success": r["feasible"],
@@ -663,7 +667,7 @@ class RiskSensitiveMPC:
         def run(x0b, Ub, graph):
             if lin:                                                       # (plain launches: graph replay of the linearised rollout is not provided)
                 from .linearised import linearised_rollout
-                return linearised_rollout(self._linearised_model(pack), x0b, Ub, cp, want_grad=True, want_traj=False)
+                return linearised_rollout(self._linearised_model(pack), x0b, Ub, cp, want_grad=True, want_traj=False, form=self.linearised_form)
             if self.full_covariance:
                 return rollout_fullcov(pack, x0b, Ub, cp, want_grad=True)
             return rollout(pack, x0b, Ub, cp, want_grad=True, want_traj=False, graph=graph)

@@ -960,9 +960,47 @@ int gpmpc_particle_rollout(const gpmpc_gp_model* model_host, int B, int P, int H
  * action_dim = 0 or with a horizon beyond the cost kernel's LDS (about 48 KiB / (8 (2 + 2ds + da)) steps); in gpmpc_mppi_solve_linearised
  * also what gpmpc_mppi_solve refuses.  A workspace below *_workspace_bytes (which return 0 for arguments that would be refused):
  * GPMPC_E_WORKSPACE.
- * Not provided: a full-covariance linearised rollout, the device L-BFGS / augmented-Lagrangian solvers on this form, graph capture, a
- * matrix-vector form for B = 1, second-order mean corrections, multi-GPU sharding, gradients w.r.t. hyper-parameters or noise parameters.
+ *
+ * Two forms of the step (gpmpc_linearised_set_form; the step, the rollout and the MPPI solve all go through the one dispatcher):
+ *   TILE    the 64-column MFMA tile kernels of csrc/linprop.hip, whatever B is: the form for large batches, and the default.
+ *   STREAM  csrc/linprop_stream.hip, for a few columns: matrix-vector work.  k of one (column, GP) is a "vector"; vectors are taken
+ *           GPMPC_LINPROP_STREAM_COLS at a time (with a matrix per GP: that many columns of one GP; with gp_stride = 0: that many
+ *           consecutive (column, GP) pairs, so B = 1 with ds <= 4 is ONE pass over the one matrix for all GPs).  Every element of Kinv is
+ *           fetched once per group, 16 bytes per lane along a row, and used for all its vectors: for the rows of Kinv k, and with the
+ *           Jacobian for 32-row partial column sums of Kinv^T k, which a later kernel adds in ascending block order (no transposed read).
+ *           q = k^T (Kinv k).  Three launches per step without the Jacobian, five with it, independent of the number of GPs; every GP
+ *           evaluates its own exp.  Any B the TILE form takes is accepted (columns run 16 at a time); `chunk` is validated and not used.
+ *   AUTO    STREAM when B <= GPMPC_LINPROP_AUTO_MAX_B, TILE above; bit for bit the form it picked.
+ * The form is read on the host when a call is enqueued.  gpmpc_linearised_*_workspace_bytes return the need of the selected form (AUTO: the
+ * larger of the two; TILE: the values they always returned).
+ * STREAM, bit for bit: two identical calls agree; column c of a call of any B equals the B = 1 call on that column (every vector has its own
+ * accumulators, also across a group or 16-column boundary); mean and variance are the same with and without the Jacobian; the rollout equals
+ * the chain of step calls; out_g / out_gjac equal gpmpc_rollout_constraints on the returned arrays; gpmpc_mppi_solve_linearised equals the
+ * host loop.  NOT bit for bit: STREAM against TILE (other summation routes); both are held to the same long double reference.
+ * Not provided: switching the default form, a full-covariance linearised rollout, the device L-BFGS / augmented-Lagrangian solvers on this
+ * rule, graph capture, a form that reads one triangle of a symmetrised Kinv, second-order mean corrections, multi-GPU sharding, gradients
+ * w.r.t. hyper-parameters or noise parameters.
  * ------------------------------------------------------------------------- */
+#define GPMPC_LINPROP_FORM_TILE   0
+#define GPMPC_LINPROP_FORM_STREAM 1
+#define GPMPC_LINPROP_FORM_AUTO   2
+#define GPMPC_LINPROP_FORM_DEFAULT GPMPC_LINPROP_FORM_TILE   /* every call returns the bits it always returned */
+#define GPMPC_LINPROP_STREAM_COLS 4    /* vectors per pass over Kinv: 8 rows x 4 vectors of fp64 accumulators per lane */
+/* MEASURED (profiles/linprop/stream_ab.txt; one MI355X, H = 20, ds = 4, da = 1, ms per call, median of five blocks; the reference of the
+ * ratios is the TILE form of the commit before STREAM existed, timed in the same session): STREAM / TILE, objective only | with gradient
+ *      B    N=2048, Kinv per GP   N=2048, one Kinv      N=300, Kinv per GP    sparse, M=256
+ *      1    0.039 | 0.055         0.128 | 0.199         0.113 | 0.130         0.449 | 0.468
+ *      2    0.040 | 0.057         0.129 | 0.200         0.114 | 0.127         0.457 | 0.477
+ *      4    0.041 | 0.059         0.132 | 0.206         0.116 | 0.132         0.448 | 0.485
+ *      8    0.055 | 0.071         0.147 | 0.230         0.116 | 0.136         0.450 | 0.474
+ *     16    0.094 | 0.111         0.235 | 0.328         0.122 | 0.140         0.463 | 0.488
+ *     32    0.189 | 0.219         0.464 | 0.654         0.242 | 0.274         0.894 | 0.972
+ *     64    0.372 | 0.423         0.926 | 1.303         0.464 | 0.525         1.781 | 1.869
+ *    256    1.490 | 1.678         3.646 | 5.121         1.766 | 1.968         7.379 | 8.198
+ * 32 is the largest B of the grid at which STREAM is not slower than TILE on every shape, with and without the gradient. */
+#define GPMPC_LINPROP_AUTO_MAX_B  32
+/* Process-wide.  -1 only asks.  Returns the previous form; anything else is refused (GPMPC_E_ARG, gpmpc_last_error) and changes nothing. */
+int gpmpc_linearised_set_form(int form);
 /* One step of B plans: mu_prev, var_prev dev [B][ds]; U_t dev, input j of plan b at U_t[b u_stride + j] (NULL with da = 0); out_mu, out_var
  * dev [B][ds]; out_jac dev or NULL, the block of plan b at out_jac + b jac_stride (in doubles: a rollout writes [B][H][2ds][2ds+da] in
  * place).  Without out_jac neither dq/dz nor h is computed.  want_jac of the size query: whether out_jac will be given. */

@@ -8,7 +8,14 @@ gradient.  No ratio is fixed in advance; a shape where the linearised form is SL
 guide of the project): a warm-up call, then ``--blocks`` timed blocks of ``--reps`` calls with one synchronisation per block; reported are
 the median block and the spread (min ... max) of the blocks, in ms per call.  The two rules do not compute the same numbers (one is exact
 moment matching, the other its first-order approximation): the last column is how far apart their costs are on the measured (random)
-plans, for orientation only."""
+plans, for orientation only.
+
+    python tools/linprop_ab.py --form all --out profiles/linprop/stream_ab.txt
+
+``--form`` measures the forms of the linearised step (gpmpc_linearised_set_form) by the same protocol on the grid B = 1 ... 256 of the four
+shapes: ``all`` prints TILE | STREAM | moment matching per row, the ratios STREAM / TILE and STREAM / moment matching, and at B = 1 the
+Kinv bandwidth STREAM reaches per step (bytes of the matrices it streams per step over its time per step); ``tile``, ``stream`` or ``auto``
+times that form alone (the parent's TILE timing is taken with the parent's build of this tool's first table or a script like it)."""
 import argparse
 import os
 import sys
@@ -76,12 +83,61 @@ def fmt(t):
     return "%9.3f (%.3f ... %.3f)" % t
 
 
+FORM_BATCHES = (1, 2, 4, 8, 16, 32, 64, 256)
+
+
+def form_table(a, lines, save):
+    """The grid of --form: per shape and B, ms per call of every requested form and of the moment-matched rollout."""
+    H, ds, da = 20, 4, 1
+    forms = ("tile", "stream") if a.form == "all" else (a.form,)
+    shapes = [("N=2048 ds=4 per-GP Kinv", 2048, False), ("N=2048 ds=4 shared Kinv", 2048, True), ("N=300 ds=4 per-GP Kinv", 300, False),
+              ("M=256 ds=4 SparseDynamics (FITC, 2048 observations)", 256, None)]
+    batches = FORM_BATCHES
+    if a.quick:
+        shapes, batches = shapes[2:3], (1, 16)
+    cost = G.CostParams(-1.0, np.eye(ds), 0.1 * np.eye(da))
+    rng = np.random.default_rng(1)
+    lines.append("# forms of the linearised step: %s; columns per mode: %s | moment matching" % (", ".join(forms), " | ".join(forms)))
+    for name, n, shared in shapes:
+        keep = None
+        if shared is None:
+            gm, pack, keep = sparse_models(n, ds, da)
+        else:
+            gm, pack = models(n, ds, da, shared)
+        nmat = 1 if gm.c.gp_stride == 0 else ds
+        for B in batches:
+            x0 = torch.as_tensor(rng.uniform(-1, 1, (B, ds)), device="cuda")
+            U = torch.as_tensor(rng.uniform(-1, 1, (B, H, da)), device="cuda")
+            t = {}
+            for grad in (False, True):
+                for f in forms:
+                    t[f, grad] = blocks_ms(lambda: G.linearised_rollout(gm, x0, U, cost, want_grad=grad, want_traj=False, form=f), a.reps, a.blocks)
+                t["mm", grad] = blocks_ms(lambda: G.rollout(pack, x0, U, cost, want_grad=grad, want_traj=False), a.reps, a.blocks)
+            txt = "%-52s B %4d" % (name, B)
+            for grad, label in ((False, "objective"), (True, "with gradient")):
+                txt += " | %s: " % label + " ".join("%s %s" % (f, fmt(t[f, grad])) for f in forms) + " moment matching %s" % fmt(t["mm", grad])
+                if a.form == "all":
+                    txt += " stream/tile %.3f stream/mm %.3f" % (t["stream", grad][0] / t["tile", grad][0], t["stream", grad][0] / t["mm", grad][0])
+            if "stream" in forms and B == 1:
+                # one pass over every matrix per step at B = 1 (ds <= GPMPC_LINPROP_STREAM_COLS): bytes of Kinv over the time of a step
+                gb = nmat * float(gm.n) * gm.n * 8 / 1e9
+                txt += " | STREAM Kinv stream per step %.1f MB: %.2f TB/s objective, %.2f TB/s with gradient (whole call / H, launches and tail included)" % (
+                    1e3 * gb, gb / (t["stream", False][0] / H), gb / (t["stream", True][0] / H))
+            lines.append(txt)
+            print(txt, flush=True)
+            save()
+        del gm, pack, keep
+        torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
     ap.add_argument("--quick", action="store_true")
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--blocks", type=int, default=5)
+    ap.add_argument("--form", choices=("tile", "stream", "auto", "all"), default=None,
+                    help="measure the forms of the linearised step on the grid B = 1 ... 256 (all: TILE | STREAM | moment matching)")
     a = ap.parse_args()
     G.require_gpu()
     lines = ["# tools/linprop_ab.py on %s: ms per call, median block (min ... max) of %d blocks of %d calls after a warm-up; H = 20, da = 1"
@@ -93,6 +149,11 @@ def main():
             os.makedirs(os.path.dirname(a.out) or ".", exist_ok=True)
             with open(a.out, "w") as f:
                 f.write("\n".join(lines) + "\n")
+    if a.form:
+        form_table(a, lines, save)
+        lines.append("# not measured: hardware counters of the new kernels, sizes above N = 2048, other ds / da, B above 256, multi-GPU")
+        save()
+        return
     shapes = [("N=2048 ds=4 per-GP Kinv", 2048, False, (1, 16, 256, 4096)), ("N=2048 ds=4 shared Kinv", 2048, True, (1, 16, 256, 4096)),
               ("N=300 ds=4 per-GP Kinv", 300, False, (256,)), ("M=256 ds=4 SparseDynamics (FITC, 2048 observations)", 256, None, (256,))]
     if a.quick:
