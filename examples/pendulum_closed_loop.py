@@ -100,15 +100,21 @@ def main():
     ap.add_argument("--process-var", choices=("sigma_n",), default=None, help="sigma_n: add each GP's noise variance to its predicted variance")
     ap.add_argument("--inducing", type=int, default=None, metavar="M", help="sparse GP dynamics on M inducing points (FITC), chosen among the pre-training inputs")
     ap.add_argument("--inducing-select", choices=("farthest", "random"), default="farthest", help="how --inducing picks its points")
-    ap.add_argument("--propagation", choices=("moment_matching", "linearised"), default="moment_matching",
-                    help="linearised: first-order propagation mu' = m(z), var' = s2(z) + grad m^T S grad m (mpc.propagation); with the default solver, --starts K or --solver mppi")
+    ap.add_argument("--propagation", choices=("moment_matching", "linearised", "linearised_full"), default="moment_matching",
+                    help="linearised: first-order propagation mu' = m(z), var' = s2(z) + grad m^T S grad m (mpc.propagation); with the default solver, --starts K or --solver mppi.  "
+                         "linearised_full: the same rule with the whole covariance, predicted under --feedback")
+    ap.add_argument("--feedback", choices=("none", "lqr"), default="none",
+                    help="with --propagation linearised_full: lqr predicts under u = v + K (x - mu) with the LQR gain of the model linearised at the upright rest "
+                         "(linearised.lqr_gain with the controller's Q and R; mpc.set_feedback_gain)")
     ap.add_argument("--linearised-form", choices=("tile", "stream", "auto"), default=None,
                     help="with --propagation linearised: the form of the linearised step (mpc.linearised_form); stream is the matrix-vector form for B = 1")
     args = ap.parse_args()
     if args.window is not None and args.window < 1:
         ap.error("--window must be >= 1")
-    if args.propagation == "linearised" and args.solver in ("lbfgs", "auglag"):
-        ap.error("--propagation linearised runs with the default solver, --starts K or --solver mppi (the device L-BFGS / augmented Lagrangian: not yet)")
+    if args.propagation != "moment_matching" and args.solver in ("lbfgs", "auglag"):
+        ap.error("--propagation %s runs with the default solver, --starts K or --solver mppi (the device L-BFGS / augmented Lagrangian: not yet)" % args.propagation)
+    if args.feedback != "none" and args.propagation != "linearised_full":
+        ap.error("--feedback needs --propagation linearised_full")
 
     rng = np.random.default_rng(0)
     plant = PendulumPlant()
@@ -138,6 +144,11 @@ def main():
     mpc.n_starts = args.starts
     mpc.propagation = args.propagation
     mpc.linearised_form = args.linearised_form
+    if args.feedback == "lqr":
+        from gaussian_process_mpc_amd import lqr_gain
+        K = lqr_gain(mpc.dynamics, np.zeros(2), np.zeros(1), 2 * np.eye(2), 0.001 * np.eye(1))
+        mpc.set_feedback_gain(K)
+        print("feedback: LQR gain K = %s" % np.array2string(K, precision=4))
     if args.solver == "mppi":
         mpc.solver = "mppi"
         mpc.mppi_options.update(samples=args.samples, iterations=args.iters)

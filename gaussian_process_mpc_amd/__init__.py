@@ -28,6 +28,7 @@ from .device_auglag import auglag_params, auglag_merit, auglag_outer, auglag_sol
 from .sparse import SparseGPState, SparseDynamics, select_inducing      # noqa: F401
 from .particles import GPModel, gp_posterior, particle_noise, particle_step, particle_stats, particle_rollout   # noqa: F401
 from .linearised import linearised_form, linearised_step, linearised_rollout, mppi_solve_linearised   # noqa: F401
+from .linearised import linearised_step_full, linearised_fc_vjp, linearised_fc_constraints, packed_dim, lqr_gain, riccati_gain   # noqa: F401
 
 __all__ = ["GaussianProcessRegression", "Dynamics", "RiskSensitiveMPC", "mean_prop_torch",
            "variance_prop_torch", "covariance_prop_torch", "GPPack", "CostParams", "CostSchedule", "StateConstraints", "rollout", "rollout_constraints",
@@ -36,4 +37,5 @@ __all__ = ["GaussianProcessRegression", "Dynamics", "RiskSensitiveMPC", "mean_pr
            "SparseGPState", "SparseDynamics", "select_inducing",
            "GPModel", "gp_posterior", "particle_noise", "particle_step", "particle_stats", "particle_rollout",
            "linearised_form", "linearised_step", "linearised_rollout", "mppi_solve_linearised",
+           "linearised_step_full", "linearised_fc_vjp", "linearised_fc_constraints", "packed_dim", "lqr_gain", "riccati_gain",
            "Simulator", "PendulumPlant", "CartPolePlant", "lib", "require_gpu"]

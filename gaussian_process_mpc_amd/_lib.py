@@ -240,6 +240,13 @@ SIGNATURES = {
     "gpmpc_mppi_solve_linearised_workspace_bytes": (_sz, [_gm, _i, ctypes.POINTER(MppiParamsC), _sc]),
     "gpmpc_mppi_solve_linearised": (_i, [_gm, _i, _vp, _vp, ctypes.POINTER(CostParamsC), _sc, ctypes.POINTER(MppiParamsC), _vp, _vp, _vp, _vp,
                                          _sz, _vp]),
+    "gpmpc_linearised_fc_step_workspace_bytes": (_sz, [_gm, _i, _i, _i]),
+    "gpmpc_linearised_fc_step": (_i, [_gm, _i, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _vp, _sz, _i, _vp, _sz, _vp]),
+    "gpmpc_linearised_fc_rollout_workspace_bytes": (_sz, [_gm, _i, _i, _u, _i]),
+    "gpmpc_linearised_fc_rollout": (_i, [_gm, _i, _i, _vp, _vp, _vp, _sz, ctypes.POINTER(CostParamsC), _sc, _u, _vp, _vp, _vp, _vp, _vp, _vp,
+                                         _vp, _i, _vp, _sz, _vp]),
+    "gpmpc_linearised_fc_vjp": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "gpmpc_linearised_fc_constraints": (_i, [_i, _i, _i, _i, _sc, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
 
 _lib = None

@@ -351,7 +351,7 @@ static int lp_groups(const gpmpc_gp_model* m, LpGroup* g) {
 // workspace of a step: Ks [np][C] | kpart [nbi][ds][1 + D][C] | part [ds][nbi][nv][C] | with the Jacobian: hpart [nbi][ds][MAX_D][C] | g [C][ds][MAX_D]
 // `form`: the process-wide form read ONCE when the layout of a call is made.  Under TILE the offsets and the total are what they always were;
 // STREAM carves its own arrays from `base` on (gpmpc_lps_workspace_bytes); AUTO sizes for the larger of the two.
-struct LpLayout { size_t off_ks, off_kpart, off_part, off_hpart, off_g, total, base; int np, nbi, C, nv, form; };
+// (struct LpLayout: linprop_internal.h)
 static LpLayout lp_layout(const gpmpc_gp_model* m, int chunk, long ncols, bool want_jac, gpmpc_carver& c) {
     LpLayout L;
     L.form = g_lp_form.load();
@@ -414,6 +414,17 @@ static int lp_step(const gpmpc_gp_model* m, const LpTail& tail, int B, const dou
     }
     GPMPC_HIP(hipGetLastError());
     return GPMPC_OK;
+}
+
+// for linprop_fc.hip (linprop_internal.h)
+int gpmpc_lp_check_model(const char* who, const gpmpc_gp_model* m, LpTail* out) { return lp_check_model(who, m, out); }
+LpLayout gpmpc_lp_layout(const gpmpc_gp_model* m, int chunk, long ncols, bool want_jac) {
+    gpmpc_carver c;
+    return lp_layout(m, chunk, ncols, want_jac, c);
+}
+int gpmpc_lp_step(const gpmpc_gp_model* m, const LpTail& tail, int B, const double* mu_prev, const double* var_prev, size_t xs, const double* U_t,
+                  size_t us, double* out_mu, double* out_var, size_t os, double* jac, size_t js, const LpLayout& L, char* ws, hipStream_t s) {
+    return lp_step(m, tail, B, mu_prev, var_prev, xs, U_t, us, out_mu, out_var, os, jac, js, L, ws, s);
 }
 
 // ---------------------------------------------------------------------------

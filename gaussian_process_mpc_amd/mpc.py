@@ -40,6 +40,13 @@ forced by moving the rollout into one fused HIP call:
   ``GPMPC_USE_GRAPH``).  ``"moment_matching"`` (the default) is everything above, unchanged.  ``mpc.linearised_form = "tile" | "stream" |
   "auto"`` hands every one of these calls its ``form=`` (linearised.py: "stream" is the matrix-vector form for the B = 1 callbacks and the
   small batches of the multi-start); ``None``, the default, leaves the process-wide choice alone.
+* ``mpc.propagation = "linearised_full"`` (extension): the linearised rule with the WHOLE covariance, predicted
+  under the state feedback u_t = v_t + K_t (x_t - mu_t) that ``mpc.set_feedback_gain(K)`` sets (``clear_feedback_gain`` drops it;
+  ``linearised.lqr_gain`` makes a stabilising one).  The chance constraints then see a_r^T Sigma_t a_r of a plant that is steered back.
+  It serves what ``"linearised"`` serves -- the callbacks, ``evaluate_batch`` (``covs`` in the place of ``vars``), the host lock-step
+  multi-start and ``solver = "mppi"`` (a host loop of sample / rollout / update calls), with and without state constraints --;
+  ``solver = "lbfgs"`` and ``"auglag"`` refuse it (not yet).  The ``full_covariance`` attribute is not consulted under it, and
+  ``"linearised"`` with ``full_covariance=True`` keeps refusing.  A gain under any other propagation raises.
 """
 import numpy as np
 import torch
@@ -57,7 +64,7 @@ except Exception:                       # pragma: no cover
 
 
 class RiskSensitiveMPC:
-    propagation = "moment_matching"                      # | "linearised" (extension; linearised.py): which rule the rollouts of the solvers use
+    propagation = "moment_matching"                      # | "linearised" | "linearised_full" (extension; linearised.py): which rule the rollouts of the solvers use
     linearised_form = None                               # | "tile" | "stream" | "auto": the form of the linearised step (None: the process-wide one)
 
     def __init__(self, gamma, horizon, state_dim, input_dim, Q, R, R_delta=None, full_covariance=False, nominal_models=None):
@@ -290,11 +297,45 @@ class RiskSensitiveMPC:
     def _linearised(self):
         """True under ``propagation = "linearised"``, after the refusals every entry shares."""
         prop = self.propagation
-        if prop not in ("moment_matching", "linearised"):
-            raise ValueError("propagation must be 'moment_matching' or 'linearised', got %r" % (prop,))
+        if prop not in ("moment_matching", "linearised", "linearised_full"):
+            raise ValueError("propagation must be 'moment_matching', 'linearised' or 'linearised_full', got %r" % (prop,))
         if prop == "linearised" and self.full_covariance:
             raise NotImplementedError("propagation='linearised' is diagonal: a full-covariance linearised rollout is not implemented (not yet)")
-        return prop == "linearised"
+        if getattr(self, "_feedback_gain", None) is not None and prop != "linearised_full":
+            raise ValueError("a feedback gain is set (set_feedback_gain): only propagation='linearised_full' predicts under state feedback, "
+                             "got propagation=%r (clear_feedback_gain drops it)" % (prop,))
+        return prop != "moment_matching"
+
+    def _lin_kw(self):
+        """The keyword arguments that select the rule of ``linearised_rollout`` / ``mppi_solve_linearised``."""
+        if self.propagation == "linearised_full":
+            return {"full_covariance": True, "feedback": getattr(self, "_feedback_gain", None)}
+        return {}
+
+    def _fullcov_mm(self):
+        """``full_covariance`` as the moment-matching paths read it: under "linearised_full" the attribute is not consulted."""
+        return bool(self.full_covariance) and self.propagation != "linearised_full"
+
+    def set_feedback_gain(self, K):
+        """The gain of the predicted input u_t = v_t + K_t (x_t - mu_t) under ``propagation = "linearised_full"``: (da, ds) for every step or
+        (H, da, ds).  It is held as a device tensor (``feedback_gain``): writing into it in place changes the next prediction.  With any
+        other propagation every evaluation raises until ``clear_feedback_gain``.  ``lqr_gain`` makes a stabilising one."""
+        K = torch.as_tensor(np.asarray(K, dtype=np.float64), device=self.device)
+        if tuple(K.shape) not in ((self.input_dim, self.state_dim), (self.horizon, self.input_dim, self.state_dim)):
+            raise ValueError("feedback gain: (%d, %d) or (%d, %d, %d), got %s" % (self.input_dim, self.state_dim, self.horizon, self.input_dim,
+                                                                                   self.state_dim, tuple(K.shape)))
+        if not bool(torch.isfinite(K).all()):
+            raise ValueError("feedback gain: non-finite entries")
+        self._feedback_gain = K.contiguous()
+        self._cache_key = None
+
+    def clear_feedback_gain(self):
+        self._feedback_gain = None
+        self._cache_key = None
+
+    @property
+    def feedback_gain(self):
+        return getattr(self, "_feedback_gain", None)
 
     def _linearised_model(self, pack):
         """The dynamics as a ``particles.GPModel``, rebuilt when the pack or the noise model has changed."""
@@ -310,12 +351,13 @@ class RiskSensitiveMPC:
         x = np.array(x, dtype=np.float64, copy=True).reshape(-1)
         cs, pack, cp = self.curr_state, self.dynamics.pack(), self._cost_params()
         lin = self._linearised()
-        key = (x.tobytes(), None if cs is None else cs._version, bool(self.full_covariance), pack.generation, lin,
-               self.linearised_form if lin else None)
+        fb = getattr(self, "_feedback_gain", None)
+        key = (x.tobytes(), None if cs is None else cs._version, bool(self.full_covariance), pack.generation, self.propagation if lin else lin,
+               self.linearised_form if lin else None, None if fb is None else (id(fb), fb._version))
         held = getattr(self, "_cache_held", (None, None, None))    # kept alive so that `is` cannot alias later objects
         sc = self.state_constraints
         if sc is not None:
-            if self.full_covariance:
+            if self._fullcov_mm():
                 raise NotImplementedError("state constraints under the full-covariance rollout are not implemented "
                                           "(q = a^T Sigma_t a and that path's Jacobian layout: a follow-up)")
             key = key + (id(sc),)
@@ -324,7 +366,7 @@ class RiskSensitiveMPC:
                 # one B = 1 linearised rollout per x: cost, gradient and, with constraints, g and its dense Jacobian from the same pass
                 from .linearised import linearised_rollout
                 r = linearised_rollout(self._linearised_model(pack), cs, x.reshape(1, self.horizon, self.input_dim), cp, want_grad=True,
-                                       want_traj=False, constraints=sc, form=self.linearised_form)
+                                       want_traj=False, constraints=sc, form=self.linearised_form, **self._lin_kw())
                 self.curr_cost = float(r["cost"][0].item())
                 self.curr_grad = r["grad"][0].cpu().numpy()
                 if sc is not None:
@@ -392,7 +434,8 @@ class RiskSensitiveMPC:
         if lin:
             from .linearised import linearised_rollout
             return linearised_rollout(self._linearised_model(self.dynamics.pack()), cs, U, self._cost_params(), want_grad=want_grad,
-                                      want_traj=True, constraints=self.state_constraints if constraints else None, form=self.linearised_form)
+                                      want_traj=True, constraints=self.state_constraints if constraints else None, form=self.linearised_form,
+                                      **self._lin_kw())
         if constraints:
             if self.full_covariance:
                 raise NotImplementedError("state constraints under the full-covariance rollout are not implemented")
@@ -491,7 +534,7 @@ class RiskSensitiveMPC:
         if solver == "mppi":
             if (self.n_starts if n_starts is None else n_starts) > 1:
                 raise ValueError("solver='mppi' is one search over its own samples: it does not combine with n_starts > 1")
-            if self.full_covariance:
+            if self._fullcov_mm():
                 raise NotImplementedError("solver='mppi' runs the diagonal rollout (gpmpc_mppi_solve): MPPI over the full-covariance "
                                           "rollout is not implemented")
         k = getattr(self, "step_index", 0)
@@ -516,7 +559,7 @@ class RiskSensitiveMPC:
             return self._keep_plan(self._solve_device_auglag(max(int(K), 1), lb, ub))
         if solver == "lbfgs":
             return self._keep_plan(self._solve_device_lbfgs(max(int(K), 1), lb, ub))
-        if sc is not None and self.full_covariance:
+        if sc is not None and self._fullcov_mm():
             raise NotImplementedError("state constraints under the full-covariance rollout are not implemented "
                                       "(q = a^T Sigma_t a and that path's Jacobian layout: a follow-up)")
         if sc is not None and K > 1:
@@ -604,7 +647,7 @@ class RiskSensitiveMPC:
         r = solve(self._linearised_model(self.dynamics.pack()) if lin else self.dynamics.pack(), self.curr_state, start, self._cost_params(),
                   constraints=self.state_constraints, samples=int(opt.get("samples", 64)), iterations=int(opt.get("iterations", 30)), sigma=sigma,
                   decay=float(opt.get("decay", 0.9)), beta=float(opt.get("beta", 0.1)), seed=int(opt.get("seed", 0)),
-                  call_index=self._solve_count, lb=lb, ub=ub, **({"form": self.linearised_form} if lin else {}))
+                  call_index=self._solve_count, lb=lb, ub=ub, **(dict(self._lin_kw(), form=self.linearised_form) if lin else {}))
         self._solve_count += 1
         self.solver_used = "mppi x%d" % int(opt.get("samples", 64))
         self.last_solve_info = {"cost": r["cost"], "violation": r["violation"], "feasible": r["feasible"], "success": r["feasible"],
@@ -667,7 +710,8 @@ class RiskSensitiveMPC:
         def run(x0b, Ub, graph):
             if lin:                                                       # (plain launches: graph replay of the linearised rollout is not provided)
                 from .linearised import linearised_rollout
-                return linearised_rollout(self._linearised_model(pack), x0b, Ub, cp, want_grad=True, want_traj=False, form=self.linearised_form)
+                return linearised_rollout(self._linearised_model(pack), x0b, Ub, cp, want_grad=True, want_traj=False, form=self.linearised_form,
+                                          **self._lin_kw())
             if self.full_covariance:
                 return rollout_fullcov(pack, x0b, Ub, cp, want_grad=True)
             return rollout(pack, x0b, Ub, cp, want_grad=True, want_traj=False, graph=graph)

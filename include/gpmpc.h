@@ -180,7 +180,8 @@ int gpmpc_pack_get_nominal(const gpmpc_pack* pack, double* weights_host, double*
  * of init_cov; a negative entry of action_var or process_var; |P_kl - P_lk| > 1e-12 max |P| (else the mean of each off-diagonal pair is
  * stored).  Zero variances are legal (an exactly known start state or input: B_k = 1 / lambda_k).
  * gpmpc_moment_match takes S from its caller and does not read the model.  Not provided: a different init_cov per trajectory of a batch, a
- * full process-noise matrix, gradients with respect to the noise parameters, state feedback inside the prediction. */
+ * full process-noise matrix, gradients with respect to the noise parameters, state feedback inside the moment-matched prediction (the
+ * linearised rule has it: "Linearised propagation, full covariance"). */
 int gpmpc_pack_set_noise(gpmpc_pack* pack, const double* init_cov_host, const double* action_var_host, const double* process_var_host,
                          void* stream);
 /* The three parts into the arrays that are not NULL.  1: some part differs from its default, 0: none does; GPMPC_E_ARG. */
@@ -947,7 +948,8 @@ int gpmpc_particle_rollout(const gpmpc_gp_model* model_host, int B, int P, int H
  * from the same numbers.  The step Jacobian has the layout of gpmpc_rollout_jac, [2ds][2ds+da], rows (mu', v'), columns (mu, v, u):
  *     row mu'_a:  g_ak in the mu columns, 0 in the v columns, g_a,ds+j in the u columns
  *     row v'_a:   -dq_a/dz_k + 2 h_ak in the mu columns, g_ak^2 in the v columns, -dq_a/dz_{ds+j} + 2 h_a,ds+j in the u columns
- * The propagation is diagonal, as in gpmpc_rollout: cross-covariances between states are dropped.
+ * The propagation is diagonal, as in gpmpc_rollout: cross-covariances between states are dropped (the rule that carries the whole Sigma,
+ * and a state feedback inside the prediction: "Linearised propagation, full covariance" below).
  *
  * No atomics, fixed summation orders, launch geometry from the sizes only: two identical calls agree bit for bit and no result depends on
  * `chunk` (columns, i.e. plans, are independent; a multiple of 64, 0: 4096).  B = 1 runs the same tile kernels with padded columns.
@@ -977,7 +979,7 @@ int gpmpc_particle_rollout(const gpmpc_gp_model* model_host, int B, int P, int H
  * accumulators, also across a group or 16-column boundary); mean and variance are the same with and without the Jacobian; the rollout equals
  * the chain of step calls; out_g / out_gjac equal gpmpc_rollout_constraints on the returned arrays; gpmpc_mppi_solve_linearised equals the
  * host loop.  NOT bit for bit: STREAM against TILE (other summation routes); both are held to the same long double reference.
- * Not provided: switching the default form, a full-covariance linearised rollout, the device L-BFGS / augmented-Lagrangian solvers on this
+ * Not provided: switching the default form, the device L-BFGS / augmented-Lagrangian solvers on this
  * rule, graph capture, a form that reads one triangle of a symmetrised Kinv, second-order mean corrections, multi-GPU sharding, gradients
  * w.r.t. hyper-parameters or noise parameters.
  * ------------------------------------------------------------------------- */
@@ -1028,6 +1030,98 @@ int gpmpc_mppi_solve_linearised(const gpmpc_gp_model* model_host, int H, const d
                                 const gpmpc_cost_params* cost_host, const gpmpc_state_constraints* cons_host,
                                 const gpmpc_mppi_params* params_host, double* out_U, double* out_best, double* out_trace, void* workspace,
                                 size_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------
+ * Linearised propagation, full covariance, with a linear state feedback: the rule above with the whole Sigma carried and the predicted
+ * input u_t = v_t + K_t (x_t - mu_t), as in the cautious-MPC literature (kernels in csrc/linprop_fc.hip).  The two
+ * belong together: feedback makes the covariance of z = (x, u) non-diagonal by construction, Cov[x, u] = Sigma K^T.
+ *
+ * One step.  Inputs: the mean mu (ds), the symmetric covariance Sigma (ds x ds; only the upper triangle k <= l is read), the nominal input
+ * v (da), a gain K (da x ds, or none: 0).  zbar = (mu, v), because the mean of u is v.  D = ds + da.  k_i, d_id, m_a, g_ad, q_a, r_a and
+ * d q_a / d z_d are those of "Linearised propagation" above, nominal model included, evaluated at zbar.  For GP a:
+ *     Hm_a[d][l] = sum_i beta_ia k_i (d_id d_il - [d = l] / lambda_ad)      (= d^2 m_a / d z_d d z_l; the nominal part has no curvature)
+ *     T   = [I_ds ; K]  (D x ds)        Sz = T Sigma T^T + diag(0...0, action_var)        (D x D, symmetric)
+ *     P_a = G_a T  (ds)                 i.e. P_ak = g_ak + sum_j g_a,ds+j K_jk             (the closed-loop gradient)
+ *     W_b = Sz G_b^T  (D)
+ *     mu'_a     = m_a
+ *     Sigma'_ab = [a = b] (sf_a^2 - q_a + process_var_a) + G_a . W_b      (unclamped; computed for a <= b and mirrored: exactly symmetric)
+ * Equivalently Sigma' = diag(s2) + P Sigma P^T + G_u diag(action_var) G_u^T.  The GPs are independent given z, so the latent part is
+ * diagonal.  With K = 0 and a diagonal Sigma the diagonal of Sigma' is v' of the diagonal rule.
+ *
+ * State vector and Jacobian.  s = (mu_1 ... mu_ds, Sigma_kl for k <= l, row-major), of length p = ds + ds (ds + 1) / 2.  The step Jacobian
+ * is [p][p + da], rows s', columns (s, v); an off-diagonal Sigma_kl = Sigma_lk counts as ONE variable; every element is written:
+ *     d mu'_a / d mu_k = g_ak        d mu'_a / d v_j = g_a,ds+j        d mu'_a / d Sigma_kl = 0
+ *     d Sigma'_ab / d zbar_d  = -[a = b] d q_a / d z_d + (Hm_a W_b)_d + (Hm_b W_a)_d          (d over the mu and the v columns)
+ *     d Sigma'_ab / d Sigma_kl = P_ak P_bl + P_al P_bk  (k < l),   P_ak P_bk  (k = l)
+ * For a = b, K = 0 and a diagonal Sigma the zbar columns are 2h - dq/dz of the diagonal rule.
+ *
+ * Rollout.  mu_0 = x0, Sigma_0 = init_cov, the whole matrix (the upper triangle, mirrored), as in the full-covariance moment-matching
+ * forms; the step at t uses K_t.  The cost is the risk-sensitive cost on full covariances, the kernels behind gpmpc_cost / gpmpc_cost_grad
+ * at (mu_t, Sigma_t, v_t), cost schedules honoured; the gradient is an adjoint sweep over the packed Jacobians seeded by d_means and
+ * d_covs (the adjoint of the variable Sigma_kl, k < l, is d_covs[k][l] + d_covs[l][k]), plus d_U.  Chance constraints use the whole
+ * matrix, g[t][r] = a_r . mu_t + kappa_r sqrt(a_r^T Sigma_t a_r) - b_r, their dense Jacobian [B][H n_rows][H da] from a forward-sensitivity
+ * sweep over the packed Jacobians by the rules of gpmpc_rollout_constraints: a radicand <= 0 gives sd = 0 and no variance part, a NaN step
+ * poisons its own rows only, columns tau >= t are exactly 0.0, every element is written.
+ *
+ * How it runs.  Stage A is the diagonal step itself, through the one dispatcher (TILE, STREAM or AUTO as selected), on a copy of the
+ * model with action_var = 0 and a zeroed variance, with its Jacobian: that gives m, s2, g and -dq/dz, and holds all the O(N^2) work; out_mu
+ * is bit for bit the out_mu of gpmpc_linearised_step in the same form.  New per step: k_lpf_hess (O(N D^2) per (plan, GP): the D (D + 1) / 2
+ * second-derivative sums, N exp), k_lpf_hfin, and k_lpf_close (one wave per plan).  Without a Jacobian the Hessian pass is skipped; stage
+ * A still computes g and dq/dz (Sigma' needs g), so the objective-only call costs more than the diagonal one's.  No atomics, fixed
+ * summation orders, launch geometry from the sizes only: two identical calls agree bit for bit, nothing depends on `chunk`, Sigma' and
+ * the mean are the same with and without the Jacobian, the rollout is the chain of step calls, out_g / out_gjac equal
+ * gpmpc_linearised_fc_constraints on the returned arrays.
+ *
+ * The gain: const double* K_dev + size_t k_step_stride (in doubles).  NULL: no feedback.  Stride 0: one [da][ds] gain for every step;
+ * stride da ds: [H][da][ds].  It lives in device memory: a closed loop can change it without touching an argument.
+ *
+ * Refusals (GPMPC_E_ARG with a text, before any launch): everything the diagonal entry points refuse, and a non-finite init_cov, an
+ * asymmetric one (|P_kl - P_lk| > 1e-12 max |P|, the particles' rule) or one with a negative pivot; k_step_stride other than 0 or da ds; a
+ * gain when da = 0; jac_stride < p (p + da) with B > 1; B H above 2^40 Jacobian elements; a horizon beyond the sweeps' grid.  The sweep
+ * kernels keep no per-step state (the adjoint holds p doubles per plan in LDS, the constraints sweep 2 p doubles per lane), so unlike
+ * the diagonal rule's tail kernel no LDS bounds H; the constraints sweep runs ceil(H da / 64) workgroups per plan along gridDim.y, which
+ * gives the limit H da <= 64 x 65535.  The workspace-size queries return 0 for arguments that would be refused.
+ *
+ * MEASURED (profiles/linprop/fc_ab.txt; one MI355X, H = 20, ds = 4, da = 1, a Kinv per GP, ms per call, median of five alternating blocks;
+ * the reference of the ratios is the diagonal linearised rollout of the same build): full / diagonal, objective only | with gradient
+ *      shape, B             TILE              STREAM
+ *      N=2048, B=1       1.285 | 1.055     2.360 | 1.768
+ *      N=2048, B=16      1.284 | 1.039     1.789 | 1.380
+ *      N=2048, B=256     1.342 | 1.065     1.533 | 1.025
+ *      N=2048, B=4096    1.138 | 1.093     1.512 | 1.010
+ *      N=300,  B=256     1.771 | 1.207     1.824 | 1.086
+ *      sparse M=256, 256 2.269 | 1.826     1.739 | 1.105
+ * With the gradient: the O(N D^2) pass and the per-plan close, small at N = 2048, visible at N = 300 and M = 256.  Objective only it is
+ * worse than the operation count says, for the reason above (stage A delivers g only with its whole Jacobian).  Not measured: one Kinv for
+ * all GPs, other ds / da / H, per-kernel times, hardware counters.
+ * Not provided: the input-cost term tr(R K Sigma K^T) and input constraints tightened by K Sigma K^T; a gain per plan of a batch; the
+ * device L-BFGS and augmented-Lagrangian solvers on this rule; graph capture; particles under feedback; gains chosen by the optimiser; a
+ * single-enqueue MPPI solve (the Python layer loops gpmpc_mppi_sample, this rollout, gpmpc_mppi_update).
+ * ------------------------------------------------------------------------- */
+/* One step of B plans.  mu_prev dev [B][ds]; cov_prev dev [B][ds][ds]; U_t dev, input j of plan b at U_t[b u_stride + j] (NULL with
+ * da = 0); K_dev dev [da][ds] or NULL; out_mu dev [B][ds]; out_cov dev [B][ds][ds]; out_jac dev or NULL, the [p][p+da] block of plan b at
+ * out_jac + b jac_stride.  want_jac of the size query: whether out_jac will be given. */
+size_t gpmpc_linearised_fc_step_workspace_bytes(const gpmpc_gp_model* model_host, int B, int want_jac, int chunk);
+int gpmpc_linearised_fc_step(const gpmpc_gp_model* model_host, int B, const double* mu_prev, const double* cov_prev, const double* U_t,
+                             size_t u_stride, const double* K_dev, double* out_mu, double* out_cov, double* out_jac, size_t jac_stride,
+                             int chunk, void* workspace, size_t workspace_bytes, void* stream);
+/* B rollouts of H steps.  The arguments of gpmpc_linearised_rollout, except: out_covs dev [B][H+1][ds][ds] in the place of out_vars,
+ * out_jac dev [B][H][p][p+da], and the gain pair. */
+size_t gpmpc_linearised_fc_rollout_workspace_bytes(const gpmpc_gp_model* model_host, int B, int H, unsigned flags, int chunk);
+int gpmpc_linearised_fc_rollout(const gpmpc_gp_model* model_host, int B, int H, const double* x0, const double* U, const double* K_dev,
+                                size_t k_step_stride, const gpmpc_cost_params* cost_host, const gpmpc_state_constraints* cons_host,
+                                unsigned flags, double* out_means, double* out_covs, double* out_jac, double* out_cost, double* out_grad,
+                                double* out_g, double* out_gjac, int chunk, void* workspace, size_t workspace_bytes, void* stream);
+/* Pure function of a propagated trajectory, like gpmpc_rollout_vjp: jac dev [B][H][p][p+da]; g_means dev [B][H+1][ds], g_covs dev
+ * [B][H+1][ds][ds] (upstream gradients of every step's mean / covariance entries; either may be NULL: zero) -> out_gU dev [B][H][da]
+ * and, unless NULL, out_gx0 dev [B][ds]. */
+int gpmpc_linearised_fc_vjp(int B, int H, int state_dim, int action_dim, const double* jac_dev, const double* g_means,
+                            const double* g_covs, double* out_gU, double* out_gx0, void* stream);
+/* Pure function of a propagated trajectory, like gpmpc_rollout_constraints: means dev [B][H+1][ds], covs dev [B][H+1][ds][ds], jac dev
+ * [B][H][p][p+da] (NULL with out_gjac NULL) -> out_g dev [B][H][n_rows] and, unless NULL, out_gjac dev [B][H n_rows][H da]. */
+int gpmpc_linearised_fc_constraints(int B, int H, int state_dim, int action_dim, const gpmpc_state_constraints* cons_host,
+                                    const double* means, const double* covs, const double* jac_dev, double* out_g, double* out_gjac,
+                                    void* stream);
 
 #ifdef __cplusplus
 }
