@@ -100,9 +100,10 @@ def main():
     ap.add_argument("--process-var", choices=("sigma_n",), default=None, help="sigma_n: add each GP's noise variance to its predicted variance")
     ap.add_argument("--inducing", type=int, default=None, metavar="M", help="sparse GP dynamics on M inducing points (FITC), chosen among the pre-training inputs")
     ap.add_argument("--inducing-select", choices=("farthest", "random"), default="farthest", help="how --inducing picks its points")
-    ap.add_argument("--propagation", choices=("moment_matching", "linearised", "linearised_full"), default="moment_matching",
+    ap.add_argument("--propagation", choices=("moment_matching", "moment_matching_full", "linearised", "linearised_full"), default="moment_matching",
                     help="linearised: first-order propagation mu' = m(z), var' = s2(z) + grad m^T S grad m (mpc.propagation); with the default solver, --starts K or --solver mppi.  "
-                         "linearised_full: the same rule with the whole covariance, predicted under --feedback")
+                         "linearised_full: the same rule with the whole covariance, predicted under --feedback.  "
+                         "moment_matching_full: exact moment matching with the whole covariance (chance rows on a^T Sigma a), every solver; not with --nominal")
     ap.add_argument("--feedback", choices=("none", "lqr"), default="none",
                     help="with --propagation linearised_full: lqr predicts under u = v + K (x - mu) with the LQR gain of the model linearised at the upright rest "
                          "(linearised.lqr_gain with the controller's Q and R; mpc.set_feedback_gain)")
@@ -111,10 +112,14 @@ def main():
     args = ap.parse_args()
     if args.window is not None and args.window < 1:
         ap.error("--window must be >= 1")
-    if args.propagation != "moment_matching" and args.solver in ("lbfgs", "auglag"):
+    if args.propagation in ("linearised", "linearised_full") and args.solver in ("lbfgs", "auglag"):
         ap.error("--propagation %s runs with the default solver, --starts K or --solver mppi (the device L-BFGS / augmented Lagrangian: not yet)" % args.propagation)
     if args.feedback != "none" and args.propagation != "linearised_full":
         ap.error("--feedback needs --propagation linearised_full")
+    if args.propagation == "moment_matching_full" and args.nominal != "none":
+        ap.error("--propagation moment_matching_full does not combine with --nominal (the full-covariance rollout knows no nominal model)")
+    if args.propagation == "moment_matching_full" and args.max_speed is not None and args.starts > 1 and args.solver == "default":
+        ap.error("--propagation moment_matching_full with --max-speed and --starts K > 1 needs --solver auglag")
 
     rng = np.random.default_rng(0)
     plant = PendulumPlant()

@@ -20,7 +20,7 @@ from .dynamics import Dynamics                                          # noqa: 
 from .mpc import RiskSensitiveMPC                                       # noqa: F401
 from .uncertainty_prop import mean_prop_torch, variance_prop_torch, covariance_prop_torch  # noqa: F401
 from .simulator import Simulator, PendulumPlant, CartPolePlant          # noqa: F401
-from .rollout import GPPack, CostParams, CostSchedule, StateConstraints, rollout, rollout_constraints, rollout_fullcov, moment_match   # noqa: F401
+from .rollout import GPPack, CostParams, CostSchedule, StateConstraints, rollout, rollout_constraints, rollout_fullcov, rollout_fullcov_jac, moment_match   # noqa: F401
 from .nominal import LinearNominalModel                                 # noqa: F401
 from .mppi import mppi_sample, mppi_update, mppi_solve                  # noqa: F401
 from .device_lbfgs import lbfgs_start, lbfgs_tick, lbfgs_solve, lbfgs_state_view, lbfgs_state_fields   # noqa: F401
@@ -32,7 +32,7 @@ from .linearised import linearised_step_full, linearised_fc_vjp, linearised_fc_c
 
 __all__ = ["GaussianProcessRegression", "Dynamics", "RiskSensitiveMPC", "mean_prop_torch",
            "variance_prop_torch", "covariance_prop_torch", "GPPack", "CostParams", "CostSchedule", "StateConstraints", "rollout", "rollout_constraints",
-           "rollout_fullcov", "moment_match", "LinearNominalModel", "mppi_sample", "mppi_update", "mppi_solve", "lbfgs_start", "lbfgs_tick", "lbfgs_solve", "lbfgs_state_view", "lbfgs_state_fields",
+           "rollout_fullcov", "rollout_fullcov_jac", "moment_match", "LinearNominalModel", "mppi_sample", "mppi_update", "mppi_solve", "lbfgs_start", "lbfgs_tick", "lbfgs_solve", "lbfgs_state_view", "lbfgs_state_fields",
            "auglag_params", "auglag_merit", "auglag_outer", "auglag_solve", "auglag_state_view", "auglag_state_fields",
            "SparseGPState", "SparseDynamics", "select_inducing",
            "GPModel", "gp_posterior", "particle_noise", "particle_step", "particle_stats", "particle_rollout",

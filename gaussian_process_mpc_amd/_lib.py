@@ -193,6 +193,19 @@ SIGNATURES = {
     "gpmpc_rollout_fullcov_workspace_bytes": (_sz, [_vp, _i, _i, _u]),
     "gpmpc_rollout_fullcov_describe": (_i, [_vp, _i, _i, _u, ctypes.c_char_p, _sz]),
     "gpmpc_rollout_fullcov": (_i, [_vp, _i, _i, _vp, _vp, ctypes.POINTER(CostParamsC), _u, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "gpmpc_rollout_fullcov_jac_workspace_bytes": (_sz, [_vp, _i, _i]),
+    "gpmpc_rollout_fullcov_jac": (_i, [_vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "gpmpc_rollout_fullcov_constrained_workspace_bytes": (_sz, [_vp, _i, _i, _u]),
+    "gpmpc_rollout_fullcov_constrained": (_i, [_vp, _i, _i, _vp, _vp, ctypes.POINTER(CostParamsC), ctypes.POINTER(StateConstraintsC), _u,
+                                               _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "gpmpc_mppi_solve_fullcov_workspace_bytes": (_sz, [_vp, _i, ctypes.POINTER(MppiParamsC), ctypes.POINTER(StateConstraintsC)]),
+    "gpmpc_mppi_solve_fullcov": (_i, [_vp, _i, _vp, _vp, ctypes.POINTER(CostParamsC), ctypes.POINTER(StateConstraintsC),
+                                      ctypes.POINTER(MppiParamsC), _vp, _vp, _vp, _vp, _sz, _vp]),
+    "gpmpc_lbfgs_solve_fullcov_workspace_bytes": (_sz, [_vp, _i, ctypes.POINTER(LbfgsParamsC)]),
+    "gpmpc_lbfgs_solve_fullcov": (_i, [_vp, _i, _vp, _vp, ctypes.POINTER(CostParamsC), ctypes.POINTER(LbfgsParamsC), _i, _i, _vp, _sz, _vp]),
+    "gpmpc_auglag_solve_fullcov_workspace_bytes": (_sz, [_vp, _i, ctypes.POINTER(StateConstraintsC), ctypes.POINTER(AuglagParamsC)]),
+    "gpmpc_auglag_solve_fullcov": (_i, [_vp, _i, _vp, _vp, ctypes.POINTER(CostParamsC), ctypes.POINTER(StateConstraintsC),
+                                        ctypes.POINTER(AuglagParamsC), _i, _i, _vp, _sz, _vp]),
     "gpmpc_timing_enable": (_i, [_i]),
     "gpmpc_debug_run_list": (_i, [_i, _i, _i, ctypes.POINTER(_i), _i, ctypes.POINTER(_i)]),
     "gpmpc_debug_work_list": (_i, [_i] * 7 + [ctypes.POINTER(_i), _i, ctypes.POINTER(_i), ctypes.POINTER(_i), ctypes.POINTER(_i)]),
@@ -280,14 +293,14 @@ def check(rc, what):
     if rc != 0:
         detail = lib().gpmpc_last_error().decode() if rc == -3 else ""
         if rc == -1 and ("mppi" in what or "lbfgs" in what or "auglag" in what or "sparse" in what or "particle" in what
-                         or "gp_posterior" in what or "linearised" in what):    # these refusals say which parameter
+                         or "gp_posterior" in what or "linearised" in what or "fullcov_" in what):    # these refusals say which parameter
             detail = lib().gpmpc_last_error().decode()
         if rc == -1 and not detail:        # refusals of a cost schedule say which and why
             why = lib().gpmpc_last_error().decode()
             detail = why if "cost schedule" in why else ""
         if rc == -5:                       # refusals on a pack with a nominal model say why (others leave the text alone)
             why = lib().gpmpc_last_error().decode()
-            detail = why if "nominal model" in why else ""
+            detail = why if ("nominal model" in why or why.startswith(what + ":")) else ""      # (its own text: never a stale one)
         raise GpmpcError(f"{what} failed: {_ERR.get(rc, rc)} {detail}".strip())
 
 

@@ -268,8 +268,8 @@ extern "C" int gpmpc_auglag_outer(int H, int da, int n_rows, const gpmpc_auglag_
 
 // workspace of a solve: state | the inner search's state | x0 [K][ds] | cost [K] | grad [K][n] | g [K][R] | g_jac [K][R][n] | M [K] |
 // merit gradient [K][n] | copy of X [K][n] | the rollout's own workspace
-struct AlWorkspace { size_t off_lb, off_x0, off_cost, off_grad, off_g, off_gjac, off_M, off_gM, off_copy, off_roll, roll_bytes, total; };
-static AlWorkspace al_workspace(const gpmpc_pack* p, int H, int K, int n_rows, const AlLayout& L, const LbfgsLayout& LB) {
+struct AlWorkspace { size_t off_lb, off_x0, off_cost, off_grad, off_g, off_gjac, off_M, off_gM, off_copy, off_roll, total; gpmpc_solver_eval_layout roll; };
+static AlWorkspace al_workspace(const gpmpc_pack* p, int H, int K, int n_rows, const AlLayout& L, const LbfgsLayout& LB, gpmpc_solver_rule rule) {
     AlWorkspace W;
     const size_t n = (size_t)H * p->da, R = (size_t)H * n_rows, d = sizeof(double);
     gpmpc_carver c;
@@ -283,36 +283,43 @@ static AlWorkspace al_workspace(const gpmpc_pack* p, int H, int K, int n_rows, c
     W.off_M = c.take(d * K);
     W.off_gM = c.take(d * K * n);
     W.off_copy = c.take(d * K * n);
-    W.roll_bytes = gpmpc_rollout_constrained_workspace_bytes(p, K, H, GPMPC_WANT_GRAD);
-    W.off_roll = c.take(W.roll_bytes);
+    W.roll = gpmpc_solver_eval_bytes(rule, p, K, H, true, GPMPC_WANT_GRAD);
+    W.off_roll = c.take(W.roll.total);
     W.total = c.total();
     return W;
 }
 
-extern "C" size_t gpmpc_auglag_solve_workspace_bytes(const gpmpc_pack* p, int H, const gpmpc_state_constraints* cons,
-                                                     const gpmpc_auglag_params* P) {
+static size_t al_solve_bytes(gpmpc_solver_rule rule, const gpmpc_pack* p, int H, const gpmpc_state_constraints* cons, const gpmpc_auglag_params* P) {
     if (!p || !P || !cons || !al_rows_ok(cons->n_rows)) return 0;
     const int K = P->inner.n_starts, m = P->inner.history;
     if (K < 1 || K > GPMPC_LBFGS_MAX_STARTS || m < 1 || m > GPMPC_LBFGS_MAX_HISTORY || !gpmpc_solver_dims_ok(H, p->ds, p->da)) return 0;
     const long n = (long)H * p->da;
-    return al_workspace(p, H, K, cons->n_rows, al_layout(K, n, (long)H * cons->n_rows), lbfgs_layout(K, n, m)).total;
+    return al_workspace(p, H, K, cons->n_rows, al_layout(K, n, (long)H * cons->n_rows), lbfgs_layout(K, n, m), rule).total;
+}
+extern "C" size_t gpmpc_auglag_solve_workspace_bytes(const gpmpc_pack* p, int H, const gpmpc_state_constraints* cons,
+                                                     const gpmpc_auglag_params* P) {
+    return al_solve_bytes(GPMPC_RULE_DIAGONAL, p, H, cons, P);
+}
+extern "C" size_t gpmpc_auglag_solve_fullcov_workspace_bytes(const gpmpc_pack* p, int H, const gpmpc_state_constraints* cons,
+                                                             const gpmpc_auglag_params* P) {
+    return al_solve_bytes(GPMPC_RULE_FULLCOV, p, H, cons, P);
 }
 
-extern "C" int gpmpc_auglag_solve(const gpmpc_pack* p, int H, const double* x0, const double* X0, const gpmpc_cost_params* cost,
-                                  const gpmpc_state_constraints* cons, const gpmpc_auglag_params* P, int first_outer, int n_outer,
-                                  void* workspace, size_t workspace_bytes, void* stream) {
-    const char* who = "gpmpc_auglag_solve";
+// the solve of both entries; the rule decides the one evaluation (solver_frame.h)
+static int al_solve(gpmpc_solver_rule rule, const char* who, const gpmpc_pack* p, int H, const double* x0, const double* X0,
+                    const gpmpc_cost_params* cost, const gpmpc_state_constraints* cons, const gpmpc_auglag_params* P, int first_outer,
+                    int n_outer, void* workspace, size_t workspace_bytes, void* stream) {
     if (!p || !x0 || !cost || !cons || !P || !workspace || H < 1 || (first_outer == 0 && !X0)) return GPMPC_E_ARG;
     if (int rc = al_check_scalars(P, who)) return rc;                    // (before the pack is looked at)
     if (first_outer < 0) return gpmpc_refuse(who, "first_outer is negative");
     if (n_outer < 0) return gpmpc_refuse(who, "n_outer is negative");
-    if (int rc = gpmpc_solver_enter(p, H, cost, cons, who, [&](int da) { return gpmpc_check_bounds(P->inner.lb, P->inner.ub, da, who); }))
+    if (int rc = gpmpc_solver_enter(p, H, cost, cons, who, [&](int da) { return gpmpc_check_bounds(P->inner.lb, P->inner.ub, da, who); }, rule))
         return rc;
     const gpmpc_lbfgs_params& PI = P->inner;
     const int K = PI.n_starts, n = H * p->da, R = H * cons->n_rows, ds = p->ds, da = p->da;
     const AlLayout L = al_layout(K, n, R);
     const LbfgsLayout LB = lbfgs_layout(K, n, PI.history);
-    const AlWorkspace W = al_workspace(p, H, K, cons->n_rows, L, LB);
+    const AlWorkspace W = al_workspace(p, H, K, cons->n_rows, L, LB, rule);
     if (workspace_bytes < W.total) return GPMPC_E_WORKSPACE;
     hipStream_t s = (hipStream_t)stream;
     char* ws = (char*)workspace;
@@ -321,8 +328,7 @@ extern "C" int gpmpc_auglag_solve(const gpmpc_pack* p, int H, const double* x0, 
     double *M = (double*)(ws + W.off_M), *gM = (double*)(ws + W.off_gM), *copy = (double*)(ws + W.off_copy);
     double *U = lb + LB.U, *X = lb + LB.X;
     auto evaluate = [&]() {
-        return gpmpc_rollout_constrained(p, K, H, x0b, U, cost, cons, GPMPC_WANT_GRAD, nullptr, nullptr, cst, grd, g, gjac, ws + W.off_roll,
-                                         W.roll_bytes, stream);
+        return gpmpc_solver_eval(rule, p, K, H, x0b, U, cost, cons, GPMPC_WANT_GRAD, cst, grd, g, gjac, ws + W.off_roll, W.roll, stream);
     };
     auto merit = [&]() { return al_launch_merit(K, n, R, cst, grd, g, gjac, st + L.lam, st + L.rho, M, gM, s); };
     if (first_outer == 0) {
@@ -355,4 +361,18 @@ extern "C" int gpmpc_auglag_solve(const gpmpc_pack* p, int H, const double* x0, 
     if (searched)
         if (int rc = lbfgs_launch_finish(n, PI, LB, lb, s)) return rc;
     return al_launch_finish(K, n, R, L, searched ? lb + LB.alive : nullptr, st, s);
+}
+
+extern "C" int gpmpc_auglag_solve(const gpmpc_pack* p, int H, const double* x0, const double* X0, const gpmpc_cost_params* cost,
+                                  const gpmpc_state_constraints* cons, const gpmpc_auglag_params* P, int first_outer, int n_outer,
+                                  void* workspace, size_t workspace_bytes, void* stream) {
+    return al_solve(GPMPC_RULE_DIAGONAL, "gpmpc_auglag_solve", p, H, x0, X0, cost, cons, P, first_outer, n_outer, workspace, workspace_bytes,
+                    stream);
+}
+
+extern "C" int gpmpc_auglag_solve_fullcov(const gpmpc_pack* p, int H, const double* x0, const double* X0, const gpmpc_cost_params* cost,
+                                          const gpmpc_state_constraints* cons, const gpmpc_auglag_params* P, int first_outer, int n_outer,
+                                          void* workspace, size_t workspace_bytes, void* stream) {
+    return al_solve(GPMPC_RULE_FULLCOV, "gpmpc_auglag_solve_fullcov", p, H, x0, X0, cost, cons, P, first_outer, n_outer, workspace,
+                    workspace_bytes, stream);
 }

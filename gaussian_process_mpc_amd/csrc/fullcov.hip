@@ -11,6 +11,7 @@
 // risk-sensitive cost with full Sigma (src/mpc.py:179-198) and runs the reverse sweep.
 #include <cstdio>
 #include "gpmpc_internal.h"
+#include "fullcov_internal.h"
 #include "moment_dev.h"
 
 int gpmpc_timed_pair_sbf(int D, bool grad, int ns2, int waves, const PairSbfArgs& a, hipStream_t s);
@@ -19,19 +20,7 @@ int gpmpc_moment_match_ex(const gpmpc_pack* p, int nq, const double* u, const do
                           double* dmean_dS, double* dvar_du, double* dvar_dS, double* dcov_du, double* dcov_dS,
                           void* workspace, size_t workspace_bytes, void* stream, int ns2);
 
-struct FcArgs {
-    int B, H, ds, da, D, grad;
-    const double* x0; const double* U;
-    double* u; double* S;                 // [B][D], [B][D][D]   inputs of the current step
-    double* mean; double* cov;            // [B][ds], [B][ds][ds] outputs of the current step
-    double* out_means; double* out_covs;  // [B][H+1][ds], [B][H+1][ds][ds]
-    // Jacobians of every step t = 1..H at slice t-1: [H][B][...]
-    double* dmean_du; double* dmean_dS; double* dcov_du; double* dcov_dS;
-    double* out_cost; double* out_grad;
-    gpmpc_cost_params cost;
-    const double* sched; int sched_hmax;   // cost schedule of the call (include/gpmpc.h), read by k_fc_tail<DS, true> only, else null
-    const double* noise;                   // noise model of the pack (gpmpc_pack::noise_dev), read by k_fc_assemble
-};
+// (struct FcArgs: fullcov_internal.h)
 
 // step t >= 1: record the state of step t-1 and assemble the input distribution of step t
 __global__ void k_fc_assemble(FcArgs A, int t) {
@@ -163,7 +152,7 @@ __device__ static double fc_input_cost(int H, int da, const gpmpc_cost_params& C
     return c;
 }
 
-#define GPMPC_FC_WORKERS 32
+// (GPMPC_FC_WORKERS and the size of the dynamic LDS below, gpmpc_fc_tail_lds: fullcov_internal.h)
 #define GPMPC_FC_TAIL_TERMS ((GPMPC_MAX_DS + GPMPC_MAX_DS * GPMPC_MAX_DS + 3) / 4)
 // One workgroup (256 threads) per trajectory.  dynamic LDS:
 //   [WORKERS][ds*2ds] LU scratch | [H+1] cost terms | [H+1][ds + ds*ds] local derivatives | adjoint (2 x (ds + ds*ds)) | g (D + D*D) |
@@ -630,18 +619,26 @@ extern "C" int gpmpc_rollout_fullcov(const gpmpc_pack* p, int B, int H, const do
                                      const gpmpc_cost_params* cost, unsigned flags, double* out_means, double* out_covs,
                                      double* out_cost, double* out_grad, void* workspace, size_t workspace_bytes,
                                      void* stream) {
+    return gpmpc_fc_run(p, B, H, x0, U, cost, flags, true, out_means, out_covs, out_cost, out_grad, workspace, workspace_bytes, stream, nullptr);
+}
+
+int gpmpc_fc_run(const gpmpc_pack* p, int B, int H, const double* x0, const double* U, const gpmpc_cost_params* cost, unsigned flags, bool tail,
+                 double* out_means, double* out_covs, double* out_cost, double* out_grad, void* workspace, size_t workspace_bytes,
+                 void* stream, FcArgs* out_args) {
     if (!p) return GPMPC_E_ARG;
     if (int rc_dev = gpmpc_check_device(p)) return rc_dev;
-    if (!p || !x0 || !U || !cost || !out_means || !out_covs || !out_cost || !workspace || B < 1 || H < 1) return GPMPC_E_ARG;
+    if (!p || !x0 || !U || (tail && (!cost || !out_cost)) || !out_means || !out_covs || !workspace || B < 1 || H < 1) return GPMPC_E_ARG;
     if (p->nominal) {       // (the cross-covariances between the linear part and the GPs are not implemented)
         gpmpc_set_error_text("gpmpc_rollout_fullcov: the full-covariance rollout does not know the linear nominal model of this pack");
         return GPMPC_E_STATE;
     }
     if (!p->built || (p->npairs > 0 && !p->fullcov)) return GPMPC_E_STATE;
     const bool grad = (flags & GPMPC_WANT_GRAD) != 0;
-    if (grad && !out_grad) return GPMPC_E_ARG;
-    gpmpc_sched_ref sched;
-    if (int rcs = gpmpc_schedule_resolve(cost, p->ds, p->da, H, "gpmpc_rollout_fullcov", &sched)) return rcs;
+    if (tail && grad && !out_grad) return GPMPC_E_ARG;
+    gpmpc_sched_ref sched = {nullptr, 0};
+    if (tail) {
+        if (int rcs = gpmpc_schedule_resolve(cost, p->ds, p->da, H, "gpmpc_rollout_fullcov", &sched)) return rcs;
+    }
     FcPlan r;
     plan_fc(p, B, H, grad, &r);
     FcPlan2 r2;
@@ -656,21 +653,23 @@ extern "C" int gpmpc_rollout_fullcov(const gpmpc_pack* p, int B, int H, const do
     A.x0 = x0; A.U = U;
     A.sched = sched.dev; A.sched_hmax = sched.H_max;
     A.noise = p->noise_dev;
-    const size_t nz = ds + ds * ds;
-    const size_t lds = sizeof(double) * ((size_t)GPMPC_FC_WORKERS * ds * 2 * ds + (H + 1) + (size_t)(H + 1) * nz + 2 * nz + D + D * D + 2 * (size_t)H * p->da);
-    if (lds > 60 * 1024) return GPMPC_E_ARG;
+    const size_t lds = gpmpc_fc_tail_lds(p->ds, p->da, H);
+    if (tail && lds > GPMPC_FC_TAIL_LDS_MAX) return GPMPC_E_ARG;      // (the tail's: a call without it is not bounded by it)
     if (two) {
-        A.out_means = out_means; A.out_covs = out_covs; A.out_cost = out_cost; A.out_grad = out_grad; A.cost = *cost;
+        A.out_means = out_means; A.out_covs = out_covs; A.out_cost = out_cost; A.out_grad = out_grad;
+        if (tail) A.cost = *cost;
         const int rc = gpmpc_dispatch_dim<2>(p->D, [&](auto d) { return run_fc2<decltype(d)::value>(p, r2, A, grad, ws, s); });
         if (rc != GPMPC_OK) return rc;
-        return launch_fc_tail(A, B, lds, s);
+        if (out_args) *out_args = A;
+        return tail ? launch_fc_tail(A, B, lds, s) : GPMPC_OK;
     }
     A.u = (double*)(ws + r.off_u); A.S = (double*)(ws + r.off_S);
     A.mean = (double*)(ws + r.off_mean); A.cov = (double*)(ws + r.off_cov);
     A.out_means = out_means; A.out_covs = out_covs;
     A.dmean_du = (double*)(ws + r.off_dmu); A.dmean_dS = (double*)(ws + r.off_dmS);
     A.dcov_du = (double*)(ws + r.off_dcu); A.dcov_dS = (double*)(ws + r.off_dcS);
-    A.out_cost = out_cost; A.out_grad = out_grad; A.cost = *cost;
+    A.out_cost = out_cost; A.out_grad = out_grad;
+    if (tail) A.cost = *cost;
     double* var = (double*)(ws + r.off_var);
     double* dvu = (double*)(ws + r.off_dvu); double* dvS = (double*)(ws + r.off_dvS);
     const dim3 gb((B + 63) / 64), tb(64);
@@ -685,5 +684,8 @@ extern "C" int gpmpc_rollout_fullcov(const gpmpc_pack* p, int B, int H, const do
         if (rc != GPMPC_OK) return rc;
     }
     hipLaunchKernelGGL(k_fc_assemble, gb, tb, 0, s, A, H + 1);      // records step H
-    return launch_fc_tail(A, B, lds, s);
+    if (out_args) *out_args = A;
+    if (tail) return launch_fc_tail(A, B, lds, s);
+    GPMPC_HIP(hipGetLastError());
+    return GPMPC_OK;
 }

@@ -331,6 +331,11 @@ struct gpmpc_carver {
 };
 // GPMPC_OK, or GPMPC_E_ARG with the reason in gpmpc_last_error: n_rows outside 1..GPMPC_MAX_CONS, a negative or NaN kappa (constraints.hip)
 int gpmpc_check_constraints(const gpmpc_state_constraints* cons, const char* who);
+// GPMPC_OK, or the code gpmpc_rollout_fullcov would return with the reason in gpmpc_last_error, for the entries that would otherwise meet it
+// after their first launch (fullcov_cons.hip): GPMPC_E_STATE on a nominal model, a pack that is not built or has no cross-covariance
+// weights; GPMPC_E_ARG on a state dimension the cost tail is not instantiated for (> 6) and, with tail_H > 0 (the call runs the tail over
+// that horizon), on a horizon beyond its LDS.
+int gpmpc_fc_refuse(const gpmpc_pack* p, const char* who, int tail_H);
 // Cost schedules (schedule.hip; layout in include/gpmpc.h): offsets, in doubles, of the parts behind x_ref, from the dimensions the
 // buffer was created with.  A cost kernel gets the buffer and H_max as launch arguments (both fixed for the life of an id) and reads
 // everything else -- rows, Q_f, has_Qf -- from the buffer.

@@ -335,8 +335,8 @@ extern "C" int gpmpc_lbfgs_tick(int H, int da, const gpmpc_lbfgs_params* P, cons
 }
 
 // workspace of a solve: state | x0 [K][ds] | cost [K] | grad [K][n] | the rollout's own workspace
-struct LbfgsWorkspace { size_t off_x0, off_cost, off_grad, off_roll, roll_bytes, total; };
-static LbfgsWorkspace lbfgs_workspace(const gpmpc_pack* p, int H, int K, const LbfgsLayout& L) {
+struct LbfgsWorkspace { size_t off_x0, off_cost, off_grad, off_roll, total; gpmpc_solver_eval_layout roll; };
+static LbfgsWorkspace lbfgs_workspace(const gpmpc_pack* p, int H, int K, const LbfgsLayout& L, gpmpc_solver_rule rule) {
     LbfgsWorkspace W;
     const size_t n = (size_t)H * p->da, d = sizeof(double);
     gpmpc_carver c;
@@ -344,45 +344,65 @@ static LbfgsWorkspace lbfgs_workspace(const gpmpc_pack* p, int H, int K, const L
     W.off_x0 = c.take(d * K * p->ds);
     W.off_cost = c.take(d * K);
     W.off_grad = c.take(d * K * n);
-    W.roll_bytes = gpmpc_rollout_workspace_bytes(p, K, H, GPMPC_WANT_GRAD);
-    W.off_roll = c.take(W.roll_bytes);
+    W.roll = gpmpc_solver_eval_bytes(rule, p, K, H, false, GPMPC_WANT_GRAD);
+    W.off_roll = c.take(W.roll.total);
     W.total = c.total();
     return W;
 }
 
-extern "C" size_t gpmpc_lbfgs_solve_workspace_bytes(const gpmpc_pack* p, int H, const gpmpc_lbfgs_params* P) {
+static size_t lbfgs_solve_bytes(gpmpc_solver_rule rule, const gpmpc_pack* p, int H, const gpmpc_lbfgs_params* P) {
     if (!p || !P || P->n_starts < 1 || P->n_starts > GPMPC_LBFGS_MAX_STARTS || P->history < 1 || P->history > GPMPC_LBFGS_MAX_HISTORY) return 0;
     if (!gpmpc_solver_dims_ok(H, p->ds, p->da)) return 0;
-    return lbfgs_workspace(p, H, P->n_starts, lbfgs_layout(P->n_starts, (long)H * p->da, P->history)).total;
+    return lbfgs_workspace(p, H, P->n_starts, lbfgs_layout(P->n_starts, (long)H * p->da, P->history), rule).total;
+}
+extern "C" size_t gpmpc_lbfgs_solve_workspace_bytes(const gpmpc_pack* p, int H, const gpmpc_lbfgs_params* P) {
+    return lbfgs_solve_bytes(GPMPC_RULE_DIAGONAL, p, H, P);
+}
+extern "C" size_t gpmpc_lbfgs_solve_fullcov_workspace_bytes(const gpmpc_pack* p, int H, const gpmpc_lbfgs_params* P) {
+    return lbfgs_solve_bytes(GPMPC_RULE_FULLCOV, p, H, P);
 }
 
-extern "C" int gpmpc_lbfgs_solve(const gpmpc_pack* p, int H, const double* x0, const double* X0, const gpmpc_cost_params* cost,
-                                 const gpmpc_lbfgs_params* P, int first_tick, int n_ticks, void* workspace, size_t workspace_bytes,
-                                 void* stream) {
-    const char* who = "gpmpc_lbfgs_solve";
+// the search of both entries; the rule decides the one evaluation (solver_frame.h)
+static int lbfgs_solve(gpmpc_solver_rule rule, const char* who, const gpmpc_pack* p, int H, const double* x0, const double* X0,
+                       const gpmpc_cost_params* cost, const gpmpc_lbfgs_params* P, int first_tick, int n_ticks, void* workspace,
+                       size_t workspace_bytes, void* stream) {
     if (!p || !x0 || !cost || !P || !workspace || H < 1 || (first_tick == 0 && !X0)) return GPMPC_E_ARG;
     if (int rc = lbfgs_check_scalars(P, who)) return rc;                 // (before the pack is looked at)
     if (first_tick < 0) return gpmpc_refuse(who, "first_tick is negative");
     if (n_ticks < 0) return gpmpc_refuse(who, "n_ticks is negative");
-    if (int rc = gpmpc_solver_enter(p, H, cost, nullptr, who, [&](int da) { return gpmpc_check_bounds(P->lb, P->ub, da, who); })) return rc;
+    if (int rc = gpmpc_solver_enter(p, H, cost, nullptr, who, [&](int da) { return gpmpc_check_bounds(P->lb, P->ub, da, who); }, rule)) return rc;
     const int K = P->n_starts, n = H * p->da;
     const LbfgsLayout L = lbfgs_layout(K, n, P->history);
-    const LbfgsWorkspace W = lbfgs_workspace(p, H, K, L);
+    const LbfgsWorkspace W = lbfgs_workspace(p, H, K, L, rule);
     if (workspace_bytes < W.total) return GPMPC_E_WORKSPACE;
     hipStream_t s = (hipStream_t)stream;
     char* ws = (char*)workspace;
     double *st = (double*)ws, *x0b = (double*)(ws + W.off_x0), *cst = (double*)(ws + W.off_cost), *grd = (double*)(ws + W.off_grad);
     double* U = st + L.U;
+    auto evaluate = [&]() {
+        return gpmpc_solver_eval(rule, p, K, H, x0b, U, cost, nullptr, GPMPC_WANT_GRAD, cst, grd, nullptr, nullptr, ws + W.off_roll, W.roll, stream);
+    };
     if (first_tick == 0) {
         if (int rc = lbfgs_launch_start(n, p->ds, p->da, *P, L, X0, nullptr, nullptr, x0, x0b, st, s)) return rc;
-        if (int rc = gpmpc_rollout(p, K, H, x0b, U, cost, GPMPC_WANT_GRAD, nullptr, nullptr, cst, grd, ws + W.off_roll, W.roll_bytes, stream))
-            return rc;
+        if (int rc = evaluate()) return rc;
         if (int rc = lbfgs_launch_start(n, p->ds, p->da, *P, L, X0, cst, grd, nullptr, nullptr, st, s)) return rc;
     }
     for (int t = 0; t < n_ticks; ++t) {
-        if (int rc = gpmpc_rollout(p, K, H, x0b, U, cost, GPMPC_WANT_GRAD, nullptr, nullptr, cst, grd, ws + W.off_roll, W.roll_bytes, stream))
-            return rc;
+        if (int rc = evaluate()) return rc;
         if (int rc = lbfgs_launch_tick(n, p->da, *P, L, cst, grd, st, s)) return rc;
     }
     return lbfgs_launch_finish(n, *P, L, st, s);
+}
+
+extern "C" int gpmpc_lbfgs_solve(const gpmpc_pack* p, int H, const double* x0, const double* X0, const gpmpc_cost_params* cost,
+                                 const gpmpc_lbfgs_params* P, int first_tick, int n_ticks, void* workspace, size_t workspace_bytes,
+                                 void* stream) {
+    return lbfgs_solve(GPMPC_RULE_DIAGONAL, "gpmpc_lbfgs_solve", p, H, x0, X0, cost, P, first_tick, n_ticks, workspace, workspace_bytes, stream);
+}
+
+extern "C" int gpmpc_lbfgs_solve_fullcov(const gpmpc_pack* p, int H, const double* x0, const double* X0, const gpmpc_cost_params* cost,
+                                         const gpmpc_lbfgs_params* P, int first_tick, int n_ticks, void* workspace, size_t workspace_bytes,
+                                         void* stream) {
+    return lbfgs_solve(GPMPC_RULE_FULLCOV, "gpmpc_lbfgs_solve_fullcov", p, H, x0, X0, cost, P, first_tick, n_ticks, workspace, workspace_bytes,
+                       stream);
 }

@@ -224,8 +224,8 @@ extern "C" int gpmpc_mppi_update(int K, int H, int da, int n_rows, double beta, 
 }
 
 // workspace of a solve: U [K][n] | x0 [K][ds] | cost [K] | g [K][H m_c] | mean [n] | best x 2 [2 + n] | the rollout's own workspace
-struct MppiLayout { size_t off_U, off_x0, off_cost, off_g, off_mean, off_best[2], off_roll, roll_bytes, total; };
-static MppiLayout mppi_layout(const gpmpc_pack* p, int H, int K, int m_c) {
+struct MppiLayout { size_t off_U, off_x0, off_cost, off_g, off_mean, off_best[2], off_roll, total; gpmpc_solver_eval_layout roll; };
+static MppiLayout mppi_layout(const gpmpc_pack* p, int H, int K, int m_c, gpmpc_solver_rule rule) {
     MppiLayout L;
     const size_t n = (size_t)H * p->da, d = sizeof(double);
     gpmpc_carver c;
@@ -236,28 +236,35 @@ static MppiLayout mppi_layout(const gpmpc_pack* p, int H, int K, int m_c) {
     L.off_mean = c.take(d * n);
     L.off_best[0] = c.take(d * (2 + n));
     L.off_best[1] = c.take(d * (2 + n));
-    L.roll_bytes = m_c ? gpmpc_rollout_constrained_workspace_bytes(p, K, H, 0) : gpmpc_rollout_workspace_bytes(p, K, H, 0);
-    L.off_roll = c.take(L.roll_bytes);
+    L.roll = gpmpc_solver_eval_bytes(rule, p, K, H, m_c != 0, 0);
+    L.off_roll = c.take(L.roll.total);
     L.total = c.total();
     return L;
 }
 
-extern "C" size_t gpmpc_mppi_solve_workspace_bytes(const gpmpc_pack* p, int H, const gpmpc_mppi_params* P, const gpmpc_state_constraints* cons) {
+static size_t mppi_solve_bytes(gpmpc_solver_rule rule, const gpmpc_pack* p, int H, const gpmpc_mppi_params* P, const gpmpc_state_constraints* cons) {
     if (!p || !P || P->n_samples < 1 || P->n_samples > GPMPC_MPPI_MAX_SAMPLES) return 0;
     if (cons && (cons->n_rows < 1 || cons->n_rows > GPMPC_MAX_CONS)) return 0;
     if (!gpmpc_solver_dims_ok(H, p->ds, p->da)) return 0;
-    return mppi_layout(p, H, P->n_samples, cons ? cons->n_rows : 0).total;
+    return mppi_layout(p, H, P->n_samples, cons ? cons->n_rows : 0, rule).total;
+}
+extern "C" size_t gpmpc_mppi_solve_workspace_bytes(const gpmpc_pack* p, int H, const gpmpc_mppi_params* P, const gpmpc_state_constraints* cons) {
+    return mppi_solve_bytes(GPMPC_RULE_DIAGONAL, p, H, P, cons);
+}
+extern "C" size_t gpmpc_mppi_solve_fullcov_workspace_bytes(const gpmpc_pack* p, int H, const gpmpc_mppi_params* P,
+                                                           const gpmpc_state_constraints* cons) {
+    return mppi_solve_bytes(GPMPC_RULE_FULLCOV, p, H, P, cons);
 }
 
-extern "C" int gpmpc_mppi_solve(const gpmpc_pack* p, int H, const double* x0, const double* start, const gpmpc_cost_params* cost,
-                                const gpmpc_state_constraints* cons, const gpmpc_mppi_params* P, double* out_U, double* out_best,
-                                double* out_trace, void* workspace, size_t workspace_bytes, void* stream) {
-    const char* who = "gpmpc_mppi_solve";
+// the search of both entries; the rule decides the one evaluation (solver_frame.h)
+static int mppi_solve(gpmpc_solver_rule rule, const char* who, const gpmpc_pack* p, int H, const double* x0, const double* start,
+                      const gpmpc_cost_params* cost, const gpmpc_state_constraints* cons, const gpmpc_mppi_params* P, double* out_U,
+                      double* out_best, double* out_trace, void* workspace, size_t workspace_bytes, void* stream) {
     if (!p || !x0 || !start || !cost || !P || !out_U || !out_best || !out_trace || !workspace || H < 1) return GPMPC_E_ARG;
     if (int rc = mppi_check_scalars(P, who)) return rc;                  // (before the pack is looked at)
-    if (int rc = gpmpc_solver_enter(p, H, cost, cons, who, [&](int da) { return mppi_check_inputs(P, da, who); })) return rc;
+    if (int rc = gpmpc_solver_enter(p, H, cost, cons, who, [&](int da) { return mppi_check_inputs(P, da, who); }, rule)) return rc;
     const int K = P->n_samples, n = H * p->da, m_c = cons ? cons->n_rows : 0;
-    const MppiLayout L = mppi_layout(p, H, K, m_c);
+    const MppiLayout L = mppi_layout(p, H, K, m_c, rule);
     if (workspace_bytes < L.total) return GPMPC_E_WORKSPACE;
     hipStream_t s = (hipStream_t)stream;
     char* ws = (char*)workspace;
@@ -270,12 +277,7 @@ extern "C" int gpmpc_mppi_solve(const gpmpc_pack* p, int H, const double* x0, co
     GPMPC_HIP(hipMemcpyAsync(mean, start, sizeof(double) * n, hipMemcpyDeviceToDevice, s));
     for (int it = 0; it < P->iterations; ++it) {
         if (int rc = mppi_launch_sample(H, p->ds, p->da, *P, it, mean, x0, U, x0b, s)) return rc;
-        int rc;
-        if (cons)
-            rc = gpmpc_rollout_constrained(p, K, H, x0b, U, cost, cons, 0, nullptr, nullptr, cst, nullptr, g, nullptr, ws + L.off_roll,
-                                           L.roll_bytes, stream);
-        else
-            rc = gpmpc_rollout(p, K, H, x0b, U, cost, 0, nullptr, nullptr, cst, nullptr, ws + L.off_roll, L.roll_bytes, stream);
+        int rc = gpmpc_solver_eval(rule, p, K, H, x0b, U, cost, cons, 0, cst, nullptr, cons ? g : nullptr, nullptr, ws + L.off_roll, L.roll, stream);
         if (rc) return rc;
         rc = gpmpc_mppi_update(K, H, p->da, m_c, P->beta, U, cst, cons ? g : nullptr, mean, best[it & 1], best[(it + 1) & 1],
                                out_trace + 6 * (size_t)it, stream);
@@ -285,4 +287,18 @@ extern "C" int gpmpc_mppi_solve(const gpmpc_pack* p, int H, const double* x0, co
     GPMPC_HIP(hipMemcpyAsync(out_best, fin, sizeof(double) * 2, hipMemcpyDeviceToDevice, s));
     GPMPC_HIP(hipMemcpyAsync(out_U, fin + 2, sizeof(double) * n, hipMemcpyDeviceToDevice, s));
     return GPMPC_OK;
+}
+
+extern "C" int gpmpc_mppi_solve(const gpmpc_pack* p, int H, const double* x0, const double* start, const gpmpc_cost_params* cost,
+                                const gpmpc_state_constraints* cons, const gpmpc_mppi_params* P, double* out_U, double* out_best,
+                                double* out_trace, void* workspace, size_t workspace_bytes, void* stream) {
+    return mppi_solve(GPMPC_RULE_DIAGONAL, "gpmpc_mppi_solve", p, H, x0, start, cost, cons, P, out_U, out_best, out_trace, workspace,
+                      workspace_bytes, stream);
+}
+
+extern "C" int gpmpc_mppi_solve_fullcov(const gpmpc_pack* p, int H, const double* x0, const double* start, const gpmpc_cost_params* cost,
+                                        const gpmpc_state_constraints* cons, const gpmpc_mppi_params* P, double* out_U, double* out_best,
+                                        double* out_trace, void* workspace, size_t workspace_bytes, void* stream) {
+    return mppi_solve(GPMPC_RULE_FULLCOV, "gpmpc_mppi_solve_fullcov", p, H, x0, start, cost, cons, P, out_U, out_best, out_trace, workspace,
+                      workspace_bytes, stream);
 }

@@ -16,7 +16,7 @@ from . import _lib
 from ._lib import AuglagParamsC, check, lib, ptr, require_gpu, stream_ptr
 from .device_lbfgs import lbfgs_params, lbfgs_state_layout
 from ._solver import enqueue_chunks, per_input, solver_problem, state_layout
-from .rollout import _dev
+from .rollout import _dev, _fullcov_pack
 
 SCALARS = ("rho", "V_prev", "v", "f", "inc_v", "inc_f", "alive", "settled")
 
@@ -125,8 +125,9 @@ def auglag_outer(state, f, g, X, K, H, da, update=True, conv=None, alive=None, p
 
 def auglag_solve(pack, x0, X0, cost, constraints, lb=None, ub=None, outer=8, inner_ticks=25, rho0=10.0, growth=10.0, shrink=0.25,
                  rho_max=1e8, lam_max=1e12, feas_tol=1e-4, history=8, gtol=1e-6, ftol=1e-12, check_outer=1, callback=None, c1=1e-4,
-                 min_step=1e-12):
-    """The whole solve (C ABI ``gpmpc_auglag_solve``): ``check_outer`` outer iterations per enqueue -- each one constrained evaluation, the
+                 min_step=1e-12, full_covariance=False):
+    """The whole solve (C ABI ``gpmpc_auglag_solve``; full_covariance=True: ``gpmpc_auglag_solve_fullcov``, the same solve with
+    ``gpmpc_rollout_fullcov_constrained`` as its evaluation, rows on a^T Sigma_t a): ``check_outer`` outer iterations per enqueue -- each one constrained evaluation, the
     outer step, the restart of the inner search and ``inner_ticks`` x (constrained rollout with gradient, merit kernel, tick kernel), no
     host synchronisation in between --, then one read of the count of alive starts that are not settled; it stops when that is 0 or
     ``outer`` is reached.  ``check_outer=0``: one chunk of ``outer``.  x0 (ds,), X0 (K, H, da) the start points, ``constraints`` a
@@ -135,6 +136,10 @@ def auglag_solve(pack, x0, X0, cost, constraints, lb=None, ub=None, outer=8, inn
     Returns (U (H, da) numpy: the incumbent of the best start, its cost, info): info holds per start f and violation (the incumbent's cost and
     max(g, 0), 0 where feasible), feasible, x (the incumbents), rho, lam, alive, settled, and best, outer, evaluations."""
     dev = pack.device
+    solve, size, what = lib().gpmpc_auglag_solve, lib().gpmpc_auglag_solve_workspace_bytes, "gpmpc_auglag_solve"
+    if full_covariance:
+        _fullcov_pack(pack)
+        solve, size, what = lib().gpmpc_auglag_solve_fullcov, lib().gpmpc_auglag_solve_fullcov_workspace_bytes, "gpmpc_auglag_solve_fullcov"
     x0, X0 = solver_problem(pack, x0, X0, cost, "X0", "(K, H, da)")
     K, H, da = X0.shape
     n = H * da
@@ -148,7 +153,7 @@ def auglag_solve(pack, x0, X0, cost, constraints, lb=None, ub=None, outer=8, inn
     m_c = constraints.m
     R = H * m_c
     P = auglag_params(K, da, lb, ub, inner_ticks, rho0, growth, shrink, rho_max, lam_max, feas_tol, history, gtol, ftol, c1, min_step)
-    nbytes = int(lib().gpmpc_auglag_solve_workspace_bytes(pack.handle, H, ctypes.byref(constraints.c), ctypes.byref(P)))
+    nbytes = int(size(pack.handle, H, ctypes.byref(constraints.c), ctypes.byref(P)))
     # a buffer of the solve's own: both states live in it between the chunks
     ws = torch.empty(max(nbytes // 8, 32), dtype=torch.float64, device=dev)
     L = auglag_state_layout(K, n, R)
@@ -156,9 +161,8 @@ def auglag_solve(pack, x0, X0, cost, constraints, lb=None, ub=None, outer=8, inn
     ws[:min(L["total"] + inner_total, ws.numel())].zero_()    # (the padding between the fields is never written by a kernel)
 
     def enqueue(first_outer, n_outer):
-        check(lib().gpmpc_auglag_solve(pack.handle, H, ptr(x0), ptr(X0), ctypes.byref(cost.c), ctypes.byref(constraints.c),
-                                       ctypes.byref(P), first_outer, n_outer, ctypes.c_void_p(ws.data_ptr()), ws.numel() * 8, stream_ptr()),
-              "gpmpc_auglag_solve")
+        check(solve(pack.handle, H, ptr(x0), ptr(X0), ctypes.byref(cost.c), ctypes.byref(constraints.c),
+                    ctypes.byref(P), first_outer, n_outer, ctypes.c_void_p(ws.data_ptr()), ws.numel() * 8, stream_ptr()), what)
 
     with torch.cuda.device(dev):
         done, calls = enqueue_chunks(outer, check_outer, enqueue, ws, None if callback is None else lambda d: callback(d, ws, L["total"]))

@@ -14,7 +14,7 @@ import torch
 from . import _lib
 from ._lib import LbfgsParamsC, check, lib, ptr, require_gpu, stream_ptr
 from ._solver import enqueue_chunks, per_input, solver_problem, state_layout
-from .rollout import _dev
+from .rollout import _dev, _fullcov_pack
 
 SCALARS = ("F", "converged", "alive", "iters", "ticks", "done", "A", "cnt", "head")
 
@@ -135,8 +135,11 @@ def lbfgs_start(X0, cost=None, grad=None, lb=None, ub=None, history=8, gtol=1e-4
     return state if x0 is None else (state, x0b)
 
 
-def lbfgs_tick(state, cost, grad, K, H, da, lb=None, ub=None, history=8, gtol=1e-4, ftol=1e-10, c1=1e-4, min_step=1e-12):
-    """One tick, in place (C ABI ``gpmpc_lbfgs_tick``): cost (K,), grad (K, H, da) the evaluation of the state's U.  Returns ``state``."""
+def lbfgs_tick(state, cost, grad, K, H, da, lb=None, ub=None, history=8, gtol=1e-4, ftol=1e-10, c1=1e-4, min_step=1e-12,
+               full_covariance=False):
+    """One tick, in place (C ABI ``gpmpc_lbfgs_tick``): cost (K,), grad (K, H, da) the evaluation of the state's U.  Returns ``state``.
+    full_covariance: accepted so that a chain of ticks takes the keywords of ``lbfgs_solve``; not consulted -- the tick is a pure function
+    of (cost, grad), whichever rollout (``rollout`` or ``rollout_fullcov``) the caller evaluated them with."""
     dev = state.device
     P = lbfgs_params(K, da, lb, ub, history, gtol, ftol, c1, min_step)
     cost, grad = _dev(cost, dev).reshape(-1), _dev(grad, dev).reshape(K, -1)
@@ -149,13 +152,18 @@ def lbfgs_tick(state, cost, grad, K, H, da, lb=None, ub=None, history=8, gtol=1e
 
 
 def lbfgs_solve(pack, x0, X0, cost, lb=None, ub=None, max_ticks=150, history=8, gtol=1e-4, ftol=1e-10, check_every=8, c1=1e-4,
-                min_step=1e-12, callback=None):
-    """The whole search (C ABI ``gpmpc_lbfgs_solve``): ``check_every`` ticks per enqueue -- each tick ``gpmpc_rollout`` with gradient over the K
+                min_step=1e-12, callback=None, full_covariance=False):
+    """The whole search (C ABI ``gpmpc_lbfgs_solve``; full_covariance=True: ``gpmpc_lbfgs_solve_fullcov``, the same search with
+    ``gpmpc_rollout_fullcov`` as its evaluation): ``check_every`` ticks per enqueue -- each tick ``gpmpc_rollout`` with gradient over the K
     trial points and the tick kernel, no host synchronisation in between --, then one read of the not-done counter; it stops when that is 0
     or ``max_ticks`` is reached.  ``check_every=0``: one chunk of ``max_ticks``.  x0 (ds,), X0 (K, H, da) the start points.
     ``callback(ticks_enqueued, state)`` (optional) is called after every chunk with the state buffer (``lbfgs_state_view``).
     Returns (U (H, da) numpy: the best plan, its cost, info) with the keys of ``multistart.lockstep_lbfgs``'s info."""
     dev = pack.device
+    solve, size, what = lib().gpmpc_lbfgs_solve, lib().gpmpc_lbfgs_solve_workspace_bytes, "gpmpc_lbfgs_solve"
+    if full_covariance:
+        _fullcov_pack(pack)
+        solve, size, what = lib().gpmpc_lbfgs_solve_fullcov, lib().gpmpc_lbfgs_solve_fullcov_workspace_bytes, "gpmpc_lbfgs_solve_fullcov"
     x0, X0 = solver_problem(pack, x0, X0, cost, "X0", "(K, H, da)")
     K, H, da = X0.shape
     n = H * da
@@ -163,15 +171,15 @@ def lbfgs_solve(pack, x0, X0, cost, lb=None, ub=None, max_ticks=150, history=8, 
     if check_every < 0:
         raise ValueError("check_every must be 0 (one chunk) or positive")
     P = lbfgs_params(K, da, lb, ub, history, gtol, ftol, c1, min_step)
-    nbytes = int(lib().gpmpc_lbfgs_solve_workspace_bytes(pack.handle, H, ctypes.byref(P)))
+    nbytes = int(size(pack.handle, H, ctypes.byref(P)))
     # a buffer of the search's own: the state lives in it between the chunks (the pack's per-stream scratch is anybody's between two calls)
     ws = torch.empty(max(nbytes // 8, 32), dtype=torch.float64, device=dev)
     L = lbfgs_state_layout(K, n, P.history)
     ws[:L["total"]].zero_()                                  # (the padding between the fields is never written by a kernel)
 
     def enqueue(first_tick, n_ticks):
-        check(lib().gpmpc_lbfgs_solve(pack.handle, H, ptr(x0), ptr(X0), ctypes.byref(cost.c), ctypes.byref(P), first_tick, n_ticks,
-                                      ctypes.c_void_p(ws.data_ptr()), ws.numel() * 8, stream_ptr()), "gpmpc_lbfgs_solve")
+        check(solve(pack.handle, H, ptr(x0), ptr(X0), ctypes.byref(cost.c), ctypes.byref(P), first_tick, n_ticks,
+                    ctypes.c_void_p(ws.data_ptr()), ws.numel() * 8, stream_ptr()), what)
 
     with torch.cuda.device(dev):
         done_ticks, _ = enqueue_chunks(max_ticks, check_every, enqueue, ws, None if callback is None else lambda done: callback(done, ws))

@@ -24,10 +24,11 @@ forced by moving the rollout into one fused HIP call:
   default) is everything above, unchanged.
 * ``solver = "lbfgs"`` (extension): the lock-step multi-start search with its state machine on the device (device_lbfgs.py,
   ``gpmpc_lbfgs_solve``) -- ``n_starts`` starts from ``make_starts``, options from ``multistart_options`` plus ``check_every``, the ticks
-  enqueued without a device-to-host copy in between.  Unconstrained, diagonal rollout only.
+  enqueued without a device-to-host copy in between.  Unconstrained; the diagonal rollout, or the full-covariance one under
+  ``propagation = "moment_matching_full"``.
 * ``solver = "auglag"`` (extension): the constrained multi-start on the device (device_auglag.py, ``gpmpc_auglag_solve``) -- an augmented
   Lagrangian over the batched constrained rollout with the search above as its inner solver; ``n_starts`` starts, options from
-  ``auglag_options``.  Needs state constraints; diagonal rollout only.
+  ``auglag_options``.  Needs state constraints; the diagonal rollout, or the full-covariance one under ``"moment_matching_full"``.
 * ``set_reference_trajectory`` / ``mpc.reference = fn`` / ``mpc.Q_terminal`` (extension; the reference measures every step against one
   ``x_ref`` under one ``Q``): references that change along the horizon and a terminal weight, through ONE ``rollout.CostSchedule`` owned
   by the controller.  Its rows live in device memory, so the solver-callback graph of the closed loop is captured once however often
@@ -47,6 +48,12 @@ forced by moving the rollout into one fused HIP call:
   multi-start and ``solver = "mppi"`` (a host loop of sample / rollout / update calls), with and without state constraints --;
   ``solver = "lbfgs"`` and ``"auglag"`` refuse it (not yet).  The ``full_covariance`` attribute is not consulted under it, and
   ``"linearised"`` with ``full_covariance=True`` keeps refusing.  A gain under any other propagation raises.
+* ``mpc.propagation = "moment_matching_full"`` (extension): exact moment matching with the WHOLE covariance in every
+  path -- the four solver callbacks (one B = 1 ``rollout_fullcov(..., constraints=)`` per x: cost, gradient, g on a_r^T Sigma_t a_r and its
+  dense Jacobian from one pass), ``evaluate_batch`` with and without constraints (``covs`` in the place of ``vars``), the unconstrained host
+  multi-start, ``solver = "mppi" | "lbfgs" | "auglag"`` (``gpmpc_*_solve_fullcov``) and ``validate_plan`` (``cov_mm``).  The
+  ``full_covariance`` attribute is not consulted under it; ``"moment_matching"`` with ``full_covariance=True`` keeps the refusals it had.
+  Refused under it: a feedback gain, a nominal model, ``n_starts > 1`` with state constraints and ``solver=None``.
 """
 import numpy as np
 import torch
@@ -64,7 +71,7 @@ except Exception:                       # pragma: no cover
 
 
 class RiskSensitiveMPC:
-    propagation = "moment_matching"                      # | "linearised" | "linearised_full" (extension; linearised.py): which rule the rollouts of the solvers use
+    propagation = "moment_matching"                      # | "moment_matching_full" | "linearised" | "linearised_full" (extension): which rule the rollouts of the solvers use
     linearised_form = None                               # | "tile" | "stream" | "auto": the form of the linearised step (None: the process-wide one)
 
     def __init__(self, gamma, horizon, state_dim, input_dim, Q, R, R_delta=None, full_covariance=False, nominal_models=None):
@@ -297,14 +304,21 @@ class RiskSensitiveMPC:
     def _linearised(self):
         """True under ``propagation = "linearised"``, after the refusals every entry shares."""
         prop = self.propagation
-        if prop not in ("moment_matching", "linearised", "linearised_full"):
-            raise ValueError("propagation must be 'moment_matching', 'linearised' or 'linearised_full', got %r" % (prop,))
+        if prop not in ("moment_matching", "moment_matching_full", "linearised", "linearised_full"):
+            raise ValueError("propagation must be 'moment_matching', 'moment_matching_full', 'linearised' or 'linearised_full', got %r" % (prop,))
         if prop == "linearised" and self.full_covariance:
             raise NotImplementedError("propagation='linearised' is diagonal: a full-covariance linearised rollout is not implemented (not yet)")
         if getattr(self, "_feedback_gain", None) is not None and prop != "linearised_full":
             raise ValueError("a feedback gain is set (set_feedback_gain): only propagation='linearised_full' predicts under state feedback, "
                              "got propagation=%r (clear_feedback_gain drops it)" % (prop,))
-        return prop != "moment_matching"
+        if prop == "moment_matching_full" and getattr(self.dynamics, "nominal_models", None) is not None:
+            raise NotImplementedError("propagation='moment_matching_full' with a nominal model: the full-covariance rollout does not know "
+                                      "the cross-covariances between a nominal model and the GPs")
+        return prop in ("linearised", "linearised_full")
+
+    def _mm_full(self):
+        """True under ``propagation = "moment_matching_full"``: every rollout is the full-covariance one, constraints included."""
+        return self.propagation == "moment_matching_full"
 
     def _lin_kw(self):
         """The keyword arguments that select the rule of ``linearised_rollout`` / ``mppi_solve_linearised``."""
@@ -313,8 +327,9 @@ class RiskSensitiveMPC:
         return {}
 
     def _fullcov_mm(self):
-        """``full_covariance`` as the moment-matching paths read it: under "linearised_full" the attribute is not consulted."""
-        return bool(self.full_covariance) and self.propagation != "linearised_full"
+        """``full_covariance`` as the paths that refuse it read it: under "linearised_full" and "moment_matching_full" the attribute is
+        not consulted."""
+        return bool(self.full_covariance) and self.propagation not in ("linearised_full", "moment_matching_full")
 
     def set_feedback_gain(self, K):
         """The gain of the predicted input u_t = v_t + K_t (x_t - mu_t) under ``propagation = "linearised_full"``: (da, ds) for every step or
@@ -352,7 +367,9 @@ class RiskSensitiveMPC:
         cs, pack, cp = self.curr_state, self.dynamics.pack(), self._cost_params()
         lin = self._linearised()
         fb = getattr(self, "_feedback_gain", None)
-        key = (x.tobytes(), None if cs is None else cs._version, bool(self.full_covariance), pack.generation, self.propagation if lin else lin,
+        mmf = self._mm_full()
+        key = (x.tobytes(), None if cs is None else cs._version, bool(self.full_covariance), pack.generation,
+               self.propagation if (lin or mmf) else lin,
                self.linearised_form if lin else None, None if fb is None else (id(fb), fb._version))
         held = getattr(self, "_cache_held", (None, None, None))    # kept alive so that `is` cannot alias later objects
         sc = self.state_constraints
@@ -367,6 +384,14 @@ class RiskSensitiveMPC:
                 from .linearised import linearised_rollout
                 r = linearised_rollout(self._linearised_model(pack), cs, x.reshape(1, self.horizon, self.input_dim), cp, want_grad=True,
                                        want_traj=False, constraints=sc, form=self.linearised_form, **self._lin_kw())
+                self.curr_cost = float(r["cost"][0].item())
+                self.curr_grad = r["grad"][0].cpu().numpy()
+                if sc is not None:
+                    self.curr_g = r["g"][0].cpu().numpy().reshape(-1)
+                    self.curr_g_jac = r["g_jac"][0].cpu().numpy()
+            elif mmf:
+                # one B = 1 full-covariance rollout per x: cost, gradient and, with constraints, g on a^T Sigma_t a and its dense Jacobian
+                r = rollout_fullcov(pack, cs, x.reshape(1, self.horizon, self.input_dim), cp, want_grad=True, constraints=sc)
                 self.curr_cost = float(r["cost"][0].item())
                 self.curr_grad = r["grad"][0].cpu().numpy()
                 if sc is not None:
@@ -436,6 +461,9 @@ class RiskSensitiveMPC:
             return linearised_rollout(self._linearised_model(self.dynamics.pack()), cs, U, self._cost_params(), want_grad=want_grad,
                                       want_traj=True, constraints=self.state_constraints if constraints else None, form=self.linearised_form,
                                       **self._lin_kw())
+        if self._mm_full():
+            return rollout_fullcov(self.dynamics.pack(), cs, U, self._cost_params(), want_grad=want_grad,
+                                   constraints=self.state_constraints if constraints else None)
         if constraints:
             if self.full_covariance:
                 raise NotImplementedError("state constraints under the full-covariance rollout are not implemented")
@@ -451,7 +479,7 @@ class RiskSensitiveMPC:
 
     # -- Monte-Carlo check of the moment-matched plan (extension)
     def validate_plan(self, U=None, x0=None, particles=4096, seed=0, linearised=False):
-        """Compare the moment-matched rollout of a plan (the last one by default; diagonal or full by ``self.full_covariance``) with a
+        """Compare the moment-matched rollout of a plan (the last one by default; diagonal or full by ``self.full_covariance``, full under ``propagation = "moment_matching_full"``) with a
         particle rollout through the same GPs (``particles.particle_rollout``).  Returns a dict of host arrays:
 
         ``mean_mm``, ``var_mm`` / ``mean_mc``, ``var_mc`` (H+1, ds): both sets of moments (``cov_mm`` / ``cov_mc`` (H+1, ds, ds) too where the
@@ -471,14 +499,15 @@ class RiskSensitiveMPC:
         if cs is None:
             raise ValueError("no start state: give x0 or solve once")
         cs = np.asarray(cs.detach().cpu().numpy() if isinstance(cs, torch.Tensor) else cs, dtype=np.float64).reshape(ds)
-        mm = self.dynamics.rollout(cs, U, full_covariance=bool(self.full_covariance))
+        full = bool(self.full_covariance) or self._mm_full()
+        mm = self.dynamics.rollout(cs, U, full_covariance=full)
         sc = self.state_constraints
         mc = particle_rollout(self.dynamics, cs, U, particles=particles, seed=seed, constraints=sc)
         P = int(particles)
         X = mc["particles"][0]                                            # (P, H+1, ds)
         out = {"particles": P, "mean_mm": mm["means"][0].cpu().numpy(), "mean_mc": mc["mean"][0].cpu().numpy()}
         cov_mc = mc["cov"][0]
-        if self.full_covariance:
+        if full:
             out["cov_mm"], out["cov_mc"] = mm["covs"][0].cpu().numpy(), cov_mc.cpu().numpy()
             out["var_mm"] = np.diagonal(out["cov_mm"], axis1=1, axis2=2).copy()
         else:
@@ -515,20 +544,22 @@ class RiskSensitiveMPC:
         solver = getattr(self, "solver", None) if solver is None else solver
         if solver not in (None, "mppi", "lbfgs", "auglag"):
             raise ValueError("solver must be None, 'mppi', 'lbfgs' or 'auglag', got %r" % (solver,))
-        if self._linearised() and solver in ("lbfgs", "auglag"):
+        lin = self._linearised()
+        mmf = self._mm_full()
+        if lin and solver in ("lbfgs", "auglag"):
             raise NotImplementedError("propagation='linearised' with solver=%r: the device L-BFGS and augmented-Lagrangian solvers run the "
                                       "moment-matched rollout (not yet); use solver=None, n_starts > 1 or solver='mppi'" % (solver,))
         if solver == "auglag":
             if getattr(self, "state_constraints", None) is None:
                 raise ValueError("solver='auglag' is the constrained multi-start: without state constraints use solver='lbfgs'")
-            if self.full_covariance:
+            if self.full_covariance and not mmf:
                 raise NotImplementedError("solver='auglag' runs the diagonal rollout (gpmpc_auglag_solve): state constraints under the "
                                           "full-covariance rollout are not implemented")
         if solver == "lbfgs":
             if getattr(self, "state_constraints", None) is not None:
                 raise NotImplementedError("solver='lbfgs' is unconstrained: state constraints under the device multi-start search (an "
                                           "augmented Lagrangian over the batched evaluation) are not implemented")
-            if self.full_covariance:
+            if self.full_covariance and not mmf:
                 raise NotImplementedError("solver='lbfgs' runs the diagonal rollout (gpmpc_lbfgs_solve): the search over the full-covariance "
                                           "rollout is not implemented")
         if solver == "mppi":
@@ -562,6 +593,9 @@ class RiskSensitiveMPC:
         if sc is not None and self._fullcov_mm():
             raise NotImplementedError("state constraints under the full-covariance rollout are not implemented "
                                       "(q = a^T Sigma_t a and that path's Jacobian layout: a follow-up)")
+        if sc is not None and K > 1 and mmf:
+            raise NotImplementedError("propagation='moment_matching_full': the host lock-step multi-start solve is unconstrained -- use "
+                                      "n_starts = 1, or solver='auglag' for a constrained multi-start on the full-covariance rule")
         if sc is not None and K > 1:
             raise NotImplementedError("the lock-step multi-start solve is unconstrained: use n_starts = 1 with state constraints "
                                       "(a constrained multi-start, e.g. an augmented Lagrangian over the batched evaluation, is a follow-up)")
@@ -647,7 +681,8 @@ class RiskSensitiveMPC:
         r = solve(self._linearised_model(self.dynamics.pack()) if lin else self.dynamics.pack(), self.curr_state, start, self._cost_params(),
                   constraints=self.state_constraints, samples=int(opt.get("samples", 64)), iterations=int(opt.get("iterations", 30)), sigma=sigma,
                   decay=float(opt.get("decay", 0.9)), beta=float(opt.get("beta", 0.1)), seed=int(opt.get("seed", 0)),
-                  call_index=self._solve_count, lb=lb, ub=ub, **(dict(self._lin_kw(), form=self.linearised_form) if lin else {}))
+                  call_index=self._solve_count, lb=lb, ub=ub,
+                  **(dict(self._lin_kw(), form=self.linearised_form) if lin else ({"full_covariance": True} if self._mm_full() else {})))
         self._solve_count += 1
         self.solver_used = "mppi x%d" % int(opt.get("samples", 64))
         self.last_solve_info = {"cost": r["cost"], "violation": r["violation"], "feasible": r["feasible"], "success": r["feasible"],
@@ -666,7 +701,7 @@ class RiskSensitiveMPC:
                                     lb=np.asarray(self.lb, dtype=np.float64), ub=np.asarray(self.ub, dtype=np.float64),
                                     max_ticks=int(opt.get("max_ticks", 150)), history=int(opt.get("history", 8)),
                                     gtol=float(opt.get("gtol", 1e-4)), ftol=float(opt.get("ftol", 1e-10)),
-                                    check_every=int(opt.get("check_every", 8)))
+                                    check_every=int(opt.get("check_every", 8)), full_covariance=self._mm_full())
         info["starts"] = K
         info["sharded_over"] = 1
         self.last_solve_info = info
@@ -682,7 +717,7 @@ class RiskSensitiveMPC:
         X0 = self._starts(K, lb, ub, self.multistart_options)
         U, cost, info = auglag_solve(self.dynamics.pack(), self.curr_state, X0.reshape(K, H, da), self._cost_params(), self.state_constraints,
                                      lb=np.asarray(self.lb, dtype=np.float64), ub=np.asarray(self.ub, dtype=np.float64),
-                                     **self.auglag_options)
+                                     full_covariance=self._mm_full(), **self.auglag_options)
         best = info["best"]
         info["starts"] = K
         info["success"] = bool(info["feasible"][best])
@@ -706,13 +741,14 @@ class RiskSensitiveMPC:
             dist = torch.distributed
 
         lin = self._linearised()
+        mmf = self._mm_full()
 
         def run(x0b, Ub, graph):
             if lin:                                                       # (plain launches: graph replay of the linearised rollout is not provided)
                 from .linearised import linearised_rollout
                 return linearised_rollout(self._linearised_model(pack), x0b, Ub, cp, want_grad=True, want_traj=False, form=self.linearised_form,
                                           **self._lin_kw())
-            if self.full_covariance:
+            if self.full_covariance or mmf:
                 return rollout_fullcov(pack, x0b, Ub, cp, want_grad=True)
             return rollout(pack, x0b, Ub, cp, want_grad=True, want_traj=False, graph=graph)
 

@@ -13,7 +13,7 @@ import torch
 from . import _lib
 from ._lib import MppiParamsC, check, lib, ptr, require_gpu, stream_ptr
 from ._solver import per_input, solver_problem
-from .rollout import _dev
+from .rollout import _dev, _fullcov_pack
 
 DEFAULTS = {"samples": 64, "iterations": 30, "sigma": None, "decay": 0.9, "beta": 0.1, "seed": 0}
 
@@ -93,12 +93,18 @@ TRACE_FIELDS = ("best_violation", "best_cost", "feasible", "alive", "s_min", "te
 
 
 def mppi_solve(pack, x0, U0, cost, constraints=None, samples=64, iterations=30, sigma=1.0, decay=0.9, beta=0.1, seed=0, call_index=0,
-               lb=None, ub=None):
+               lb=None, ub=None, full_covariance=False):
     """The whole search as one enqueue (C ABI ``gpmpc_mppi_solve``): per iteration the sample kernel, ``gpmpc_rollout`` (or
     ``gpmpc_rollout_constrained`` with ``constraints``, a :class:`StateConstraints`) objective-only over the K samples, the update kernel;
     one device-to-host copy at the end.  x0 (ds,), U0 (H, da) the plan the search starts from.
+    full_covariance=True: the same search over the full-covariance rollout (C ABI ``gpmpc_mppi_solve_fullcov``:
+    ``gpmpc_rollout_fullcov`` / ``gpmpc_rollout_fullcov_constrained``, rows on a^T Sigma_t a).
     Returns dict(U (H, da) numpy: the best plan seen, cost, violation, feasible, trace (iterations, 6) numpy, columns TRACE_FIELDS)."""
     dev = pack.device
+    solve, size, what = lib().gpmpc_mppi_solve, lib().gpmpc_mppi_solve_workspace_bytes, "gpmpc_mppi_solve"
+    if full_covariance:
+        _fullcov_pack(pack)
+        solve, size, what = lib().gpmpc_mppi_solve_fullcov, lib().gpmpc_mppi_solve_fullcov_workspace_bytes, "gpmpc_mppi_solve_fullcov"
     x0, U0 = solver_problem(pack, x0, U0, cost, "U0", "(H, da)")
     H, da = U0.shape
     if constraints is not None and constraints.ds != pack.ds:
@@ -108,12 +114,11 @@ def mppi_solve(pack, x0, U0, cost, constraints=None, samples=64, iterations=30, 
     n = H * da
     # [best plan | key | trace]: one block, one copy
     res = torch.empty(n + 2 + 6 * max(P.iterations, 1), dtype=torch.float64, device=dev)
-    nbytes = lib().gpmpc_mppi_solve_workspace_bytes(pack.handle, H, ctypes.byref(P), cons)
+    nbytes = size(pack.handle, H, ctypes.byref(P), cons)
     ws = pack.workspace(max(int(nbytes), 256))
     with torch.cuda.device(dev):
-        check(lib().gpmpc_mppi_solve(pack.handle, H, ptr(x0), ptr(U0), ctypes.byref(cost.c), cons, ctypes.byref(P), ptr(res[:n]),
-                                     ptr(res[n:n + 2]), ptr(res[n + 2:]), ctypes.c_void_p(ws.data_ptr()), ws.numel(), stream_ptr()),
-              "gpmpc_mppi_solve")
+        check(solve(pack.handle, H, ptr(x0), ptr(U0), ctypes.byref(cost.c), cons, ctypes.byref(P), ptr(res[:n]),
+                    ptr(res[n:n + 2]), ptr(res[n + 2:]), ctypes.c_void_p(ws.data_ptr()), ws.numel(), stream_ptr()), what)
     host = res.cpu().numpy()
     return {"U": host[:n].reshape(H, da).copy(), "violation": float(host[n]), "cost": float(host[n + 1]), "feasible": bool(host[n] == 0.0),
             "trace": host[n + 2:].reshape(-1, 6).copy()}

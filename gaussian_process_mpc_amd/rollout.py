@@ -639,21 +639,44 @@ def rollout_constraints(means, vars, jac, sc, ds, da):
     return out
 
 
-def rollout_fullcov(pack, x0, U, cost, want_grad=True):
-    """Like :func:`rollout` but propagating the FULL state covariance (C ABI ``gpmpc_rollout_fullcov``;
-    BASELINE config 5).  Returns cost (B,), grad (B,H,da), means (B,H+1,ds), covs (B,H+1,ds,ds)."""
-    dev = pack.device
+def _fullcov_pack(pack):
+    """What every full-covariance entry asks of a pack: no nominal model, cross-covariance weights."""
     if pack._nominal is not None:
         raise NotImplementedError("the full-covariance rollout does not support a pack with a linear nominal model "
                                   "(its cross-covariances with the linear part are not implemented)")
     if not pack.fullcov:
         pack.enable_fullcov()
+
+
+def rollout_fullcov(pack, x0, U, cost, want_grad=True, constraints=None):
+    """Like :func:`rollout` but propagating the FULL state covariance (C ABI ``gpmpc_rollout_fullcov``;
+    BASELINE config 5).  Returns cost (B,), grad (B,H,da), means (B,H+1,ds), covs (B,H+1,ds,ds).
+
+    constraints: a :class:`StateConstraints` -- the same device pass also returns g (B, H, m_c) under the full rule
+    g[t, r] = A[r] . mu_t + kappa[r] sqrt(A[r]^T Sigma_t A[r]) - b[r] and, with ``want_grad``, g_jac (B, H m_c, H da) (C ABI
+    ``gpmpc_rollout_fullcov_constrained``); cost, grad, means and covs keep their bits.  None: the function is exactly what it was."""
+    dev = pack.device
+    _fullcov_pack(pack)
     x0, U, B, H, da = _problem(pack, x0, _dev(U, dev), cost)
     flags = _lib.WANT_GRAD if want_grad else 0
     e = functools.partial(_empty, dev)
     out = {"cost": e(B), "means": e(B, H + 1, pack.ds), "covs": e(B, H + 1, pack.ds, pack.ds)}
     if want_grad:
         out["grad"] = e(B, H, da)
+    if constraints is not None:
+        sc = constraints
+        if sc.ds != pack.ds:
+            raise ValueError("the constraint rows have %d state coefficients, the pack has %d states" % (sc.ds, pack.ds))
+        out["g"] = e(B, H, sc.m)
+        if want_grad:
+            out["g_jac"] = e(B, H * sc.m, H * da)
+        ws = pack.workspace(lib().gpmpc_rollout_fullcov_constrained_workspace_bytes(pack.handle, B, H, flags))
+        with torch.cuda.device(dev):
+            check(lib().gpmpc_rollout_fullcov_constrained(pack.handle, B, H, ptr(x0), ptr(U), ctypes.byref(cost.c), ctypes.byref(sc.c), flags,
+                                                          ptr(out["means"]), ptr(out["covs"]), ptr(out["cost"]), ptr(out.get("grad")),
+                                                          ptr(out["g"]), ptr(out.get("g_jac")), ctypes.c_void_p(ws.data_ptr()), ws.numel(),
+                                                          stream_ptr()), "gpmpc_rollout_fullcov_constrained")
+        return out
     nbytes = lib().gpmpc_rollout_fullcov_workspace_bytes(pack.handle, B, H, flags)
     ws = pack.workspace(nbytes)
     with torch.cuda.device(dev):
@@ -661,6 +684,33 @@ def rollout_fullcov(pack, x0, U, cost, want_grad=True):
                                           ptr(out["means"]), ptr(out["covs"]), ptr(out["cost"]), ptr(out.get("grad")),
                                           ctypes.c_void_p(ws.data_ptr()), ws.numel(), stream_ptr()),
               "gpmpc_rollout_fullcov")
+    return out
+
+
+def rollout_fullcov_jac(pack, x0, U):
+    """Means, covariances and the PACKED step Jacobians of B full-covariance rollouts, no cost (C ABI ``gpmpc_rollout_fullcov_jac``, the
+    counterpart of ``gpmpc_rollout_jac``).  x0: (B, ds) or (ds,); U: (B, H, da) or (H, da).  Returns means (B, H+1, ds), covs
+    (B, H+1, ds, ds), jac (B, H, p, p + da) with p = ds + ds (ds + 1) / 2 in the convention of ``linearised.linearised_step_full``: what
+    ``linearised.linearised_fc_vjp`` and ``linearised.linearised_fc_constraints`` take.  Not differentiable by autograd."""
+    dev = pack.device
+    _fullcov_pack(pack)
+    U = _dev(U, dev)
+    if U.ndim == 2:
+        U = U[None]
+    B, H, da = U.shape
+    x0 = _dev(x0, dev).reshape(-1, pack.ds)
+    if x0.shape[0] == 1 and B > 1:
+        x0 = x0.expand(B, pack.ds).contiguous()
+    if da != pack.da or x0.shape[0] != B:
+        raise ValueError("shape mismatch between pack, x0 and U")
+    ds = pack.ds
+    p = ds + ds * (ds + 1) // 2
+    e = functools.partial(_empty, dev)
+    out = {"means": e(B, H + 1, ds), "covs": e(B, H + 1, ds, ds), "jac": e(B, H, p, p + da)}
+    ws = pack.workspace(lib().gpmpc_rollout_fullcov_jac_workspace_bytes(pack.handle, B, H))
+    with torch.cuda.device(dev):
+        check(lib().gpmpc_rollout_fullcov_jac(pack.handle, B, H, ptr(x0), ptr(U), ptr(out["means"]), ptr(out["covs"]), ptr(out["jac"]),
+                                              ctypes.c_void_p(ws.data_ptr()), ws.numel(), stream_ptr()), "gpmpc_rollout_fullcov_jac")
     return out
 
 

@@ -646,6 +646,64 @@ int gpmpc_rollout_fullcov(const gpmpc_pack* pack, int B, int H, const double* x0
  * four (assemble, prepare, pair kernel on 256x256 tiles, close).  out_bytes >= 64; returns 0 or GPMPC_E_ARG. */
 int gpmpc_rollout_fullcov_describe(const gpmpc_pack* pack, int B, int H, unsigned flags, char* out, size_t out_bytes);
 
+/* ---------------------------------------------------------------------------
+ * Full-covariance rollout: Jacobian and chance constraints (no reference counterpart; DESIGN.md section 3l, csrc/fullcov_cons.hip).
+ * Both forms of gpmpc_rollout_fullcov keep the Jacobians of every moment-matched step; k_fc_pack_jac gathers them into the PACKED step
+ * Jacobian of gpmpc_linearised_fc_step ("Linearised propagation, full covariance", below), p = ds + ds (ds + 1) / 2:
+ *     out_jac dev [B][H][p][p + da]: rows (mu'_a, Sigma'_ab for a <= b, row-major), columns (mu_k, Sigma_kl for k <= l, u_j).
+ *     An off-diagonal Sigma_kl = Sigma_lk is ONE variable: its column is d/dS_kl + d/dS_lk of the stored derivative, formed as that sum.
+ *     Sigma is the STORED covariance (out_covs: process_var on the diagonal of every step t >= 1).  The state columns of step 1 are written
+ *     (Sigma_0 = init_cov is a constant: gpmpc_linearised_fc_vjp / _constraints never read them).  Every element is written.
+ * gpmpc_rollout_fullcov_jac is the counterpart of gpmpc_rollout_jac: means, covariances and that Jacobian, no cost.  Its pair
+ * (out_means, out_covs, out_jac) is what gpmpc_linearised_fc_vjp and gpmpc_linearised_fc_constraints take.
+ *
+ * gpmpc_rollout_fullcov_constrained is the counterpart of gpmpc_rollout_constrained under the full rule,
+ *     g[t][r] = a_r . mu_t + kappa_r sqrt(a_r^T Sigma_t a_r) - b_r,      Sigma_t as stored,
+ * with the rules of gpmpc_rollout_constraints unchanged: a radicand <= 0 gives sd = 0 and no variance part, columns tau >= t of out_gjac are
+ * exactly 0.0, every element is written.  out_g dev [B][H][n_rows], out_gjac dev [B][H n_rows][H da].
+ *   With GPMPC_WANT_GRAD: the launches of gpmpc_rollout_fullcov (gradient), k_fc_pack_jac into the workspace, then the sweep of
+ *   gpmpc_linearised_fc_constraints.  Without: the objective-only rollout (no Jacobian is kept) and the values-only sweep; out_grad and
+ *   out_gjac are not written and may be NULL.  out_cost, out_grad, out_means, out_covs are bit-identical to gpmpc_rollout_fullcov's on the
+ *   same inputs; out_g does not depend on the flag.  out_means / out_covs may be NULL (kept in the workspace).
+ * Refused before anything is launched, text in gpmpc_last_error: GPMPC_E_STATE on what gpmpc_rollout_fullcov refuses in a pack (a linear
+ * nominal model, not built, no gpmpc_pack_enable_fullcov); GPMPC_E_ARG on what gpmpc_check_constraints refuses in the rows (n_rows, kappa),
+ * on flags other than GPMPC_WANT_GRAD (GPMPC_USE_GRAPH and the GPMPC_FP32_* modes included), on a bad cost schedule, action_dim < 1,
+ * sizes beyond the sweeps' grids, state_dim > 6 (the cost kernel of the full-covariance rollout is built up to 6: gpmpc_rollout_fullcov
+ * returns the same code there, after its rollout has been enqueued) and -- gpmpc_rollout_fullcov_constrained only, which runs that kernel --
+ * a horizon beyond its LDS.  gpmpc_rollout_fullcov_jac runs no cost kernel: the LDS does not bound its horizon.  GPMPC_E_WORKSPACE.
+ * ------------------------------------------------------------------------- */
+size_t gpmpc_rollout_fullcov_jac_workspace_bytes(const gpmpc_pack* pack, int B, int H);
+int gpmpc_rollout_fullcov_jac(const gpmpc_pack* pack, int B, int H, const double* x0_dev, const double* U_dev,
+                              double* out_means, double* out_covs, double* out_jac,
+                              void* workspace, size_t workspace_bytes, void* stream);
+size_t gpmpc_rollout_fullcov_constrained_workspace_bytes(const gpmpc_pack* pack, int B, int H, unsigned flags);
+int gpmpc_rollout_fullcov_constrained(const gpmpc_pack* pack, int B, int H, const double* x0_dev, const double* U_dev,
+                                      const gpmpc_cost_params* cost_host, const gpmpc_state_constraints* cons_host, unsigned flags,
+                                      double* out_means, double* out_covs, double* out_cost, double* out_grad,
+                                      double* out_g, double* out_gjac, void* workspace, size_t workspace_bytes, void* stream);
+
+/* The device solvers on the full-covariance rule: gpmpc_mppi_solve, gpmpc_lbfgs_solve and gpmpc_auglag_solve with ONE difference, the
+ * evaluation of the batch -- gpmpc_rollout_fullcov_constrained objective-only (gpmpc_rollout_fullcov without constraints) for MPPI,
+ * gpmpc_rollout_fullcov with GPMPC_WANT_GRAD for the L-BFGS search, gpmpc_rollout_fullcov_constrained with GPMPC_WANT_GRAD for the
+ * augmented Lagrangian.  Parameters, state layouts, the order of the checks and every other kernel are those of the entries above, and
+ * those entries return what they returned.  More refusals, after "not built" and before the cost schedule, all with text: GPMPC_E_STATE on a
+ * pack with a linear nominal model or without gpmpc_pack_enable_fullcov; GPMPC_E_ARG on state_dim > 6 and on a horizon beyond the LDS of
+ * the full-covariance cost kernel.  A workspace is sized by the query of the SAME rule. */
+size_t gpmpc_mppi_solve_fullcov_workspace_bytes(const gpmpc_pack* pack, int H, const gpmpc_mppi_params* params_host,
+                                                const gpmpc_state_constraints* cons_host);
+int gpmpc_mppi_solve_fullcov(const gpmpc_pack* pack, int H, const double* x0_dev, const double* start_dev, const gpmpc_cost_params* cost_host,
+                             const gpmpc_state_constraints* cons_host, const gpmpc_mppi_params* params_host, double* out_U, double* out_best,
+                             double* out_trace, void* workspace, size_t workspace_bytes, void* stream);
+size_t gpmpc_lbfgs_solve_fullcov_workspace_bytes(const gpmpc_pack* pack, int H, const gpmpc_lbfgs_params* params_host);
+int gpmpc_lbfgs_solve_fullcov(const gpmpc_pack* pack, int H, const double* x0_dev, const double* X0_dev, const gpmpc_cost_params* cost_host,
+                              const gpmpc_lbfgs_params* params_host, int first_tick, int n_ticks, void* workspace, size_t workspace_bytes,
+                              void* stream);
+size_t gpmpc_auglag_solve_fullcov_workspace_bytes(const gpmpc_pack* pack, int H, const gpmpc_state_constraints* cons_host,
+                                                  const gpmpc_auglag_params* params_host);
+int gpmpc_auglag_solve_fullcov(const gpmpc_pack* pack, int H, const double* x0_dev, const double* X0_dev, const gpmpc_cost_params* cost_host,
+                               const gpmpc_state_constraints* cons_host, const gpmpc_auglag_params* params_host, int first_outer, int n_outer,
+                               void* workspace, size_t workspace_bytes, void* stream);
+
 /* The solver callback pair RiskSensitiveMPC.objective(x) / gradient(x) (src/mpc.py:202-255) for ONE candidate, host in and
  * host out like the cyipopt callbacks themselves: x0_host [ds] current state, U_host [H][da] the candidate (Ipopt's x),
  * out_host [1 + H da] = cost, then d cost / d U row-major (flags = GPMPC_WANT_GRAD; 0: cost only, out_host [1]).
