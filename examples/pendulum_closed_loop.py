@@ -7,6 +7,7 @@ src/experiments/pretrain_uncertainty.py: pre-train the GP on random transitions,
                                             [--max-speed V [--prob P]] [--solver mppi [--samples K] [--iters I]] [--solver lbfgs [--starts K]]
                                             [--max-speed V --solver auglag [--starts K]] [--track AMPLITUDE,PERIOD [--terminal W]]
                                             [--obs-var V [--process-var sigma_n]] [--inducing M [--inducing-select farthest|random]]
+                                            [--propagation particles --solver mppi [--particles P]]
 
 --window N: fixed-size training window -- once the model holds N points every new observation replaces the oldest one (first-in
 first-out), so the cost of the data update and the memory stay constant however long the loop runs (what the solver makes of a model
@@ -39,6 +40,11 @@ set_xref every step would capture it every step.  --terminal W: terminal weight 
 told so: V I is the covariance of the start state of every prediction (RiskSensitiveMPC.set_initial_covariance -- where an estimator runs, its
 covariance goes there, before every solve; the values live in device memory, the callback graph is captured once).  --process-var sigma_n
 adds each GP's noise variance to its predicted variance at every step: the spread of the next STATE, not of the latent function.
+
+--propagation particles --solver mppi [--particles P]: the planner scores every sample on P Monte-Carlo particles through the GP posterior
+(RiskSensitiveMPC.propagation = "particles", particles.mppi_solve_particles): the entropic risk of the stage cost over the particles, and with
+--max-speed the empirical quantile of |theta_dot| - V in the place of mean + kappa sd.  No gradients: it needs --solver mppi.  Works with
+--nominal identity, --inducing and --window.
 
 --inducing M [--inducing-select farthest|random]: sparse GP dynamics (RiskSensitiveMPC.use_inducing_points, sparse.py): M inducing points
 chosen among the pre-training inputs summarise ALL observations (FITC); every new observation is an O(M^2) rank-one update on the device
@@ -100,10 +106,12 @@ def main():
     ap.add_argument("--process-var", choices=("sigma_n",), default=None, help="sigma_n: add each GP's noise variance to its predicted variance")
     ap.add_argument("--inducing", type=int, default=None, metavar="M", help="sparse GP dynamics on M inducing points (FITC), chosen among the pre-training inputs")
     ap.add_argument("--inducing-select", choices=("farthest", "random"), default="farthest", help="how --inducing picks its points")
-    ap.add_argument("--propagation", choices=("moment_matching", "moment_matching_full", "linearised", "linearised_full"), default="moment_matching",
+    ap.add_argument("--propagation", choices=("moment_matching", "moment_matching_full", "linearised", "linearised_full", "particles"), default="moment_matching",
                     help="linearised: first-order propagation mu' = m(z), var' = s2(z) + grad m^T S grad m (mpc.propagation); with the default solver, --starts K or --solver mppi.  "
                          "linearised_full: the same rule with the whole covariance, predicted under --feedback.  "
-                         "moment_matching_full: exact moment matching with the whole covariance (chance rows on a^T Sigma a), every solver; not with --nominal")
+                         "moment_matching_full: exact moment matching with the whole covariance (chance rows on a^T Sigma a), every solver; not with --nominal.  "
+                         "particles: cost and chance rows on --particles Monte-Carlo particles; needs --solver mppi")
+    ap.add_argument("--particles", type=int, default=256, metavar="P", help="with --propagation particles: particles per sample (1 ... 4096; mpc.particle_options)")
     ap.add_argument("--feedback", choices=("none", "lqr"), default="none",
                     help="with --propagation linearised_full: lqr predicts under u = v + K (x - mu) with the LQR gain of the model linearised at the upright rest "
                          "(linearised.lqr_gain with the controller's Q and R; mpc.set_feedback_gain)")
@@ -114,6 +122,10 @@ def main():
         ap.error("--window must be >= 1")
     if args.propagation in ("linearised", "linearised_full") and args.solver in ("lbfgs", "auglag"):
         ap.error("--propagation %s runs with the default solver, --starts K or --solver mppi (the device L-BFGS / augmented Lagrangian: not yet)" % args.propagation)
+    if args.propagation == "particles" and args.solver != "mppi":
+        ap.error("--propagation particles needs --solver mppi (there are no gradients through particles)")
+    if not 1 <= args.particles <= 4096:
+        ap.error("--particles must lie in 1...4096")
     if args.feedback != "none" and args.propagation != "linearised_full":
         ap.error("--feedback needs --propagation linearised_full")
     if args.propagation == "moment_matching_full" and args.nominal != "none":
@@ -149,6 +161,7 @@ def main():
     mpc.n_starts = args.starts
     mpc.propagation = args.propagation
     mpc.linearised_form = args.linearised_form
+    mpc.particle_options = {"particles": args.particles}
     if args.feedback == "lqr":
         from gaussian_process_mpc_amd import lqr_gain
         K = lqr_gain(mpc.dynamics, np.zeros(2), np.zeros(1), 2 * np.eye(2), 0.001 * np.eye(1))

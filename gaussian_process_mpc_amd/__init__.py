@@ -27,6 +27,7 @@ from .device_lbfgs import lbfgs_start, lbfgs_tick, lbfgs_solve, lbfgs_state_view
 from .device_auglag import auglag_params, auglag_merit, auglag_outer, auglag_solve, auglag_state_view, auglag_state_fields   # noqa: F401
 from .sparse import SparseGPState, SparseDynamics, select_inducing      # noqa: F401
 from .particles import GPModel, gp_posterior, particle_noise, particle_step, particle_stats, particle_rollout   # noqa: F401
+from .particles import particle_cost, particle_evaluate, mppi_solve_particles   # noqa: F401
 from .linearised import linearised_form, linearised_step, linearised_rollout, mppi_solve_linearised   # noqa: F401
 from .linearised import linearised_step_full, linearised_fc_vjp, linearised_fc_constraints, packed_dim, lqr_gain, riccati_gain   # noqa: F401
 
@@ -36,6 +37,7 @@ __all__ = ["GaussianProcessRegression", "Dynamics", "RiskSensitiveMPC", "mean_pr
            "auglag_params", "auglag_merit", "auglag_outer", "auglag_solve", "auglag_state_view", "auglag_state_fields",
            "SparseGPState", "SparseDynamics", "select_inducing",
            "GPModel", "gp_posterior", "particle_noise", "particle_step", "particle_stats", "particle_rollout",
+           "particle_cost", "particle_evaluate", "mppi_solve_particles",
            "linearised_form", "linearised_step", "linearised_rollout", "mppi_solve_linearised",
            "linearised_step_full", "linearised_fc_vjp", "linearised_fc_constraints", "packed_dim", "lqr_gain", "riccati_gain",
            "Simulator", "PendulumPlant", "CartPolePlant", "lib", "require_gpu"]

@@ -17,6 +17,7 @@ MAX_D = 8
 MAX_DS = 8
 MAX_CONS = 16
 MPPI_MAX_SAMPLES = 4096
+PARTICLE_COST_MAX_P = 4096
 LBFGS_MAX_STARTS = 256
 LBFGS_MAX_HISTORY = 16
 WANT_GRAD = 1
@@ -244,6 +245,12 @@ SIGNATURES = {
     "gpmpc_particle_stats": (_i, [_i, _i, _i, _i, _vp, _vp, _sc, _vp, _vp, _vp, _vp, _vp, _vp]),
     "gpmpc_particle_rollout_workspace_bytes": (_sz, [_gm, _i, _i, _i, _i]),
     "gpmpc_particle_rollout": (_i, [_gm, _i, _i, _i, _vp, _vp, _ull, _u, _sc, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _sz, _vp]),
+    "gpmpc_particle_cost": (_i, [_i, _i, _i, _i, _i, ctypes.POINTER(CostParamsC), _sc, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "gpmpc_particle_evaluate_workspace_bytes": (_sz, [_gm, _i, _i, _i, _i]),
+    "gpmpc_particle_evaluate": (_i, [_gm, _i, _i, _i, _vp, _vp, _ull, _u, ctypes.POINTER(CostParamsC), _sc, _vp, _vp, _vp, _i, _vp, _sz, _vp]),
+    "gpmpc_mppi_solve_particles_workspace_bytes": (_sz, [_gm, _i, _i, ctypes.POINTER(MppiParamsC), _sc]),
+    "gpmpc_mppi_solve_particles": (_i, [_gm, _i, _i, _vp, _vp, ctypes.POINTER(CostParamsC), _sc, ctypes.POINTER(MppiParamsC), _vp, _vp, _vp,
+                                        _vp, _sz, _vp]),
     "gpmpc_linearised_set_form": (_i, [_i]),
     "gpmpc_linearised_step_workspace_bytes": (_sz, [_gm, _i, _i, _i]),
     "gpmpc_linearised_step": (_i, [_gm, _i, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _sz, _i, _vp, _sz, _vp]),

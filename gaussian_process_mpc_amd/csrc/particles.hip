@@ -14,6 +14,7 @@
 #include "gpmpc_internal.h"
 #include "tile_stage.h"
 #include "philox.h"
+#include "particles_internal.h"
 
 #define PT_DEFAULT_CHUNK 4096
 #define PT_KEY_XOR 0x50415254u      // "PART": keeps the particle streams apart from the MPPI streams of the same seed
@@ -435,6 +436,13 @@ static bool pt_model_sizes_ok(const gpmpc_gp_model* m) {
     return m && m->state_dim >= 1 && m->state_dim <= GPMPC_MAX_DS && m->action_dim >= 0 && m->state_dim + m->action_dim <= GPMPC_MAX_D && m->n >= 1;
 }
 
+// for particle_cost.hip (particles_internal.h)
+bool gpmpc_pt_model_sizes_ok(const gpmpc_gp_model* m) { return pt_model_sizes_ok(m); }
+int gpmpc_pt_check_model(const char* who, const gpmpc_gp_model* m) {
+    PtNoise noise;
+    return pt_check_model(who, m, &noise);
+}
+
 extern "C" size_t gpmpc_gp_posterior_workspace_bytes(const gpmpc_gp_model* m, int nq, int chunk) {
     if (!pt_model_sizes_ok(m) || nq < 1 || chunk < 0 || chunk % 64) return 0;
     gpmpc_carver c;
@@ -488,6 +496,18 @@ static int pt_check_bp(const char* who, int B, int P) {
     if (B < 1) return gpmpc_refuse(who, "B < 1");
     if (P < 1) return gpmpc_refuse(who, "P < 1");
     return pt_check_count(who, (long)B * P, GPMPC_MAX_D);
+}
+
+int gpmpc_pt_check_bp(const char* who, int B, int P) { return pt_check_bp(who, B, P); }
+
+int gpmpc_pt_initial(const gpmpc_gp_model* m, int B, int P, const double* x0, const double* eps, double* out, hipStream_t s) {
+    PtNoise noise;
+    if (int rc = pt_noise("gpmpc_pt_initial", m, &noise)) return rc;
+    PtVec L;
+    memcpy(L.v, noise.L, sizeof(L.v));
+    hipLaunchKernelGGL(k_pt_init, dim3(pt_blocks((long)B * P * m->state_dim)), dim3(256), 0, s, B, P, m->state_dim, x0, eps, L, out);
+    GPMPC_HIP(hipGetLastError());
+    return GPMPC_OK;
 }
 
 static int pt_step(const gpmpc_gp_model* m, const PtNoise& noise, int B, int P, const double* x_prev, const double* U_t, size_t u_stride,

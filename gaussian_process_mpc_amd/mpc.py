@@ -54,6 +54,14 @@ forced by moving the rollout into one fused HIP call:
   multi-start, ``solver = "mppi" | "lbfgs" | "auglag"`` (``gpmpc_*_solve_fullcov``) and ``validate_plan`` (``cov_mm``).  The
   ``full_covariance`` attribute is not consulted under it; ``"moment_matching"`` with ``full_covariance=True`` keeps the refusals it had.
   Refused under it: a feedback gain, a nominal model, ``n_starts > 1`` with state constraints and ``solver=None``.
+* ``mpc.propagation = "particles"`` (extension; particles.py): no moments at all -- the plan is scored on
+  ``mpc.particle_options["particles"]`` Monte-Carlo particles through the GP posterior: the entropic risk of the stage cost over the
+  particles and, for the chance constraints, the empirical quantile of every row's margin (kappa = 0 constrains the MEDIAN where the
+  Gaussian rule constrains the mean).  It is the distribution ``validate_plan`` checks a moment-matched plan against, and it serves
+  nominal models, the noise model, ``SparseDynamics`` and windows.  There are no gradients through particles: ``solver = "mppi"``
+  (``gpmpc_mppi_solve_particles``; the seed is ``mppi_options["seed"]``, the call index the solve count, the particle noise the same in
+  every iteration of a solve), ``evaluate_batch`` (cost and g, ``grad`` None) and ``objective(x)`` work; ``gradient``, ``jacobian`` and
+  every other solver, the default included, raise ``NotImplementedError``.  A feedback gain raises; ``full_covariance`` is not consulted.
 """
 import numpy as np
 import torch
@@ -71,7 +79,8 @@ except Exception:                       # pragma: no cover
 
 
 class RiskSensitiveMPC:
-    propagation = "moment_matching"                      # | "moment_matching_full" | "linearised" | "linearised_full" (extension): which rule the rollouts of the solvers use
+    propagation = "moment_matching"                      # | "moment_matching_full" | "linearised" | "linearised_full" | "particles" (extension): which rule the rollouts of the solvers use
+    particle_options = {"particles": 256}                # propagation = "particles": particles per plan (1 ... 4096); assign a new dict to change it
     linearised_form = None                               # | "tile" | "stream" | "auto": the form of the linearised step (None: the process-wide one)
 
     def __init__(self, gamma, horizon, state_dim, input_dim, Q, R, R_delta=None, full_covariance=False, nominal_models=None):
@@ -304,8 +313,9 @@ class RiskSensitiveMPC:
     def _linearised(self):
         """True under ``propagation = "linearised"``, after the refusals every entry shares."""
         prop = self.propagation
-        if prop not in ("moment_matching", "moment_matching_full", "linearised", "linearised_full"):
-            raise ValueError("propagation must be 'moment_matching', 'moment_matching_full', 'linearised' or 'linearised_full', got %r" % (prop,))
+        if prop not in ("moment_matching", "moment_matching_full", "linearised", "linearised_full", "particles"):
+            raise ValueError("propagation must be 'moment_matching', 'moment_matching_full', 'linearised', 'linearised_full' or 'particles', "
+                             "got %r" % (prop,))
         if prop == "linearised" and self.full_covariance:
             raise NotImplementedError("propagation='linearised' is diagonal: a full-covariance linearised rollout is not implemented (not yet)")
         if getattr(self, "_feedback_gain", None) is not None and prop != "linearised_full":
@@ -329,7 +339,7 @@ class RiskSensitiveMPC:
     def _fullcov_mm(self):
         """``full_covariance`` as the paths that refuse it read it: under "linearised_full" and "moment_matching_full" the attribute is
         not consulted."""
-        return bool(self.full_covariance) and self.propagation not in ("linearised_full", "moment_matching_full")
+        return bool(self.full_covariance) and self.propagation not in ("linearised_full", "moment_matching_full", "particles")
 
     def set_feedback_gain(self, K):
         """The gain of the predicted input u_t = v_t + K_t (x_t - mu_t) under ``propagation = "linearised_full"``: (da, ds) for every step or
@@ -351,6 +361,28 @@ class RiskSensitiveMPC:
     @property
     def feedback_gain(self):
         return getattr(self, "_feedback_gain", None)
+
+    # -- propagation = "particles" (extension)
+    def _particles(self):
+        """True under ``propagation = "particles"``."""
+        return self.propagation == "particles"
+
+    def _particles_refuse(self, what):
+        raise NotImplementedError("propagation='particles' has no gradients through particles: %s is not available -- use solver='mppi' "
+                                  "(mppi_solve_particles), evaluate_batch or objective" % (what,))
+
+    def _particle_kw(self):
+        """particles / seed / call index of every particle evaluation: ``particle_options``, ``mppi_options["seed"]`` and the solve count
+        (the call index the NEXT solve uses, so an evaluation between two solves sees the noise of the coming one)."""
+        return {"particles": int(self.particle_options.get("particles", 256)), "seed": int(self.mppi_options.get("seed", 0)),
+                "call_index": self._solve_count}
+
+    def _particle_evaluate(self, U, cs, constraints):
+        from .particles import particle_evaluate
+        r = particle_evaluate(self._linearised_model(self.dynamics.pack()), cs, U, self._cost_params(),
+                              constraints=self.state_constraints if constraints else None, **self._particle_kw())
+        r["grad"] = None
+        return r
 
     def _linearised_model(self, pack):
         """The dynamics as a ``particles.GPModel``, rebuilt when the pack or the noise model has changed."""
@@ -426,22 +458,34 @@ class RiskSensitiveMPC:
         return self.curr_cost, self.curr_grad
 
     def objective(self, x):
+        if self._particles():
+            self._linearised()
+            x = np.array(x, dtype=np.float64, copy=True).reshape(1, self.horizon, self.input_dim)
+            return float(self._particle_evaluate(x, self.curr_state, False)["cost"][0].item())
         return self._evaluate(x)[0]
 
     def gradient(self, x):
         """d cost / d U, shape (horizon, input_dim) like the reference (cyipopt flattens it)."""
+        if self._particles():
+            self._particles_refuse("gradient")
         return self._evaluate(x)[1]
 
     def constraints(self, x):
         """0 without state constraints (src/mpc.py:257-262); else g flattened to (H m_c,), row (t-1) m_c + r, feasible where <= 0."""
         if self.state_constraints is None:
             return 0
+        if self._particles():
+            self._linearised()
+            x = np.array(x, dtype=np.float64, copy=True).reshape(1, self.horizon, self.input_dim)
+            return self._particle_evaluate(x, self.curr_state, True)["g"][0].cpu().numpy().reshape(-1)
         self._evaluate(x)
         return self.curr_g
 
     def jacobian(self, x):
         """Zeros without state constraints (src/mpc.py:264-267); else the dense (H m_c, H da) Jacobian flattened row-major (cyipopt's
         default dense structure)."""
+        if self._particles():
+            self._particles_refuse("jacobian")
         if self.state_constraints is None:
             return np.zeros(x.shape)
         self._evaluate(x)
@@ -456,6 +500,8 @@ class RiskSensitiveMPC:
         lin = self._linearised()
         if constraints and self.state_constraints is None:
             raise ValueError("no state constraints are set (set_state_constraints / set_state_bounds)")
+        if self._particles():                                             # cost (B,), stage (B, H+1), g (B, H, m_c) or None, grad None
+            return self._particle_evaluate(U, cs, constraints)
         if lin:
             from .linearised import linearised_rollout
             return linearised_rollout(self._linearised_model(self.dynamics.pack()), cs, U, self._cost_params(), want_grad=want_grad,
@@ -489,6 +535,8 @@ class RiskSensitiveMPC:
         sum_t (x_t - x_ref)^T Q (x_t - x_ref) + sum_t (u_t - u_ref)^T R (u_t - u_ref) (torch, from the particles);
         with state constraints ``satisfaction`` (H, rows), the fraction of particles with a . x_t <= b at t = 1..H, next to
         ``requested`` (rows,) = Phi(kappa), and ``joint_satisfaction``, the fraction satisfying every row at every step.
+        With at most 4096 particles also what ``propagation = "particles"`` optimises, from ``particles.particle_cost`` on the same
+        particles: ``cost_mc``, ``stage_mc`` (H+1,) and, with state constraints, ``g_mc`` (H, rows).
         linearised=True adds the third column: ``mean_lin``, ``var_lin`` (H+1, ds) of the linearised rollout (linearised.py) and
         ``z_mean_lin``, ``z_var_lin``, its distance from the particles in the same Monte-Carlo standard errors."""
         from statistics import NormalDist
@@ -537,6 +585,12 @@ class RiskSensitiveMPC:
             out["satisfaction"] = 1.0 - mc["violation"][0, 1:].cpu().numpy()
             out["requested"] = np.array([NormalDist().cdf(float(k)) for k in sc.kappa])
             out["joint_satisfaction"] = 1.0 - float(mc["joint_violation"][0].item())
+        if P <= 4096:                                                     # (GPMPC_PARTICLE_COST_MAX_P: the particle cost sorts a row in LDS)
+            from .particles import particle_cost
+            pc = particle_cost(X.permute(1, 0, 2)[:, None].contiguous(), U[None], self._cost_params(), constraints=sc)
+            out["cost_mc"], out["stage_mc"] = float(pc["cost"][0].item()), pc["stage"][0].cpu().numpy()
+            if sc is not None:
+                out["g_mc"] = pc["g"][0].cpu().numpy()
         return out
 
     # -- solve (src/mpc.py:269-330)
@@ -546,6 +600,11 @@ class RiskSensitiveMPC:
             raise ValueError("solver must be None, 'mppi', 'lbfgs' or 'auglag', got %r" % (solver,))
         lin = self._linearised()
         mmf = self._mm_full()
+        if self._particles():
+            if solver != "mppi":
+                self._particles_refuse("solver=%r" % (solver,))
+            if not 1 <= int(self.particle_options.get("particles", 256)) <= 4096:
+                raise ValueError("particle_options['particles'] must be in 1..4096, got %r" % (self.particle_options.get("particles"),))
         if lin and solver in ("lbfgs", "auglag"):
             raise NotImplementedError("propagation='linearised' with solver=%r: the device L-BFGS and augmented-Lagrangian solvers run the "
                                       "moment-matched rollout (not yet); use solver=None, n_starts > 1 or solver='mppi'" % (solver,))
@@ -677,14 +736,26 @@ class RiskSensitiveMPC:
             prev = np.asarray(self.last_traj, dtype=np.float64).reshape(H, da)
             start = np.clip(np.concatenate((prev[1:], prev[-1:]), axis=0), lb, ub)
         lin = self._linearised()
+        if self._particles():
+            from .particles import mppi_solve_particles
+            pk = self._particle_kw()
+            r = mppi_solve_particles(self._linearised_model(self.dynamics.pack()), self.curr_state, start, self._cost_params(),
+                                     constraints=self.state_constraints, particles=pk["particles"], samples=int(opt.get("samples", 64)),
+                                     iterations=int(opt.get("iterations", 30)), sigma=sigma, decay=float(opt.get("decay", 0.9)),
+                                     beta=float(opt.get("beta", 0.1)), seed=pk["seed"], call_index=pk["call_index"], lb=lb, ub=ub)
+            return self._mppi_done(r, opt, "mppi-particles x%d P%d" % (int(opt.get("samples", 64)), pk["particles"]))
         solve = mppi_solve_linearised if lin else mppi_solve
         r = solve(self._linearised_model(self.dynamics.pack()) if lin else self.dynamics.pack(), self.curr_state, start, self._cost_params(),
                   constraints=self.state_constraints, samples=int(opt.get("samples", 64)), iterations=int(opt.get("iterations", 30)), sigma=sigma,
                   decay=float(opt.get("decay", 0.9)), beta=float(opt.get("beta", 0.1)), seed=int(opt.get("seed", 0)),
                   call_index=self._solve_count, lb=lb, ub=ub,
                   **(dict(self._lin_kw(), form=self.linearised_form) if lin else ({"full_covariance": True} if self._mm_full() else {})))
+        return self._mppi_done(r, opt, "mppi x%d" % int(opt.get("samples", 64)))
+
+    def _mppi_done(self, r, opt, used):
+        """The end of an MPPI solve under every propagation: the solve is counted and its result kept."""
         self._solve_count += 1
-        self.solver_used = "mppi x%d" % int(opt.get("samples", 64))
+        self.solver_used = used
         self.last_solve_info = {"cost": r["cost"], "violation": r["violation"], "feasible": r["feasible"], "success": r["feasible"],
                                 "max_violation": r["violation"], "iterations": int(opt.get("iterations", 30)), "trace": r["trace"]}
         self._cache_key = None

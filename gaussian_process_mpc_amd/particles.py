@@ -245,3 +245,112 @@ def particle_rollout(model_or_dynamics, x0, U, particles=1024, seed=0, call_inde
         out["particles"] = part.reshape(H + 1, B, P, ds).permute(1, 2, 0, 3)
     out["model"] = model                                 # (keeps the tensors the call read alive until the caller drops the result)
     return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------
+# Particle cost (C ABI "Particle cost" of include/gpmpc.h): the entropic risk of the stage cost and empirical quantiles
+# of the constraint margins ON the particles, the streaming evaluation, and MPPI over it.
+#
+#     r = particle_evaluate(dyn, x0, U, cost, constraints=sc, particles=256)       # r["cost"] (B,), r["stage"] (B, H+1), r["g"] (B, H, rows)
+#     s = mppi_solve_particles(dyn, x0, U0, cost, constraints=sc, particles=256, samples=64)
+# ---------------------------------------------------------------------------------------------------------------------------------------
+def _check_rows(constraints, ds):
+    if constraints is not None and not isinstance(constraints, StateConstraints):
+        raise TypeError("constraints: a StateConstraints")
+    if constraints is not None and constraints.ds != ds:
+        raise ValueError("constraint rows have %d columns, the state %d" % (constraints.ds, ds))
+
+
+def particle_cost(particles, U, cost, constraints=None):
+    """The particle cost of stored particles (C ABI ``gpmpc_particle_cost``): particles (H+1, B, P, ds) -- ``particle_rollout``'s
+    ``particles`` permuted to (2, 0, 1, 3) -- or (H+1, B P, ds) with U (B, H, da); cost: a ``CostParams``.  Returns dict(cost (B,),
+    stage (B, H+1) [, g (B, H, rows)]): J_b = sum_i s_i + the input terms of ``gpmpc_cost``, s_i the entropic risk (gamma != 0) or the mean
+    (gamma == 0) of e^T Q e over the particles of step i, g the (P - m_r)-th smallest margin a_r . x - b_r with m_r = floor(eps_r P + 1e-9)."""
+    assert particles.is_cuda and particles.dtype == torch.float64 and particles.is_contiguous()
+    dev = particles.device
+    U = _dev(U, dev)
+    if U.dim() == 2:
+        U = U[None]
+    B, H, da = U.shape
+    U = U.contiguous()
+    T, ds = particles.shape[0], particles.shape[-1]
+    if T != H + 1 or particles.numel() % (T * B * ds):
+        raise ValueError("particles: (H+1, B, P, ds) for U (B, H, da), got %s and %s" % (tuple(particles.shape), tuple(U.shape)))
+    P = particles.numel() // (T * B * ds)
+    if cost.ds != ds or cost.da != da:
+        raise ValueError("shape mismatch between particles, U and cost parameters")
+    _check_rows(constraints, ds)
+    sc = constraints
+    out = {"cost": _empty(dev, B), "stage": _empty(dev, B, H + 1)}
+    g = _empty(dev, B, H, sc.m) if sc is not None else None
+    with torch.cuda.device(dev):
+        check(lib().gpmpc_particle_cost(B, P, H, ds, da, ctypes.byref(cost.c), ctypes.byref(sc.c) if sc is not None else None, ptr(particles),
+                                        _vp(U) if da else None, ptr(out["cost"]), ptr(out["stage"]), _vp(g), stream_ptr(dev)),
+              "gpmpc_particle_cost")
+    if sc is not None:
+        out["g"] = g
+    return out
+
+
+def particle_evaluate(model_or_dynamics, x0, U, cost, constraints=None, particles=256, seed=0, call_index=0, chunk=0):
+    """Rollout and particle cost in one pass that never stores the horizon (C ABI ``gpmpc_particle_evaluate``): bit for bit
+    ``particle_cost`` on the particles ``particle_rollout`` stores for the same (seed, call_index).  x0 (ds,) or (B, ds); U (H, da) or
+    (B, H, da).  Returns dict(cost (B,), stage (B, H+1), g (B, H, rows) or None)."""
+    model = _model(model_or_dynamics)
+    ds, da, dev = model.ds, model.da, model.device
+    U = _dev(U, dev)
+    if U.dim() == 2:
+        U = U[None]
+    B, H = U.shape[0], U.shape[1]
+    U = U.reshape(B, H, da).contiguous()
+    x0 = _dev(x0, dev).reshape(-1, ds)
+    if x0.shape[0] == 1 and B > 1:
+        x0 = x0.expand(B, ds).contiguous()
+    if x0.shape[0] != B:
+        raise ValueError("x0: (%d,) or (%d, %d), got %s" % (ds, B, ds, tuple(x0.shape)))
+    if cost.ds != ds or cost.da != da:
+        raise ValueError("shape mismatch between model and cost parameters")
+    _check_rows(constraints, ds)
+    P, sc = int(particles), constraints
+    out = {"cost": _empty(dev, B), "stage": _empty(dev, B, H + 1), "g": _empty(dev, B, H, sc.m) if sc is not None else None}
+    with torch.cuda.device(dev):
+        nb = lib().gpmpc_particle_evaluate_workspace_bytes(ctypes.byref(model.c), B, P, H, chunk)
+        ws = _workspace(dev, nb)
+        check(lib().gpmpc_particle_evaluate(ctypes.byref(model.c), B, P, H, ptr(x0), _vp(U) if da else None, int(seed) & (2 ** 64 - 1),
+                                            int(call_index), ctypes.byref(cost.c), ctypes.byref(sc.c) if sc is not None else None,
+                                            ptr(out["cost"]), ptr(out["stage"]), _vp(out["g"]), chunk, _vp(ws), nb, stream_ptr(dev)),
+              "gpmpc_particle_evaluate")
+    out["model"] = model
+    return out
+
+
+def mppi_solve_particles(model_or_dynamics, x0, U0, cost, constraints=None, particles=256, samples=64, iterations=30, sigma=1.0, decay=0.9,
+                         beta=0.1, seed=0, call_index=0, lb=None, ub=None):
+    """``mppi.mppi_solve`` over the particle cost (C ABI ``gpmpc_mppi_solve_particles``): per iteration the sample kernel,
+    ``gpmpc_particle_evaluate`` over the K samples with ``particles`` particles each, the update kernel; the whole search one enqueue,
+    one device-to-host copy at the end.  The particle noise is that of (seed, call_index) and THE SAME in every iteration (common random
+    numbers: the search minimises one fixed sample-average objective).  Returns what ``mppi_solve`` returns."""
+    from .mppi import mppi_params
+    model = _model(model_or_dynamics)
+    dev = model.device
+    U0 = _dev(U0, dev)
+    if U0.dim() != 2 or U0.shape[-1] != model.da:
+        raise ValueError("U0 must have shape (H, da)")
+    x0 = _dev(x0, dev).reshape(-1)
+    if x0.shape[0] != model.ds or cost.ds != model.ds or cost.da != model.da:
+        raise ValueError("shape mismatch between model, x0, U0 and cost parameters")
+    H, da = U0.shape
+    _check_rows(constraints, model.ds)
+    Pm = mppi_params(samples, da, sigma, lb, ub, iterations=iterations, decay=decay, beta=beta, seed=seed, call_index=call_index)
+    cons = None if constraints is None else ctypes.byref(constraints.c)
+    n = H * da
+    res = torch.empty(n + 2 + 6 * max(Pm.iterations, 1), dtype=torch.float64, device=dev)     # [best plan | key | trace]: one block, one copy
+    with torch.cuda.device(dev):
+        nb = lib().gpmpc_mppi_solve_particles_workspace_bytes(ctypes.byref(model.c), H, int(particles), ctypes.byref(Pm), cons)
+        ws = _workspace(dev, nb)
+        check(lib().gpmpc_mppi_solve_particles(ctypes.byref(model.c), H, int(particles), ptr(x0), ptr(U0.contiguous()), ctypes.byref(cost.c), cons,
+                                               ctypes.byref(Pm), ptr(res[:n]), ptr(res[n:n + 2]), ptr(res[n + 2:]), _vp(ws), ws.numel(),
+                                               stream_ptr(dev)), "gpmpc_mppi_solve_particles")
+    host = res.cpu().numpy()
+    return {"U": host[:n].reshape(H, da).copy(), "violation": float(host[n]), "cost": float(host[n + 1]), "feasible": bool(host[n] == 0.0),
+            "trace": host[n + 2:].reshape(-1, 6).copy()}

@@ -926,8 +926,8 @@ int gpmpc_sparse_replace(int D, int M, int n_targets, const double* x_old_dev, c
  * lambda or sigma_f that is not positive and finite, a non-finite or negative action_var / process_var, an init_cov that is non-finite,
  * asymmetric (|P_kl - P_lk| > 1e-12 max |P|) or has a negative pivot, constraint rows outside 1...GPMPC_MAX_CONS, more than 2^31 - 1
  * elements in one array.  A workspace below *_workspace_bytes (which return 0 for arguments that would be refused): GPMPC_E_WORKSPACE.
- * Not provided: gradients through particles, joint (function-space) sampling across steps, a particle-cost MPPI, multi-GPU sharding,
- * a form that reads only one triangle of a symmetrised Kinv.
+ * Not provided: gradients through particles, joint (function-space) sampling across steps, multi-GPU sharding,
+ * a form that reads only one triangle of a symmetrised Kinv.  (A planner on the particles: "Particle cost" below.)
  * ------------------------------------------------------------------------- */
 typedef struct gpmpc_gp_model {
     int n, state_dim, action_dim;                     /* training (or inducing) points; D = state_dim + action_dim */
@@ -983,6 +983,68 @@ int gpmpc_particle_rollout(const gpmpc_gp_model* model_host, int B, int P, int H
                            unsigned long long seed, unsigned call_index, const gpmpc_state_constraints* cons_host,
                            double* out_particles, double* out_mean, double* out_cov, int* out_clamped, double* out_viol,
                            double* out_joint, int chunk, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------
+ * Particle cost: the risk-sensitive cost and the chance constraints evaluated ON the particles of gpmpc_particle_rollout, and MPPI over
+ * them -- the planner that optimises against the distribution validate_plan checks a moment-matched plan with (DESIGN.md section 3m,
+ * kernels in csrc/particle_cost.hip).  It serves every model the particle rollout serves: dense, sparse, nominal, with a noise model.
+ *
+ * For plan b with P particles x_i^p, i = 0...H (exactly the particles of gpmpc_particle_rollout):
+ *     J_b  = sum_{i = 0...H} s_i + input_cost(U_b)
+ *     c_p  = e_p^T Q_i e_p,  e_p = x_i^p - x_ref,i       (Q_i, x_ref,i as the cost kernels choose them: the struct or the row of a cost
+ *                                                         schedule, Q_f at i = H where the schedule has one; Q as given, symmetric or not)
+ *     gamma == 0:  s_i = (1 / P) sum_p c_p
+ *     otherwise:   a_p = -(gamma / 2) c_p,  M = max_p a_p,  s_i = -(2 / gamma) (M + log((1 / P) sum_p exp(a_p - M)))
+ * input_cost is bit for bit the input and input-rate terms of gpmpc_cost: on the plan's own inputs (not the noisy ones), with u_ref,
+ * R_delta / last_u and the schedule's input rows.  s_i is the sample version of the functional gpmpc_cost evaluates in closed form: for
+ * x ~ N(mu, Sigma), a symmetric Q and I + gamma Q Sigma positive definite,
+ *     -(2 / gamma) log E exp(-(gamma / 2) e^T Q e) = (1 / gamma) log det(I + gamma Q Sigma) + ebar^T (I + gamma Q Sigma)^-1 Q ebar.
+ * Chance constraints, t = 1...H, row r: y_p = a_r . x_t^p - b_r, sorted ascending y_(1) <= ... <= y_(P);
+ *     eps_r = 1/2 erfc(kappa_r / sqrt 2),  m_r = floor(eps_r P + 1e-9)   (host, double),   g[t-1][r] = y_(P - m_r).
+ * This is the empirical counterpart of a . mu + kappa sd - b, the Phi(kappa) quantile of the margin, in the same units; g <= 0 exactly when
+ * at most m_r particles violate the row, and g is continuous in U.  kappa = 0 constrains the MEDIAN of the margin where the Gaussian rule
+ * constrains its mean.
+ * NaN: a NaN coordinate in any particle of (b, i) makes s_i, J_b and every g[b][i-1][.] NaN, and nothing else (gpmpc_mppi_update treats
+ * such a sample as dead).
+ *
+ * Kernels: one 256-thread workgroup per (plan, step); thread i owns the particles i, i + 256, ... in ascending order, the 256 partial sums
+ * are folded in halves, the maximum is exact; per row the margins are sorted in LDS (bitonic, padded with -inf to a power of two) and one
+ * value is read, so ties are harmless.  No atomics, fixed summation orders: two identical calls agree bit for bit; a plan evaluated alone
+ * gives the bits it has inside a batch; gpmpc_particle_evaluate equals gpmpc_particle_cost on the particles gpmpc_particle_rollout stores
+ * for the same (seed, call_index), whatever `chunk`; gpmpc_mppi_solve_particles equals the chain of its three public parts.
+ * All refusals are GPMPC_E_ARG with a text in gpmpc_last_error, before any launch: everything gpmpc_particle_rollout refuses (in the solve
+ * also what gpmpc_mppi_solve_linearised refuses of its parameters), P outside 1...GPMPC_PARTICLE_COST_MAX_P, a bad cost schedule, bad
+ * constraint rows, out_g not given exactly when cons_host is.  A workspace below *_workspace_bytes (which return 0 for arguments that
+ * would be refused): GPMPC_E_WORKSPACE.
+ * Not provided: gradients through particles, CVaR or other risk measures, joint (function-space) sampling across steps, a state feedback
+ * inside the prediction, multi-GPU sharding.
+ * ------------------------------------------------------------------------- */
+#define GPMPC_PARTICLE_COST_MAX_P 4096
+/* A pure function of stored particles dev [H+1][B P][ds] (the layout of gpmpc_particle_rollout's out_particles) and the plans U dev
+ * [B][H][da] (NULL with da = 0): out_cost dev [B]; out_stage dev [B][H+1] or NULL (the s_i); out_g dev [B][H][n_rows], given exactly when
+ * cons_host is.  out_cost is the same bits with and without out_stage. */
+int gpmpc_particle_cost(int B, int P, int H, int state_dim, int action_dim, const gpmpc_cost_params* cost_host,
+                        const gpmpc_state_constraints* cons_host, const double* particles, const double* U, double* out_cost,
+                        double* out_stage, double* out_g, void* stream);
+/* Rollout and cost in one pass that never stores the horizon: noise(0) -> initial particles -> stage 0; for t = 1...H: noise(t) ->
+ * gpmpc_particle_step -> stage t and the rows of step t; then the sum.  One stream, no host round trip, no allocation; two particle
+ * buffers that alternate, so the workspace has no term proportional to H B P.  x0 dev [B][ds]; outputs as gpmpc_particle_cost. */
+size_t gpmpc_particle_evaluate_workspace_bytes(const gpmpc_gp_model* model_host, int B, int P, int H, int chunk);
+int gpmpc_particle_evaluate(const gpmpc_gp_model* model_host, int B, int P, int H, const double* x0, const double* U,
+                            unsigned long long seed, unsigned call_index, const gpmpc_cost_params* cost_host,
+                            const gpmpc_state_constraints* cons_host, double* out_cost, double* out_stage, double* out_g, int chunk,
+                            void* workspace, size_t workspace_bytes, void* stream);
+/* gpmpc_mppi_solve_linearised with the evaluation above in the place of the rollout: per iteration gpmpc_mppi_sample (with the start
+ * state once per sample), gpmpc_particle_evaluate (B = n_samples, default chunk), gpmpc_mppi_update.  Outputs and trace as there.
+ * COMMON RANDOM NUMBERS: the particle noise is that of (params->seed, params->call_index) -- its Philox key differs from the sampler's --
+ * and it is THE SAME in every iteration of a solve.  The key of the best plan kept compares costs across iterations, which is sound only
+ * on ONE fixed sample-average objective; a fresh draw per iteration would let a lucky draw win. */
+size_t gpmpc_mppi_solve_particles_workspace_bytes(const gpmpc_gp_model* model_host, int H, int P, const gpmpc_mppi_params* params_host,
+                                                  const gpmpc_state_constraints* cons_host);
+int gpmpc_mppi_solve_particles(const gpmpc_gp_model* model_host, int H, int P, const double* x0_dev, const double* start_dev,
+                               const gpmpc_cost_params* cost_host, const gpmpc_state_constraints* cons_host,
+                               const gpmpc_mppi_params* params_host, double* out_U, double* out_best, double* out_trace, void* workspace,
+                               size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------
  * Linearised propagation: the first-order (Taylor, "mean-equivalent") rule of the cautious-MPC literature, beside the exact moment matching
