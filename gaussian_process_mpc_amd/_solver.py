@@ -1,6 +1,8 @@
-"""What the host sides of the device solvers share (mppi.py, device_lbfgs.py, device_auglag.py): per-input parameters, the check of a
-solve's problem, the layout arithmetic of a state buffer and the chunked enqueue of a search.  Plumbing only."""
+"""What the host sides of the device solvers share (mppi.py, device_lbfgs.py, device_auglag.py, and the MPPI solves of linearised.py and
+particles.py): per-input parameters, the check of a solve's problem, the result of an MPPI solve, the layout arithmetic of a state
+buffer and the chunked enqueue of a search.  Plumbing only."""
 import numpy as np
+import torch
 
 from .rollout import _dev
 
@@ -20,6 +22,30 @@ def solver_problem(pack, x0, start, cost, name, shape):
     if x0.shape[0] != pack.ds or cost.ds != pack.ds or cost.da != pack.da:
         raise ValueError("shape mismatch between pack, x0, %s and cost parameters" % name)
     return x0, start
+
+
+def model_problem(model, x0, U0, cost):
+    """``solver_problem`` for the MPPI solves that take a ``GPModel`` in the place of a pack: (x0 (ds,), U0 (H, da)) on the model's device."""
+    U0 = _dev(U0, model.device)
+    if U0.dim() != 2 or U0.shape[-1] != model.da:
+        raise ValueError("U0 must have shape (H, da)")
+    x0 = _dev(x0, model.device).reshape(-1)
+    if x0.shape[0] != model.ds or cost.ds != model.ds or cost.da != model.da:
+        raise ValueError("shape mismatch between model, x0, U0 and cost parameters")
+    return x0, U0
+
+
+def mppi_result_block(n, iterations, dev):
+    """The device block an MPPI solve writes, [best plan (n) | key (2) | trace (6 per iteration)]: one block, one copy at the end."""
+    return torch.empty(n + 2 + 6 * max(iterations, 1), dtype=torch.float64, device=dev)
+
+
+def mppi_result(host, H, da, key_first=False):
+    """What every MPPI solve returns, from the host copy of its block (``key_first``: [key | best plan | trace], a host loop's)."""
+    n = H * da
+    plan, key = (host[2:2 + n], host[:2]) if key_first else (host[:n], host[n:n + 2])
+    return {"U": plan.reshape(H, da).copy(), "violation": float(key[0]), "cost": float(key[1]), "feasible": bool(key[0] == 0.0),
+            "trace": host[n + 2:].reshape(-1, 6).copy()}
 
 
 def state_layout(sizes):

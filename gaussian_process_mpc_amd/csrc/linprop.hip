@@ -2,7 +2,7 @@
 // step Jacobian in the layout of gpmpc_rollout_jac.  Formulas, layouts and refusals: include/gpmpc.h, "Linearised propagation"; the why and
 // what was measured: DESIGN.md section 3j.
 //
-// Per chunk of C columns (plans) and per group of GPs with bit-identical (lambda, sigma_f) -- the grouping of particles.hip:
+// Per chunk of C columns (plans) and per group of GPs with bit-identical (lambda, sigma_f) (GpGroup, model_frame.h):
 //   k_lp_kstar   Ks[i][c] = k(X_i, z_c), zero-padded to multiples of 64 both ways (written by the workgroups of the group's first GP), and the
 //                row-block partial sums of m and of the D components of g:  kpart[bi][slot][0 | 1 + d][c]
 //   k_lp_quad    workgroup (bc, bi, matrix): T = (Kinv + Kinv^T)[64 bi ...][:] Ks[:][64 bc ...] by MFMA stages (tile_stage.h) = the rows of r.
@@ -14,28 +14,21 @@
 //   k_lp_jac     dq and h added in ascending order -> the two Jacobian rows of (column, GP), every element written (zeros included)
 // Rules: no atomics; every output element is owned by one thread or one workgroup, which sums in a fixed order; launch geometry depends on
 // sizes only; columns are independent, so no result depends on `chunk`.
-#include <cfloat>
 #include <cmath>
-#include "roll_dev.h"        // RollArgs and gpmpc_launch_roll_tail: the cost and the adjoint sweep of the rollout are the existing tail kernel
-#include "solver_frame.h"
+#include "roll_dev.h"        // RollArgs, gpmpc_launch_roll_tail and its LDS budget: the cost and the adjoint sweep are the existing tail kernel
+#include "mppi_internal.h"   // the MPPI search
 #include "tile_stage.h"
-#include "linprop_internal.h"   // LpTail, LpIn, lp_z, and the STREAM form of the step (linprop_stream.hip)
+#include "linprop_internal.h"   // the model frame, LpTail, LpIn, lp_z, and the STREAM form of the step (linprop_stream.hip)
 #include <atomic>
 
-#define LP_DEFAULT_CHUNK 4096
+static_assert(SP_T == GPMPC_MODEL_TILE, "the chunk rule of model_frame.h rounds to the tile of tile_stage.h");
 
-struct LpGroup {
-    double ilam[GPMPC_MAX_D];       // 1 / lambda_d
-    double sf2;
-    int ng;                         // GPs of the group
-    int gp[GPMPC_MAX_DS];           // their indices, ascending
-};
 // ---------------------------------------------------------------------------
 // kernels
 // ---------------------------------------------------------------------------
 // grid (cnp / 64, np / 64, G.ng).  Thread (c = t & 63, q = t >> 6) owns column c0 + c and the rows i0 + 16 q ... + 15 (ascending) for GP slot z.
 __global__ __launch_bounds__(256) void k_lp_kstar(int n, int cn, int D, int ds, const double* __restrict__ X, LpIn I,
-                                                   const double* __restrict__ beta, LpGroup G, double* __restrict__ Ks, int ldk,
+                                                   const double* __restrict__ beta, GpGroup G, double* __restrict__ Ks, int ldk,
                                                    double* __restrict__ kpart, int nvk) {
     __shared__ double s_x[SP_T][GPMPC_MAX_D], s_b[SP_T], s_p[4][1 + GPMPC_MAX_D][SP_T];
     const int t = threadIdx.x, c = t & 63, q = t >> 6, slot = blockIdx.z;
@@ -79,7 +72,7 @@ __global__ __launch_bounds__(256) void k_lp_kstar(int n, int cn, int D, int ds, 
 // grid (cnp / 64, np / 64, matrices).  Matrix z is GP G.gp[z]'s (gp_stride != 0) or the one matrix of all GPs.  nv = 1: q only; 1 + D: q and dq/dz.
 // part[matrix][bi][0][c] = 1/2 sum_{i in tile} Ks[i][c] T[i][c];  part[matrix][bi][1 + d][c] = sum_{i in tile} Ks[i][c] T[i][c] d_id(c)
 __global__ __launch_bounds__(256) void k_lp_quad(int n, int np, int cn, int D, int ds, const double* __restrict__ Kinv, size_t ld,
-                                                  size_t gp_stride, LpGroup G, const double* __restrict__ X, LpIn I,
+                                                  size_t gp_stride, GpGroup G, const double* __restrict__ X, LpIn I,
                                                   const double* __restrict__ Ks, int ldk, double* __restrict__ part, int nv) {
     __shared__ double s_a[SP_KB][SP_T + 1], s_b[SP_KB][SP_T + 1];
     __shared__ double s_x[SP_T][GPMPC_MAX_D], s_z[SP_T][GPMPC_MAX_D];
@@ -149,7 +142,7 @@ __global__ __launch_bounds__(256) void k_lp_quad(int n, int np, int cn, int D, i
 }
 
 // one thread per (column, GP of the group): mu', v', and g (with the nominal weights) for the Jacobian passes
-__global__ __launch_bounds__(256) void k_lp_sums(int cn, int nbi, int D, int ds, int shared_mat, LpGroup G, LpTail M, LpIn I,
+__global__ __launch_bounds__(256) void k_lp_sums(int cn, int nbi, int D, int ds, int shared_mat, GpGroup G, LpTail M, LpIn I,
                                                   const double* __restrict__ kpart, int nvk, const double* __restrict__ part, int nv, int ldk,
                                                   double* __restrict__ out_mu, double* __restrict__ out_var, size_t os,
                                                   double* __restrict__ gbuf) {
@@ -179,7 +172,7 @@ __global__ __launch_bounds__(256) void k_lp_sums(int cn, int nbi, int D, int ds,
 
 // grid (cnp / 64, np / 64, G.ng), threads as k_lp_kstar.  Reads Ks back (no second exp).
 __global__ __launch_bounds__(256) void k_lp_hess(int n, int cn, int D, int ds, const double* __restrict__ X, LpIn I,
-                                                  const double* __restrict__ beta, LpGroup G, LpTail M, const double* __restrict__ Ks, int ldk,
+                                                  const double* __restrict__ beta, GpGroup G, LpTail M, const double* __restrict__ Ks, int ldk,
                                                   const double* __restrict__ gbuf, double* __restrict__ hpart) {
     __shared__ double s_x[SP_T][GPMPC_MAX_D], s_b[SP_T], s_p[4][GPMPC_MAX_D][SP_T];
     const int t = threadIdx.x, c = t & 63, q = t >> 6, slot = blockIdx.z;
@@ -223,7 +216,7 @@ __global__ __launch_bounds__(256) void k_lp_hess(int n, int cn, int D, int ds, c
 }
 
 // one thread per (column, GP of the group): rows mu'_a and v'_a of the column's [2ds][2ds + da] block, every element
-__global__ __launch_bounds__(256) void k_lp_jac(int cn, int nbi, int D, int ds, int shared_mat, LpGroup G, const double* __restrict__ part,
+__global__ __launch_bounds__(256) void k_lp_jac(int cn, int nbi, int D, int ds, int shared_mat, GpGroup G, const double* __restrict__ part,
                                                  int nv, const double* __restrict__ hpart, const double* __restrict__ gbuf, int ldk,
                                                  double* __restrict__ jac, size_t js) {
     const long e = (long)blockIdx.x * 256 + threadIdx.x;
@@ -257,7 +250,7 @@ __global__ __launch_bounds__(256) void k_lp_init(int B, int ds, size_t stride, c
 // ---------------------------------------------------------------------------
 // host: the form, checks
 // ---------------------------------------------------------------------------
-// which form of the step lp_step launches (process-wide; read once per call, in lp_layout)
+// which form of the step gpmpc_lp_step launches (process-wide; read once per call, in lp_layout)
 static std::atomic<int> g_lp_form{GPMPC_LINPROP_FORM_DEFAULT};
 
 extern "C" int gpmpc_linearised_set_form(int form) {
@@ -268,53 +261,30 @@ extern "C" int gpmpc_linearised_set_form(int form) {
     return g_lp_form.exchange(form);
 }
 
-static bool lp_finite(double v) { return v - v == 0.0; }
-static int lp_chunk(int chunk) { return chunk == 0 ? LP_DEFAULT_CHUNK : chunk; }
-static unsigned lp_blocks(long threads) { return (unsigned)((threads + 255) / 256); }
-
-static bool lp_model_sizes_ok(const gpmpc_gp_model* m) {
-    return m && m->state_dim >= 1 && m->state_dim <= GPMPC_MAX_DS && m->action_dim >= 0 && m->state_dim + m->action_dim <= GPMPC_MAX_D && m->n >= 1;
-}
-
-// The model, and what the sums kernels need of it: nominal model, diag(init_cov), action_var, process_var (or the defaults).
-static int lp_check_model(const char* who, const gpmpc_gp_model* m, LpTail* out) {
-    if (!m) return gpmpc_refuse(who, "NULL pointer (model)");
+// The core checks of the model (model_frame.h), then what the sums kernels need of it -- nominal model, diag(init_cov), action_var,
+// process_var (or the defaults) -- with the refusals of the diagonal noise model.  (linprop_internal.h: linprop_fc.hip starts from it.)
+int gpmpc_lp_check_model(const char* who, const gpmpc_gp_model* m, LpTail* out) {
+    if (int rc = gpmpc_model_check_core(who, m)) return rc;
     const int ds = m->state_dim, da = m->action_dim, D = ds + da;
-    if (ds < 1 || ds > GPMPC_MAX_DS) return gpmpc_refuse(who, "state_dim = %d outside 1...GPMPC_MAX_DS", ds);
-    if (da < 0 || D > GPMPC_MAX_D) return gpmpc_refuse(who, "action_dim = %d: D = state_dim + action_dim outside 1...GPMPC_MAX_D", da);
-    if (m->n < 1) return gpmpc_refuse(who, "n < 1");
-    if (m->ld < (size_t)m->n) return gpmpc_refuse(who, "ld < n");
-    if (!m->X || !m->beta || !m->Kinv) return gpmpc_refuse(who, "NULL pointer (model arrays)");
     memset(out, 0, sizeof(*out));
-    for (int a = 0; a < ds; ++a) {
-        if (!(m->sigma_f[a] > 0.0) || !lp_finite(m->sigma_f[a])) return gpmpc_refuse(who, "sigma_f[%d] = %g is not positive and finite", a, m->sigma_f[a]);
-        for (int d = 0; d < D; ++d)
-            if (!(m->lambdas[a * D + d] > 0.0) || !lp_finite(m->lambdas[a * D + d]))
-                return gpmpc_refuse(who, "lambdas[%d][%d] = %g is not positive and finite", a, d, m->lambdas[a * D + d]);
-    }
     out->has_nominal = m->has_nominal ? 1 : 0;
-    if (m->has_nominal)
-        for (int a = 0; a < ds; ++a) {
-            if (!lp_finite(m->nom_b[a])) return gpmpc_refuse(who, "the nominal model holds a non-finite value");
-            out->nom_b[a] = m->nom_b[a];
-            for (int d = 0; d < D; ++d) {
-                if (!lp_finite(m->nom_w[a * D + d])) return gpmpc_refuse(who, "the nominal model holds a non-finite value");
-                out->nom_w[a * D + d] = m->nom_w[a * D + d];
-            }
-        }
+    if (m->has_nominal) {
+        memcpy(out->nom_b, m->nom_b, sizeof(double) * ds);
+        memcpy(out->nom_w, m->nom_w, sizeof(double) * ds * D);
+    }
     for (int a = 0; a < ds; ++a) out->init_var[a] = GPMPC_INIT_VAR;
     for (int j = 0; j < da; ++j) out->action_var[j] = GPMPC_ACTION_VAR;
     if (m->has_noise) {
         for (int a = 0; a < ds; ++a) {
             const double v = m->init_cov[a * ds + a];
-            if (!lp_finite(v) || v < 0.0) return gpmpc_refuse(who, "init_cov[%d][%d] = %g is negative or not finite", a, a, v);
+            if (!gpmpc_finite(v) || v < 0.0) return gpmpc_refuse(who, "init_cov[%d][%d] = %g is negative or not finite", a, a, v);
             out->init_var[a] = v;
-            if (!lp_finite(m->process_var[a]) || m->process_var[a] < 0.0)
+            if (!gpmpc_finite(m->process_var[a]) || m->process_var[a] < 0.0)
                 return gpmpc_refuse(who, "process_var[%d] = %g is negative or not finite", a, m->process_var[a]);
             out->process_var[a] = m->process_var[a];
         }
         for (int j = 0; j < da; ++j) {
-            if (!lp_finite(m->action_var[j]) || m->action_var[j] < 0.0)
+            if (!gpmpc_finite(m->action_var[j]) || m->action_var[j] < 0.0)
                 return gpmpc_refuse(who, "action_var[%d] = %g is negative or not finite", j, m->action_var[j]);
             out->action_var[j] = m->action_var[j];
         }
@@ -322,31 +292,7 @@ static int lp_check_model(const char* who, const gpmpc_gp_model* m, LpTail* out)
     return GPMPC_OK;
 }
 
-static int lp_check_chunk(const char* who, int chunk) {
-    return (chunk < 0 || chunk % 64) ? gpmpc_refuse(who, "chunk must be 0 or a positive multiple of 64") : GPMPC_OK;
-}
 static bool lp_count_ok(long B, long H) { return B >= 1 && H >= 1 && B * H * (2L * GPMPC_MAX_DS) * (2L * GPMPC_MAX_DS + GPMPC_MAX_D) <= (1L << 40); }
-
-// groups of GPs with bit-identical (lambda, sigma_f), in order of their first GP
-static int lp_groups(const gpmpc_gp_model* m, LpGroup* g) {
-    const int ds = m->state_dim, D = ds + m->action_dim;
-    int ngroups = 0;
-    bool done[GPMPC_MAX_DS] = {};
-    for (int a = 0; a < ds; ++a) {
-        if (done[a]) continue;
-        LpGroup& G = g[ngroups++];
-        memset(&G, 0, sizeof(G));
-        for (int d = 0; d < D; ++d) G.ilam[d] = 1.0 / m->lambdas[a * D + d];
-        G.sf2 = m->sigma_f[a] * m->sigma_f[a];
-        for (int b = a; b < ds; ++b)
-            if (!done[b] && memcmp(&m->lambdas[a * D], &m->lambdas[b * D], sizeof(double) * D) == 0 &&
-                memcmp(&m->sigma_f[a], &m->sigma_f[b], sizeof(double)) == 0) {
-                done[b] = true;
-                G.gp[G.ng++] = b;
-            }
-    }
-    return ngroups;
-}
 
 // workspace of a step: Ks [np][C] | kpart [nbi][ds][1 + D][C] | part [ds][nbi][nv][C] | with the Jacobian: hpart [nbi][ds][MAX_D][C] | g [C][ds][MAX_D]
 // `form`: the process-wide form read ONCE when the layout of a call is made.  Under TILE the offsets and the total are what they always were;
@@ -359,8 +305,7 @@ static LpLayout lp_layout(const gpmpc_gp_model* m, int chunk, long ncols, bool w
     const int ds = m->state_dim, D = ds + m->action_dim;
     L.nbi = (m->n + SP_T - 1) / SP_T;
     L.np = L.nbi * SP_T;
-    const long colsp = (ncols + SP_T - 1) / SP_T * SP_T;
-    L.C = (int)(colsp < lp_chunk(chunk) ? colsp : lp_chunk(chunk));      // no more columns than the call has
+    L.C = gpmpc_chunk_cols(ncols, chunk);
     L.nv = want_jac ? 1 + D : 1;
     const size_t d = sizeof(double);
     L.off_ks = c.take(d * L.np * L.C);
@@ -378,14 +323,14 @@ static LpLayout lp_layout(const gpmpc_gp_model* m, int chunk, long ncols, bool w
 }
 
 // One step of B columns.  mu_prev / var_prev: column b at + b xs; U_t: + b us; outputs at + b os; jac (or null): + b js.
-// THE place that picks the form: the step, the rollout and (through the rollout) the MPPI solve all come here.
-static int lp_step(const gpmpc_gp_model* m, const LpTail& tail, int B, const double* mu_prev, const double* var_prev, size_t xs, const double* U_t,
+// THE place that picks the form: the step, the rollout, (through the rollout) the MPPI solve and stage A of linprop_fc.hip all come here.
+int gpmpc_lp_step(const gpmpc_gp_model* m, const LpTail& tail, int B, const double* mu_prev, const double* var_prev, size_t xs, const double* U_t,
                    size_t us, double* out_mu, double* out_var, size_t os, double* jac, size_t js, const LpLayout& L, char* ws, hipStream_t s) {
     if (L.form == GPMPC_LINPROP_FORM_STREAM || (L.form == GPMPC_LINPROP_FORM_AUTO && B <= GPMPC_LINPROP_AUTO_MAX_B))
         return gpmpc_lps_step(m, tail, B, mu_prev, var_prev, xs, U_t, us, out_mu, out_var, os, jac, js, ws + L.base, s);
     const int ds = m->state_dim, da = m->action_dim, D = ds + da;
-    LpGroup groups[GPMPC_MAX_DS];
-    const int ngroups = lp_groups(m, groups);
+    GpGroup groups[GPMPC_MAX_DS];
+    const int ngroups = gpmpc_model_groups(m, groups);
     double* Ks = (double*)(ws + L.off_ks);
     double* kpart = (double*)(ws + L.off_kpart);
     double* part = (double*)(ws + L.off_part);
@@ -398,16 +343,16 @@ static int lp_step(const gpmpc_gp_model* m, const LpTail& tail, int B, const dou
         I.mu = mu_prev + (size_t)c0 * xs; I.var = var_prev + (size_t)c0 * xs; I.U = U_t ? U_t + (size_t)c0 * us : nullptr;
         I.xs = xs; I.us = us;
         for (int g = 0; g < ngroups; ++g) {
-            const LpGroup& G = groups[g];
+            const GpGroup& G = groups[g];
             hipLaunchKernelGGL(k_lp_kstar, dim3(cnp / SP_T, L.nbi, G.ng), dim3(256), 0, s, m->n, cn, D, ds, m->X, I, m->beta, G, Ks, L.C, kpart, nvk);
             hipLaunchKernelGGL(k_lp_quad, dim3(cnp / SP_T, L.nbi, shared_mat ? 1 : G.ng), dim3(256), 0, s, m->n, L.np, cn, D, ds, m->Kinv, m->ld,
                                m->gp_stride, G, m->X, I, (const double*)Ks, L.C, part, nv);
-            hipLaunchKernelGGL(k_lp_sums, dim3(lp_blocks((long)cn * G.ng)), dim3(256), 0, s, cn, L.nbi, D, ds, shared_mat, G, tail, I,
+            hipLaunchKernelGGL(k_lp_sums, dim3(gpmpc_blocks256((long)cn * G.ng)), dim3(256), 0, s, cn, L.nbi, D, ds, shared_mat, G, tail, I,
                                (const double*)kpart, nvk, (const double*)part, nv, L.C, out_mu + (size_t)c0 * os, out_var + (size_t)c0 * os, os, gbuf);
             if (jac) {
                 hipLaunchKernelGGL(k_lp_hess, dim3(cnp / SP_T, L.nbi, G.ng), dim3(256), 0, s, m->n, cn, D, ds, m->X, I, m->beta, G, tail,
                                    (const double*)Ks, L.C, (const double*)gbuf, hpart);
-                hipLaunchKernelGGL(k_lp_jac, dim3(lp_blocks((long)cn * G.ng)), dim3(256), 0, s, cn, L.nbi, D, ds, shared_mat, G, (const double*)part,
+                hipLaunchKernelGGL(k_lp_jac, dim3(gpmpc_blocks256((long)cn * G.ng)), dim3(256), 0, s, cn, L.nbi, D, ds, shared_mat, G, (const double*)part,
                                    nv, (const double*)hpart, (const double*)gbuf, L.C, jac + (size_t)c0 * js, js);
             }
         }
@@ -417,21 +362,16 @@ static int lp_step(const gpmpc_gp_model* m, const LpTail& tail, int B, const dou
 }
 
 // for linprop_fc.hip (linprop_internal.h)
-int gpmpc_lp_check_model(const char* who, const gpmpc_gp_model* m, LpTail* out) { return lp_check_model(who, m, out); }
 LpLayout gpmpc_lp_layout(const gpmpc_gp_model* m, int chunk, long ncols, bool want_jac) {
     gpmpc_carver c;
     return lp_layout(m, chunk, ncols, want_jac, c);
-}
-int gpmpc_lp_step(const gpmpc_gp_model* m, const LpTail& tail, int B, const double* mu_prev, const double* var_prev, size_t xs, const double* U_t,
-                  size_t us, double* out_mu, double* out_var, size_t os, double* jac, size_t js, const LpLayout& L, char* ws, hipStream_t s) {
-    return lp_step(m, tail, B, mu_prev, var_prev, xs, U_t, us, out_mu, out_var, os, jac, js, L, ws, s);
 }
 
 // ---------------------------------------------------------------------------
 // host: entries
 // ---------------------------------------------------------------------------
 extern "C" size_t gpmpc_linearised_step_workspace_bytes(const gpmpc_gp_model* m, int B, int want_jac, int chunk) {
-    if (!lp_model_sizes_ok(m) || !lp_count_ok(B, 1) || chunk < 0 || chunk % 64) return 0;
+    if (!gpmpc_model_sizes_ok(m) || !lp_count_ok(B, 1) || !gpmpc_chunk_ok(chunk)) return 0;
     gpmpc_carver c;
     return lp_layout(m, chunk, B, want_jac != 0, c).total;
 }
@@ -441,10 +381,10 @@ extern "C" int gpmpc_linearised_step(const gpmpc_gp_model* m, int B, const doubl
                                      void* workspace, size_t workspace_bytes, void* stream) {
     const char* who = "gpmpc_linearised_step";
     LpTail tail;
-    if (int rc = lp_check_model(who, m, &tail)) return rc;
+    if (int rc = gpmpc_lp_check_model(who, m, &tail)) return rc;
     if (B < 1) return gpmpc_refuse(who, "B < 1");
     if (!lp_count_ok(B, 1)) return gpmpc_refuse(who, "B is too large");
-    if (int rc = lp_check_chunk(who, chunk)) return rc;
+    if (int rc = gpmpc_check_chunk(who, chunk)) return rc;
     if (!mu_prev || !var_prev || !out_mu || !out_var || !workspace || (m->action_dim > 0 && !U_t)) return gpmpc_refuse(who, "NULL pointer");
     if (out_mu == mu_prev || out_var == var_prev || out_mu == var_prev || out_var == mu_prev || out_mu == out_var)
         return gpmpc_refuse(who, "the outputs must not alias the inputs or each other");
@@ -454,7 +394,7 @@ extern "C" int gpmpc_linearised_step(const gpmpc_gp_model* m, int B, const doubl
     gpmpc_carver c;
     const LpLayout L = lp_layout(m, chunk, B, out_jac != nullptr, c);
     if (workspace_bytes < L.total) return GPMPC_E_WORKSPACE;
-    return lp_step(m, tail, B, mu_prev, var_prev, ds, U_t, u_stride, out_mu, out_var, ds, out_jac, jac_stride, L, (char*)workspace,
+    return gpmpc_lp_step(m, tail, B, mu_prev, var_prev, ds, U_t, u_stride, out_mu, out_var, ds, out_jac, jac_stride, L, (char*)workspace,
                    (hipStream_t)stream);
 }
 
@@ -473,14 +413,8 @@ static LpRollLayout lp_roll_layout(const gpmpc_gp_model* m, int B, int H, bool g
     return R;
 }
 
-// the dynamic LDS of the tail kernel (step_tail.hip) for ONE step Jacobian: horizons beyond it cannot be costed
-static bool lp_tail_fits(int H, int ds, int da) {
-    const size_t lds0 = sizeof(double) * ((size_t)(H + 1) * (1 + 2 * ds) + (size_t)H * da + (size_t)H);
-    return lds0 + sizeof(double) * (size_t)2 * ds * (2 * ds + da) <= 48 * 1024;
-}
-
 extern "C" size_t gpmpc_linearised_rollout_workspace_bytes(const gpmpc_gp_model* m, int B, int H, unsigned flags, int chunk) {
-    if (!lp_model_sizes_ok(m) || !lp_count_ok(B, H) || (flags & ~GPMPC_WANT_GRAD) || chunk < 0 || chunk % 64) return 0;
+    if (!gpmpc_model_sizes_ok(m) || !lp_count_ok(B, H) || (flags & ~GPMPC_WANT_GRAD) || !gpmpc_chunk_ok(chunk)) return 0;
     return lp_roll_layout(m, B, H, (flags & GPMPC_WANT_GRAD) != 0, chunk).total;
 }
 
@@ -490,14 +424,14 @@ extern "C" int gpmpc_linearised_rollout(const gpmpc_gp_model* m, int B, int H, c
                                         double* out_gjac, int chunk, void* workspace, size_t workspace_bytes, void* stream) {
     const char* who = "gpmpc_linearised_rollout";
     LpTail tail;
-    if (int rc = lp_check_model(who, m, &tail)) return rc;
+    if (int rc = gpmpc_lp_check_model(who, m, &tail)) return rc;
     if (B < 1) return gpmpc_refuse(who, "B < 1");
     if (H < 1) return gpmpc_refuse(who, "H < 1");
     if (!lp_count_ok(B, H)) return gpmpc_refuse(who, "B x H is too large");
     if (flags & GPMPC_USE_GRAPH) return gpmpc_refuse(who, "GPMPC_USE_GRAPH is not supported by the linearised rollout (not yet)");
     if (flags & (GPMPC_FP32_ACCUM | GPMPC_FP32_ALL)) return gpmpc_refuse(who, "the GPMPC_FP32_* modes are not supported by the linearised rollout");
     if (flags & ~GPMPC_WANT_GRAD) return gpmpc_refuse(who, "flags: GPMPC_WANT_GRAD or 0");
-    if (int rc = lp_check_chunk(who, chunk)) return rc;
+    if (int rc = gpmpc_check_chunk(who, chunk)) return rc;
     const bool grad = (flags & GPMPC_WANT_GRAD) != 0;
     const int ds = m->state_dim, da = m->action_dim;
     if (!x0 || !workspace || (da > 0 && !U)) return gpmpc_refuse(who, "NULL pointer");
@@ -509,7 +443,7 @@ extern "C" int gpmpc_linearised_rollout(const gpmpc_gp_model* m, int B, int H, c
     sched.dev = nullptr; sched.H_max = 0;
     if (cost) {
         if (da < 1) return gpmpc_refuse(who, "a cost needs action_dim >= 1");
-        if (!lp_tail_fits(H, ds, da)) return gpmpc_refuse(who, "H = %d is too long for the cost kernel", H);
+        if (!gpmpc_roll_tail_fits(H, ds, da, false)) return gpmpc_refuse(who, "H = %d is too long for the cost kernel", H);
         if (int rc = gpmpc_schedule_resolve(cost, ds, da, H, who, &sched)) return rc;
     }
     const LpRollLayout R = lp_roll_layout(m, B, H, grad, chunk);
@@ -520,9 +454,9 @@ extern "C" int gpmpc_linearised_rollout(const gpmpc_gp_model* m, int B, int H, c
     double* vars = out_vars ? out_vars : (double*)(ws + R.off_vars);
     double* jac = grad ? (out_jac ? out_jac : (double*)(ws + R.off_jac)) : nullptr;
     const size_t xs = (size_t)(H + 1) * ds, js = (size_t)H * (2 * ds) * (2 * ds + da), jblock = (size_t)(2 * ds) * (2 * ds + da);
-    hipLaunchKernelGGL(k_lp_init, dim3(lp_blocks((long)B * ds)), dim3(256), 0, s, B, ds, xs, x0, tail, means, vars);
+    hipLaunchKernelGGL(k_lp_init, dim3(gpmpc_blocks256((long)B * ds)), dim3(256), 0, s, B, ds, xs, x0, tail, means, vars);
     for (int t = 1; t <= H; ++t) {
-        if (int rc = lp_step(m, tail, B, means + (size_t)(t - 1) * ds, vars + (size_t)(t - 1) * ds, xs, U ? U + (size_t)(t - 1) * da : nullptr,
+        if (int rc = gpmpc_lp_step(m, tail, B, means + (size_t)(t - 1) * ds, vars + (size_t)(t - 1) * ds, xs, U ? U + (size_t)(t - 1) * da : nullptr,
                              (size_t)H * da, means + (size_t)t * ds, vars + (size_t)t * ds, xs, jac ? jac + (size_t)(t - 1) * jblock : nullptr, js,
                              R.step, ws, s))
             return rc;
@@ -547,21 +481,14 @@ extern "C" int gpmpc_linearised_rollout(const gpmpc_gp_model* m, int B, int H, c
 }
 
 // ---------------------------------------------------------------------------
-// MPPI over the linearised rollout: gpmpc_mppi_solve with a model in the place of the pack
+// MPPI over the linearised rollout: the search of mppi_internal.h with a model in the place of the pack
 // ---------------------------------------------------------------------------
-// workspace: U [K][n] | x0 [K][ds] | cost [K] | g [K][H m_c] | mean [n] | best x 2 [2 + n] | the rollout's own workspace
-struct LpMppiLayout { size_t off_U, off_x0, off_cost, off_g, off_mean, off_best[2], off_roll, roll_bytes, total; };
+// workspace: the head of every MPPI solve | the rollout's own workspace
+struct LpMppiLayout { gpmpc_mppi_head head; size_t off_roll, roll_bytes, total; };
 static LpMppiLayout lp_mppi_layout(const gpmpc_gp_model* m, int H, int K, int m_c) {
     LpMppiLayout L;
-    const size_t n = (size_t)H * m->action_dim, d = sizeof(double);
     gpmpc_carver c;
-    L.off_U = c.take(d * K * n);
-    L.off_x0 = c.take(d * K * m->state_dim);
-    L.off_cost = c.take(d * K);
-    L.off_g = c.take(d * K * H * m_c);
-    L.off_mean = c.take(d * n);
-    L.off_best[0] = c.take(d * (2 + n));
-    L.off_best[1] = c.take(d * (2 + n));
+    L.head = gpmpc_mppi_head_take(c, H, m->state_dim, m->action_dim, K, m_c);
     L.roll_bytes = lp_roll_layout(m, K, H, false, 0).total;
     L.off_roll = c.take(L.roll_bytes);
     L.total = c.total();
@@ -570,7 +497,7 @@ static LpMppiLayout lp_mppi_layout(const gpmpc_gp_model* m, int H, int K, int m_
 
 extern "C" size_t gpmpc_mppi_solve_linearised_workspace_bytes(const gpmpc_gp_model* m, int H, const gpmpc_mppi_params* P,
                                                               const gpmpc_state_constraints* cons) {
-    if (!lp_model_sizes_ok(m) || !P || P->n_samples < 1 || P->n_samples > GPMPC_MPPI_MAX_SAMPLES) return 0;
+    if (!gpmpc_model_sizes_ok(m) || !P || P->n_samples < 1 || P->n_samples > GPMPC_MPPI_MAX_SAMPLES) return 0;
     if (cons && (cons->n_rows < 1 || cons->n_rows > GPMPC_MAX_CONS)) return 0;
     if (!gpmpc_solver_dims_ok(H, m->state_dim, m->action_dim)) return 0;
     return lp_mppi_layout(m, H, P->n_samples, cons ? cons->n_rows : 0).total;
@@ -582,46 +509,23 @@ extern "C" int gpmpc_mppi_solve_linearised(const gpmpc_gp_model* m, int H, const
     const char* who = "gpmpc_mppi_solve_linearised";
     if (!m || !x0 || !start || !cost || !P || !out_U || !out_best || !out_trace || !workspace) return gpmpc_refuse(who, "NULL pointer");
     if (H < 1) return gpmpc_refuse(who, "H < 1");
-    if (P->n_samples < 1 || P->n_samples > GPMPC_MPPI_MAX_SAMPLES)
-        return gpmpc_refuse(who, "n_samples = %d outside 1..%d", P->n_samples, GPMPC_MPPI_MAX_SAMPLES);
-    if (P->iterations < 1) return gpmpc_refuse(who, "iterations = %d is less than 1", P->iterations);
-    if (!(P->sigma_decay > 0.0)) return gpmpc_refuse(who, "sigma_decay = %g is not positive", P->sigma_decay);
-    if (!(P->beta > 0.0)) return gpmpc_refuse(who, "beta = %g is not positive", P->beta);
+    if (int rc = gpmpc_mppi_check_scalars(P, who)) return rc;
     if (cons) if (int rc = gpmpc_check_constraints(cons, who)) return rc;
     LpTail tail;
-    if (int rc = lp_check_model(who, m, &tail)) return rc;
+    if (int rc = gpmpc_lp_check_model(who, m, &tail)) return rc;
     const int ds = m->state_dim, da = m->action_dim;
     if (!gpmpc_solver_dims_ok(H, ds, da)) return gpmpc_refuse(who, "H, state_dim or action_dim outside what a solver takes");
-    for (int j = 0; j < da; ++j) {
-        if (!(P->sigma[j] > 0.0)) return gpmpc_refuse(who, "sigma[%d] = %g is not positive", j, P->sigma[j]);
-        if (!(P->lb[j] <= P->ub[j])) return gpmpc_refuse(who, "lb[%d] = %g exceeds ub[%d] = %g", j, P->lb[j], j, P->ub[j]);
-    }
-    if (!lp_tail_fits(H, ds, da)) return gpmpc_refuse(who, "H = %d is too long for the cost kernel", H);
+    if (int rc = gpmpc_mppi_check_inputs(P, da, who)) return rc;
+    if (!gpmpc_roll_tail_fits(H, ds, da, false)) return gpmpc_refuse(who, "H = %d is too long for the cost kernel", H);
     gpmpc_sched_ref sched;
     if (int rc = gpmpc_schedule_resolve(cost, ds, da, H, who, &sched)) return rc;
-    const int K = P->n_samples, n = H * da, m_c = cons ? cons->n_rows : 0;
+    const int K = P->n_samples, m_c = cons ? cons->n_rows : 0;
     const LpMppiLayout L = lp_mppi_layout(m, H, K, m_c);
     if (workspace_bytes < L.total) return GPMPC_E_WORKSPACE;
-    hipStream_t s = (hipStream_t)stream;
     char* ws = (char*)workspace;
-    double *U = (double*)(ws + L.off_U), *x0b = (double*)(ws + L.off_x0), *cst = (double*)(ws + L.off_cost), *g = (double*)(ws + L.off_g);
-    double *mean = (double*)(ws + L.off_mean), *best[2] = {(double*)(ws + L.off_best[0]), (double*)(ws + L.off_best[1])};
-    // best = (+inf, +inf, start plan), mean = start plan
-    const double key0[2] = {__builtin_huge_val(), __builtin_huge_val()};
-    if (int rc = gpmpc_upload_small(best[0], key0, sizeof(key0), s)) return rc;
-    GPMPC_HIP(hipMemcpyAsync(best[0] + 2, start, sizeof(double) * n, hipMemcpyDeviceToDevice, s));
-    GPMPC_HIP(hipMemcpyAsync(mean, start, sizeof(double) * n, hipMemcpyDeviceToDevice, s));
-    for (int it = 0; it < P->iterations; ++it) {
-        if (int rc = gpmpc_mppi_sample(H, ds, da, P, it, mean, x0, U, x0b, stream)) return rc;
-        if (int rc = gpmpc_linearised_rollout(m, K, H, x0b, U, cost, cons, 0, nullptr, nullptr, nullptr, cst, nullptr, cons ? g : nullptr, nullptr, 0,
-                                              ws + L.off_roll, L.roll_bytes, stream))
-            return rc;
-        if (int rc = gpmpc_mppi_update(K, H, da, m_c, P->beta, U, cst, cons ? g : nullptr, mean, best[it & 1], best[(it + 1) & 1],
-                                       out_trace + 6 * (size_t)it, stream))
-            return rc;
-    }
-    const double* fin = best[P->iterations & 1];
-    GPMPC_HIP(hipMemcpyAsync(out_best, fin, sizeof(double) * 2, hipMemcpyDeviceToDevice, s));
-    GPMPC_HIP(hipMemcpyAsync(out_U, fin + 2, sizeof(double) * n, hipMemcpyDeviceToDevice, s));
-    return GPMPC_OK;
+    auto eval = [&](int, const double* x0b, const double* U, double* cst, double* g) {
+        return gpmpc_linearised_rollout(m, K, H, x0b, U, cost, cons, 0, nullptr, nullptr, nullptr, cst, nullptr, g, nullptr, 0, ws + L.off_roll,
+                                        L.roll_bytes, stream);
+    };
+    return gpmpc_mppi_search(L.head, ws, H, ds, da, m_c, P, x0, start, eval, out_U, out_best, out_trace, stream);
 }

@@ -15,16 +15,13 @@
 //   k_lpf_constraints   the forward-sensitivity sweep of the chance constraints, one lane per column of the dense Jacobian
 // Rules: no atomics; launch geometry from the sizes only; columns are independent, so nothing depends on `chunk`; two identical calls
 // agree bit for bit; the rollout is the chain of step calls.
-#include <cfloat>
 #include <cmath>
-#include "linprop_internal.h"
+#include "linprop_internal.h"                   // the model frame, LpTail, LpHyp, LpIn, and the dispatcher of linprop.hip
 
-#define LPF_DEFAULT_CHUNK 4096
-#define LPF_T 64                                // columns / rows per tile, as SP_T of linprop.hip
+#define LPF_T GPMPC_MODEL_TILE                  // columns / rows per tile: what the chunk rule of model_frame.h rounds to
 #define LPF_MAX_TRI (GPMPC_MAX_DS * (GPMPC_MAX_DS + 1) / 2)
 #define LPF_MAX_P (GPMPC_MAX_DS + LPF_MAX_TRI)
 
-struct LpfHyp { double ilam[GPMPC_MAX_DS][GPMPC_MAX_D]; double sf2[GPMPC_MAX_DS]; };      // 1 / lambda_ad, sf_a^2
 struct LpfNoise { double init_cov[GPMPC_MAX_DS * GPMPC_MAX_DS]; double action_var[GPMPC_MAX_D]; };
 
 // index e of the row-major upper triangle of an n x n matrix -> (a, b), a <= b; and back
@@ -41,7 +38,7 @@ static __host__ __device__ __forceinline__ int lpf_tri(int a, int b, int n) { re
 // grid (cnp / 64, ceil(n / 64), ds).  hpart[bi][a][v][c], v < NH = D (D + 1) / 2: the (d <= l) sums, row-major; v = NH: sum_i beta_i k_i.
 template <int D>
 __global__ __launch_bounds__(256) void k_lpf_hess(int n, int cn, int ds, const double* __restrict__ X, LpIn I, const double* __restrict__ beta,
-                                                   LpfHyp Hy, double* __restrict__ hpart, int ldk) {
+                                                   LpHyp Hy, double* __restrict__ hpart, int ldk) {
     constexpr int NH = D * (D + 1) / 2;
     __shared__ double s_x[LPF_T][D], s_b[LPF_T], s_p[3][NH + 1][LPF_T];
     const int t = threadIdx.x, c = t & 63, q = t >> 6, a = blockIdx.z;
@@ -96,7 +93,7 @@ __global__ __launch_bounds__(256) void k_lpf_hess(int n, int cn, int ds, const d
 }
 
 // one thread per (GP, v < NH, column): Hm[c][a][v] = sum over the row blocks, ascending, - [d = l] (sum_i beta_i k_i) / lambda_ad
-__global__ __launch_bounds__(256) void k_lpf_hfin(int cn, int nbi, int D, int ds, LpfHyp Hy, const double* __restrict__ hpart, int ldk,
+__global__ __launch_bounds__(256) void k_lpf_hfin(int cn, int nbi, int D, int ds, LpHyp Hy, const double* __restrict__ hpart, int ldk,
                                                    double* __restrict__ Hm) {
     const int NH = D * (D + 1) / 2;
     const long e = (long)blockIdx.x * 256 + threadIdx.x;
@@ -341,34 +338,25 @@ __global__ __launch_bounds__(64) void k_lpf_constraints(int H, int da, gpmpc_sta
 // ---------------------------------------------------------------------------
 // host: checks, layouts
 // ---------------------------------------------------------------------------
-static bool lpf_finite(double v) { return v - v == 0.0; }
-static unsigned lpf_blocks(long threads) { return (unsigned)((threads + 255) / 256); }
 static int lpf_p(int ds) { return ds + ds * (ds + 1) / 2; }
-static bool lpf_sizes_ok(const gpmpc_gp_model* m) {
-    return m && m->state_dim >= 1 && m->state_dim <= GPMPC_MAX_DS && m->action_dim >= 0 && m->state_dim + m->action_dim <= GPMPC_MAX_D && m->n >= 1;
-}
 // B H packed Jacobians of at most LPF_MAX_P (LPF_MAX_P + GPMPC_MAX_D) elements stay below 2^40 elements; the constraints sweep runs
 // ceil(H da / 64) workgroups per plan in gridDim.y (at most 65535).  The sweeps keep no per-step state: these are the only limits on H.
 static bool lpf_count_ok(long B, long H) { return B >= 1 && H >= 1 && B * H * (long)LPF_MAX_P * (LPF_MAX_P + GPMPC_MAX_D) <= (1L << 40); }
 static bool lpf_sweep_fits(long H, int da) { return H * (da > 0 ? da : 1) <= 64L * 65535; }
 
-struct LpfModel { LpTail tail, tailA; LpfHyp hyp; LpfNoise noise; };
+struct LpfModel { LpTail tail, tailA; LpHyp hyp; LpfNoise noise; };
 // What the diagonal entries refuse, then the whole init_cov: finite, symmetric (the particles' rule), no negative pivot.
 static int lpf_check_model(const char* who, const gpmpc_gp_model* m, LpfModel* out) {
     if (int rc = gpmpc_lp_check_model(who, m, &out->tail)) return rc;
-    const int ds = m->state_dim, da = m->action_dim, D = ds + da;
+    const int ds = m->state_dim, da = m->action_dim;
     memset(&out->noise, 0, sizeof(out->noise));
-    memset(&out->hyp, 0, sizeof(out->hyp));
-    for (int a = 0; a < ds; ++a) {
-        out->noise.init_cov[a * ds + a] = out->tail.init_var[a];
-        out->hyp.sf2[a] = m->sigma_f[a] * m->sigma_f[a];
-        for (int d = 0; d < D; ++d) out->hyp.ilam[a][d] = 1.0 / m->lambdas[a * D + d];
-    }
+    out->hyp = lp_hyp(m);
+    for (int a = 0; a < ds; ++a) out->noise.init_cov[a * ds + a] = out->tail.init_var[a];
     for (int j = 0; j < da; ++j) out->noise.action_var[j] = out->tail.action_var[j];
     if (m->has_noise) {
         double big = 0.0;
         for (int k = 0; k < ds * ds; ++k) {
-            if (!lpf_finite(m->init_cov[k])) return gpmpc_refuse(who, "init_cov holds a non-finite value");
+            if (!gpmpc_finite(m->init_cov[k])) return gpmpc_refuse(who, "init_cov holds a non-finite value");
             big = fmax(big, fabs(m->init_cov[k]));
         }
         for (int a = 0; a < ds; ++a)
@@ -378,19 +366,10 @@ static int lpf_check_model(const char* who, const gpmpc_gp_model* m, LpfModel* o
         double Pm[GPMPC_MAX_DS * GPMPC_MAX_DS], L[GPMPC_MAX_DS * GPMPC_MAX_DS] = {};
         for (int a = 0; a < ds; ++a)
             for (int b = a; b < ds; ++b) Pm[a * ds + b] = Pm[b * ds + a] = m->init_cov[a * ds + b];
-        for (int j = 0; j < ds; ++j) {
-            double d = Pm[j * ds + j];
-            for (int k = 0; k < j; ++k) d -= L[j * ds + k] * L[j * ds + k];
-            if (d < -1e-12 * big) return gpmpc_refuse(who, "init_cov has a negative pivot (%g at %d): it is not positive semi-definite", d, j);
-            if (d <= 16.0 * DBL_EPSILON * Pm[j * ds + j]) continue;
-            const double r = sqrt(d);
-            L[j * ds + j] = r;
-            for (int i = j + 1; i < ds; ++i) {
-                double s = Pm[i * ds + j];
-                for (int k = 0; k < j; ++k) s -= L[i * ds + k] * L[j * ds + k];
-                L[i * ds + j] = s / r;
-            }
-        }
+        double d = 0.0;
+        int j = 0;
+        if (!gpmpc_psd_pivots(Pm, ds, big, L, &d, &j))
+            return gpmpc_refuse(who, "init_cov has a negative pivot (%g at %d): it is not positive semi-definite", d, j);
         memcpy(out->noise.init_cov, Pm, sizeof(double) * ds * ds);
     }
     out->tailA = out->tail;
@@ -413,8 +392,7 @@ static LpfLayout lpf_layout(const gpmpc_gp_model* m, long B, size_t xs, bool wan
     const int ds = m->state_dim, da = m->action_dim, D = ds + da, NH = D * (D + 1) / 2;
     const size_t d = sizeof(double);
     L.nbi = (m->n + LPF_T - 1) / LPF_T;
-    const long colsp = (B + LPF_T - 1) / LPF_T * LPF_T, ch = chunk == 0 ? LPF_DEFAULT_CHUNK : chunk;
-    L.C = (int)(colsp < ch ? colsp : ch);
+    L.C = gpmpc_chunk_cols(B, chunk);
     L.zero_bytes = d * ((size_t)(B - 1) * xs + ds);
     L.off_zero = c.take(L.zero_bytes);
     L.off_var = c.take(L.zero_bytes);                    // s2 lands with the stride of out_mu: the dispatcher has one output stride
@@ -452,7 +430,7 @@ static int lpf_step(const gpmpc_gp_model* m, const LpfModel& M, int B, const dou
                     return GPMPC_OK;
                 }))
                 return rc;
-            hipLaunchKernelGGL(k_lpf_hfin, dim3(lpf_blocks((long)cn * ds * NH)), dim3(256), 0, s, cn, L.nbi, D, ds, M.hyp, (const double*)hpart, L.C,
+            hipLaunchKernelGGL(k_lpf_hfin, dim3(gpmpc_blocks256((long)cn * ds * NH)), dim3(256), 0, s, cn, L.nbi, D, ds, M.hyp, (const double*)hpart, L.C,
                                Hm + (size_t)c0 * ds * NH);
         }
         hipLaunchKernelGGL(k_lpf_close<true>, dim3(B), dim3(64), 0, s, ds, da, M.noise, cov_prev, cs, K_t, (const double*)a_var, os,
@@ -469,7 +447,7 @@ static int lpf_step(const gpmpc_gp_model* m, const LpfModel& M, int B, const dou
 // host: entries
 // ---------------------------------------------------------------------------
 extern "C" size_t gpmpc_linearised_fc_step_workspace_bytes(const gpmpc_gp_model* m, int B, int want_jac, int chunk) {
-    if (!lpf_sizes_ok(m) || !lpf_count_ok(B, 1) || chunk < 0 || chunk % 64) return 0;
+    if (!gpmpc_model_sizes_ok(m) || !lpf_count_ok(B, 1) || !gpmpc_chunk_ok(chunk)) return 0;
     gpmpc_carver c;
     return lpf_layout(m, B, m->state_dim, want_jac != 0, chunk, c).total;
 }
@@ -482,7 +460,7 @@ extern "C" int gpmpc_linearised_fc_step(const gpmpc_gp_model* m, int B, const do
     if (int rc = lpf_check_model(who, m, &M)) return rc;
     if (B < 1) return gpmpc_refuse(who, "B < 1");
     if (!lpf_count_ok(B, 1)) return gpmpc_refuse(who, "B is too large");
-    if (chunk < 0 || chunk % 64) return gpmpc_refuse(who, "chunk must be 0 or a positive multiple of 64");
+    if (int rc = gpmpc_check_chunk(who, chunk)) return rc;
     if (!mu_prev || !cov_prev || !out_mu || !out_cov || !workspace || (m->action_dim > 0 && !U_t)) return gpmpc_refuse(who, "NULL pointer");
     if (out_mu == mu_prev || out_cov == cov_prev || out_mu == cov_prev || out_cov == mu_prev || out_mu == out_cov)
         return gpmpc_refuse(who, "the outputs must not alias the inputs or each other");
@@ -557,7 +535,7 @@ static LpfRollLayout lpf_roll_layout(const gpmpc_gp_model* m, int B, int H, bool
 }
 
 extern "C" size_t gpmpc_linearised_fc_rollout_workspace_bytes(const gpmpc_gp_model* m, int B, int H, unsigned flags, int chunk) {
-    if (!lpf_sizes_ok(m) || !lpf_count_ok(B, H) || !lpf_sweep_fits(H, m->action_dim) || (flags & ~GPMPC_WANT_GRAD) || chunk < 0 || chunk % 64)
+    if (!gpmpc_model_sizes_ok(m) || !lpf_count_ok(B, H) || !lpf_sweep_fits(H, m->action_dim) || (flags & ~GPMPC_WANT_GRAD) || !gpmpc_chunk_ok(chunk))
         return 0;
     return lpf_roll_layout(m, B, H, (flags & GPMPC_WANT_GRAD) != 0, chunk).total;
 }
@@ -576,7 +554,7 @@ extern "C" int gpmpc_linearised_fc_rollout(const gpmpc_gp_model* m, int B, int H
     if (flags & GPMPC_USE_GRAPH) return gpmpc_refuse(who, "GPMPC_USE_GRAPH is not supported by the linearised rollout (not yet)");
     if (flags & (GPMPC_FP32_ACCUM | GPMPC_FP32_ALL)) return gpmpc_refuse(who, "the GPMPC_FP32_* modes are not supported by the linearised rollout");
     if (flags & ~GPMPC_WANT_GRAD) return gpmpc_refuse(who, "flags: GPMPC_WANT_GRAD or 0");
-    if (chunk < 0 || chunk % 64) return gpmpc_refuse(who, "chunk must be 0 or a positive multiple of 64");
+    if (int rc = gpmpc_check_chunk(who, chunk)) return rc;
     const bool grad = (flags & GPMPC_WANT_GRAD) != 0;
     const int ds = m->state_dim, da = m->action_dim, p = lpf_p(ds);
     if (!x0 || !workspace || (da > 0 && !U)) return gpmpc_refuse(who, "NULL pointer");
@@ -601,7 +579,7 @@ extern "C" int gpmpc_linearised_fc_rollout(const gpmpc_gp_model* m, int B, int H
     double* jac = grad ? (out_jac ? out_jac : (double*)(ws + R.off_jac)) : nullptr;
     const size_t xs = (size_t)(H + 1) * ds, cs = xs * ds, jblock = (size_t)p * (p + da), js = (size_t)H * jblock;
     GPMPC_HIP(hipMemsetAsync(ws + R.step.off_zero, 0, R.step.zero_bytes, s));
-    hipLaunchKernelGGL(k_lpf_init, dim3(lpf_blocks((long)B * (ds + ds * ds))), dim3(256), 0, s, B, H, ds, x0, M.noise, means, covs);
+    hipLaunchKernelGGL(k_lpf_init, dim3(gpmpc_blocks256((long)B * (ds + ds * ds))), dim3(256), 0, s, B, H, ds, x0, M.noise, means, covs);
     for (int t = 1; t <= H; ++t) {
         const double* K_t = K_dev ? K_dev + (size_t)(t - 1) * k_step_stride : nullptr;
         if (int rc = lpf_step(m, M, B, means + (size_t)(t - 1) * ds, xs, covs + (size_t)(t - 1) * ds * ds, cs, U ? U + (size_t)(t - 1) * da : nullptr,

@@ -1,13 +1,25 @@
-// What the two forms of the linearised step share (linprop.hip: TILE and the dispatcher; linprop_stream.hip: STREAM): the tail of the model,
-// the inputs of a step, and the host interface of the STREAM form.  Formulas: include/gpmpc.h, "Linearised propagation".
+// What the linearised rules share (linprop.hip: TILE and the dispatcher; linprop_stream.hip: STREAM; linprop_fc.hip: the full covariance):
+// the model frame (model_frame.h), the tail of the model, the hyper-parameters by GP, the inputs of a step, the dispatcher's host
+// interface and that of the STREAM form.  Formulas: include/gpmpc.h, "Linearised propagation".
 #pragma once
-#include "gpmpc_internal.h"
+#include "model_frame.h"
 
 struct LpTail {                     // what the sums / Jacobian kernels need of the model besides the hyper-parameters
     double nom_w[GPMPC_MAX_DS * GPMPC_MAX_D], nom_b[GPMPC_MAX_DS], process_var[GPMPC_MAX_DS], action_var[GPMPC_MAX_D];
     double init_var[GPMPC_MAX_DS];  // diag(init_cov): the variance of step 0 (host side only)
     int has_nominal;
 };
+struct LpHyp { double ilam[GPMPC_MAX_DS][GPMPC_MAX_D]; double sf2[GPMPC_MAX_DS]; };      // 1 / lambda_ad, sf_a^2: the kernels that take GPs one by one
+static inline LpHyp lp_hyp(const gpmpc_gp_model* m) {
+    const int ds = m->state_dim, D = ds + m->action_dim;
+    LpHyp Hy;
+    memset(&Hy, 0, sizeof(Hy));
+    for (int a = 0; a < ds; ++a) {
+        for (int d = 0; d < D; ++d) Hy.ilam[a][d] = 1.0 / m->lambdas[a * D + d];
+        Hy.sf2[a] = m->sigma_f[a] * m->sigma_f[a];
+    }
+    return Hy;
+}
 struct LpIn {                       // the inputs of a step, column c: mu + c xs, var + c xs, U + c us
     const double* mu; const double* var; const double* U;
     size_t xs, us;
@@ -17,9 +29,9 @@ static __device__ __forceinline__ double lp_z(const LpIn& I, int c, int d, int d
     return d < ds ? I.mu[(size_t)c * I.xs + d] : I.U[(size_t)c * I.us + (d - ds)];
 }
 
-// The dispatcher of linprop.hip for the full-covariance rule (linprop_fc.hip), whose stage A is the diagonal step itself: the model checks
-// of the diagonal entries, the layout of one step (the form is read here, once; offsets start at 0) and the step on a workspace of
-// gpmpc_lp_layout(...).total bytes.  Arguments as lp_step of linprop.hip.
+// The dispatcher of linprop.hip, also stage A of the full-covariance rule: the model checks of the diagonal entries (they fill `out`), the
+// layout of one step (the form is read here, once; offsets start at 0) and the step of B columns on a workspace of gpmpc_lp_layout(...).total
+// bytes -- mu_prev / var_prev: column b at + b xs; U_t: + b us; outputs at + b os; jac (or null): + b js.
 struct LpLayout { size_t off_ks, off_kpart, off_part, off_hpart, off_g, total, base; int np, nbi, C, nv, form; };
 int gpmpc_lp_check_model(const char* who, const gpmpc_gp_model* m, LpTail* out);
 LpLayout gpmpc_lp_layout(const gpmpc_gp_model* m, int chunk, long ncols, bool want_jac);
@@ -27,7 +39,7 @@ int gpmpc_lp_step(const gpmpc_gp_model* m, const LpTail& tail, int B, const doub
                   size_t us, double* out_mu, double* out_var, size_t os, double* jac, size_t js, const LpLayout& L, char* ws, hipStream_t s);
 
 // STREAM (linprop_stream.hip).  The bytes of a step of `ncols` columns, and the step itself on a workspace of that size (256-byte aligned);
-// arguments as lp_step of linprop.hip, checked by its callers.
+// arguments as gpmpc_lp_step, checked by its callers.
 size_t gpmpc_lps_workspace_bytes(const gpmpc_gp_model* m, long ncols, bool want_jac);
 int gpmpc_lps_step(const gpmpc_gp_model* m, const LpTail& tail, int B, const double* mu_prev, const double* var_prev, size_t xs, const double* U_t,
                    size_t us, double* out_mu, double* out_var, size_t os, double* jac, size_t js, char* ws, hipStream_t s);

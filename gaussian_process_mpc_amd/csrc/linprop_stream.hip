@@ -19,12 +19,13 @@
 // Rules: no atomics; every output element is owned by one thread or one workgroup, which sums in a fixed order (block reductions are
 // trees over the thread index, wave reductions butterflies over the lane index); launch geometry depends on sizes only; every vector
 // has its own accumulators, so a column's bits do not depend on what else is in its group, its chunk or the batch.
+// Host: no checks of its own -- gpmpc_lps_step is reached through the dispatcher of linprop.hip (gpmpc_lp_step) on a checked model; the
+// kernels take the hyper-parameters GP by GP as LpHyp (linprop_internal.h), which linprop_fc.hip's kernels take too.
 // Cost of the row block: colpart holds np / LPS_RB partial vectors per (column, GP): at N = 2048, LPS_RB = 32 that is 1 MiB per vector,
 // written and read once per step (1/8 of a per-GP Kinv per column of the group on top of the one read of Kinv).
-#include <cfloat>
 #include <cmath>
 #include <cstdint>
-#include "linprop_internal.h"
+#include "linprop_internal.h"   // LpTail, LpHyp, LpIn, lp_z
 
 #define LPS_COLS GPMPC_LINPROP_STREAM_COLS
 #define LPS_RB 32                   // rows of a workgroup: N = 2048, ds = 4 gives 64 x 4 = 256 workgroups per group of vectors
@@ -32,8 +33,6 @@
 #define LPS_CHUNK 16                // columns per set of launches: bounds colpart at 16 ds (np / 32) np doubles
 #define LPS_NV (1 + GPMPC_MAX_D)
 static_assert(LPS_COLS == 4, "the lane maps of k_lps_quad are written for four vectors");
-
-struct LpsHyp { double ilam[GPMPC_MAX_DS][GPMPC_MAX_D]; double sf2[GPMPC_MAX_DS]; };
 
 // the tree over the thread index: s[v][0] = sum of s[v][0 ... 255], the same association for every v and every call
 template <int NV>
@@ -51,7 +50,7 @@ static __device__ __forceinline__ void lps_block_sum(double (*s)[256], int t) {
 // kernels
 // ---------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_lps_kstar(int n, int np, int D, int ds, const double* __restrict__ X, LpIn I,
-                                                    const double* __restrict__ beta, LpsHyp Hy, double* __restrict__ ks,
+                                                    const double* __restrict__ beta, LpHyp Hy, double* __restrict__ ks,
                                                     double* __restrict__ kpart) {
     __shared__ double s_p[LPS_NV][256];
     const int t = threadIdx.x, i = blockIdx.x * 256 + t, a = blockIdx.y, c = blockIdx.z;
@@ -185,7 +184,7 @@ __global__ __launch_bounds__(256) void k_lps_quad(int n, int np, int ds, int cn,
 }
 
 // one thread per vector f = c ds + a: mu', v', and g (with the nominal weights) for the Jacobian passes.  The tail of k_lp_sums.
-__global__ __launch_bounds__(256) void k_lps_sums(int cn, int nbk, int nrb, int D, int ds, LpsHyp Hy, LpTail M, LpIn I,
+__global__ __launch_bounds__(256) void k_lps_sums(int cn, int nbk, int nrb, int D, int ds, LpHyp Hy, LpTail M, LpIn I,
                                                    const double* __restrict__ kpart, const double* __restrict__ qpart,
                                                    double* __restrict__ out_mu, double* __restrict__ out_var, size_t os,
                                                    double* __restrict__ gbuf) {
@@ -215,7 +214,7 @@ __global__ __launch_bounds__(256) void k_lps_sums(int cn, int nbk, int nrb, int 
 
 // grid (np / 256, ds, columns).  Reads ks back (no second exp).
 __global__ __launch_bounds__(256) void k_lps_grad(int n, int np, int nrb, int D, int ds, const double* __restrict__ X, LpIn I,
-                                                   const double* __restrict__ beta, LpsHyp Hy, LpTail M, const double* __restrict__ ks,
+                                                   const double* __restrict__ beta, LpHyp Hy, LpTail M, const double* __restrict__ ks,
                                                    const double* __restrict__ y, const double* __restrict__ colpart,
                                                    const double* __restrict__ gbuf, double* __restrict__ jpart) {
     __shared__ double s_p[2 * GPMPC_MAX_D][256];
@@ -300,12 +299,7 @@ int gpmpc_lps_step(const gpmpc_gp_model* m, const LpTail& tail, int B, const dou
                    size_t us, double* out_mu, double* out_var, size_t os, double* jac, size_t js, char* ws, hipStream_t s) {
     const int ds = m->state_dim, D = ds + m->action_dim, n = m->n;
     const LpsLayout L = lps_layout(m, B, jac != nullptr);
-    LpsHyp Hy;
-    memset(&Hy, 0, sizeof(Hy));
-    for (int a = 0; a < ds; ++a) {
-        for (int d = 0; d < D; ++d) Hy.ilam[a][d] = 1.0 / m->lambdas[a * D + d];
-        Hy.sf2[a] = m->sigma_f[a] * m->sigma_f[a];
-    }
+    const LpHyp Hy = lp_hyp(m);
     double* ks = (double*)(ws + L.off_ks);
     double* y = (double*)(ws + L.off_y);
     double* kpart = (double*)(ws + L.off_kpart);

@@ -16,7 +16,7 @@
 //             then the 256 partial sums are folded in halves, p[i] <- p[i] + p[i + h], h = 128, 64, ... 1
 //   mean[c]   wave w adds w_k U[k][c] over its quarter of the samples in ascending k (zero weights skipped), the four are added in wave
 //             order, one division by the sum of the weights
-#include "solver_frame.h"
+#include "mppi_internal.h"   // the search itself, shared with linprop.hip and particle_cost.hip
 #include <cmath>
 
 #include "philox.h"      // Philox4x32-10, the 53-bit uniform, the fixed-order folds (shared with particles.hip)
@@ -170,7 +170,7 @@ __global__ __launch_bounds__(MPPI_THREADS) void k_mppi_update(int K, int n, int 
 // host entries
 // ---------------------------------------------------------------------------
 // the part of the parameters that needs no dimension
-static int mppi_check_scalars(const gpmpc_mppi_params* P, const char* who) {
+int gpmpc_mppi_check_scalars(const gpmpc_mppi_params* P, const char* who) {
     if (!P) return GPMPC_E_ARG;
     if (P->n_samples < 1 || P->n_samples > GPMPC_MPPI_MAX_SAMPLES)
         return gpmpc_refuse(who, "n_samples = %d outside 1..%d", P->n_samples, GPMPC_MPPI_MAX_SAMPLES);
@@ -181,7 +181,7 @@ static int mppi_check_scalars(const gpmpc_mppi_params* P, const char* who) {
 }
 
 // sigma and the bounds of input j are checked together, input by input
-static int mppi_check_inputs(const gpmpc_mppi_params* P, int da, const char* who) {
+int gpmpc_mppi_check_inputs(const gpmpc_mppi_params* P, int da, const char* who) {
     for (int j = 0; j < da; ++j) {
         if (!(P->sigma[j] > 0.0)) return gpmpc_refuse(who, "sigma[%d] = %g is not positive", j, P->sigma[j]);
         if (!(P->lb[j] <= P->ub[j])) return gpmpc_refuse(who, "lb[%d] = %g exceeds ub[%d] = %g", j, P->lb[j], j, P->ub[j]);      // lb > ub, or NaN
@@ -189,8 +189,8 @@ static int mppi_check_inputs(const gpmpc_mppi_params* P, int da, const char* who
     return GPMPC_OK;
 }
 
-static int mppi_launch_sample(int H, int ds, int da, const gpmpc_mppi_params& P, int iteration, const double* mean, const double* x0,
-                              double* U, double* x0b, hipStream_t s) {
+int gpmpc_mppi_launch_sample(int H, int ds, int da, const gpmpc_mppi_params& P, int iteration, const double* mean, const double* x0, double* U,
+                             double* x0b, hipStream_t s) {
     const long n = (long)H * da, pairs = ((long)P.n_samples * n + 1) / 2, states = x0b ? (long)P.n_samples * ds : 0;
     const long threads = pairs > states ? pairs : states;
     const double scale = pow(P.sigma_decay, (double)iteration);
@@ -203,9 +203,9 @@ static int mppi_launch_sample(int H, int ds, int da, const gpmpc_mppi_params& P,
 extern "C" int gpmpc_mppi_sample(int H, int ds, int da, const gpmpc_mppi_params* P, int iteration, const double* mean, const double* x0,
                                  double* out_U, double* out_x0_batch, void* stream) {
     if (!P || !mean || !out_U || iteration < 0 || !gpmpc_solver_dims_ok(H, ds, da) || (out_x0_batch && (!x0 || ds < 1))) return GPMPC_E_ARG;
-    if (int rc = mppi_check_scalars(P, "gpmpc_mppi_sample")) return rc;
-    if (int rc = mppi_check_inputs(P, da, "gpmpc_mppi_sample")) return rc;
-    return mppi_launch_sample(H, ds, da, *P, iteration, mean, x0, out_U, out_x0_batch, (hipStream_t)stream);
+    if (int rc = gpmpc_mppi_check_scalars(P, "gpmpc_mppi_sample")) return rc;
+    if (int rc = gpmpc_mppi_check_inputs(P, da, "gpmpc_mppi_sample")) return rc;
+    return gpmpc_mppi_launch_sample(H, ds, da, *P, iteration, mean, x0, out_U, out_x0_batch, (hipStream_t)stream);
 }
 
 extern "C" int gpmpc_mppi_update(int K, int H, int da, int n_rows, double beta, const double* U, const double* cost, const double* g,
@@ -223,19 +223,12 @@ extern "C" int gpmpc_mppi_update(int K, int H, int da, int n_rows, double beta, 
     return GPMPC_OK;
 }
 
-// workspace of a solve: U [K][n] | x0 [K][ds] | cost [K] | g [K][H m_c] | mean [n] | best x 2 [2 + n] | the rollout's own workspace
-struct MppiLayout { size_t off_U, off_x0, off_cost, off_g, off_mean, off_best[2], off_roll, total; gpmpc_solver_eval_layout roll; };
+// workspace of a solve: the head of every MPPI solve (mppi_internal.h) | the rollout's own workspace
+struct MppiLayout { gpmpc_mppi_head head; size_t off_roll, total; gpmpc_solver_eval_layout roll; };
 static MppiLayout mppi_layout(const gpmpc_pack* p, int H, int K, int m_c, gpmpc_solver_rule rule) {
     MppiLayout L;
-    const size_t n = (size_t)H * p->da, d = sizeof(double);
     gpmpc_carver c;
-    L.off_U = c.take(d * K * n);
-    L.off_x0 = c.take(d * K * p->ds);
-    L.off_cost = c.take(d * K);
-    L.off_g = c.take(d * K * H * m_c);
-    L.off_mean = c.take(d * n);
-    L.off_best[0] = c.take(d * (2 + n));
-    L.off_best[1] = c.take(d * (2 + n));
+    L.head = gpmpc_mppi_head_take(c, H, p->ds, p->da, K, m_c);
     L.roll = gpmpc_solver_eval_bytes(rule, p, K, H, m_c != 0, 0);
     L.off_roll = c.take(L.roll.total);
     L.total = c.total();
@@ -261,32 +254,16 @@ static int mppi_solve(gpmpc_solver_rule rule, const char* who, const gpmpc_pack*
                       const gpmpc_cost_params* cost, const gpmpc_state_constraints* cons, const gpmpc_mppi_params* P, double* out_U,
                       double* out_best, double* out_trace, void* workspace, size_t workspace_bytes, void* stream) {
     if (!p || !x0 || !start || !cost || !P || !out_U || !out_best || !out_trace || !workspace || H < 1) return GPMPC_E_ARG;
-    if (int rc = mppi_check_scalars(P, who)) return rc;                  // (before the pack is looked at)
-    if (int rc = gpmpc_solver_enter(p, H, cost, cons, who, [&](int da) { return mppi_check_inputs(P, da, who); }, rule)) return rc;
-    const int K = P->n_samples, n = H * p->da, m_c = cons ? cons->n_rows : 0;
+    if (int rc = gpmpc_mppi_check_scalars(P, who)) return rc;            // (before the pack is looked at)
+    if (int rc = gpmpc_solver_enter(p, H, cost, cons, who, [&](int da) { return gpmpc_mppi_check_inputs(P, da, who); }, rule)) return rc;
+    const int K = P->n_samples, m_c = cons ? cons->n_rows : 0;
     const MppiLayout L = mppi_layout(p, H, K, m_c, rule);
     if (workspace_bytes < L.total) return GPMPC_E_WORKSPACE;
-    hipStream_t s = (hipStream_t)stream;
     char* ws = (char*)workspace;
-    double *U = (double*)(ws + L.off_U), *x0b = (double*)(ws + L.off_x0), *cst = (double*)(ws + L.off_cost), *g = (double*)(ws + L.off_g);
-    double *mean = (double*)(ws + L.off_mean), *best[2] = {(double*)(ws + L.off_best[0]), (double*)(ws + L.off_best[1])};
-    // best = (+inf, +inf, start plan), mean = start plan
-    const double key0[2] = {__builtin_huge_val(), __builtin_huge_val()};
-    if (int rc = gpmpc_upload_small(best[0], key0, sizeof(key0), s)) return rc;
-    GPMPC_HIP(hipMemcpyAsync(best[0] + 2, start, sizeof(double) * n, hipMemcpyDeviceToDevice, s));
-    GPMPC_HIP(hipMemcpyAsync(mean, start, sizeof(double) * n, hipMemcpyDeviceToDevice, s));
-    for (int it = 0; it < P->iterations; ++it) {
-        if (int rc = mppi_launch_sample(H, p->ds, p->da, *P, it, mean, x0, U, x0b, s)) return rc;
-        int rc = gpmpc_solver_eval(rule, p, K, H, x0b, U, cost, cons, 0, cst, nullptr, cons ? g : nullptr, nullptr, ws + L.off_roll, L.roll, stream);
-        if (rc) return rc;
-        rc = gpmpc_mppi_update(K, H, p->da, m_c, P->beta, U, cst, cons ? g : nullptr, mean, best[it & 1], best[(it + 1) & 1],
-                               out_trace + 6 * (size_t)it, stream);
-        if (rc) return rc;
-    }
-    const double* fin = best[P->iterations & 1];
-    GPMPC_HIP(hipMemcpyAsync(out_best, fin, sizeof(double) * 2, hipMemcpyDeviceToDevice, s));
-    GPMPC_HIP(hipMemcpyAsync(out_U, fin + 2, sizeof(double) * n, hipMemcpyDeviceToDevice, s));
-    return GPMPC_OK;
+    auto eval = [&](int, const double* x0b, const double* U, double* cst, double* g) {
+        return gpmpc_solver_eval(rule, p, K, H, x0b, U, cost, cons, 0, cst, nullptr, g, nullptr, ws + L.off_roll, L.roll, stream);
+    };
+    return gpmpc_mppi_search(L.head, ws, H, p->ds, p->da, m_c, P, x0, start, eval, out_U, out_best, out_trace, stream);
 }
 
 extern "C" int gpmpc_mppi_solve(const gpmpc_pack* p, int H, const double* x0, const double* start, const gpmpc_cost_params* cost,

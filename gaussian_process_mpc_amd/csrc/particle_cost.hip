@@ -10,11 +10,13 @@
 //   k_pc_close   one lane per plan: J = sum_i s_i (ascending) + the input terms of gpmpc_cost.
 // Rules: no atomics; every output element is owned by one workgroup or one lane, which sums in a fixed order; launch geometry depends on
 // sizes (and on which optional outputs are given) only.
+// Host: the model is checked by particles.hip (gpmpc_pt_check_model: the core of model_frame.h, then the noise model), sizes and chunk by
+// model_frame.h; gpmpc_mppi_solve_particles is its entry checks and gpmpc_mppi_search (mppi_internal.h) with pc_evaluate as the evaluation.
 #include <cmath>
-#include "gpmpc_internal.h"
+#include "model_frame.h"
 #include "philox.h"
 #include "particles_internal.h"
-#include "solver_frame.h"
+#include "mppi_internal.h"
 
 #define PC_PER_THREAD (GPMPC_PARTICLE_COST_MAX_P / MPPI_THREADS)
 #define PC_MAX_NORMALS (GPMPC_MAX_D + GPMPC_MAX_DS)
@@ -314,8 +316,8 @@ static PcEvalLayout pc_eval_layout(const gpmpc_gp_model* m, int B, int P, int H,
 }
 
 static bool pc_eval_sizes_ok(const gpmpc_gp_model* m, int B, int P, int H, int chunk) {
-    return gpmpc_pt_model_sizes_ok(m) && B >= 1 && B <= 65535 && P >= 1 && P <= GPMPC_PARTICLE_COST_MAX_P && H >= 1 && H <= 65534 &&
-           (long)B * P * GPMPC_MAX_D <= 0x7fffffffL && (long)B * P * GPMPC_MAX_DS * (H + 1) <= (1L << 40) && chunk >= 0 && chunk % 64 == 0;
+    return gpmpc_model_sizes_ok(m) && B >= 1 && B <= 65535 && P >= 1 && P <= GPMPC_PARTICLE_COST_MAX_P && H >= 1 && H <= 65534 &&
+           (long)B * P * GPMPC_MAX_D <= 0x7fffffffL && (long)B * P * GPMPC_MAX_DS * (H + 1) <= (1L << 40) && gpmpc_chunk_ok(chunk);
 }
 
 extern "C" size_t gpmpc_particle_evaluate_workspace_bytes(const gpmpc_gp_model* m, int B, int P, int H, int chunk) {
@@ -356,7 +358,7 @@ extern "C" int gpmpc_particle_evaluate(const gpmpc_gp_model* m, int B, int P, in
     if (int rc = gpmpc_pt_check_model(who, m)) return rc;
     PcProblem pb;
     if (int rc = pc_check(who, B, P, H, m->state_dim, m->action_dim, cost, cons, out_g, &pb)) return rc;
-    if (chunk < 0 || chunk % 64) return gpmpc_refuse(who, "chunk must be 0 or a positive multiple of 64");
+    if (int rc = gpmpc_check_chunk(who, chunk)) return rc;
     if (!x0 || !out_cost || !workspace || (m->action_dim > 0 && !U)) return gpmpc_refuse(who, "NULL pointer");
     const PcEvalLayout L = pc_eval_layout(m, B, P, H, chunk);
     if (workspace_bytes < L.total) return GPMPC_E_WORKSPACE;
@@ -364,21 +366,14 @@ extern "C" int gpmpc_particle_evaluate(const gpmpc_gp_model* m, int B, int P, in
 }
 
 // ---------------------------------------------------------------------------
-// MPPI over the particle cost: gpmpc_mppi_solve_linearised with the evaluation above in the place of the rollout
+// MPPI over the particle cost: the search of mppi_internal.h with the evaluation above
 // ---------------------------------------------------------------------------
-// workspace: U [K][n] | x0 [K][ds] | cost [K] | g [K][H m_c] | mean [n] | best x 2 [2 + n] | the evaluation's own workspace
-struct PcMppiLayout { size_t off_U, off_x0, off_cost, off_g, off_mean, off_best[2], off_eval, total; PcEvalLayout eval; };
+// workspace: the head of every MPPI solve | the evaluation's own workspace
+struct PcMppiLayout { gpmpc_mppi_head head; size_t off_eval, total; PcEvalLayout eval; };
 static PcMppiLayout pc_mppi_layout(const gpmpc_gp_model* m, int H, int P, int K, int m_c) {
     PcMppiLayout L;
-    const size_t n = (size_t)H * m->action_dim, d = sizeof(double);
     gpmpc_carver c;
-    L.off_U = c.take(d * K * n);
-    L.off_x0 = c.take(d * K * m->state_dim);
-    L.off_cost = c.take(d * K);
-    L.off_g = c.take(d * K * H * m_c);
-    L.off_mean = c.take(d * n);
-    L.off_best[0] = c.take(d * (2 + n));
-    L.off_best[1] = c.take(d * (2 + n));
+    L.head = gpmpc_mppi_head_take(c, H, m->state_dim, m->action_dim, K, m_c);
     L.eval = pc_eval_layout(m, K, P, H, 0);
     L.off_eval = c.take(L.eval.total);
     L.total = c.total();
@@ -400,45 +395,21 @@ extern "C" int gpmpc_mppi_solve_particles(const gpmpc_gp_model* m, int H, int P,
     const char* who = "gpmpc_mppi_solve_particles";
     if (!m || !x0 || !start || !cost || !Pm || !out_U || !out_best || !out_trace || !workspace) return gpmpc_refuse(who, "NULL pointer");
     if (H < 1) return gpmpc_refuse(who, "H < 1");
-    if (Pm->n_samples < 1 || Pm->n_samples > GPMPC_MPPI_MAX_SAMPLES)
-        return gpmpc_refuse(who, "n_samples = %d outside 1..%d", Pm->n_samples, GPMPC_MPPI_MAX_SAMPLES);
-    if (Pm->iterations < 1) return gpmpc_refuse(who, "iterations = %d is less than 1", Pm->iterations);
-    if (!(Pm->sigma_decay > 0.0)) return gpmpc_refuse(who, "sigma_decay = %g is not positive", Pm->sigma_decay);
-    if (!(Pm->beta > 0.0)) return gpmpc_refuse(who, "beta = %g is not positive", Pm->beta);
+    if (int rc = gpmpc_mppi_check_scalars(Pm, who)) return rc;
     if (int rc = gpmpc_pt_check_model(who, m)) return rc;
     const int ds = m->state_dim, da = m->action_dim;
     if (!gpmpc_solver_dims_ok(H, ds, da)) return gpmpc_refuse(who, "H, state_dim or action_dim outside what a solver takes");
-    for (int j = 0; j < da; ++j) {
-        if (!(Pm->sigma[j] > 0.0)) return gpmpc_refuse(who, "sigma[%d] = %g is not positive", j, Pm->sigma[j]);
-        if (!(Pm->lb[j] <= Pm->ub[j])) return gpmpc_refuse(who, "lb[%d] = %g exceeds ub[%d] = %g", j, Pm->lb[j], j, Pm->ub[j]);
-    }
-    const int K = Pm->n_samples, n = H * da, m_c = cons ? cons->n_rows : 0;
+    if (int rc = gpmpc_mppi_check_inputs(Pm, da, who)) return rc;
+    const int K = Pm->n_samples, m_c = cons ? cons->n_rows : 0;
     PcProblem pb;
     // (out_g of the evaluation is the solve's own buffer: given exactly when rows are)
     if (int rc = pc_check(who, K, P, H, ds, da, cost, cons, cons ? (const double*)workspace : nullptr, &pb)) return rc;
     const PcMppiLayout L = pc_mppi_layout(m, H, P, K, m_c);
     if (workspace_bytes < L.total) return GPMPC_E_WORKSPACE;
-    hipStream_t s = (hipStream_t)stream;
     char* ws = (char*)workspace;
-    double *U = (double*)(ws + L.off_U), *x0b = (double*)(ws + L.off_x0), *cst = (double*)(ws + L.off_cost), *g = (double*)(ws + L.off_g);
-    double *mean = (double*)(ws + L.off_mean), *best[2] = {(double*)(ws + L.off_best[0]), (double*)(ws + L.off_best[1])};
-    // best = (+inf, +inf, start plan), mean = start plan
-    const double key0[2] = {__builtin_huge_val(), __builtin_huge_val()};
-    if (int rc = gpmpc_upload_small(best[0], key0, sizeof(key0), s)) return rc;
-    GPMPC_HIP(hipMemcpyAsync(best[0] + 2, start, sizeof(double) * n, hipMemcpyDeviceToDevice, s));
-    GPMPC_HIP(hipMemcpyAsync(mean, start, sizeof(double) * n, hipMemcpyDeviceToDevice, s));
-    for (int it = 0; it < Pm->iterations; ++it) {
-        if (int rc = gpmpc_mppi_sample(H, ds, da, Pm, it, mean, x0, U, x0b, stream)) return rc;
-        // the SAME particle noise in every iteration: one fixed sample-average objective, so that keys compare across iterations
-        if (int rc = pc_evaluate(m, K, P, H, x0b, U, Pm->seed, Pm->call_index, pb, cst, nullptr, cons ? g : nullptr, 0, L.eval, ws + L.off_eval,
-                                 stream))
-            return rc;
-        if (int rc = gpmpc_mppi_update(K, H, da, m_c, Pm->beta, U, cst, cons ? g : nullptr, mean, best[it & 1], best[(it + 1) & 1],
-                                       out_trace + 6 * (size_t)it, stream))
-            return rc;
-    }
-    const double* fin = best[Pm->iterations & 1];
-    GPMPC_HIP(hipMemcpyAsync(out_best, fin, sizeof(double) * 2, hipMemcpyDeviceToDevice, s));
-    GPMPC_HIP(hipMemcpyAsync(out_U, fin + 2, sizeof(double) * n, hipMemcpyDeviceToDevice, s));
-    return GPMPC_OK;
+    // the SAME particle noise in every iteration: one fixed sample-average objective, so that keys compare across iterations
+    auto eval = [&](int, const double* x0b, const double* U, double* cst, double* g) {
+        return pc_evaluate(m, K, P, H, x0b, U, Pm->seed, Pm->call_index, pb, cst, nullptr, g, 0, L.eval, ws + L.off_eval, stream);
+    };
+    return gpmpc_mppi_search(L.head, ws, H, ds, da, m_c, Pm, x0, start, eval, out_U, out_best, out_trace, stream);
 }

@@ -1,7 +1,7 @@
 // Particles: the pointwise posterior of all GPs at many points, and Monte-Carlo rollouts through it.  Formulas, layouts, the noise
 // addressing and the refusals: include/gpmpc.h, "Particles"; the why and the measurements: DESIGN.md section 3i.
 //
-// Per chunk of C columns (points) and per group of GPs with bit-identical (lambda, sigma_f):
+// Per chunk of C columns (points) and per group of GPs with bit-identical (lambda, sigma_f) (GpGroup, model_frame.h):
 //   k_pt_kstar   Ks[i][c] = k(X_i, z_c), c fastest, zero-padded to multiples of 64 both ways, and the partial sums of the means
 //                mpart[bi][slot][c] = sum_{i in row block bi} beta_{i, gp(slot)} Ks[i][c]
 //   k_pt_quad    workgroup (bc, bi, matrix): T = Kinv[64 bi ...][:] Ks[:][64 bc ...] by MFMA stages (tile_stage.h), contracted in the
@@ -9,23 +9,16 @@
 //   k_pt_finish  q = sum_bi part (ascending), m = sum_bi mpart (ascending) + the nominal term, s2 = sf^2 - q + process_var, the draw
 // Rules: no atomics; every output element is owned by one thread or one workgroup, which sums in a fixed order; launch geometry depends
 // on sizes only.
-#include <cfloat>
 #include <cmath>
-#include "gpmpc_internal.h"
+#include "model_frame.h"     // the model checks, GpGroup, the chunk rule, the pivots of init_cov
 #include "tile_stage.h"
 #include "philox.h"
 #include "particles_internal.h"
 
-#define PT_DEFAULT_CHUNK 4096
+static_assert(SP_T == GPMPC_MODEL_TILE, "the chunk rule of model_frame.h rounds to the tile of tile_stage.h");
 #define PT_KEY_XOR 0x50415254u      // "PART": keeps the particle streams apart from the MPPI streams of the same seed
 #define PT_MAX_NORMALS (GPMPC_MAX_D + GPMPC_MAX_DS)
 
-struct PtGroup {
-    double ilam[GPMPC_MAX_D];       // 1 / lambda_d
-    double sf2;
-    int ng;                         // GPs of the group
-    int gp[GPMPC_MAX_DS];           // their indices, ascending
-};
 struct PtTail {                     // what k_pt_finish needs of the model besides the group
     double nom_w[GPMPC_MAX_DS * GPMPC_MAX_D], nom_b[GPMPC_MAX_DS], process_var[GPMPC_MAX_DS];
     int has_nominal;
@@ -37,7 +30,7 @@ struct PtVec { double v[GPMPC_MAX_DS * GPMPC_MAX_DS]; };
 // ---------------------------------------------------------------------------
 // grid (cnp / 64, np / 64).  Thread (c = t & 63, q = t >> 6) owns column c0 + c and the rows i0 + 16 q ... + 15 (ascending).
 __global__ __launch_bounds__(256) void k_pt_kstar(int n, int cn, int D, int ds, const double* __restrict__ X, const double* __restrict__ Z,
-                                                   const double* __restrict__ beta, PtGroup G, double* __restrict__ Ks, int ldk,
+                                                   const double* __restrict__ beta, GpGroup G, double* __restrict__ Ks, int ldk,
                                                    double* __restrict__ mpart) {
     __shared__ double s_x[SP_T][GPMPC_MAX_D], s_b[SP_T][GPMPC_MAX_DS], s_p[4][GPMPC_MAX_DS][SP_T];
     const int t = threadIdx.x, c = t & 63, q = t >> 6;
@@ -72,7 +65,7 @@ __global__ __launch_bounds__(256) void k_pt_kstar(int n, int cn, int D, int ds, 
 }
 
 // grid (cnp / 64, np / 64, matrices).  Matrix z is GP G.gp[z]'s (gp_stride != 0) or the one matrix of all GPs.
-__global__ __launch_bounds__(256) void k_pt_quad(int n, int np, const double* __restrict__ Kinv, size_t ld, size_t gp_stride, PtGroup G,
+__global__ __launch_bounds__(256) void k_pt_quad(int n, int np, const double* __restrict__ Kinv, size_t ld, size_t gp_stride, GpGroup G,
                                                   const double* __restrict__ Ks, int ldk, double* __restrict__ part) {
     __shared__ double s_a[SP_KB][SP_T + 1], s_b[SP_KB][SP_T + 1];
     const int t = threadIdx.x, tx = t & 15, ty = t >> 4;
@@ -124,7 +117,7 @@ __global__ __launch_bounds__(256) void k_pt_quad(int n, int np, const double* __
 }
 
 // one thread per (column, GP of the group).  col0: index of the chunk's first column in the whole call (p = column % P addresses eps).
-__global__ __launch_bounds__(256) void k_pt_finish(int cn, int nbi, int D, int ds, int da, int shared_mat, PtGroup G, PtTail M,
+__global__ __launch_bounds__(256) void k_pt_finish(int cn, int nbi, int D, int ds, int da, int shared_mat, GpGroup G, PtTail M,
                                                     const double* __restrict__ Z, const double* __restrict__ mpart,
                                                     const double* __restrict__ part, int ldk, double* __restrict__ out_mean,
                                                     double* __restrict__ out_var, const double* __restrict__ eps, int P, long col0,
@@ -276,10 +269,6 @@ __global__ __launch_bounds__(MPPI_THREADS) void k_pt_joint(int B, int P, int T, 
 // ---------------------------------------------------------------------------
 // host: checks
 // ---------------------------------------------------------------------------
-static bool pt_finite(double v) { return v - v == 0.0; }
-static int pt_chunk(int chunk) { return chunk == 0 ? PT_DEFAULT_CHUNK : chunk; }
-static unsigned pt_blocks(long threads) { return (unsigned)((threads + 255) / 256); }
-
 struct PtNoise { double L[GPMPC_MAX_DS * GPMPC_MAX_DS], action_sd[GPMPC_MAX_D], process_var[GPMPC_MAX_DS]; };
 
 // The noise model of `m` (or the defaults): the lower Cholesky factor of init_cov, sqrt(action_var), process_var.
@@ -292,7 +281,7 @@ static int pt_noise(const char* who, const gpmpc_gp_model* m, PtNoise* out) {
     if (m->has_noise) {
         double big = 0.0;
         for (int k = 0; k < ds * ds; ++k) {
-            if (!pt_finite(m->init_cov[k])) return gpmpc_refuse(who, "init_cov holds a non-finite value");
+            if (!gpmpc_finite(m->init_cov[k])) return gpmpc_refuse(who, "init_cov holds a non-finite value");
             big = fmax(big, fabs(m->init_cov[k]));
         }
         for (int a = 0; a < ds; ++a)
@@ -301,84 +290,30 @@ static int pt_noise(const char* who, const gpmpc_gp_model* m, PtNoise* out) {
         for (int a = 0; a < ds; ++a)
             for (int b = 0; b < ds; ++b) Pm[a * ds + b] = 0.5 * (m->init_cov[a * ds + b] + m->init_cov[b * ds + a]);
         for (int j = 0; j < da; ++j) {
-            if (!pt_finite(m->action_var[j]) || m->action_var[j] < 0.0) return gpmpc_refuse(who, "action_var[%d] = %g is negative or not finite", j, m->action_var[j]);
+            if (!gpmpc_finite(m->action_var[j]) || m->action_var[j] < 0.0) return gpmpc_refuse(who, "action_var[%d] = %g is negative or not finite", j, m->action_var[j]);
             out->action_sd[j] = sqrt(m->action_var[j]);
         }
         for (int a = 0; a < ds; ++a) {
-            if (!pt_finite(m->process_var[a]) || m->process_var[a] < 0.0) return gpmpc_refuse(who, "process_var[%d] = %g is negative or not finite", a, m->process_var[a]);
+            if (!gpmpc_finite(m->process_var[a]) || m->process_var[a] < 0.0) return gpmpc_refuse(who, "process_var[%d] = %g is negative or not finite", a, m->process_var[a]);
             out->process_var[a] = m->process_var[a];
         }
     }
-    // lower Cholesky factor, column by column.  A pivot within rounding of zero (16 ulp of the diagonal entry it is left of) gives a zero
-    // column: zero variances are legal; one below -1e-12 max |P| is a refusal.
-    double big = 0.0;
+    double big = 0.0, d = 0.0;
     for (int k = 0; k < ds * ds; ++k) big = fmax(big, fabs(Pm[k]));
-    double* L = out->L;
-    for (int j = 0; j < ds; ++j) {
-        double d = Pm[j * ds + j];
-        for (int k = 0; k < j; ++k) d -= L[j * ds + k] * L[j * ds + k];
-        if (d < -1e-12 * big) return gpmpc_refuse(who, "init_cov has a negative pivot (%g at %d): it is not positive semi-definite", d, j);
-        if (d <= 16.0 * DBL_EPSILON * Pm[j * ds + j]) continue;      // (also d <= 0 with a zero diagonal entry)
-        const double r = sqrt(d);
-        L[j * ds + j] = r;
-        for (int i = j + 1; i < ds; ++i) {
-            double s = Pm[i * ds + j];
-            for (int k = 0; k < j; ++k) s -= L[i * ds + k] * L[j * ds + k];
-            L[i * ds + j] = s / r;
-        }
-    }
+    int j = 0;
+    if (!gpmpc_psd_pivots(Pm, ds, big, out->L, &d, &j))
+        return gpmpc_refuse(who, "init_cov has a negative pivot (%g at %d): it is not positive semi-definite", d, j);
     return GPMPC_OK;
 }
 
+// the core (model_frame.h), then the whole noise model
 static int pt_check_model(const char* who, const gpmpc_gp_model* m, PtNoise* noise) {
-    if (!m) return gpmpc_refuse(who, "NULL pointer (model)");
-    const int ds = m->state_dim, da = m->action_dim, D = ds + da;
-    if (ds < 1 || ds > GPMPC_MAX_DS) return gpmpc_refuse(who, "state_dim = %d outside 1...GPMPC_MAX_DS", ds);
-    if (da < 0 || D > GPMPC_MAX_D) return gpmpc_refuse(who, "action_dim = %d: D = state_dim + action_dim outside 1...GPMPC_MAX_D", da);
-    if (m->n < 1) return gpmpc_refuse(who, "n < 1");
-    if (m->ld < (size_t)m->n) return gpmpc_refuse(who, "ld < n");
-    if (!m->X || !m->beta || !m->Kinv) return gpmpc_refuse(who, "NULL pointer (model arrays)");
-    for (int a = 0; a < ds; ++a) {
-        if (!(m->sigma_f[a] > 0.0) || !pt_finite(m->sigma_f[a])) return gpmpc_refuse(who, "sigma_f[%d] = %g is not positive and finite", a, m->sigma_f[a]);
-        for (int d = 0; d < D; ++d)
-            if (!(m->lambdas[a * D + d] > 0.0) || !pt_finite(m->lambdas[a * D + d]))
-                return gpmpc_refuse(who, "lambdas[%d][%d] = %g is not positive and finite", a, d, m->lambdas[a * D + d]);
-    }
-    if (m->has_nominal)
-        for (int a = 0; a < ds; ++a) {
-            if (!pt_finite(m->nom_b[a])) return gpmpc_refuse(who, "the nominal model holds a non-finite value");
-            for (int d = 0; d < D; ++d)
-                if (!pt_finite(m->nom_w[a * D + d])) return gpmpc_refuse(who, "the nominal model holds a non-finite value");
-        }
+    if (int rc = gpmpc_model_check_core(who, m)) return rc;
     return pt_noise(who, m, noise);
 }
 
-static int pt_check_chunk(const char* who, int chunk) {
-    return (chunk < 0 || chunk % 64) ? gpmpc_refuse(who, "chunk must be 0 or a positive multiple of 64") : GPMPC_OK;
-}
 static int pt_check_count(const char* who, long cols, int width) {
     return cols * width > 0x7fffffffL ? gpmpc_refuse(who, "more than 2^31 - 1 elements in one array") : GPMPC_OK;
-}
-
-// groups of GPs with bit-identical (lambda, sigma_f), in order of their first GP
-static int pt_groups(const gpmpc_gp_model* m, PtGroup* g) {
-    const int ds = m->state_dim, D = ds + m->action_dim;
-    int ngroups = 0;
-    bool done[GPMPC_MAX_DS] = {};
-    for (int a = 0; a < ds; ++a) {
-        if (done[a]) continue;
-        PtGroup& G = g[ngroups++];
-        memset(&G, 0, sizeof(G));
-        for (int d = 0; d < D; ++d) G.ilam[d] = 1.0 / m->lambdas[a * D + d];
-        G.sf2 = m->sigma_f[a] * m->sigma_f[a];
-        for (int b = a; b < ds; ++b)
-            if (!done[b] && memcmp(&m->lambdas[a * D], &m->lambdas[b * D], sizeof(double) * D) == 0 &&
-                memcmp(&m->sigma_f[a], &m->sigma_f[b], sizeof(double)) == 0) {
-                done[b] = true;
-                G.gp[G.ng++] = b;
-            }
-    }
-    return ngroups;
 }
 
 // workspace of the posterior: Ks [np][C] | mpart [nbi][GPMPC_MAX_DS][C] | part [ds][nbi][C]
@@ -387,8 +322,7 @@ static PtLayout pt_layout(int n, int ds, int chunk, long ncols, gpmpc_carver& c)
     PtLayout L;
     L.nbi = (n + SP_T - 1) / SP_T;
     L.np = L.nbi * SP_T;
-    const long colsp = (ncols + SP_T - 1) / SP_T * SP_T;
-    L.C = (int)(colsp < pt_chunk(chunk) ? colsp : pt_chunk(chunk));      // no more columns than the call has
+    L.C = gpmpc_chunk_cols(ncols, chunk);
     const size_t d = sizeof(double);
     L.off_ks = c.take(d * L.np * L.C);
     L.off_mpart = c.take(d * L.nbi * GPMPC_MAX_DS * L.C);
@@ -401,8 +335,8 @@ static PtLayout pt_layout(int n, int ds, int chunk, long ncols, gpmpc_carver& c)
 static int pt_posterior(const gpmpc_gp_model* m, const PtNoise& noise, long nq, const double* z, double* out_mean, double* out_var,
                         const double* eps, int P, double* out_next, const PtLayout& L, char* ws, hipStream_t s) {
     const int ds = m->state_dim, da = m->action_dim, D = ds + da;
-    PtGroup groups[GPMPC_MAX_DS];
-    const int ngroups = pt_groups(m, groups);
+    GpGroup groups[GPMPC_MAX_DS];
+    const int ngroups = gpmpc_model_groups(m, groups);
     PtTail tail;
     memset(&tail, 0, sizeof(tail));
     tail.has_nominal = m->has_nominal;
@@ -416,11 +350,11 @@ static int pt_posterior(const gpmpc_gp_model* m, const PtNoise& noise, long nq, 
         const int cn = (int)(nq - c0 < L.C ? nq - c0 : L.C), cnp = (cn + SP_T - 1) / SP_T * SP_T;
         const double* zc = z + (size_t)c0 * D;
         for (int g = 0; g < ngroups; ++g) {
-            const PtGroup& G = groups[g];
+            const GpGroup& G = groups[g];
             hipLaunchKernelGGL(k_pt_kstar, dim3(cnp / SP_T, L.nbi), dim3(256), 0, s, m->n, cn, D, ds, m->X, zc, m->beta, G, Ks, L.C, mpart);
             hipLaunchKernelGGL(k_pt_quad, dim3(cnp / SP_T, L.nbi, shared_mat ? 1 : G.ng), dim3(256), 0, s, m->n, L.np, m->Kinv, m->ld,
                                m->gp_stride, G, (const double*)Ks, L.C, part);
-            hipLaunchKernelGGL(k_pt_finish, dim3(pt_blocks((long)cn * G.ng)), dim3(256), 0, s, cn, L.nbi, D, ds, da, shared_mat, G, tail, zc,
+            hipLaunchKernelGGL(k_pt_finish, dim3(gpmpc_blocks256((long)cn * G.ng)), dim3(256), 0, s, cn, L.nbi, D, ds, da, shared_mat, G, tail, zc,
                                (const double*)mpart, (const double*)part, L.C, out_mean ? out_mean + (size_t)c0 * ds : nullptr,
                                out_var ? out_var + (size_t)c0 * ds : nullptr, eps, P, c0, out_next ? out_next + (size_t)c0 * ds : nullptr);
         }
@@ -432,19 +366,14 @@ static int pt_posterior(const gpmpc_gp_model* m, const PtNoise& noise, long nq, 
 // ---------------------------------------------------------------------------
 // host: entries
 // ---------------------------------------------------------------------------
-static bool pt_model_sizes_ok(const gpmpc_gp_model* m) {
-    return m && m->state_dim >= 1 && m->state_dim <= GPMPC_MAX_DS && m->action_dim >= 0 && m->state_dim + m->action_dim <= GPMPC_MAX_D && m->n >= 1;
-}
-
 // for particle_cost.hip (particles_internal.h)
-bool gpmpc_pt_model_sizes_ok(const gpmpc_gp_model* m) { return pt_model_sizes_ok(m); }
 int gpmpc_pt_check_model(const char* who, const gpmpc_gp_model* m) {
     PtNoise noise;
     return pt_check_model(who, m, &noise);
 }
 
 extern "C" size_t gpmpc_gp_posterior_workspace_bytes(const gpmpc_gp_model* m, int nq, int chunk) {
-    if (!pt_model_sizes_ok(m) || nq < 1 || chunk < 0 || chunk % 64) return 0;
+    if (!gpmpc_model_sizes_ok(m) || nq < 1 || !gpmpc_chunk_ok(chunk)) return 0;
     gpmpc_carver c;
     return pt_layout(m->n, m->state_dim, chunk, nq, c).total;
 }
@@ -455,7 +384,7 @@ extern "C" int gpmpc_gp_posterior(const gpmpc_gp_model* m, int nq, const double*
     PtNoise noise;
     if (int rc = pt_check_model(who, m, &noise)) return rc;
     if (nq < 1) return gpmpc_refuse(who, "nq < 1");
-    if (int rc = pt_check_chunk(who, chunk)) return rc;
+    if (int rc = gpmpc_check_chunk(who, chunk)) return rc;
     if (int rc = pt_check_count(who, nq, GPMPC_MAX_D)) return rc;
     if (!z_dev || !out_mean || !out_var || !workspace) return gpmpc_refuse(who, "NULL pointer");
     gpmpc_carver c;
@@ -465,7 +394,7 @@ extern "C" int gpmpc_gp_posterior(const gpmpc_gp_model* m, int nq, const double*
 }
 
 static int pt_launch_noise(int P, int nn, int t, unsigned long long seed, unsigned call_index, double* out, hipStream_t s) {
-    hipLaunchKernelGGL(k_pt_noise, dim3(pt_blocks((long)P * ((nn + 1) / 2))), dim3(256), 0, s, P, nn, (unsigned)t, (unsigned)seed,
+    hipLaunchKernelGGL(k_pt_noise, dim3(gpmpc_blocks256((long)P * ((nn + 1) / 2))), dim3(256), 0, s, P, nn, (unsigned)t, (unsigned)seed,
                        (unsigned)(seed >> 32), call_index, out);
     GPMPC_HIP(hipGetLastError());
     return GPMPC_OK;
@@ -492,20 +421,18 @@ static PtStepLayout pt_step_layout(const gpmpc_gp_model* m, int B, int P, int ch
     return S;
 }
 
-static int pt_check_bp(const char* who, int B, int P) {
+int gpmpc_pt_check_bp(const char* who, int B, int P) {
     if (B < 1) return gpmpc_refuse(who, "B < 1");
     if (P < 1) return gpmpc_refuse(who, "P < 1");
     return pt_check_count(who, (long)B * P, GPMPC_MAX_D);
 }
-
-int gpmpc_pt_check_bp(const char* who, int B, int P) { return pt_check_bp(who, B, P); }
 
 int gpmpc_pt_initial(const gpmpc_gp_model* m, int B, int P, const double* x0, const double* eps, double* out, hipStream_t s) {
     PtNoise noise;
     if (int rc = pt_noise("gpmpc_pt_initial", m, &noise)) return rc;
     PtVec L;
     memcpy(L.v, noise.L, sizeof(L.v));
-    hipLaunchKernelGGL(k_pt_init, dim3(pt_blocks((long)B * P * m->state_dim)), dim3(256), 0, s, B, P, m->state_dim, x0, eps, L, out);
+    hipLaunchKernelGGL(k_pt_init, dim3(gpmpc_blocks256((long)B * P * m->state_dim)), dim3(256), 0, s, B, P, m->state_dim, x0, eps, L, out);
     GPMPC_HIP(hipGetLastError());
     return GPMPC_OK;
 }
@@ -517,12 +444,12 @@ static int pt_step(const gpmpc_gp_model* m, const PtNoise& noise, int B, int P, 
     PtVec sd;
     memset(&sd, 0, sizeof(sd));
     memcpy(sd.v, noise.action_sd, sizeof(double) * GPMPC_MAX_D);
-    hipLaunchKernelGGL(k_pt_assemble, dim3(pt_blocks((long)B * P * D)), dim3(256), 0, s, B, P, ds, da, x_prev, U_t, u_stride, eps, sd, z);
+    hipLaunchKernelGGL(k_pt_assemble, dim3(gpmpc_blocks256((long)B * P * D)), dim3(256), 0, s, B, P, ds, da, x_prev, U_t, u_stride, eps, sd, z);
     return pt_posterior(m, noise, (long)B * P, z, out_mean, out_var, eps, P, out_next, S.post, ws, s);
 }
 
 extern "C" size_t gpmpc_particle_step_workspace_bytes(const gpmpc_gp_model* m, int B, int P, int chunk) {
-    if (!pt_model_sizes_ok(m) || B < 1 || P < 1 || (long)B * P * GPMPC_MAX_D > 0x7fffffffL || chunk < 0 || chunk % 64) return 0;
+    if (!gpmpc_model_sizes_ok(m) || B < 1 || P < 1 || (long)B * P * GPMPC_MAX_D > 0x7fffffffL || !gpmpc_chunk_ok(chunk)) return 0;
     gpmpc_carver c;
     return pt_step_layout(m, B, P, chunk, c).total;
 }
@@ -533,8 +460,8 @@ extern "C" int gpmpc_particle_step(const gpmpc_gp_model* m, int B, int P, const 
     const char* who = "gpmpc_particle_step";
     PtNoise noise;
     if (int rc = pt_check_model(who, m, &noise)) return rc;
-    if (int rc = pt_check_bp(who, B, P)) return rc;
-    if (int rc = pt_check_chunk(who, chunk)) return rc;
+    if (int rc = gpmpc_pt_check_bp(who, B, P)) return rc;
+    if (int rc = gpmpc_check_chunk(who, chunk)) return rc;
     if (!x_prev || !eps || !out_next || !workspace || (m->action_dim > 0 && !U_t)) return gpmpc_refuse(who, "NULL pointer");
     if (u_stride < (size_t)m->action_dim && B > 1) return gpmpc_refuse(who, "u_stride < action_dim");
     gpmpc_carver c;
@@ -557,7 +484,7 @@ static int pt_stats(int B, int P, int T, int ds, const double* particles, const 
 
 static int pt_check_stats_args(const char* who, int B, int P, int T, const gpmpc_state_constraints* cons, const double* out_viol,
                                const double* out_joint) {
-    if (int rc = pt_check_bp(who, B, P)) return rc;
+    if (int rc = gpmpc_pt_check_bp(who, B, P)) return rc;
     if (T < 1 || T > 65535) return gpmpc_refuse(who, "T (steps) outside 1...65535");
     if (B > 65535) return gpmpc_refuse(who, "B > 65535");
     if ((long)B * P * GPMPC_MAX_DS * T > (1L << 40)) return gpmpc_refuse(who, "more than 2^40 particle values");
@@ -591,7 +518,7 @@ static PtRollLayout pt_roll_layout(const gpmpc_gp_model* m, int B, int P, int H,
 }
 
 extern "C" size_t gpmpc_particle_rollout_workspace_bytes(const gpmpc_gp_model* m, int B, int P, int H, int chunk) {
-    if (!pt_model_sizes_ok(m) || B < 1 || P < 1 || H < 1 || H > 65534 || (long)B * P * GPMPC_MAX_D > 0x7fffffffL || chunk < 0 || chunk % 64) return 0;
+    if (!gpmpc_model_sizes_ok(m) || B < 1 || P < 1 || H < 1 || H > 65534 || (long)B * P * GPMPC_MAX_D > 0x7fffffffL || !gpmpc_chunk_ok(chunk)) return 0;
     return pt_roll_layout(m, B, P, H, chunk).total;
 }
 
@@ -604,7 +531,7 @@ extern "C" int gpmpc_particle_rollout(const gpmpc_gp_model* m, int B, int P, int
     if (int rc = pt_check_model(who, m, &noise)) return rc;
     if (H < 1) return gpmpc_refuse(who, "H < 1");
     if (int rc = pt_check_stats_args(who, B, P, H + 1, cons, out_viol, out_joint)) return rc;
-    if (int rc = pt_check_chunk(who, chunk)) return rc;
+    if (int rc = gpmpc_check_chunk(who, chunk)) return rc;
     if (!x0 || !out_particles || !out_mean || !out_cov || !out_clamped || !workspace || (m->action_dim > 0 && !U))
         return gpmpc_refuse(who, "NULL pointer");
     const PtRollLayout R = pt_roll_layout(m, B, P, H, chunk);
@@ -618,7 +545,7 @@ extern "C" int gpmpc_particle_rollout(const gpmpc_gp_model* m, int B, int P, int
     if (int rc = pt_launch_noise(P, ds, 0, seed, call_index, eps, s)) return rc;
     PtVec L;
     memcpy(L.v, noise.L, sizeof(L.v));
-    hipLaunchKernelGGL(k_pt_init, dim3(pt_blocks((long)slab)), dim3(256), 0, s, B, P, ds, x0, (const double*)eps, L, out_particles);
+    hipLaunchKernelGGL(k_pt_init, dim3(gpmpc_blocks256((long)slab)), dim3(256), 0, s, B, P, ds, x0, (const double*)eps, L, out_particles);
     for (int t = 1; t <= H; ++t) {
         if (int rc = pt_launch_noise(P, da + ds, t, seed, call_index, eps, s)) return rc;
         if (int rc = pt_step(m, noise, B, P, out_particles + (size_t)(t - 1) * slab, U ? U + (size_t)(t - 1) * da : nullptr, (size_t)H * da, eps,

@@ -254,3 +254,6 @@ __device__ static void finish_step(const RollArgs& A, int b, int t, int own, dou
 // step_tail.hip: finish step H, the cost and (grad) the adjoint sweep of A.B trajectories on s; GPMPC_E_ARG when the horizon does not fit
 // the tail kernel's LDS budget
 int gpmpc_launch_roll_tail(const RollArgs& A, bool grad, hipStream_t s);
+// The 48 KB budget of its dynamic LDS: the per-step terms of the horizon plus the step Jacobians of all H steps (grad) or of one (no grad, and
+// what the launcher falls back to with grad).  A horizon that fails with grad = false cannot be costed at all.
+bool gpmpc_roll_tail_fits(int H, int ds, int da, bool grad);

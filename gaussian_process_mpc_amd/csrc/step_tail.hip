@@ -236,14 +236,19 @@ __global__ __launch_bounds__(256) void k_roll_tail(RollArgs A) {
     for (int q = tid; q < H * da; q += blockDim.x) A.out_grad[(size_t)b * H * da + q] = s_gU[q];
 }
 
+// the dynamic LDS of k_roll_tail with `njac` step Jacobians resident
+static size_t roll_tail_lds(int H, int ds, int da, int njac) {
+    const size_t nzc = (size_t)2 * ds * (2 * ds + da);
+    const size_t lds0 = sizeof(double) * ((size_t)(H + 1) * (1 + 2 * ds) + (size_t)H * da + (size_t)H);
+    return lds0 + sizeof(double) * nzc * njac;
+}
+bool gpmpc_roll_tail_fits(int H, int ds, int da, bool grad) { return roll_tail_lds(H, ds, da, grad ? H : 1) <= 48 * 1024; }
+
 int gpmpc_launch_roll_tail(const RollArgs& A, bool grad, hipStream_t s) {
     const int B = A.B, H = A.H;
-    const size_t nzc = (size_t)2 * A.ds * (2 * A.ds + A.da);
-    const size_t lds0 = sizeof(double) * ((size_t)(H + 1) * (1 + 2 * A.ds) + (size_t)H * A.da + (size_t)H);
-    const size_t lds_all = lds0 + sizeof(double) * nzc * (grad ? H : 1), lds_one = lds0 + sizeof(double) * nzc;
-    const bool allj = lds_all <= 48 * 1024;
-    if (!allj && lds_one > 48 * 1024) return GPMPC_E_ARG;   // horizon too long for the tail kernel's LDS budget
-    const size_t lds = allj ? lds_all : lds_one;
+    const bool allj = gpmpc_roll_tail_fits(H, A.ds, A.da, grad);
+    if (!allj && !gpmpc_roll_tail_fits(H, A.ds, A.da, false)) return GPMPC_E_ARG;   // horizon too long for the tail kernel's LDS budget
+    const size_t lds = roll_tail_lds(H, A.ds, A.da, allj && grad ? H : 1);
     const int rc = gpmpc_dispatch_dim<1>(A.ds, [&](auto d) {
         constexpr int DS = decltype(d)::value;
         if (A.sched) {                                       // the schedule variants (the pack's ds is the schedule's: resolved by the enqueue)

@@ -26,6 +26,7 @@ import torch
 
 from . import _lib
 from ._lib import check, lib, ptr, stream_ptr
+from ._solver import model_problem, mppi_result, mppi_result_block
 from .mppi import mppi_params
 from .particles import GPModel, _dev, _empty, _model, _vp, _workspace
 from .rollout import StateConstraints
@@ -239,39 +240,26 @@ def mppi_solve_linearised(model, x0, U0, cost, constraints=None, samples=64, ite
         return _mppi_host_loop_full(model, x0, U0, cost, constraints, samples, iterations, sigma, decay, beta, seed, call_index, lb, ub, form,
                                     feedback)
     dev = model.device
-    U0 = _dev(U0, dev)
-    if U0.dim() != 2 or U0.shape[-1] != model.da:
-        raise ValueError("U0 must have shape (H, da)")
-    x0 = _dev(x0, dev).reshape(-1)
-    if x0.shape[0] != model.ds or cost.ds != model.ds or cost.da != model.da:
-        raise ValueError("shape mismatch between model, x0, U0 and cost parameters")
+    x0, U0 = model_problem(model, x0, U0, cost)
     H, da = U0.shape
     if constraints is not None and constraints.ds != model.ds:
         raise ValueError("the constraint rows have %d state coefficients, the model has %d states" % (constraints.ds, model.ds))
     P = mppi_params(samples, da, sigma, lb, ub, iterations=iterations, decay=decay, beta=beta, seed=seed, call_index=call_index)
     cons = None if constraints is None else ctypes.byref(constraints.c)
     n = H * da
-    res = torch.empty(n + 2 + 6 * max(P.iterations, 1), dtype=torch.float64, device=dev)      # [best plan | key | trace]: one block, one copy
+    res = mppi_result_block(n, P.iterations, dev)
     with torch.cuda.device(dev), linearised_form(form):
         nb = lib().gpmpc_mppi_solve_linearised_workspace_bytes(ctypes.byref(model.c), H, ctypes.byref(P), cons)
         ws = _workspace(dev, nb)
         check(lib().gpmpc_mppi_solve_linearised(ctypes.byref(model.c), H, ptr(x0), ptr(U0), ctypes.byref(cost.c), cons, ctypes.byref(P),
                                                 ptr(res[:n]), ptr(res[n:n + 2]), ptr(res[n + 2:]), _vp(ws), ws.numel(), stream_ptr(dev)),
               "gpmpc_mppi_solve_linearised")
-    host = res.cpu().numpy()
-    return {"U": host[:n].reshape(H, da).copy(), "violation": float(host[n]), "cost": float(host[n + 1]), "feasible": bool(host[n] == 0.0),
-            "trace": host[n + 2:].reshape(-1, 6).copy()}
+    return mppi_result(res.cpu().numpy(), H, da)
 
 
 def _mppi_host_loop_full(model, x0, U0, cost, constraints, samples, iterations, sigma, decay, beta, seed, call_index, lb, ub, form, feedback):
     from .mppi import mppi_sample, mppi_start, mppi_update
-    dev = model.device
-    U0 = _dev(U0, dev)
-    if U0.dim() != 2 or U0.shape[-1] != model.da:
-        raise ValueError("U0 must have shape (H, da)")
-    x0 = _dev(x0, dev).reshape(-1)
-    if x0.shape[0] != model.ds or cost.ds != model.ds or cost.da != model.da:
-        raise ValueError("shape mismatch between model, x0, U0 and cost parameters")
+    x0, U0 = model_problem(model, x0, U0, cost)
     if iterations < 1:
         raise ValueError("iterations must be at least 1")
     H, da = U0.shape
@@ -285,10 +273,7 @@ def _mppi_host_loop_full(model, x0, U0, cost, constraints, samples, iterations, 
         u = mppi_update(U, r["cost"], best, beta, g=r.get("g"), mean=mean)
         mean, best = u["mean"], u["best"]
         trace.append(u["trace"])
-    host = torch.cat([best] + trace).cpu().numpy()
-    n = H * da
-    return {"U": host[2:2 + n].reshape(H, da).copy(), "violation": float(host[0]), "cost": float(host[1]), "feasible": bool(host[0] == 0.0),
-            "trace": host[2 + n:].reshape(-1, 6).copy()}
+    return mppi_result(torch.cat([best] + trace).cpu().numpy(), H, da, key_first=True)
 
 
 def lqr_gain(model, x_eq, u_eq, Q, R, iterations=500):

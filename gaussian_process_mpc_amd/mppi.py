@@ -12,7 +12,7 @@ import torch
 
 from . import _lib
 from ._lib import MppiParamsC, check, lib, ptr, require_gpu, stream_ptr
-from ._solver import per_input, solver_problem
+from ._solver import mppi_result, mppi_result_block, per_input, solver_problem
 from .rollout import _dev, _fullcov_pack
 
 DEFAULTS = {"samples": 64, "iterations": 30, "sigma": None, "decay": 0.9, "beta": 0.1, "seed": 0}
@@ -112,13 +112,10 @@ def mppi_solve(pack, x0, U0, cost, constraints=None, samples=64, iterations=30, 
     P = mppi_params(samples, da, sigma, lb, ub, iterations=iterations, decay=decay, beta=beta, seed=seed, call_index=call_index)
     cons = None if constraints is None else ctypes.byref(constraints.c)
     n = H * da
-    # [best plan | key | trace]: one block, one copy
-    res = torch.empty(n + 2 + 6 * max(P.iterations, 1), dtype=torch.float64, device=dev)
+    res = mppi_result_block(n, P.iterations, dev)
     nbytes = size(pack.handle, H, ctypes.byref(P), cons)
     ws = pack.workspace(max(int(nbytes), 256))
     with torch.cuda.device(dev):
         check(solve(pack.handle, H, ptr(x0), ptr(U0), ctypes.byref(cost.c), cons, ctypes.byref(P), ptr(res[:n]),
                     ptr(res[n:n + 2]), ptr(res[n + 2:]), ctypes.c_void_p(ws.data_ptr()), ws.numel(), stream_ptr()), what)
-    host = res.cpu().numpy()
-    return {"U": host[:n].reshape(H, da).copy(), "violation": float(host[n]), "cost": float(host[n + 1]), "feasible": bool(host[n] == 0.0),
-            "trace": host[n + 2:].reshape(-1, 6).copy()}
+    return mppi_result(res.cpu().numpy(), H, da)

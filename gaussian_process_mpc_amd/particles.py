@@ -330,27 +330,21 @@ def mppi_solve_particles(model_or_dynamics, x0, U0, cost, constraints=None, part
     ``gpmpc_particle_evaluate`` over the K samples with ``particles`` particles each, the update kernel; the whole search one enqueue,
     one device-to-host copy at the end.  The particle noise is that of (seed, call_index) and THE SAME in every iteration (common random
     numbers: the search minimises one fixed sample-average objective).  Returns what ``mppi_solve`` returns."""
+    from ._solver import model_problem, mppi_result, mppi_result_block
     from .mppi import mppi_params
     model = _model(model_or_dynamics)
     dev = model.device
-    U0 = _dev(U0, dev)
-    if U0.dim() != 2 or U0.shape[-1] != model.da:
-        raise ValueError("U0 must have shape (H, da)")
-    x0 = _dev(x0, dev).reshape(-1)
-    if x0.shape[0] != model.ds or cost.ds != model.ds or cost.da != model.da:
-        raise ValueError("shape mismatch between model, x0, U0 and cost parameters")
+    x0, U0 = model_problem(model, x0, U0, cost)
     H, da = U0.shape
     _check_rows(constraints, model.ds)
     Pm = mppi_params(samples, da, sigma, lb, ub, iterations=iterations, decay=decay, beta=beta, seed=seed, call_index=call_index)
     cons = None if constraints is None else ctypes.byref(constraints.c)
     n = H * da
-    res = torch.empty(n + 2 + 6 * max(Pm.iterations, 1), dtype=torch.float64, device=dev)     # [best plan | key | trace]: one block, one copy
+    res = mppi_result_block(n, Pm.iterations, dev)
     with torch.cuda.device(dev):
         nb = lib().gpmpc_mppi_solve_particles_workspace_bytes(ctypes.byref(model.c), H, int(particles), ctypes.byref(Pm), cons)
         ws = _workspace(dev, nb)
         check(lib().gpmpc_mppi_solve_particles(ctypes.byref(model.c), H, int(particles), ptr(x0), ptr(U0.contiguous()), ctypes.byref(cost.c), cons,
                                                ctypes.byref(Pm), ptr(res[:n]), ptr(res[n:n + 2]), ptr(res[n + 2:]), _vp(ws), ws.numel(),
                                                stream_ptr(dev)), "gpmpc_mppi_solve_particles")
-    host = res.cpu().numpy()
-    return {"U": host[:n].reshape(H, da).copy(), "violation": float(host[n]), "cost": float(host[n + 1]), "feasible": bool(host[n] == 0.0),
-            "trace": host[n + 2:].reshape(-1, 6).copy()}
+    return mppi_result(res.cpu().numpy(), H, da)

@@ -151,6 +151,60 @@ int main() {
     EXPECT_NEG(gpmpc_kinv_append(4, nullptr, dummy, 1.0, dummy, dummy, 64, nullptr));
     EXPECT_NEG(gpmpc_ml_grad(0, 3, dummy, dummy, dummy, dummy, dummy, 1.0, 0.0, dummy, dummy, 64, nullptr));
     EXPECT_NEG(gpmpc_ml_grad(4, 3, nullptr, dummy, dummy, dummy, dummy, 1.0, 0.0, dummy, dummy, 64, nullptr));
+    {   // the three MPPI solves share one search and their parameter checks (csrc/mppi_internal.h): calls with TWO faults walk the refusal
+        // paths, and the earlier check's text must be the one reported.  Nothing is dereferenced: every call is refused on the host.
+        gpmpc_gp_model gm;
+        memset(&gm, 0, sizeof(gm));
+        gm.n = 4; gm.state_dim = 2; gm.action_dim = 1; gm.ld = 4;
+        gm.X = gm.beta = gm.Kinv = dummy;
+        for (int k = 0; k < GPMPC_MAX_DS * GPMPC_MAX_D; ++k) gm.lambdas[k] = 1.0;
+        for (int k = 0; k < GPMPC_MAX_DS; ++k) gm.sigma_f[k] = 1.0;
+        gpmpc_mppi_params mp;
+        memset(&mp, 0, sizeof(mp));
+        mp.n_samples = 8; mp.iterations = 2; mp.sigma_decay = 0.9; mp.beta = 0.1;
+        mp.sigma[0] = 0.5; mp.lb[0] = -1.0; mp.ub[0] = 1.0;
+        gpmpc_state_constraints sc;
+        memset(&sc, 0, sizeof(sc));
+        sc.n_rows = 1;
+        const gpmpc_pack* fake = (const gpmpc_pack*)dummy;     // (never looked at: the scalar checks come first)
+        auto text = [&](const char* want) {
+            if (strcmp(gpmpc_last_error(), want)) { printf("FAIL refusal text: \"%s\" (expected \"%s\")\n", gpmpc_last_error(), want); ++failures; }
+        };
+        gpmpc_mppi_params bad = mp;
+        gpmpc_state_constraints rows0 = sc;
+        rows0.n_rows = 0;
+        bad.sigma_decay = 0.0;                                  // sigma_decay + constraint rows: the scalar first, in all three
+        EXPECT_NEG(gpmpc_mppi_solve(fake, 3, dummy, dummy, &cp, &rows0, &bad, dummy, dummy, dummy, dummy, 64, nullptr));
+        text("gpmpc_mppi_solve: sigma_decay = 0 is not positive");
+        EXPECT_NEG(gpmpc_mppi_solve_linearised(&gm, 3, dummy, dummy, &cp, &rows0, &bad, dummy, dummy, dummy, dummy, 64, nullptr));
+        text("gpmpc_mppi_solve_linearised: sigma_decay = 0 is not positive");
+        EXPECT_NEG(gpmpc_mppi_solve_particles(&gm, 3, 16, dummy, dummy, &cp, &rows0, &bad, dummy, dummy, dummy, dummy, 64, nullptr));
+        text("gpmpc_mppi_solve_particles: sigma_decay = 0 is not positive");
+        gpmpc_gp_model lam = gm;
+        lam.lambdas[1] = 0.0;                                   // constraint rows + lambdas: the rows first in the linearised solve, the model in the particle one
+        EXPECT_NEG(gpmpc_mppi_solve_linearised(&lam, 3, dummy, dummy, &cp, &rows0, &mp, dummy, dummy, dummy, dummy, 64, nullptr));
+        text("gpmpc_mppi_solve_linearised: n_rows = 0 outside 1..16");
+        EXPECT_NEG(gpmpc_mppi_solve_particles(&lam, 3, 16, dummy, dummy, &cp, &rows0, &mp, dummy, dummy, dummy, dummy, 64, nullptr));
+        text("gpmpc_mppi_solve_particles: lambdas[0][1] = 0 is not positive and finite");
+        bad = mp;
+        bad.sigma[0] = 0.0;                                     // sigma + a horizon too long for the cost kernel / too many particles
+        EXPECT_NEG(gpmpc_mppi_solve_linearised(&gm, 2000, dummy, dummy, &cp, &sc, &bad, dummy, dummy, dummy, dummy, 64, nullptr));
+        text("gpmpc_mppi_solve_linearised: sigma[0] = 0 is not positive");
+        EXPECT_NEG(gpmpc_mppi_solve_particles(&gm, 3, GPMPC_PARTICLE_COST_MAX_P + 1, dummy, dummy, &cp, &sc, &bad, dummy, dummy, dummy, dummy, 64, nullptr));
+        text("gpmpc_mppi_solve_particles: sigma[0] = 0 is not positive");
+        gpmpc_cost_params sched = cp;
+        sched.schedule_id = 12345;                              // the horizon + an unknown cost schedule
+        EXPECT_NEG(gpmpc_mppi_solve_linearised(&gm, 2000, dummy, dummy, &sched, &sc, &mp, dummy, dummy, dummy, dummy, 64, nullptr));
+        text("gpmpc_mppi_solve_linearised: H = 2000 is too long for the cost kernel");
+        EXPECT_NEG(gpmpc_mppi_solve_particles(&gm, 3, 16, dummy, dummy, &sched, &rows0, &mp, dummy, dummy, dummy, dummy, 64, nullptr));
+        text("gpmpc_mppi_solve_particles: n_rows = 0 outside 1..16");
+        // fault-free up to the workspace: the whole entry preamble and the layouts run
+        EXPECT_NEG(gpmpc_mppi_solve_linearised(&gm, 3, dummy, dummy, &cp, &sc, &mp, dummy, dummy, dummy, dummy, 64, nullptr));
+        EXPECT_NEG(gpmpc_mppi_solve_particles(&gm, 3, 16, dummy, dummy, &cp, &sc, &mp, dummy, dummy, dummy, dummy, 64, nullptr));
+        EXPECT_NEG(gpmpc_mppi_solve_linearised(nullptr, 3, dummy, dummy, &cp, &sc, &mp, dummy, dummy, dummy, dummy, 64, nullptr));
+        EXPECT_NEG(gpmpc_mppi_solve_particles(nullptr, 3, 16, dummy, dummy, &cp, &sc, &mp, dummy, dummy, dummy, dummy, 64, nullptr));
+        EXPECT_NEG(gpmpc_mppi_solve(nullptr, 3, dummy, dummy, &cp, &sc, &mp, dummy, dummy, dummy, dummy, 64, nullptr));
+    }
     // a pack cannot be created without a device: the failing HIP call must surface as a code, with its text recorded
     int rc = gpmpc_pack_create(&pk, 32, 2, 1);
     if (rc == GPMPC_OK) {                       // (a GPU is present after all: exercise the "not built" state and clean up)

@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """Compare two device-assembly listings kernel by kernel: python tools/isa_diff.py <old.s> <new.s> [--quiet]
 
-The listings come from the Makefile's CXXFLAGS plus `--cuda-device-only -S`.  Comment lines, `.ident`, `.file` and lines that
-carry the per-compile `__hip_cuid_` symbol are dropped; what is left is cut at the global labels (one piece per kernel symbol,
+The listings come from the Makefile's CXXFLAGS plus `--cuda-device-only -S`.  Comment lines, the comment behind a label, `.ident`,
+`.file` and lines that carry the per-compile `__hip_cuid_` symbol are dropped; what is left is cut at the global labels (one piece per kernel symbol,
 with its descriptor and metadata lines) and each piece gets one of three results:
   identical         every line equal
   commutative only  same number of lines, and every differing line is a v_add_f64 / v_mul_f64 / v_fma_f64 with the same
@@ -29,6 +29,7 @@ def kernels(path):
         if m:
             cur = m.group(1)
             out.setdefault(cur, [])
+            s = s.split(";")[0].rstrip()       # (the "; @symbol" behind a label is padded to a column: a renamed symbol moves it)
         out[cur].append(s)
     return out
 

@@ -130,9 +130,71 @@ def form_table(a, lines, save):
         torch.cuda.empty_cache()
 
 
+def bits_table(a):
+    """--bits: a SHA-256 of every output of the entries that take a model (and of the pack MPPI solves) at small ragged shapes, one line
+    each.  Run once per library (GPMPC_LIB_PATH) and compare the two files: a host refactor must leave every line as it was.
+    N = 70 (one full and one ragged 64-row block, 128 padded rows, eight k-stages), ds = 2, da = 1, B = 65 columns (one full and one ragged
+    tile), H = 3; per-GP and shared Kinv, the two GPs in one (lambda, sigma_f) group and in two."""
+    import hashlib
+    n, ds, da, B, H, K = 70, 2, 1, 65, 3, 8
+    rng = np.random.default_rng(7)
+    x0 = torch.as_tensor(rng.uniform(-1, 1, (B, ds)), device="cuda")
+    U = torch.as_tensor(rng.uniform(-1, 1, (B, H, da)), device="cuda")
+    Z = torch.as_tensor(rng.uniform(-1, 1, (B, ds + da)), device="cuda")
+    cost = G.CostParams(-1.0, np.eye(ds), 0.1 * np.eye(da))
+    rows = G.StateConstraints(np.array([[1.0, 0.0], [0.0, -1.0]]), np.array([0.8, 0.9]), 1.0)
+    lines = []
+
+    def put(name, t):
+        t = t if isinstance(t, np.ndarray) else t.detach().cpu().contiguous().numpy()
+        lines.append("%-64s %s %s" % (name, "x".join(map(str, t.shape)), hashlib.sha256(np.ascontiguousarray(t).tobytes()).hexdigest()))
+
+    for shared in (False, True):
+        for one_group in (False, True):
+            gm, pack = models(n, ds, da, one_group)
+            if shared != one_group:                      # the other pairing of matrices and groups: the model's arrays, regrouped
+                Kinv = gm.Kinv[0].contiguous() if shared else torch.stack([gm.Kinv, gm.Kinv])
+                gm = G.GPModel(gm.X, gm.beta, Kinv, gm.lambdas, gm.sigma_f, ds, da)
+            tag = "%s Kinv, %d group%s: " % ("shared" if shared else "per-GP", 1 if one_group else 2, "" if one_group else "s")
+            for k, t in zip(("mean", "var"), G.gp_posterior(gm, Z)):
+                put(tag + "gp_posterior " + k, t)
+            r = G.particle_rollout(gm, x0, U, particles=8, seed=3, constraints=rows)
+            for k in ("particles", "mean", "cov", "clamped", "violation", "joint_violation"):
+                put(tag + "particle_rollout P=8 " + k, r[k])
+            for form in ("tile", "stream"):
+                r = G.linearised_rollout(gm, x0, U, cost, want_grad=True, want_jac=True, constraints=rows, form=form)
+                for k in ("cost", "grad", "means", "vars", "jac", "g", "g_jac"):
+                    put(tag + "linearised_rollout %s %s" % (form, k), r[k])
+            r = G.linearised_rollout(gm, x0, U, cost, want_grad=True, want_jac=True, constraints=rows, full_covariance=True)
+            for k in ("cost", "grad", "means", "covs", "jac", "g", "g_jac"):
+                put(tag + "linearised_fc_rollout " + k, r[k])
+            kw = dict(samples=K, iterations=3, sigma=0.5, lb=-2.0, ub=2.0, seed=5)
+            for cons in (None, rows):
+                solves = [("mppi_solve_linearised", lambda: G.mppi_solve_linearised(gm, x0[0], U[0], cost, constraints=cons, **kw)),
+                          ("mppi_solve_particles P=8", lambda: G.mppi_solve_particles(gm, x0[0], U[0], cost, constraints=cons, particles=8, **kw))]
+                if shared == one_group:                  # (the pack solves do not see the regrouped model: once per pack)
+                    solves += [("mppi_solve", lambda: G.mppi_solve(pack, x0[0], U[0], cost, constraints=cons, **kw)),
+                               ("mppi_solve_fullcov", lambda: G.mppi_solve(pack, x0[0], U[0], cost, constraints=cons, full_covariance=True, **kw))]
+                for name, solve in solves:
+                    s = solve()
+                    for k in ("U", "trace"):
+                        put(tag + "%s rows=%d %s" % (name, 0 if cons is None else 2, k), s[k])
+                    put(tag + "%s rows=%d key" % (name, 0 if cons is None else 2), np.array([s["violation"], s["cost"]]))
+            del gm, pack
+    torch.cuda.synchronize()
+    out = "\n".join(lines) + "\n"
+    if a.bits != "-":
+        os.makedirs(os.path.dirname(a.bits) or ".", exist_ok=True)
+        with open(a.bits, "w") as f:
+            f.write(out)
+    print(out, end="")
+    print("# %d outputs hashed" % len(lines))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
+    ap.add_argument("--bits", default=None, metavar="FILE", help="write a SHA-256 of every model-entry output at small ragged shapes and stop")
     ap.add_argument("--quick", action="store_true")
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--blocks", type=int, default=5)
@@ -140,6 +202,8 @@ def main():
                     help="measure the forms of the linearised step on the grid B = 1 ... 256 (all: TILE | STREAM | moment matching)")
     a = ap.parse_args()
     G.require_gpu()
+    if a.bits:
+        return bits_table(a)
     lines = ["# tools/linprop_ab.py on %s: ms per call, median block (min ... max) of %d blocks of %d calls after a warm-up; H = 20, da = 1"
              % (torch.cuda.get_device_name(0), a.blocks, a.reps)]
     H, ds, da = 20, 4, 1
