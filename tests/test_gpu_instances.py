@@ -18,6 +18,8 @@ means 1e-5, variances / covariances 1e-4 (BASELINE north star), cost 1e-6, gradi
 Reference: src/dynamics.py:126-191, src/tools/uncertainty_prop.py:296-465, src/mpc.py:156-255.
 Every problem here has sigma_f = 1 for all GPs, zero references and a diagonal Q (synth_problem): tests/test_gpu_offgrid.py runs the same forms
 with per-GP amplitudes in [0.6, 1.8], non-zero x_ref / u_ref and a coupled Q.
+action_dim >= 3 (no scalar-broadcast, fused or whole-horizon kernel; the full covariance in its four-launch form only) is held to the same
+references by tests/test_gpu_offgrid.py::test_wide_action_* and to the rounding-error budget by tests/test_gpu_accuracy.py::test_wide_action_*.
 """
 import numpy as np
 import pytest
@@ -182,10 +184,8 @@ def test_fullcov_rollout_every_shape_vs_cport(G, ds, da, monkeypatch):
     rng = np.random.default_rng(ds * 10 + da)
     # (B, overrides): the default plan at a small and a large batch (two launches per step on 256x64 tiles | four on 256x256 tiles +
     # pair_kernel_sbf.h), the two-launch form forced on each of its tilings, and the four-launch form forced at the small batch
-    cases = [(3, None), (b_big, None)]
-    if da <= 2:
-        cases += [(3, {"GPMPC_FC_FORM": "1", "GPMPC_FC_TILING": "4"}), (2, {"GPMPC_FC_FORM": "1", "GPMPC_FC_TILING": "0"}),
-                  (1, {"GPMPC_FC_FORM": "1", "GPMPC_FC_TILING": "2"}), (3, {"GPMPC_FC_FORM": "0"}), (b_big, {"GPMPC_FC_FORM": "0"})]
+    cases = [(3, None), (b_big, None), (3, {"GPMPC_FC_FORM": "1", "GPMPC_FC_TILING": "4"}), (2, {"GPMPC_FC_FORM": "1", "GPMPC_FC_TILING": "0"}),
+             (1, {"GPMPC_FC_FORM": "1", "GPMPC_FC_TILING": "2"}), (3, {"GPMPC_FC_FORM": "0"}), (b_big, {"GPMPC_FC_FORM": "0"})]
     ref3 = None
     for B, env in cases:
         for k, v in (env or {}).items():

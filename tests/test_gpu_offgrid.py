@@ -18,6 +18,9 @@ Observed on an MI355X, worst deviation per form as a fraction of its tolerance (
     persist 9e-6 | 6e-4 | 3e-4 | 1e-6        one lambda (pair_sbs, fused_sb_shared, persist over units) 4e-3 | 4e-3 | 4e-4 | 4e-6
     full covariance two- / four-launch 3e-5 | 1.4e-2 | 3e-4 | 1e-5        cross-unit kernel 1e-5 | 9e-5 | 4e-6 | 1e-6        nominal 2e-4 | 3e-3 | 2e-4 | 1e-5
     constraints 8e-4, dense Jacobian 4e-5        moment_match 1e-5 | 3e-5        class path 4e-4 | 1e-3 | 1e-4 | 2e-6
+    action_dim >= 3 (section 8): staged 64x64 2e-5 | 2.2e-3 | 7e-4 | 6e-6        256x256 3e-5 | 7e-4 | 2e-4 | 4e-6        64x128 behind row chunks 5e-6 | 3e-4 | 2e-5 | 2e-6
+    its full covariance (four-launch) 4e-6 | 2e-4 | 4e-5 | 1e-6        nominal 1e-6 | 2e-4 | 1e-4 | 1e-6        noise model 2e-5 | 2e-5 | 5e-5 | 1e-6
+    constraints 1e-4, dense Jacobian rows 3e-9 relative        autograd path against the fused adjoint: equal        inert overrides: bit-equal
 No form deviates by more than 1.4 % of a tolerance: no kernel was found wrong.
 (What these fractions mean in units of rounding error, form by form: tests/test_gpu_accuracy.py.  The step tables live in tests/offgrid_problems.py.)
 """
@@ -284,8 +287,8 @@ def test_fullcov_rollout_vs_cport(G, case):
     pack, cost = _pack(G, pb, kinv), _cost(G, pb)
     pack.enable_fullcov()
     cases = OG.fullcov_steps(ds, shared)                     # (B, overrides, form)
-    if shared:
-        assert pack.shared_lambda
+    if shared:                                               # (a pack with da >= 3 has no kernel that shares the exponent and does not report one lambda)
+        assert np.all(pb["lambdas"] == pb["lambdas"][0]) and pack.shared_lambda == (da <= 2)
     res = {}
     for B, env, form in cases:
         what = "fullcov ds=%d da=%d N=%d B=%d %s" % (ds, da, N, B, env or "default")
@@ -293,7 +296,7 @@ def test_fullcov_rollout_vs_cport(G, case):
         ref = _ref_fullcov(args, pick)
         with _tuning(pack, env):
             plan = pack.plan_fullcov(B, H)
-            what += OG.assert_fullcov_plan(plan, (B, env, form), ds)
+            what += OG.assert_fullcov_plan(plan, (B, env, form), ds, da)
             r = G.rollout_fullcov(pack, pb["x0"][:B], pb["U"][:B], cost)
             f = G.rollout_fullcov(pack, pb["x0"][:B], pb["U"][:B], cost, want_grad=False)
         _check_fullcov(r, ref, pick, what)
@@ -581,3 +584,182 @@ def test_mpc_callbacks_with_distinct_sigma_f_references_and_input_rate_cost(G):
     r = _np(mpc.evaluate_batch(torch.as_tensor(pb["U"][:B], device=mpc.device), curr_state=torch.as_tensor(pb["x0"][:B], device=mpc.device)))
     ref = {k: np.stack([np.asarray(o[k]) for o in refs]) for k in ("means", "vars", "cost", "grad")}
     _check_diag(r, ref, list(range(B)), "class path evaluate_batch")
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# 8. action_dim >= 3: the default plan of every plant with three or more inputs (csrc/plan.hip: head kernel + staged pair_kernel.h + tail
+#    kernel at every batch; fullcov.hip: the four-launch form at every batch)
+# ------------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("ds,da,N", OG.WIDEACT_CASES, ids=["ds%d-da%d-N%d" % c for c in OG.WIDEACT_CASES])
+def test_wide_action_ladder_vs_cport(G, ds, da, N):
+    """Every D from 4 to 8 at da >= 3 (N = 150: Np = 192), each plan asserted from ``pack.plan``: the staged fp64 kernel on 64x64 tiles with one,
+    two (odd batch, eager and as a captured graph) and four (4 + 1) trajectories per workgroup, on the 256x256 list from ceil(B / 2) ds >= 1024 with
+    two (odd batch) and one; the tail sweep over da >= 3 columns per step Jacobian.  The long case (N = 1415: Np = 1472) runs the 64x128 list
+    behind a head kernel in row chunks.  Objective + gradient and objective only, against cport.rollout."""
+    D = ds + da
+    args, steps, expected = OG.wideact_case(ds, da, N)
+    pb, kinv = OG.problem(*args)
+    H = pb["H"]
+    pack, cost = _pack(G, pb, kinv), _cost(G, pb)
+    reached = set()
+    for step in steps:
+        B, env, form, tiling, tb, mode = step
+        graph = mode == "graph"
+        with _tuning(pack, env):
+            plan = pack.plan(B, H, graph=graph)
+            OG.assert_wideact_plan(plan, step, D)
+            OG.assert_wideact_plan(pack.plan(B, H, want_grad=False, graph=graph), step, D)
+            _run_diag(G, pack, pb, cost, B, args, -1.0, "wideact ds=%d da=%d N=%d B=%d %s %s tb=%d %s" % (ds, da, N, B, form, tiling, tb, mode), graph=graph)
+        reached.add(step[2:])
+    print(sorted(reached))
+    assert reached == expected, reached ^ expected
+    del pack
+    torch.cuda.empty_cache()
+
+
+@pytest.mark.parametrize("ds,da", OG.WIDEACT_INERT_DIMS)
+def test_wide_action_overrides_are_inert(G, ds, da):
+    """Overrides that select among kernels a da >= 3 pack does not have (whole-horizon, fused, scalar-broadcast, their tilings, the step-1 quadratic
+    form) leave the plan what it was -- head+pair_staged on the same tiling, no step1=quad -- and, the same kernel on the same work list, every
+    bit of the result."""
+    D = ds + da
+    bs = OG.wideact_batches(ds)
+    args, steps, _ = OG.wideact_case(ds, da, OG.LADDER_N)
+    pb, kinv = OG.problem(*args)
+    H = pb["H"]
+    pack, cost = _pack(G, pb, kinv), _cost(G, pb)
+    for step in steps:
+        B, env, form, tiling, tb, mode = step
+        if env or mode == "graph" or B not in (bs["small"], bs["big"]):
+            continue
+        OG.assert_wideact_plan(pack.plan(B, H), step, D)
+        base = _np(G.rollout(pack, pb["x0"][:B], pb["U"][:B], cost))
+        _check_diag(base, _ref_diag(args, -1.0, OG.picks(B)), OG.picks(B), "wideact inert ds=%d da=%d B=%d default" % (ds, da, B))
+        for over in OG.WIDEACT_INERT:
+            with _tuning(pack, over):
+                OG.assert_wideact_plan(pack.plan(B, H), step, D)
+                r = _np(G.rollout(pack, pb["x0"][:B], pb["U"][:B], cost))
+            for k in ("means", "vars", "cost", "grad"):
+                assert np.array_equal(r[k], base[k]), (over, B, k)
+
+
+@pytest.mark.parametrize("case", OG.WIDEACT_FULLCOV, ids=lambda c: "ds%d-da%d-N%d%s" % (c[2], c[3], c[1], "-shared" if c[4] else ""))
+def test_wide_action_fullcov_vs_cport(G, case):
+    """test_fullcov_rollout_vs_cport at da >= 3, step for step: the two-launch form has no instance there, so every step -- GPMPC_FC_FORM, _TILING
+    and _SHARED included -- must plan and run the four-launch form (staged kernel at the small batches, pair_kernel_sbf.h at the large one) with
+    per-unit cross terms, also on the pack with one lambda.  Means, covariances, cost, complex-step directional derivatives of the C port."""
+    test_fullcov_rollout_vs_cport(G, case)
+
+
+def _model_ref(kind, args, b):
+    """Trajectory b of a WIDEACT_MODEL problem by the reference of its kind, once per module, sanity re-asserted."""
+    if (kind, args, b) not in _refs:
+        import noise_reference as NR
+        from oracle import gpmpc_oracle as O
+        pb, kinv = OG.problem(*args)
+        ds, da, H = pb["ds"], pb["da"], pb["H"]
+        gp = O.GPBundle(pb["X"], pb["Y"], pb["lambdas"], pb["sigma_f"], pb["sigma_n"], Ky_inv=kinv)
+        common = (H, pb["x0"][b], pb["U"][b], pb["x_ref"], pb["u_ref"], pb["Q"], pb["R"], -1.0)
+        if kind == "nominal":
+            r = nominal_rollout(gp, *synth_nominal(ds, da), *common)
+        elif kind == "noise":
+            P, av, w = NR.ladder_noise(ds, da)
+            r = NR.rollout(gp, *common, init_cov=P, action_var=av, process_var=w)
+        else:
+            r = reference_constraints(gp, H, pb["x0"][b], pb["U"][b], *_rows(ds))
+            assert np.all(np.isfinite(r["jac"]))
+        OG.assert_diag_reference_is_sane(r["means"], r["vars"], r.get("cost", 0.0), pb["Q"], -1.0)
+        _refs[(kind, args, b)] = r
+    return _refs[(kind, args, b)]
+
+
+@pytest.mark.parametrize("kind", ["nominal", "noise"])
+@pytest.mark.parametrize("case", OG.WIDEACT_MODEL, ids=lambda c: "ds%d-da%d" % (c[2], c[3]))
+def test_wide_action_nominal_and_noise_models_vs_reference(G, case, kind):
+    """da >= 3 through the head / tail kernels' other variants: a pack with a linear nominal model (k_roll_head<D, 1 | 2>: with and without
+    gradient) against tests/nominal_reference.py; a pack under a noise model -- init_cov with off-diagonal entries, a different action_var per
+    action (the first exactly 0), process_var > 0: the offsets of the noise image behind da >= 3 action variances -- against
+    tests/noise_reference.py.  B = 1, 2, 5; objective + gradient and objective only."""
+    import noise_reference as NR
+    cfg, N, ds, da, H = case
+    args = (cfg, N, ds, da, H, max(OG.WIDEACT_MODEL_B), False)
+    pb, kinv = OG.problem(*args)
+    cost = _cost(G, pb)
+    if kind == "nominal":
+        pack = _pack(G, pb, kinv, nominal=synth_nominal(ds, da))
+    else:
+        P, av, w = NR.ladder_noise(ds, da)
+        assert np.abs(P - np.diag(np.diag(P))).max() > 0 and len(set(av)) == da and np.all(w > 0)
+        pack = _pack(G, pb, kinv).set_noise(init_cov=P, action_var=av, process_var=w)
+        assert not pack.noise_is_default
+    for B in OG.WIDEACT_MODEL_B:
+        plan = pack.plan(B, H)
+        assert plan["form"] == "head+pair_staged" and "gpmpc_pair_kernel<%d,true," % (ds + da) in plan["kernel"] and plan["tb"] == min(B, 2), plan
+        assert (plan.get("nominal") == 1) == (kind == "nominal"), plan
+        r = _np(G.rollout(pack, pb["x0"][:B], pb["U"][:B], cost))
+        f = _np(G.rollout(pack, pb["x0"][:B], pb["U"][:B], cost, want_grad=False))
+        pick = OG.picks(B)
+        refs = [_model_ref(kind, args, b) for b in pick]
+        ref = {k: np.stack([np.asarray(x[k]) for x in refs]) for k in ("means", "vars", "cost", "grad")}
+        _check_diag(r, ref, pick, "wideact %s ds=%d da=%d B=%d" % (kind, ds, da, B))
+        _check_diag(f, ref, pick, "wideact %s ds=%d da=%d B=%d objective only" % (kind, ds, da, B), grad=False)
+
+
+@pytest.mark.parametrize("case", OG.WIDEACT_MODEL, ids=lambda c: "ds%d-da%d" % (c[2], c[3]))
+def test_wide_action_jacobians_and_constraints_vs_reference(G, case):
+    """gpmpc_rollout_jac (step Jacobians with da >= 3 action columns) through gpmpc_rollout_constraints, and gpmpc_rollout_constrained in one pass,
+    on the three mixed rows, B = 1, 2, 5, against tests/constraints_reference.py by the criteria of tests/test_gpu_constraints.py -- the
+    exact-zero causality blocks, da columns wide, included."""
+    import test_gpu_constraints as TC
+    cfg, N, ds, da, H = case
+    args = (cfg, N, ds, da, H, max(OG.WIDEACT_MODEL_B), False)
+    pb, kinv = OG.problem(*args)
+    A, bb, kap = _rows(ds)
+    sc, cost, pack = G.StateConstraints(A, bb, kappa=kap), _cost(G, pb), _pack(G, pb, kinv)
+    for B in OG.WIDEACT_MODEL_B:
+        assert pack.plan(B, H)["form"] == "head+pair_staged"
+        means, vars_, jac = TC._rollout_jac(pack, pb["x0"][:B], pb["U"][:B])
+        assert torch.isfinite(jac).all()
+        pure = _np(G.rollout_constraints(means, vars_, jac, sc, ds, da))
+        one = _np(G.rollout(pack, pb["x0"][:B], pb["U"][:B], cost, want_grad=True, constraints=sc))
+        val = _np(G.rollout(pack, pb["x0"][:B], pb["U"][:B], cost, want_grad=False, constraints=sc))
+        np.testing.assert_array_equal(val["g"], one["g"])
+        means, vars_ = means.cpu().numpy(), vars_.cpu().numpy()
+        for b in OG.picks(B):
+            ref = _model_ref("constraints", args, b)
+            for name, got in (("gpmpc_rollout_jac + gpmpc_rollout_constraints", pure), ("gpmpc_rollout_constrained", one)):
+                what = "wideact constraints ds=%d da=%d B=%d [%d] %s" % (ds, da, B, b, name)
+                TC._assert_g(got["g"][b], ref, A, kap, what)
+                TC._assert_jac(got["g_jac"][b], ref["jac"], H, 3, da, what)
+            for m, v in ((means, vars_), (one["means"], one["vars"])):
+                np.testing.assert_allclose(m[b], ref["means"], rtol=MEAN_RTOL, atol=1e-9)
+                np.testing.assert_allclose(v[b], ref["vars"], rtol=VAR_RTOL, atol=1e-12)
+
+
+def test_wide_action_autograd_path_equals_the_fused_adjoint(G):
+    """autograd.RolloutFunction (gpmpc_rollout_jac + gpmpc_rollout_vjp) at ds = 2, da = 3: u.grad of cost_torch(forward_propagate_torch(...)) against
+    the gradient of ``rollout`` on the same pack and cost, 1e-9 relative (tests/test_gpu_autograd.py's tolerance for the same pair)."""
+    cfg, N, ds, da, H = OG.WIDEACT_MODEL[0]
+    pb, _ = OG.problem(cfg, N, ds, da, H, max(OG.WIDEACT_MODEL_B), False)
+    mpc = G.RiskSensitiveMPC(-1.0, H, ds, da, pb["Q"], pb["R"])
+    for a, g in enumerate(mpc.dynamics.gpr_err):
+        g.set_lambdas(pb["lambdas"][a])
+        g.set_sigma_n(np.array(pb["sigma_n"][a]))
+        g.set_sigma_f(np.array(pb["sigma_f"][a]))
+    mpc.dynamics.append_train_data(pb["X"][:, :ds], pb["X"][:, ds:], pb["Y"])
+    mpc.set_xref(pb["x_ref"])
+    mpc.set_uref(pb["u_ref"])
+    pack, cost = mpc.dynamics.pack(), _cost(G, pb)
+    for b in (0, 1):
+        x0 = torch.tensor(pb["x0"][b], dtype=torch.float64, device=mpc.device)
+        u = torch.as_tensor(pb["U"][b], device=mpc.device).type(torch.float64).requires_grad_(True)
+        means, covs = mpc.dynamics.forward_propagate_torch(H, x0, u)
+        assert means[1].requires_grad and covs[1].requires_grad
+        c = mpc.cost_torch(means, u, covs, mpc.x_ref, mpc.u_ref)
+        c.backward()
+        r = _np(G.rollout(pack, pb["x0"][b:b + 1], pb["U"][b:b + 1], cost))
+        got, ref = u.grad.cpu().numpy(), r["grad"][0]
+        print("DEV wideact autograd [%d]: cost %.3g grad %.3g relative" % (b, abs(c.item() - r["cost"][0]) / abs(r["cost"][0]), np.abs(got - ref).max() / np.abs(ref).max()))
+        assert got.shape == (H, da) and np.all(np.isfinite(got))
+        np.testing.assert_allclose(c.item(), r["cost"][0], rtol=1e-12)
+        np.testing.assert_allclose(got, ref, rtol=1e-9, atol=1e-12)

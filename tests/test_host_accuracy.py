@@ -8,6 +8,11 @@ K_ref measured here (worst over the compared trajectories and steps; means | var
     one lambda (N = 150)     ds = 2: 0.52 | 0.50    3: 0.93 | 0.27    4: 0.75 | 0.25    5: 1.1 | 0.37
     256x128 (N = 520): 0.85 | 0.44        balanced runs (N = 2310): 0.92 | 0.32
     full covariance          ds = 2: 1.0 | 0.29 | 0.29    3: 0.61 | 0.36 | 0.36    4: 1.3 | 0.33 | 0.33    5: 1.2 | 0.34 | 0.34    6: 1.0 | 0.22 | 0.22
+    action_dim >= 3 (N = 150, H = 3)  (1, 3): 0.27 | 0.19    (2, 3): 0.47 | 0.24    (3, 3): 1.4 | 0.31    (2, 5): 0.53 | 0.20    (4, 3): 1.0 | 0.15
+                             (1, 7): 0.48 | 0.24    (4, 4): 1.8 | 0.37    (5, 3): 1.2 | 0.31    long case (N = 1415): 0.16 | 0.29
+    full covariance, da >= 3 (2, 3): 0.98 | 0.24 | 0.24    (3, 3): 0.65 | 0.23 | 0.23    (4, 4): 1.1 | 0.19 | 0.20    (5, 3): 0.94 | 0.20 | 0.24
+    (all within OG.BUDGET_K; their double complex floors: cost 8.8e-10 and gradient 1.2e-9 at most, the largest at N = 1415 and at (1, 3):
+    test_wide_action_yardstick_is_within_the_budget)
 The variances sit at 0.13 ... 0.57 (not the 0.03 ... 0.05 of a single step: these are maxima over 3 ... 39 steps and all GPs, and the compiler
 contracts multiply-adds; another build of the same source moved single entries by a factor 2), with sum|terms| / var from 3.5e4 (ds = 7) to 1.1e11
 (N = 2310): the unit holds over six orders of magnitude of conditioning.  Weighted with the expanded exponent of the HIP kernels
@@ -46,7 +51,8 @@ FC_MEAN_RTOL, FC_MEAN_ATOL, FC_COV_RTOL, FC_COV_ATOL_OF_MAX, FC_COST_RTOL, FC_DD
 # evaluation beyond these would be a systematic error of the yardstick itself.
 K_REF_MAX = {"mean": 4.0, "var": 1.0, "cov": 1.0}
 
-SHAPES = [s for s in OG.gpu_rollout_shapes() if s[0].split(" ")[0] in ("ladder", "shared", "256x128", "runs", "fullcov")]
+SHAPES = [s for s in OG.gpu_rollout_shapes() if s[0].split(" ")[0] in ("ladder", "shared", "256x128", "runs", "fullcov")
+          or s[0].startswith(("wideact ds", "wideact long", "wideact fullcov"))]
 _IDS = [s[0].replace(" ", "-") for s in SHAPES]
 
 
@@ -172,6 +178,51 @@ def test_k_ref_of_the_plain_fp64_evaluation(shape):
         "" if full else "; expanded exponent: A_exp / A_var up to %.3g" % float((ld["A_exp"] / ld["A_var"]).max())))
     for q, v in k.items():
         assert v <= K_REF_MAX[q], (label, q, v)
+
+
+_WIDEACT = [s for s in SHAPES if s[0].startswith("wideact")]
+
+
+@pytest.mark.parametrize("shape", _WIDEACT, ids=[s[0].replace(" ", "-") for s in _WIDEACT])
+def test_wide_action_yardstick_is_within_the_budget(shape):
+    """The action_dim >= 3 problems of tests/test_gpu_accuracy.py, on the trajectories it compares: K_ref of the double build lies within
+    OG.BUDGET_K, and the floors -- cost and gradient (in norm) of the double complex build against the long double complex step -- within
+    OG.BUDGET_TRAJ, so that on these problems the budget can only be exceeded by the kernels.  Printed as well: the floor of trajectory 0 alone,
+    the whole yardstick of the B = 1 steps (a double evaluation that happens to land 60 times closer than its neighbours -- seed 221 at ds = 2,
+    da = 5 -- measures nothing; OG.wideact_config).  (A drawn problem that fails this gets another config id, not another budget.)"""
+    from oracle import cport
+    label, args, tr, gamma, full = shape
+    pb, kinv = OG.problem(*args)
+    ds = pb["ds"]
+    beta, W = cport.constants(pb, kinv)
+    kw = dict(x0=pb["x0"][tr], U=pb["U"][tr], full=full, nthreads=THREADS)
+    t = cport.given_rollout(pb, beta, W, gamma, prec="d", **kw)
+    if full:
+        OG.assert_fullcov_reference_is_sane(t["means"], t["covs"], t["cost"])
+        u, S = _inputs_full(pb, tr, t["means"], t["covs"])
+        d = cport.given_step_full(pb, beta, W, u, S, prec="d", nthreads=THREADS)
+        ld = cport.given_step_full(pb, beta, W, u, S, prec="ld", nthreads=THREADS)
+        dg = np.arange(ds)
+        k = {"mean": _K(d["mean"], ld["mean"], ld["A_mean"]), "var": _K(d["cov"][:, dg, dg], ld["cov"][:, dg, dg], ld["A_cov"][:, dg, dg]),
+             "cov": _K(d["cov"], ld["cov"], ld["A_cov"])}
+    else:
+        OG.assert_diag_reference_is_sane(t["means"], t["vars"], t["cost"], pb["Q"], gamma)
+        u, s = _inputs_diag(pb, tr, t["means"], t["vars"])
+        d = cport.given_step_diag(pb, beta, W, u, s, prec="d", nthreads=THREADS)
+        ld = cport.given_step_diag(pb, beta, W, u, s, prec="ld", nthreads=THREADS)
+        k = {"mean": _K(d["mean"], ld["mean"], ld["A_mean"]), "var": _K(d["var"], ld["var"], ld["A_var"])}
+    cld = cport.given_rollout(pb, beta, W, gamma, prec="cld", **kw)
+    cd = cport.given_rollout(pb, beta, W, gamma, prec="cd", **kw)
+    each = {"cost": np.abs(cd["cost"] - cld["cost"]) / np.abs(cld["cost"]),
+            "grad": np.array([np.linalg.norm(cd["grad"][b] - cld["grad"][b]) / np.linalg.norm(cld["grad"][b]) for b in range(len(tr))])}
+    floor = {q: float(v.max()) for q, v in each.items()}
+    print("YARDSTICK %s: K_ref %s; floors cost %.3g grad %.3g, of trajectory 0 alone %.3g %.3g" % (
+        label, " ".join("%s %.3g" % kv for kv in k.items()), floor["cost"], floor["grad"], each["cost"][0], each["grad"][0]))
+    assert tr[0] == 0
+    for q, v in k.items():
+        assert v <= OG.BUDGET_K[q], (label, q, v)
+    for q, v in floor.items():
+        assert v <= OG.BUDGET_TRAJ[q], (label, q, v)
 
 
 # ------------------------------------------------------------------------------------------------------------------------------

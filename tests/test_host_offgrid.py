@@ -42,7 +42,12 @@ def _fullcov_id(c):
     return "cfg%d-N%d-ds%d-da%d%s" % (cfg, N, ds, da, "-shared" if shared else "")
 
 
-@pytest.mark.parametrize("case", OG.DIAG_CASES, ids=_diag_id)
+# action_dim >= 3 (tests/test_gpu_offgrid.py::test_wide_action_ladder_vs_cport and its long case), in the format of OG.DIAG_CASES
+WIDEACT_DIAG = [(OG.wideact_config(ds, da), OG.LADDER_N, ds, da, OG.LADDER_H, False, -1.0) for ds, da in OG.WIDEACT_DIMS] + \
+               [OG.WIDEACT_LONG + (False, -1.0)] + [c + (False, -1.0) for c in OG.WIDEACT_MODEL]
+
+
+@pytest.mark.parametrize("case", OG.DIAG_CASES + WIDEACT_DIAG, ids=_diag_id)
 def test_cport_rollout_matches_torch_oracle_off_the_grid(case):
     """cport.rollout (analytic adjoint) against oracle.objective_and_gradient(mode="o2") (autograd), trajectories 0 and B - 1 of B = 4.
 
@@ -57,6 +62,8 @@ def test_cport_rollout_matches_torch_oracle_off_the_grid(case):
         5       320 5  2  5    1.2e-10  1.4e-10    2.1e-12  2.6e-12
         7       260 7  1  4    2.0e-13  3.2e-12    3.9e-14  1.9e-13
     The variances deviate by at most 2.9e-7 (inside the neighbour's 1e-6); element by element the gradient stays below 3 % of rtol 1e-6 + atol 1e-9.
+    action_dim >= 3 (WIDEACT_DIAG: (ds, da) = (1, 3) ... (5, 3) at N = 150, H = 3; the long case N = 1415, ds = 1, da = 3, H = 2; the H = 4 problems of the
+    model tests): means 1.0e-8 and less, variances 6.8e-8 and less, cost 3.2e-10 and less, gradient 6.1e-10 and less; min(1 + gamma Q_kk var) = 0.916.
     The oracle's own trajectories: variances from step 1 on in [1.1e-3, 1.53], min(1 + gamma Q_kk var) = 0.847 -- asserted, not assumed.
     """
     from oracle import cport
@@ -84,7 +91,7 @@ def test_cport_rollout_matches_torch_oracle_off_the_grid(case):
         np.testing.assert_allclose(r["grad"][k], o["grad"], rtol=DIAG_GRAD_RTOL, atol=DIAG_GRAD_ATOL)
 
 
-@pytest.mark.parametrize("case", OG.FULLCOV_CASES, ids=_fullcov_id)
+@pytest.mark.parametrize("case", OG.FULLCOV_CASES + OG.WIDEACT_FULLCOV, ids=_fullcov_id)
 def test_cport_fullcov_rollout_matches_torch_oracle_off_the_grid(case):
     """cport.rollout_fullcov (complex-step directional derivatives) against oracle.objective_and_gradient_fullcov (autograd): H = 3, both
     trajectories of B = 2, two seeded directions each.
@@ -166,6 +173,11 @@ def test_offgrid_inputs_discriminate(shape):
     ds = 3: 1.3e3 | 2.4e3; ds = 4 ... 7: 6.6e3 and more.  One lambda (N = 150): ds = 2: 138 | 119; ds = 3: 730 | 506; ds = 4, 5: 6.0e3 and more.
     256x128 tiles (N = 520): 512 | 814; balanced runs (N = 2310): above 4.0e3.  Full covariance: ds = 2: 798 | 876; ds = 3 ... 6: 2.3e3 and more.
     Configs 1 / 3 / 3 with one lambda (nominal packs, life cycle, class path): 4.7e3 | 8.4e3, 4.9e3 | 1.3e3, 3.2e3 | 698.  Jacobian cases: 1.9e3 and more.
+    action_dim >= 3: ladder (1, 3): 1.1e3; (2, 3): 3.3e3 | 1.9e3; the other dimensions 2.1e3 and more; full covariance 1.7e3 and more; the H = 4 model
+    problems 1.4e3 | 471 and 9.4e3 | 1.3e4.  The long case (N = 1415, one GP, H = 2): 117 -- a GP with ten times the data barely feels its amplitude
+    (seeds 260 ... 479 give 1.4 ... 324; of the nine above 100, 318, 336, 371 and 472 also keep the double complex floor of
+    tests/test_host_accuracy.py within the budget; 472 is taken).  On these shapes also: with x_ref = u_ref = 0 the cost of every trajectory moves by
+    1.1e4 ... 4.1e5 x the GPU's cost tolerance, with the coupling of Q dropped (ds >= 2) by 2.1e3 ... 1.0e5.
     """
     from oracle import cport
     label, args, tr, gamma, fullcov = shape
@@ -182,6 +194,15 @@ def test_offgrid_inputs_discriminate(shape):
     if ds >= 2:
         ratios.append(_discriminates(label, off, run(*OG.with_sigma_f(pb, pb["sigma_f"][::-1])), fullcov, "sigma_f reversed"))
     assert min(ratios) >= DISCRIMINATION, (label, ratios)
+    if label.startswith("wideact"):
+        # the references and the coupling of Q enter the cost alone: back on the grid (x_ref = u_ref = 0; Q diagonal) the cost of every trajectory
+        # moves by more than 100 x the GPU's cost tolerance -- a cost kernel that drops u_ref beyond two actions, or the coupling, cannot pass
+        for what, q in (("x_ref = u_ref = 0", dict(pb, x_ref=np.zeros(ds), u_ref=np.zeros(pb["da"]))), ("diagonal Q", dict(pb, Q=np.diag(np.diag(pb["Q"]))))):
+            if what == "diagonal Q" and ds == 1:
+                continue                                    # (one state: Q has no coupling to drop)
+            moved = np.abs(run(q, kinv)["cost"] - off["cost"]) / (OG.GPU_COST_RTOL * np.abs(off["cost"]))
+            print("%s, %s: the cost of every trajectory moves by at least %.3g x the GPU tolerance" % (label, what, moved.min()))
+            assert moved.min() >= DISCRIMINATION, (label, what, moved.min())
 
 
 @pytest.mark.parametrize("case", [OG.DIAG_CASES[0], OG.DIAG_CASES[2], OG.DIAG_CASES[3]], ids=_diag_id)
