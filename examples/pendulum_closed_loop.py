@@ -115,6 +115,11 @@ def main():
     ap.add_argument("--feedback", choices=("none", "lqr"), default="none",
                     help="with --propagation linearised_full: lqr predicts under u = v + K (x - mu) with the LQR gain of the model linearised at the upright rest "
                          "(linearised.lqr_gain with the controller's Q and R; mpc.set_feedback_gain)")
+    ap.add_argument("--input-prob", type=float, default=None, metavar="P",
+                    help="with --feedback lqr: chance constraints on the COMMANDED input u = v + K (x - mu): each actuator bound holds with "
+                         "probability P (mpc.set_input_chance_bounds); the out-of-sample figure is validate_plan(feedback=True) on the last plan")
+    ap.add_argument("--feedback-input-cost", action="store_true",
+                    help="with --feedback lqr: charge tr(R K Sigma K^T), the spread of the commanded input (mpc.feedback_input_cost)")
     ap.add_argument("--linearised-form", choices=("tile", "stream", "auto"), default=None,
                     help="with --propagation linearised: the form of the linearised step (mpc.linearised_form); stream is the matrix-vector form for B = 1")
     args = ap.parse_args()
@@ -128,6 +133,8 @@ def main():
         ap.error("--particles must lie in 1...4096")
     if args.feedback != "none" and args.propagation != "linearised_full":
         ap.error("--feedback needs --propagation linearised_full")
+    if (args.input_prob is not None or args.feedback_input_cost) and args.feedback == "none":
+        ap.error("--input-prob and --feedback-input-cost need --feedback lqr (without a gain the commanded input has no spread)")
     if args.propagation == "moment_matching_full" and args.nominal != "none":
         ap.error("--propagation moment_matching_full does not combine with --nominal (the full-covariance rollout knows no nominal model)")
     if args.propagation == "moment_matching_full" and args.max_speed is not None and args.starts > 1 and args.solver == "default":
@@ -167,6 +174,9 @@ def main():
         K = lqr_gain(mpc.dynamics, np.zeros(2), np.zeros(1), 2 * np.eye(2), 0.001 * np.eye(1))
         mpc.set_feedback_gain(K)
         print("feedback: LQR gain K = %s" % np.array2string(K, precision=4))
+        mpc.feedback_input_cost = args.feedback_input_cost
+        if args.input_prob is not None:
+            mpc.set_input_chance_bounds(args.input_prob)
     if args.solver == "mppi":
         mpc.solver = "mppi"
         mpc.mppi_options.update(samples=args.samples, iterations=args.iters)
@@ -239,6 +249,18 @@ def main():
               f"data update + pack refill {np.mean(data_ms[:q]):.3f} ms per step over the first {q} steps, {np.mean(data_ms[-q:]):.3f} ms over the last {q}; "
               f"pack handle kept: {mpc.dynamics.pack().handle is handle0}, "
               f"gpmpc_pack_callback_captures = {lib().gpmpc_pack_callback_captures(mpc.dynamics.pack().handle)}")
+    if args.feedback == "lqr":
+        # the last plan from the last state, out of sample: particles under the gain against the actuator bounds
+        from gaussian_process_mpc_amd import InputConstraints
+        had = mpc.input_constraints
+        if had is None:                                  # (count against the bounds also where they were not imposed)
+            mpc.input_constraints = InputConstraints.box([-2.0], [2.0], 1, prob=0.95 if args.input_prob is None else args.input_prob)
+        v = mpc.validate_plan(x0=hist[-1][0], particles=4096, seed=1, feedback=True)
+        mpc.input_constraints = had
+        print("commanded input under the gain, last plan, 4096 particles: satisfaction of |u| <= 2 per step, worst row %.4f, joint %.4f "
+              "(requested %s); input sd, particles %.3g ... %.3g, linearised_full %.3g ... %.3g" % (
+                  v["input_satisfaction"].min(), v["joint_input_satisfaction"], "none" if args.input_prob is None else "%.2f per bound" % args.input_prob,
+                  np.sqrt(v["input_cov_mc"].min()), np.sqrt(v["input_cov_mc"].max()), np.sqrt(v["input_cov_lf"].min()), np.sqrt(v["input_cov_lf"].max())))
     if args.max_speed is not None:
         sp = np.array([abs(h[0][1]) for h in hist])
         print(f"|theta_dot| <= {args.max_speed} with probability {args.prob}: largest visited {sp.max():.3f}; "

@@ -66,6 +66,14 @@ class StateConstraintsC(ctypes.Structure):
                 ("kappa", ctypes.c_double * MAX_CONS)]
 
 
+class InputConstraintsC(ctypes.Structure):
+    _fields_ = [("n_rows", ctypes.c_int),
+                ("reserved", ctypes.c_int),
+                ("C", ctypes.c_double * (MAX_CONS * MAX_D)),
+                ("d", ctypes.c_double * MAX_CONS),
+                ("kappa", ctypes.c_double * MAX_CONS)]
+
+
 class MppiParamsC(ctypes.Structure):
     _fields_ = [("n_samples", ctypes.c_int),
                 ("iterations", ctypes.c_int),
@@ -127,6 +135,7 @@ _vp, _i, _d, _sz, _u = ctypes.c_void_p, ctypes.c_int, ctypes.c_double, ctypes.c_
 _dp = ctypes.POINTER(ctypes.c_double)
 _ull = ctypes.c_ulonglong
 _gm, _sc = ctypes.POINTER(GPModelC), ctypes.POINTER(StateConstraintsC)
+_ic = ctypes.POINTER(InputConstraintsC)
 
 # name -> (restype, argtypes); every symbol include/gpmpc.h declares
 SIGNATURES = {
@@ -267,6 +276,18 @@ SIGNATURES = {
                                          _vp, _i, _vp, _sz, _vp]),
     "gpmpc_linearised_fc_vjp": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "gpmpc_linearised_fc_constraints": (_i, [_i, _i, _i, _i, _sc, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "gpmpc_feedback_input_cost": (_i, [_i, _i, _i, _i, ctypes.POINTER(CostParamsC), _vp, _sz, _vp, _vp, _vp, _vp]),
+    "gpmpc_feedback_input_constraints": (_i, [_i, _i, _i, _i, _ic, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "gpmpc_particle_inputs": (_i, [_i, _i, _i, _i, _vp, _vp, _sz, _vp, _vp, _sz, _vp, _vp]),
+    "gpmpc_particle_step_inputs_workspace_bytes": (_sz, [_gm, _i, _i, _i]),
+    "gpmpc_particle_step_inputs": (_i, [_gm, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _sz, _vp]),
+    "gpmpc_particle_input_stats": (_i, [_i, _i, _i, _i, _vp, _ic, _vp, _vp, _vp, _vp, _vp]),
+    "gpmpc_particle_rollout_feedback_workspace_bytes": (_sz, [_gm, _i, _i, _i, _i, _i]),
+    "gpmpc_particle_rollout_feedback": (_i, [_gm, _i, _i, _i, _vp, _vp, _ull, _u, _sc, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _ic, _vp, _vp,
+                                             _vp, _vp, _vp, _i, _vp, _sz, _vp]),
+    "gpmpc_linearised_fc_rollout_inputs_workspace_bytes": (_sz, [_gm, _i, _i, _u, _i, _i, _ic]),
+    "gpmpc_linearised_fc_rollout_inputs": (_i, [_gm, _i, _i, _vp, _vp, _vp, _sz, ctypes.POINTER(CostParamsC), _sc, _u, _vp, _vp, _vp, _vp, _vp,
+                                                _vp, _vp, _i, _ic, _vp, _vp, _i, _vp, _sz, _vp]),
 }
 
 _lib = None

@@ -545,7 +545,16 @@ extern "C" int gpmpc_linearised_fc_rollout(const gpmpc_gp_model* m, int B, int H
                                            unsigned flags, double* out_means, double* out_covs, double* out_jac, double* out_cost,
                                            double* out_grad, double* out_g, double* out_gjac, int chunk, void* workspace, size_t workspace_bytes,
                                            void* stream) {
-    const char* who = "gpmpc_linearised_fc_rollout";
+    return gpmpc_lpf_rollout("gpmpc_linearised_fc_rollout", m, B, H, x0, U, K_dev, k_step_stride, cost, cons, flags, out_means, out_covs, out_jac,
+                             out_cost, out_grad, out_g, out_gjac, chunk, workspace, workspace_bytes, stream, nullptr);
+}
+
+// `in` (or null): the input cost and the input chance constraints of gpmpc_linearised_fc_rollout_inputs (linprop_inputs.hip).  They read the
+// trajectory and add to the cost and to the covariance seed of the adjoint sweep: means, covs, jac, g and g_jac never see them.
+int gpmpc_lpf_rollout(const char* who, const gpmpc_gp_model* m, int B, int H, const double* x0, const double* U, const double* K_dev,
+                      size_t k_step_stride, const gpmpc_cost_params* cost, const gpmpc_state_constraints* cons, unsigned flags, double* out_means,
+                      double* out_covs, double* out_jac, double* out_cost, double* out_grad, double* out_g, double* out_gjac, int chunk,
+                      void* workspace, size_t workspace_bytes, void* stream, const LpfInputs* in) {
     LpfModel M;
     if (int rc = lpf_check_model(who, m, &M)) return rc;
     if (B < 1) return gpmpc_refuse(who, "B < 1");
@@ -570,6 +579,16 @@ extern "C" int gpmpc_linearised_fc_rollout(const gpmpc_gp_model* m, int B, int H
         gpmpc_sched_ref sched;
         if (int rc = gpmpc_schedule_resolve(cost, ds, da, H, who, &sched)) return rc;
     }
+    if (in) {
+        if (in->input_cost && !cost) return gpmpc_refuse(who, "input_cost needs a cost: R is the cost's");
+        if ((in->input_cost || in->ucons) && da < 1) return gpmpc_refuse(who, "the input cost and input constraints need action_dim >= 1");
+        if (in->ucons) {
+            if (int rc = gpmpc_lpi_check_rows(who, in->ucons)) return rc;
+            if (!in->out_gu || (grad && !in->out_gujac)) return gpmpc_refuse(who, "NULL pointer (out_gu, or out_gujac with GPMPC_WANT_GRAD)");
+            if (!grad && in->out_gujac) return gpmpc_refuse(who, "out_gujac needs GPMPC_WANT_GRAD: without it no Jacobian is computed");
+        } else if (in->out_gu || in->out_gujac)
+            return gpmpc_refuse(who, "out_gu / out_gujac without input constraints");
+    }
     const LpfRollLayout R = lpf_roll_layout(m, B, H, grad, chunk);
     if (workspace_bytes < R.total) return GPMPC_E_WORKSPACE;
     hipStream_t s = (hipStream_t)stream;
@@ -591,12 +610,18 @@ extern "C" int gpmpc_linearised_fc_rollout(const gpmpc_gp_model* m, int B, int H
         double *dm = grad ? (double*)(ws + R.off_dm) : nullptr, *dc = grad ? (double*)(ws + R.off_dc) : nullptr;
         double* du = grad ? (double*)(ws + R.off_du) : nullptr;
         if (int rc = gpmpc_cost_grad(B, H, ds, da, cost, means, covs, U, out_cost, dm, dc, du, stream)) return rc;
+        if (in && in->input_cost)
+            if (int rc = gpmpc_lpi_cost(B, H, ds, da, cost, K_dev, k_step_stride, covs, nullptr, nullptr, out_cost, dc, s)) return rc;
         if (grad)
             hipLaunchKernelGGL(k_lpf_vjp, dim3(B), dim3(64), 0, s, H, ds, da, (const double*)jac, (const double*)dm, (const double*)dc,
                                (const double*)du, out_grad, (double*)nullptr);
     }
     if (cons)
         if (int rc = lpf_constraints(B, H, ds, da, cons, means, covs, grad ? jac : nullptr, out_g, grad ? out_gjac : nullptr, s)) return rc;
+    if (in && in->ucons)
+        if (int rc = gpmpc_lpi_constraints(B, H, ds, da, in->ucons, K_dev, k_step_stride, U, covs, grad ? jac : nullptr, in->out_gu,
+                                           grad ? in->out_gujac : nullptr, s))
+            return rc;
     GPMPC_HIP(hipGetLastError());
     return GPMPC_OK;
 }

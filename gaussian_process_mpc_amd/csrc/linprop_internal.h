@@ -38,6 +38,20 @@ LpLayout gpmpc_lp_layout(const gpmpc_gp_model* m, int chunk, long ncols, bool wa
 int gpmpc_lp_step(const gpmpc_gp_model* m, const LpTail& tail, int B, const double* mu_prev, const double* var_prev, size_t xs, const double* U_t,
                   size_t us, double* out_mu, double* out_var, size_t os, double* jac, size_t js, const LpLayout& L, char* ws, hipStream_t s);
 
+// The full-covariance rollout (linprop_fc.hip) behind gpmpc_linearised_fc_rollout and gpmpc_linearised_fc_rollout_inputs: `in` null is the
+// former, launch for launch.  The launches of the commanded input's statistics (linprop_inputs.hip) are checked by their callers:
+// gpmpc_lpi_cost writes out_c / out_dcovs (either may be null) and, where add_cost / add_dcovs are given, adds the same values to them.
+struct LpfInputs { int input_cost; const gpmpc_input_constraints* ucons; double* out_gu; double* out_gujac; };
+int gpmpc_lpf_rollout(const char* who, const gpmpc_gp_model* m, int B, int H, const double* x0, const double* U, const double* K_dev,
+                      size_t k_step_stride, const gpmpc_cost_params* cost, const gpmpc_state_constraints* cons, unsigned flags, double* out_means,
+                      double* out_covs, double* out_jac, double* out_cost, double* out_grad, double* out_g, double* out_gjac, int chunk,
+                      void* workspace, size_t workspace_bytes, void* stream, const LpfInputs* in);
+int gpmpc_lpi_check_rows(const char* who, const gpmpc_input_constraints* C);
+int gpmpc_lpi_cost(int B, int H, int ds, int da, const gpmpc_cost_params* cost, const double* K, size_t k_step_stride, const double* covs,
+                   double* out_c, double* out_dcovs, double* add_cost, double* add_dcovs, hipStream_t s);
+int gpmpc_lpi_constraints(int B, int H, int ds, int da, const gpmpc_input_constraints* C, const double* K, size_t k_step_stride,
+                          const double* U, const double* covs, const double* jac, double* out_gu, double* out_gujac, hipStream_t s);
+
 // STREAM (linprop_stream.hip).  The bytes of a step of `ncols` columns, and the step itself on a workspace of that size (256-byte aligned);
 // arguments as gpmpc_lp_step, checked by its callers.
 size_t gpmpc_lps_workspace_bytes(const gpmpc_gp_model* m, long ncols, bool want_jac);

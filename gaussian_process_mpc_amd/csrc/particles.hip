@@ -437,14 +437,20 @@ int gpmpc_pt_initial(const gpmpc_gp_model* m, int B, int P, const double* x0, co
     return GPMPC_OK;
 }
 
+// U_p (or null): an input per particle, dev [B P][da], in the place of U_t / u_stride (the assemble kernel of linprop_inputs.hip)
 static int pt_step(const gpmpc_gp_model* m, const PtNoise& noise, int B, int P, const double* x_prev, const double* U_t, size_t u_stride,
-                   const double* eps, double* out_next, double* out_mean, double* out_var, const PtStepLayout& S, char* ws, hipStream_t s) {
+                   const double* eps, double* out_next, double* out_mean, double* out_var, const PtStepLayout& S, char* ws, hipStream_t s,
+                   const double* U_p = nullptr) {
     const int ds = m->state_dim, da = m->action_dim, D = ds + da;
     double* z = (double*)(ws + S.off_z);
-    PtVec sd;
-    memset(&sd, 0, sizeof(sd));
-    memcpy(sd.v, noise.action_sd, sizeof(double) * GPMPC_MAX_D);
-    hipLaunchKernelGGL(k_pt_assemble, dim3(gpmpc_blocks256((long)B * P * D)), dim3(256), 0, s, B, P, ds, da, x_prev, U_t, u_stride, eps, sd, z);
+    if (U_p) {
+        if (int rc = gpmpc_lpi_assemble(B, P, ds, da, x_prev, U_p, eps, noise.action_sd, z, s)) return rc;
+    } else {
+        PtVec sd;
+        memset(&sd, 0, sizeof(sd));
+        memcpy(sd.v, noise.action_sd, sizeof(double) * GPMPC_MAX_D);
+        hipLaunchKernelGGL(k_pt_assemble, dim3(gpmpc_blocks256((long)B * P * D)), dim3(256), 0, s, B, P, ds, da, x_prev, U_t, u_stride, eps, sd, z);
+    }
     return pt_posterior(m, noise, (long)B * P, z, out_mean, out_var, eps, P, out_next, S.post, ws, s);
 }
 
@@ -468,6 +474,28 @@ extern "C" int gpmpc_particle_step(const gpmpc_gp_model* m, int B, int P, const 
     const PtStepLayout S = pt_step_layout(m, B, P, chunk, c);
     if (workspace_bytes < S.total) return GPMPC_E_WORKSPACE;
     return pt_step(m, noise, B, P, x_prev, U_t, u_stride, eps, out_next, out_mean, out_var, S, (char*)workspace, (hipStream_t)stream);
+}
+
+// gpmpc_particle_step with an input per particle, U_p dev [B P][da] (gpmpc_particle_inputs makes them), in the place of U_t / u_stride
+extern "C" size_t gpmpc_particle_step_inputs_workspace_bytes(const gpmpc_gp_model* m, int B, int P, int chunk) {
+    if (!m || m->action_dim < 1) return 0;
+    return gpmpc_particle_step_workspace_bytes(m, B, P, chunk);
+}
+
+extern "C" int gpmpc_particle_step_inputs(const gpmpc_gp_model* m, int B, int P, const double* x_prev, const double* U_p, const double* eps,
+                                          double* out_next, double* out_mean, double* out_var, int chunk, void* workspace,
+                                          size_t workspace_bytes, void* stream) {
+    const char* who = "gpmpc_particle_step_inputs";
+    PtNoise noise;
+    if (int rc = pt_check_model(who, m, &noise)) return rc;
+    if (m->action_dim < 1) return gpmpc_refuse(who, "an input per particle needs action_dim >= 1");
+    if (int rc = gpmpc_pt_check_bp(who, B, P)) return rc;
+    if (int rc = gpmpc_check_chunk(who, chunk)) return rc;
+    if (!x_prev || !U_p || !eps || !out_next || !workspace) return gpmpc_refuse(who, "NULL pointer");
+    gpmpc_carver c;
+    const PtStepLayout S = pt_step_layout(m, B, P, chunk, c);
+    if (workspace_bytes < S.total) return GPMPC_E_WORKSPACE;
+    return pt_step(m, noise, B, P, x_prev, nullptr, 0, eps, out_next, out_mean, out_var, S, (char*)workspace, (hipStream_t)stream, U_p);
 }
 
 static int pt_stats(int B, int P, int T, int ds, const double* particles, const double* var, int t0v, const gpmpc_state_constraints* cons,
@@ -506,16 +534,28 @@ extern "C" int gpmpc_particle_stats(int B, int P, int T, int ds, const double* p
 }
 
 // workspace of a rollout: eps [P][da + ds] | var [H][B P][ds] | a step's
-struct PtRollLayout { size_t off_eps, off_var; PtStepLayout step; size_t total; };
-static PtRollLayout pt_roll_layout(const gpmpc_gp_model* m, int B, int P, int H, int chunk) {
+// under feedback without out_inputs: | inputs [H][B P][da]
+struct PtRollLayout { size_t off_eps, off_var; PtStepLayout step; size_t off_u, total; };
+static PtRollLayout pt_roll_layout(const gpmpc_gp_model* m, int B, int P, int H, int chunk, bool ubuf = false) {
     PtRollLayout R;
     gpmpc_carver c;
     R.off_eps = c.take(sizeof(double) * (size_t)P * PT_MAX_NORMALS);
     R.off_var = c.take(sizeof(double) * (size_t)H * B * P * m->state_dim);
     R.step = pt_step_layout(m, B, P, chunk, c);
+    R.off_u = c.take(ubuf ? sizeof(double) * (size_t)H * B * P * m->action_dim : 0);
     R.total = c.total();
     return R;
 }
+
+// what gpmpc_particle_rollout_feedback adds to gpmpc_particle_rollout
+struct PtFeedback {
+    const double* K; size_t kss; const double* mu_ref; const gpmpc_input_constraints* ucons;
+    double *out_inputs, *out_umean, *out_ucov, *out_uviol, *out_ujoint;
+};
+static int pt_rollout(const char* who, const gpmpc_gp_model* m, int B, int P, int H, const double* x0, const double* U, unsigned long long seed,
+                      unsigned call_index, const gpmpc_state_constraints* cons, double* out_particles, double* out_mean, double* out_cov,
+                      int* out_clamped, double* out_viol, double* out_joint, int chunk, void* workspace, size_t workspace_bytes, void* stream,
+                      const PtFeedback* fb);
 
 extern "C" size_t gpmpc_particle_rollout_workspace_bytes(const gpmpc_gp_model* m, int B, int P, int H, int chunk) {
     if (!gpmpc_model_sizes_ok(m) || B < 1 || P < 1 || H < 1 || H > 65534 || (long)B * P * GPMPC_MAX_D > 0x7fffffffL || !gpmpc_chunk_ok(chunk)) return 0;
@@ -526,7 +566,33 @@ extern "C" int gpmpc_particle_rollout(const gpmpc_gp_model* m, int B, int P, int
                                       unsigned long long seed, unsigned call_index, const gpmpc_state_constraints* cons,
                                       double* out_particles, double* out_mean, double* out_cov, int* out_clamped, double* out_viol,
                                       double* out_joint, int chunk, void* workspace, size_t workspace_bytes, void* stream) {
-    const char* who = "gpmpc_particle_rollout";
+    return pt_rollout("gpmpc_particle_rollout", m, B, P, H, x0, U, seed, call_index, cons, out_particles, out_mean, out_cov, out_clamped, out_viol,
+                      out_joint, chunk, workspace, workspace_bytes, stream, nullptr);
+}
+
+// The particle rollout under u^p_t = v_t + K_t (x^p_t - mu_ref_t): the arguments of gpmpc_particle_rollout, the same noise addressing (no new
+// normals are drawn), each step the chain gpmpc_particle_noise -> gpmpc_particle_inputs -> gpmpc_particle_step_inputs.
+extern "C" size_t gpmpc_particle_rollout_feedback_workspace_bytes(const gpmpc_gp_model* m, int B, int P, int H, int chunk, int want_inputs) {
+    if (!m || m->action_dim < 1 || gpmpc_particle_rollout_workspace_bytes(m, B, P, H, chunk) == 0) return 0;
+    return pt_roll_layout(m, B, P, H, chunk, want_inputs == 0).total;
+}
+
+extern "C" int gpmpc_particle_rollout_feedback(const gpmpc_gp_model* m, int B, int P, int H, const double* x0, const double* U,
+                                               unsigned long long seed, unsigned call_index, const gpmpc_state_constraints* cons,
+                                               double* out_particles, double* out_mean, double* out_cov, int* out_clamped, double* out_viol,
+                                               double* out_joint, const double* K_dev, size_t k_step_stride, const double* mu_ref,
+                                               const gpmpc_input_constraints* ucons, double* out_inputs, double* out_umean, double* out_ucov,
+                                               double* out_uviol, double* out_ujoint, int chunk, void* workspace, size_t workspace_bytes,
+                                               void* stream) {
+    const PtFeedback fb = {K_dev, k_step_stride, mu_ref, ucons, out_inputs, out_umean, out_ucov, out_uviol, out_ujoint};
+    return pt_rollout("gpmpc_particle_rollout_feedback", m, B, P, H, x0, U, seed, call_index, cons, out_particles, out_mean, out_cov, out_clamped,
+                      out_viol, out_joint, chunk, workspace, workspace_bytes, stream, &fb);
+}
+
+static int pt_rollout(const char* who, const gpmpc_gp_model* m, int B, int P, int H, const double* x0, const double* U, unsigned long long seed,
+                      unsigned call_index, const gpmpc_state_constraints* cons, double* out_particles, double* out_mean, double* out_cov,
+                      int* out_clamped, double* out_viol, double* out_joint, int chunk, void* workspace, size_t workspace_bytes, void* stream,
+                      const PtFeedback* fb) {
     PtNoise noise;
     if (int rc = pt_check_model(who, m, &noise)) return rc;
     if (H < 1) return gpmpc_refuse(who, "H < 1");
@@ -534,7 +600,17 @@ extern "C" int gpmpc_particle_rollout(const gpmpc_gp_model* m, int B, int P, int
     if (int rc = gpmpc_check_chunk(who, chunk)) return rc;
     if (!x0 || !out_particles || !out_mean || !out_cov || !out_clamped || !workspace || (m->action_dim > 0 && !U))
         return gpmpc_refuse(who, "NULL pointer");
-    const PtRollLayout R = pt_roll_layout(m, B, P, H, chunk);
+    if (fb) {
+        const size_t full = (size_t)m->action_dim * m->state_dim;
+        if (m->action_dim < 1) return gpmpc_refuse(who, "a state feedback needs action_dim >= 1");
+        if (fb->kss != 0 && fb->kss != full) return gpmpc_refuse(who, "k_step_stride must be 0 or action_dim state_dim");
+        if (fb->K && !fb->mu_ref) return gpmpc_refuse(who, "a gain needs the mean trajectory it acts around (mu_ref is NULL)");
+        if (!fb->out_umean || !fb->out_ucov) return gpmpc_refuse(who, "NULL pointer (out_umean, out_ucov)");
+        if (fb->ucons) { if (int rc = gpmpc_lpi_check_rows(who, fb->ucons)) return rc; }
+        if ((fb->ucons != nullptr) != (fb->out_uviol != nullptr) || (fb->ucons != nullptr) != (fb->out_ujoint != nullptr))
+            return gpmpc_refuse(who, "out_uviol and out_ujoint are given exactly when input rows are");
+    }
+    const PtRollLayout R = pt_roll_layout(m, B, P, H, chunk, fb && !fb->out_inputs);
     if (workspace_bytes < R.total) return GPMPC_E_WORKSPACE;
     hipStream_t s = (hipStream_t)stream;
     char* ws = (char*)workspace;
@@ -546,11 +622,21 @@ extern "C" int gpmpc_particle_rollout(const gpmpc_gp_model* m, int B, int P, int
     PtVec L;
     memcpy(L.v, noise.L, sizeof(L.v));
     hipLaunchKernelGGL(k_pt_init, dim3(gpmpc_blocks256((long)slab)), dim3(256), 0, s, B, P, ds, x0, (const double*)eps, L, out_particles);
+    double* inputs = fb ? (fb->out_inputs ? fb->out_inputs : (double*)(ws + R.off_u)) : nullptr;
+    const size_t uslab = (size_t)B * P * da;
     for (int t = 1; t <= H; ++t) {
         if (int rc = pt_launch_noise(P, da + ds, t, seed, call_index, eps, s)) return rc;
+        double* u_t = fb ? inputs + (size_t)(t - 1) * uslab : nullptr;
+        if (fb)
+            if (int rc = gpmpc_lpi_particle_inputs(B, P, ds, da, out_particles + (size_t)(t - 1) * slab, U + (size_t)(t - 1) * da, (size_t)H * da,
+                                                   fb->K ? fb->K + (size_t)(t - 1) * fb->kss : nullptr,
+                                                   fb->mu_ref ? fb->mu_ref + (size_t)(t - 1) * ds : nullptr, (size_t)(H + 1) * ds, u_t, s))
+                return rc;
         if (int rc = pt_step(m, noise, B, P, out_particles + (size_t)(t - 1) * slab, U ? U + (size_t)(t - 1) * da : nullptr, (size_t)H * da, eps,
-                             out_particles + (size_t)t * slab, nullptr, var + (size_t)(t - 1) * slab, R.step, ws, s))
+                             out_particles + (size_t)t * slab, nullptr, var + (size_t)(t - 1) * slab, R.step, ws, s, u_t))
             return rc;
     }
-    return pt_stats(B, P, H + 1, ds, out_particles, var, 1, cons, out_mean, out_cov, out_clamped, out_viol, out_joint, s);
+    if (int rc = pt_stats(B, P, H + 1, ds, out_particles, var, 1, cons, out_mean, out_cov, out_clamped, out_viol, out_joint, s)) return rc;
+    if (fb) return gpmpc_lpi_input_stats(B, P, H, da, inputs, fb->ucons, fb->out_umean, fb->out_ucov, fb->out_uviol, fb->out_ujoint, s);
+    return GPMPC_OK;
 }

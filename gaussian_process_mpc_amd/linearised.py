@@ -29,7 +29,7 @@ from ._lib import check, lib, ptr, stream_ptr
 from ._solver import model_problem, mppi_result, mppi_result_block
 from .mppi import mppi_params
 from .particles import GPModel, _dev, _empty, _model, _vp, _workspace
-from .rollout import StateConstraints
+from .rollout import InputConstraints, StateConstraints
 
 
 FORMS = {"tile": _lib.LINPROP_FORM_TILE, "stream": _lib.LINPROP_FORM_STREAM, "auto": _lib.LINPROP_FORM_AUTO}
@@ -150,8 +150,41 @@ def linearised_fc_constraints(means, covs, jac, sc, ds, da):
     return out
 
 
+def feedback_input_cost(cost, covs, feedback, da, want_dcovs=True):
+    """c (B,) = sum_j tr(R K_j Sigma_j K_j^T) over the steps j = 0 ... H-1 of given covariances covs (B, H+1, ds, ds), and with
+    ``want_dcovs`` its derivative dcovs (B, H+1, ds, ds) (C ABI ``gpmpc_feedback_input_cost``; a pure function of a trajectory).
+    cost: the ``CostParams`` whose R is used; feedback: (da, ds), (H, da, ds) or None (then c = 0)."""
+    B, H, ds = covs.shape[0], covs.shape[1] - 1, covs.shape[2]
+    dev = covs.device
+    K, kstride = _gain(feedback, H, ds, da, dev)
+    out = {"c": _empty(dev, B)}
+    if want_dcovs:
+        out["dcovs"] = _empty(dev, B, H + 1, ds, ds)
+    with torch.cuda.device(dev):
+        check(lib().gpmpc_feedback_input_cost(B, H, ds, da, ctypes.byref(cost.c), _vp(K), kstride, ptr(covs.contiguous()), ptr(out["c"]),
+                                              _vp(out.get("dcovs")), stream_ptr(dev)), "gpmpc_feedback_input_cost")
+    return out
+
+
+def feedback_input_constraints(U, covs, jac, ic, feedback):
+    """Input chance-constraint values g_u (B, H, m_u) and, when ``jac`` (B, H, p, p + da) is given, their dense Jacobian g_u_jac
+    (B, H m_u, H da) (C ABI ``gpmpc_feedback_input_constraints``; a pure function of a trajectory).  U (B, H, da); covs (B, H+1, ds, ds)."""
+    B, H, da = U.shape
+    ds = covs.shape[2]
+    dev = covs.device
+    K, kstride = _gain(feedback, H, ds, da, dev)
+    out = {"g_u": _empty(dev, B, H, ic.m)}
+    if jac is not None:
+        out["g_u_jac"] = _empty(dev, B, H * ic.m, H * da)
+    with torch.cuda.device(dev):
+        check(lib().gpmpc_feedback_input_constraints(B, H, ds, da, ctypes.byref(ic.c), _vp(K), kstride, ptr(_dev(U, dev)), ptr(covs.contiguous()),
+                                                     _vp(jac), ptr(out["g_u"]), _vp(out.get("g_u_jac")), stream_ptr(dev)),
+              "gpmpc_feedback_input_constraints")
+    return out
+
+
 def linearised_rollout(model_or_dynamics, x0, U, cost=None, want_grad=True, want_traj=True, want_jac=False, constraints=None, chunk=0,
-                       form=None, full_covariance=False, feedback=None):
+                       form=None, full_covariance=False, feedback=None, input_cost=False, input_constraints=None):
     """B linearised rollouts (+ cost, gradient, chance constraints) in one call (C ABI ``gpmpc_linearised_rollout``): what ``rollout``
     returns for the same arguments -- cost (B,), grad (B, H, da), means / vars (B, H+1, ds), with ``constraints`` g (B, H, m_c) and g_jac
     (B, H m_c, H da) --, plus ``jac`` (B, H, 2ds, 2ds+da) with ``want_jac`` (which needs ``want_grad``: without it no Jacobian is computed).
@@ -159,7 +192,10 @@ def linearised_rollout(model_or_dynamics, x0, U, cost=None, want_grad=True, want
     cost: ``CostParams`` or None (no cost, no grad).  form: see ``linearised_form``.
     full_covariance=True (or a ``feedback`` gain, which implies it): the rule with the whole covariance under u_t = U_t + K_t (x_t - mu_t)
     (C ABI ``gpmpc_linearised_fc_rollout``): ``covs`` (B, H+1, ds, ds) in the place of ``vars``, and ``jac`` is the packed
-    (B, H, p, p + da), p = ``packed_dim(ds)``.  feedback: (da, ds) for every step, (H, da, ds), or None."""
+    (B, H, p, p + da), p = ``packed_dim(ds)``.  feedback: (da, ds) for every step, (H, da, ds), or None.
+    input_cost=True / input_constraints (an ``InputConstraints``; either implies the full rule; C ABI ``gpmpc_linearised_fc_rollout_inputs``):
+    the commanded input u_t ~ N(U_t, K_t Sigma_t K_t^T) is charged tr(R K_t Sigma_t K_t^T) per step in ``cost`` / ``grad``, and its rows come
+    back as ``g_u`` (B, H, m_u) (steps t = 0 ... H-1) and, with ``want_grad``, ``g_u_jac`` (B, H m_u, H da)."""
     _form_code(form)
     model = _model(model_or_dynamics)
     ds, da, dev = model.ds, model.da, model.device
@@ -184,6 +220,13 @@ def linearised_rollout(model_or_dynamics, x0, U, cost=None, want_grad=True, want
         raise ValueError("the constraint rows have %d state coefficients, the model has %d states" % (sc.ds, ds))
     if want_jac and not want_grad:
         raise ValueError("want_jac needs want_grad: without it no Jacobian is computed")
+    ic = input_constraints
+    if ic is not None and not isinstance(ic, InputConstraints):
+        raise TypeError("input_constraints: an InputConstraints")
+    if ic is not None and ic.da != da:
+        raise ValueError("the input constraint rows have %d coefficients, the model has %d inputs" % (ic.da, da))
+    if input_cost and cost is None:
+        raise ValueError("input_cost needs a cost: R is the cost's")
     flags = _lib.WANT_GRAD if want_grad else 0
     out = {}
     if cost is not None:
@@ -194,13 +237,29 @@ def linearised_rollout(model_or_dynamics, x0, U, cost=None, want_grad=True, want
         out["g"] = _empty(dev, B, H, sc.m)
         if want_grad:
             out["g_jac"] = _empty(dev, B, H * sc.m, H * da)
-    if full_covariance or feedback is not None:
+    if full_covariance or feedback is not None or input_cost or ic is not None:
         K, kstride = _gain(feedback, H, ds, da, dev)
         p = packed_dim(ds)
         if want_traj:
             out["means"], out["covs"] = _empty(dev, B, H + 1, ds), _empty(dev, B, H + 1, ds, ds)
         if want_jac:
             out["jac"] = _empty(dev, B, H, p, p + da)
+        if input_cost or ic is not None:
+            if ic is not None:
+                out["g_u"] = _empty(dev, B, H, ic.m)
+                if want_grad:
+                    out["g_u_jac"] = _empty(dev, B, H * ic.m, H * da)
+            icp = ctypes.byref(ic.c) if ic is not None else None
+            with torch.cuda.device(dev), linearised_form(form):
+                nb = lib().gpmpc_linearised_fc_rollout_inputs_workspace_bytes(ctypes.byref(model.c), B, H, flags, chunk, 1 if input_cost else 0, icp)
+                ws = _workspace(dev, nb)
+                check(lib().gpmpc_linearised_fc_rollout_inputs(
+                    ctypes.byref(model.c), B, H, ptr(x0), _vp(U) if da else None, _vp(K), kstride,
+                    ctypes.byref(cost.c) if cost is not None else None, ctypes.byref(sc.c) if sc is not None else None, flags,
+                    _vp(out.get("means")), _vp(out.get("covs")), _vp(out.get("jac")), _vp(out.get("cost")), _vp(out.get("grad")),
+                    _vp(out.get("g")), _vp(out.get("g_jac")), 1 if input_cost else 0, icp, _vp(out.get("g_u")), _vp(out.get("g_u_jac")), chunk,
+                    _vp(ws), nb, stream_ptr(dev)), "gpmpc_linearised_fc_rollout_inputs")
+            return out
         with torch.cuda.device(dev), linearised_form(form):
             nb = lib().gpmpc_linearised_fc_rollout_workspace_bytes(ctypes.byref(model.c), B, H, flags, chunk)
             ws = _workspace(dev, nb)
@@ -227,18 +286,21 @@ def linearised_rollout(model_or_dynamics, x0, U, cost=None, want_grad=True, want
 
 
 def mppi_solve_linearised(model, x0, U0, cost, constraints=None, samples=64, iterations=30, sigma=1.0, decay=0.9, beta=0.1, seed=0,
-                          call_index=0, lb=None, ub=None, form=None, full_covariance=False, feedback=None):
+                          call_index=0, lb=None, ub=None, form=None, full_covariance=False, feedback=None, input_cost=False,
+                          input_constraints=None):
     """``mppi.mppi_solve`` over the linearised rollout (C ABI ``gpmpc_mppi_solve_linearised``): per iteration the sample kernel,
     ``gpmpc_linearised_rollout`` objective only over the K samples (with the constraint values when ``constraints`` is given), the update
     kernel; one device-to-host copy at the end.  Returns what ``mppi_solve`` returns.  form: see ``linearised_form``.
     With ``full_covariance=True`` or a ``feedback`` gain ((da, ds) or (H, da, ds)) the search runs on the full-covariance rule.  That is a
     HOST LOOP, not a single enqueue: per iteration ``mppi_sample``, ``linearised_rollout(..., full_covariance=True, feedback=...)``
-    objective only and ``mppi_update`` -- the same kernels, the same sample stream, one launch sequence per iteration from Python."""
+    objective only and ``mppi_update`` -- the same kernels, the same sample stream, one launch sequence per iteration from Python.
+    ``input_cost`` / ``input_constraints`` (which imply the full rule) are passed on to that rollout; the update sees the state rows followed
+    by the input rows, at most 16 together."""
     _form_code(form)
     model = _model(model)
-    if full_covariance or feedback is not None:
+    if full_covariance or feedback is not None or input_cost or input_constraints is not None:
         return _mppi_host_loop_full(model, x0, U0, cost, constraints, samples, iterations, sigma, decay, beta, seed, call_index, lb, ub, form,
-                                    feedback)
+                                    feedback, input_cost, input_constraints)
     dev = model.device
     x0, U0 = model_problem(model, x0, U0, cost)
     H, da = U0.shape
@@ -257,11 +319,15 @@ def mppi_solve_linearised(model, x0, U0, cost, constraints=None, samples=64, ite
     return mppi_result(res.cpu().numpy(), H, da)
 
 
-def _mppi_host_loop_full(model, x0, U0, cost, constraints, samples, iterations, sigma, decay, beta, seed, call_index, lb, ub, form, feedback):
+def _mppi_host_loop_full(model, x0, U0, cost, constraints, samples, iterations, sigma, decay, beta, seed, call_index, lb, ub, form, feedback,
+                         input_cost=False, input_constraints=None):
     from .mppi import mppi_sample, mppi_start, mppi_update
     x0, U0 = model_problem(model, x0, U0, cost)
     if iterations < 1:
         raise ValueError("iterations must be at least 1")
+    ic = input_constraints
+    if ic is not None and (0 if constraints is None else constraints.m) + ic.m > _lib.MAX_CONS:
+        raise ValueError("state and input rows together exceed %d" % _lib.MAX_CONS)
     H, da = U0.shape
     mean = U0.contiguous()
     best = mppi_start(mean)
@@ -269,8 +335,11 @@ def _mppi_host_loop_full(model, x0, U0, cost, constraints, samples, iterations, 
     for it in range(iterations):
         U, x0b = mppi_sample(mean, samples, sigma, lb=lb, ub=ub, seed=seed, call_index=call_index, iteration=it, decay=decay, x0=x0)
         r = linearised_rollout(model, x0b, U, cost, want_grad=False, want_traj=False, constraints=constraints, form=form, full_covariance=True,
-                               feedback=feedback)
-        u = mppi_update(U, r["cost"], best, beta, g=r.get("g"), mean=mean)
+                               feedback=feedback, input_cost=input_cost, input_constraints=ic)
+        g = r.get("g")
+        if ic is not None:
+            g = r["g_u"] if g is None else torch.cat([g, r["g_u"]], -1)
+        u = mppi_update(U, r["cost"], best, beta, g=g, mean=mean)
         mean, best = u["mean"], u["best"]
         trace.append(u["trace"])
     return mppi_result(torch.cat([best] + trace).cpu().numpy(), H, da, key_first=True)
@@ -309,4 +378,5 @@ def riccati_gain(A, B, Q, R, iterations=500):
 
 
 __all__ = ["GPModel", "linearised_form", "linearised_step", "linearised_rollout", "mppi_solve_linearised", "linearised_step_full",
-           "linearised_fc_vjp", "linearised_fc_constraints", "packed_dim", "lqr_gain", "riccati_gain"]
+           "linearised_fc_vjp", "linearised_fc_constraints", "packed_dim", "lqr_gain", "riccati_gain", "feedback_input_cost",
+           "feedback_input_constraints"]

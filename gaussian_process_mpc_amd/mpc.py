@@ -48,6 +48,12 @@ forced by moving the rollout into one fused HIP call:
   multi-start and ``solver = "mppi"`` (a host loop of sample / rollout / update calls), with and without state constraints --;
   ``solver = "lbfgs"`` and ``"auglag"`` refuse it (not yet).  The ``full_covariance`` attribute is not consulted under it, and
   ``"linearised"`` with ``full_covariance=True`` keeps refusing.  A gain under any other propagation raises.
+* ``mpc.feedback_input_cost`` / ``set_input_chance_bounds`` / ``set_input_constraints`` (extension; under
+  ``"linearised_full"`` only, any other propagation raises): with a gain the commanded input is N(v_t, K_t Sigma_t K_t^T).  The first adds
+  sum_t tr(R K_t Sigma_t K_t^T) to the cost; the others add rows c . v_t + kappa sqrt(a^T Sigma_t a) <= d, a = K_t^T c, on the steps
+  t = 0..H-1.  ``constraints(x)`` / ``jacobian(x)`` return the state block followed by the input block, ``evaluate_batch(constraints=True)``
+  carries ``g_u`` / ``g_u_jac``, ``solver = "mppi"`` honours both; the box lb <= v <= ub of the solvers stays.
+  ``validate_plan(feedback=True)`` runs the particles under the gain and reports the inputs' spread and satisfaction.
 * ``mpc.propagation = "moment_matching_full"`` (extension): exact moment matching with the WHOLE covariance in every
   path -- the four solver callbacks (one B = 1 ``rollout_fullcov(..., constraints=)`` per x: cost, gradient, g on a_r^T Sigma_t a_r and its
   dense Jacobian from one pass), ``evaluate_batch`` with and without constraints (``covs`` in the place of ``vars``), the unconstrained host
@@ -68,7 +74,7 @@ import torch
 
 from .autograd import CostFunction, wants_grad
 from .dynamics import Dynamics
-from .rollout import CostParams, CostSchedule, StateConstraints, cost_full, rollout, rollout_fullcov
+from .rollout import CostParams, CostSchedule, InputConstraints, StateConstraints, cost_full, rollout, rollout_fullcov
 
 try:                                    # the solver binding is optional (not installed in the build image)
     import cyipopt                      # noqa: F401
@@ -79,6 +85,8 @@ except Exception:                       # pragma: no cover
 
 
 class RiskSensitiveMPC:
+    feedback_input_cost = False                          # charge tr(R K Sigma K^T), the spread of the commanded input ("linearised_full" only)
+    input_constraints = None                             # rollout.InputConstraints on the commanded input, or None ("linearised_full" only)
     propagation = "moment_matching"                      # | "moment_matching_full" | "linearised" | "linearised_full" | "particles" (extension): which rule the rollouts of the solvers use
     particle_options = {"particles": 256}                # propagation = "particles": particles per plan (1 ... 4096); assign a new dict to change it
     linearised_form = None                               # | "tile" | "stream" | "auto": the form of the linearised step (None: the process-wide one)
@@ -321,6 +329,10 @@ class RiskSensitiveMPC:
         if getattr(self, "_feedback_gain", None) is not None and prop != "linearised_full":
             raise ValueError("a feedback gain is set (set_feedback_gain): only propagation='linearised_full' predicts under state feedback, "
                              "got propagation=%r (clear_feedback_gain drops it)" % (prop,))
+        if (self.feedback_input_cost or self.input_constraints is not None) and prop != "linearised_full":
+            raise ValueError("an input cost or input chance constraints under feedback are set (feedback_input_cost, set_input_constraints / "
+                             "set_input_chance_bounds): only propagation='linearised_full' knows the spread of the commanded input, got "
+                             "propagation=%r (clear_input_constraints / feedback_input_cost = False drop them)" % (prop,))
         if prop == "moment_matching_full" and getattr(self.dynamics, "nominal_models", None) is not None:
             raise NotImplementedError("propagation='moment_matching_full' with a nominal model: the full-covariance rollout does not know "
                                       "the cross-covariances between a nominal model and the GPs")
@@ -333,8 +345,37 @@ class RiskSensitiveMPC:
     def _lin_kw(self):
         """The keyword arguments that select the rule of ``linearised_rollout`` / ``mppi_solve_linearised``."""
         if self.propagation == "linearised_full":
-            return {"full_covariance": True, "feedback": getattr(self, "_feedback_gain", None)}
+            return {"full_covariance": True, "feedback": getattr(self, "_feedback_gain", None),
+                    "input_cost": bool(self.feedback_input_cost), "input_constraints": self.input_constraints}
         return {}
+
+    # -- the commanded input under feedback (extension; propagation = "linearised_full" only)
+    def set_input_constraints(self, C, d, prob=None, kappa=None):
+        """Rows C[r] . v_t + kappa[r] sqrt(a^T Sigma_t a) <= d[r], a = K_t^T C[r], on the commanded input u_t = v_t + K_t (x_t - mu_t) of
+        every step t = 0..H-1 (rollout.InputConstraints: exactly one of ``prob`` and ``kappa``).  The box lb <= v <= ub of the solvers
+        stays as it is."""
+        ic = InputConstraints(C, d, kappa=kappa, prob=prob)
+        if ic.da != self.input_dim:
+            raise ValueError("the input constraint rows have %d coefficients, the problem has %d inputs" % (ic.da, self.input_dim))
+        self.input_constraints = ic
+        self._cache_key = None
+
+    def set_input_chance_bounds(self, prob):
+        """Input chance constraints from the finite entries of ``lb`` / ``ub``: P(lb_j <= u_j <= ub_j) >= prob per bound and step."""
+        big = 1e15                                                        # (the setters' "no bound")
+        lb = [None if v <= -big else float(v) for v in self.lb]
+        ub = [None if v >= big else float(v) for v in self.ub]
+        self.input_constraints = InputConstraints.box(lb, ub, self.input_dim, prob=prob)
+        self._cache_key = None
+
+    def clear_input_constraints(self):
+        self.input_constraints = None
+        self._cache_key = None
+
+    def _rows(self):
+        """(m_c, m_u): the state and the input rows per step that the callbacks stack."""
+        sc, ic = self.state_constraints, self.input_constraints
+        return (0 if sc is None else sc.m), (0 if ic is None else ic.m)
 
     def _fullcov_mm(self):
         """``full_covariance`` as the paths that refuse it read it: under "linearised_full" and "moment_matching_full" the attribute is
@@ -410,6 +451,9 @@ class RiskSensitiveMPC:
                 raise NotImplementedError("state constraints under the full-covariance rollout are not implemented "
                                           "(q = a^T Sigma_t a and that path's Jacobian layout: a follow-up)")
             key = key + (id(sc),)
+        ic = self.input_constraints
+        if lin and (ic is not None or self.feedback_input_cost):
+            key = key + (None if ic is None else id(ic), bool(self.feedback_input_cost))
         if key != self._cache_key or cs is not held[0] or pack is not held[1] or cp is not held[2]:
             if lin:
                 # one B = 1 linearised rollout per x: cost, gradient and, with constraints, g and its dense Jacobian from the same pass
@@ -421,6 +465,10 @@ class RiskSensitiveMPC:
                 if sc is not None:
                     self.curr_g = r["g"][0].cpu().numpy().reshape(-1)
                     self.curr_g_jac = r["g_jac"][0].cpu().numpy()
+                if ic is not None:                                        # the state block, then the input block
+                    gu, guj = r["g_u"][0].cpu().numpy().reshape(-1), r["g_u_jac"][0].cpu().numpy()
+                    self.curr_g = gu if sc is None else np.concatenate([self.curr_g, gu])
+                    self.curr_g_jac = guj if sc is None else np.concatenate([self.curr_g_jac, guj], axis=0)
             elif mmf:
                 # one B = 1 full-covariance rollout per x: cost, gradient and, with constraints, g on a^T Sigma_t a and its dense Jacobian
                 r = rollout_fullcov(pack, cs, x.reshape(1, self.horizon, self.input_dim), cp, want_grad=True, constraints=sc)
@@ -472,7 +520,7 @@ class RiskSensitiveMPC:
 
     def constraints(self, x):
         """0 without state constraints (src/mpc.py:257-262); else g flattened to (H m_c,), row (t-1) m_c + r, feasible where <= 0."""
-        if self.state_constraints is None:
+        if self.state_constraints is None and self.input_constraints is None:
             return 0
         if self._particles():
             self._linearised()
@@ -486,7 +534,7 @@ class RiskSensitiveMPC:
         default dense structure)."""
         if self._particles():
             self._particles_refuse("jacobian")
-        if self.state_constraints is None:
+        if self.state_constraints is None and self.input_constraints is None:
             return np.zeros(x.shape)
         self._evaluate(x)
         return self.curr_g_jac.reshape(-1)
@@ -498,7 +546,8 @@ class RiskSensitiveMPC:
         constraints=True: also g (B, H, m_c) and, with want_grad, g_jac (B, H m_c, H da) of the state constraints that are set."""
         cs = self.curr_state if curr_state is None else curr_state
         lin = self._linearised()
-        if constraints and self.state_constraints is None:
+        lin_full = self.propagation == "linearised_full"
+        if constraints and self.state_constraints is None and self.input_constraints is None:
             raise ValueError("no state constraints are set (set_state_constraints / set_state_bounds)")
         if self._particles():                                             # cost (B,), stage (B, H+1), g (B, H, m_c) or None, grad None
             return self._particle_evaluate(U, cs, constraints)
@@ -506,7 +555,7 @@ class RiskSensitiveMPC:
             from .linearised import linearised_rollout
             return linearised_rollout(self._linearised_model(self.dynamics.pack()), cs, U, self._cost_params(), want_grad=want_grad,
                                       want_traj=True, constraints=self.state_constraints if constraints else None, form=self.linearised_form,
-                                      **self._lin_kw())
+                                      **dict(self._lin_kw(), **({} if constraints or not lin_full else {"input_constraints": None})))
         if self._mm_full():
             return rollout_fullcov(self.dynamics.pack(), cs, U, self._cost_params(), want_grad=want_grad,
                                    constraints=self.state_constraints if constraints else None)
@@ -524,7 +573,7 @@ class RiskSensitiveMPC:
         return r["cost"].cpu().numpy(), r["grad"].cpu().numpy()
 
     # -- Monte-Carlo check of the moment-matched plan (extension)
-    def validate_plan(self, U=None, x0=None, particles=4096, seed=0, linearised=False):
+    def validate_plan(self, U=None, x0=None, particles=4096, seed=0, linearised=False, feedback=False):
         """Compare the moment-matched rollout of a plan (the last one by default; diagonal or full by ``self.full_covariance``, full under ``propagation = "moment_matching_full"``) with a
         particle rollout through the same GPs (``particles.particle_rollout``).  Returns a dict of host arrays:
 
@@ -538,7 +587,12 @@ class RiskSensitiveMPC:
         With at most 4096 particles also what ``propagation = "particles"`` optimises, from ``particles.particle_cost`` on the same
         particles: ``cost_mc``, ``stage_mc`` (H+1,) and, with state constraints, ``g_mc`` (H, rows).
         linearised=True adds the third column: ``mean_lin``, ``var_lin`` (H+1, ds) of the linearised rollout (linearised.py) and
-        ``z_mean_lin``, ``z_var_lin``, its distance from the particles in the same Monte-Carlo standard errors."""
+        ``z_mean_lin``, ``z_var_lin``, its distance from the particles in the same Monte-Carlo standard errors.
+        feedback=True (needs ``set_feedback_gain``): the particles run under the gain, u = U_t + K_t (x - mean_lf_t), around the mean
+        trajectory of the ``"linearised_full"`` rollout of the plan (``gpmpc_particle_rollout_feedback``), and ``stage_cost`` uses each
+        particle's own inputs.  New keys: ``mean_lf`` (H+1, ds), ``cov_lf`` (H+1, ds, ds), ``input_cov_lf`` (H, da, da) = K Sigma K^T,
+        ``input_mean_mc`` (H, da), ``input_cov_mc`` (H, da, da) and, with input rows set, ``input_satisfaction`` (H, m_u), the fraction of
+        particles with c . u_t <= d at t = 0..H-1, ``input_requested`` (m_u,) and ``joint_input_satisfaction``."""
         from statistics import NormalDist
         from .particles import particle_rollout
         H, ds, da = self.horizon, self.state_dim, self.input_dim
@@ -550,7 +604,14 @@ class RiskSensitiveMPC:
         full = bool(self.full_covariance) or self._mm_full()
         mm = self.dynamics.rollout(cs, U, full_covariance=full)
         sc = self.state_constraints
-        mc = particle_rollout(self.dynamics, cs, U, particles=particles, seed=seed, constraints=sc)
+        fb_kw, lf, Kfb = {}, None, getattr(self, "_feedback_gain", None)
+        if feedback:
+            from .linearised import linearised_rollout
+            if Kfb is None:
+                raise ValueError("validate_plan(feedback=True) needs a feedback gain (set_feedback_gain)")
+            lf = linearised_rollout(self.dynamics, cs, U, None, want_grad=False, form=self.linearised_form, full_covariance=True, feedback=Kfb)
+            fb_kw = {"feedback": Kfb, "mean_ref": lf["means"], "input_constraints": self.input_constraints}
+        mc = particle_rollout(self.dynamics, cs, U, particles=particles, seed=seed, constraints=sc, **fb_kw)
         P = int(particles)
         X = mc["particles"][0]                                            # (P, H+1, ds)
         out = {"particles": P, "mean_mm": mm["means"][0].cpu().numpy(), "mean_mc": mc["mean"][0].cpu().numpy()}
@@ -580,6 +641,17 @@ class RiskSensitiveMPC:
         Ud = torch.as_tensor(U, device=X.device)
         ex, eu = X - self.x_ref.to(X.device, torch.float64), Ud - self.u_ref.to(X.device, torch.float64)
         stage = torch.einsum("pti,ij,ptj->p", ex, self.Q_tor.to(X.device), ex) + torch.einsum("ti,ij,tj->", eu, self.R_tor.to(X.device), eu)
+        if feedback:                                                      # each particle's own inputs
+            eu = mc["inputs"][0] - self.u_ref.to(X.device, torch.float64)
+            stage = torch.einsum("pti,ij,ptj->p", ex, self.Q_tor.to(X.device), ex) + torch.einsum("pti,ij,ptj->p", eu, self.R_tor.to(X.device), eu)
+            Kh = Kfb if Kfb.dim() == 3 else Kfb[None].expand(H, da, ds)
+            out["mean_lf"], out["cov_lf"] = lf["means"][0].cpu().numpy(), lf["covs"][0].cpu().numpy()
+            out["input_cov_lf"] = torch.einsum("tik,tkl,tjl->tij", Kh, lf["covs"][0, :H], Kh).cpu().numpy()
+            out["input_mean_mc"], out["input_cov_mc"] = mc["input_mean"][0].cpu().numpy(), mc["input_cov"][0].cpu().numpy()
+            if self.input_constraints is not None:
+                out["input_satisfaction"] = 1.0 - mc["input_violation"][0].cpu().numpy()
+                out["input_requested"] = np.array([NormalDist().cdf(float(k)) for k in self.input_constraints.kappa])
+                out["joint_input_satisfaction"] = 1.0 - float(mc["joint_input_violation"][0].item())
         out["stage_cost"] = float(stage.mean().item())
         if sc is not None:
             out["satisfaction"] = 1.0 - mc["violation"][0, 1:].cpu().numpy()
@@ -655,16 +727,16 @@ class RiskSensitiveMPC:
         if sc is not None and K > 1 and mmf:
             raise NotImplementedError("propagation='moment_matching_full': the host lock-step multi-start solve is unconstrained -- use "
                                       "n_starts = 1, or solver='auglag' for a constrained multi-start on the full-covariance rule")
-        if sc is not None and K > 1:
+        if (sc is not None or self.input_constraints is not None) and K > 1:
             raise NotImplementedError("the lock-step multi-start solve is unconstrained: use n_starts = 1 with state constraints "
                                       "(a constrained multi-start, e.g. an augmented Lagrangian over the batched evaluation, is a follow-up)")
         if K > 1:
             return self._keep_plan(self._solve_multistart(K, lb, ub))
         if HAVE_CYIPOPT:
-            if sc is None:
+            if sc is None and self.input_constraints is None:
                 nlp = cyipopt.Problem(n=len(x0), m=0, problem_obj=self, lb=lb, ub=ub, cl=[0], cu=[0])
             else:
-                m = self.horizon * sc.m                  # g <= 0: cl = -2e19 is Ipopt's "no lower bound"
+                m = self.horizon * sum(self._rows())     # g <= 0: cl = -2e19 is Ipopt's "no lower bound"
                 nlp = cyipopt.Problem(n=len(x0), m=m, problem_obj=self, lb=lb, ub=ub, cl=[-2e19] * m, cu=[0] * m)
             for k, v in (("mu_strategy", "adaptive"), ("accept_every_trial_step", "yes"), ("max_iter", 300),
                          ("tol", 1e-4), ("acceptable_tol", 1e-4), ("constr_viol_tol", 1e-4), ("compl_inf_tol", 1e-4),
@@ -701,10 +773,10 @@ class RiskSensitiveMPC:
         from scipy.optimize import minimize
         big = 1e15
         bounds = [(None if l <= -big else l, None if u >= big else u) for l, u in zip(lb, ub)]
-        if self.state_constraints is not None:
+        if self.state_constraints is not None or self.input_constraints is not None:
             # SLSQP wants c(x) >= 0: c = -g.  Same callbacks as Ipopt would use; objective, gradient, g and its Jacobian on one x are
             # one device pass (the cache of _evaluate)
-            m_c, n = self.state_constraints.m, len(x0)
+            m_c, n = sum(self._rows()), len(x0)
             cons = {"type": "ineq", "fun": lambda v: -np.asarray(self.constraints(v)),
                     "jac": lambda v: -np.asarray(self.jacobian(v)).reshape(self.horizon * m_c, n)}
             res = minimize(lambda v: self.objective(v), x0, jac=lambda v: np.asarray(self.gradient(v)).reshape(-1),

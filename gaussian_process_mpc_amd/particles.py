@@ -15,7 +15,7 @@ import torch
 
 from . import _lib
 from ._lib import GPModelC, check, lib, ptr, stream_ptr, require_gpu
-from .rollout import StateConstraints, noise_arrays
+from .rollout import InputConstraints, StateConstraints, noise_arrays
 
 _WS = {}                       # (device index, stream) -> workspace (grown, never shrunk)
 
@@ -205,12 +205,65 @@ def particle_stats(particles, var=None, constraints=None):
     return out
 
 
-def particle_rollout(model_or_dynamics, x0, U, particles=1024, seed=0, call_index=0, constraints=None, return_particles=True, chunk=0):
+def particle_inputs(x_prev, U_t, K_t=None, mu_t=None):
+    """The inputs of particles under a state feedback (C ABI ``gpmpc_particle_inputs``): x_prev (B, P, ds), U_t (B, da), K_t (da, ds) or
+    None (a copy of U_t per particle), mu_t (B, ds) -> u (B, P, da) = U_t + K_t (x - mu_t)."""
+    dev = x_prev.device
+    B, P, ds = x_prev.shape
+    x_prev, U_t = x_prev.contiguous(), _dev(U_t, dev).reshape(B, -1).contiguous()
+    da = U_t.shape[1]
+    K_t = None if K_t is None else _dev(K_t, dev).reshape(da, ds).contiguous()
+    mu_t = None if mu_t is None else _dev(mu_t, dev).reshape(B, ds).contiguous()
+    out = _empty(dev, B, P, da)
+    with torch.cuda.device(dev):
+        check(lib().gpmpc_particle_inputs(B, P, ds, da, ptr(x_prev), ptr(U_t), da, _vp(K_t), _vp(mu_t), ds, ptr(out), stream_ptr(dev)),
+              "gpmpc_particle_inputs")
+    return out
+
+
+def particle_step_inputs(model_or_dynamics, x_prev, U_p, eps, chunk=0):
+    """``particle_step`` with an input per particle (C ABI ``gpmpc_particle_step_inputs``): x_prev (B, P, ds), U_p (B, P, da) (what
+    ``particle_inputs`` returns), eps (P, da + ds) -> (next (B, P, ds), mean, var (B, P, ds))."""
+    model = _model(model_or_dynamics)
+    ds, da, dev = model.ds, model.da, model.device
+    B, P = x_prev.shape[0], x_prev.shape[1]
+    x_prev, U_p, eps = _dev(x_prev, dev).contiguous(), _dev(U_p, dev).reshape(B, P, da).contiguous(), _dev(eps, dev).reshape(P, da + ds).contiguous()
+    nxt, mean, var = _empty(dev, B, P, ds), _empty(dev, B, P, ds), _empty(dev, B, P, ds)
+    with torch.cuda.device(dev):
+        nb = lib().gpmpc_particle_step_inputs_workspace_bytes(ctypes.byref(model.c), B, P, chunk)
+        ws = _workspace(dev, nb)
+        check(lib().gpmpc_particle_step_inputs(ctypes.byref(model.c), B, P, ptr(x_prev), ptr(U_p), ptr(eps), ptr(nxt), ptr(mean), ptr(var), chunk,
+                                               _vp(ws), nb, stream_ptr(dev)), "gpmpc_particle_step_inputs")
+    return nxt, mean, var
+
+
+def particle_input_stats(inputs, input_constraints=None):
+    """Statistics of particle inputs (C ABI ``gpmpc_particle_input_stats``): inputs (H, B, P, da) -> dict(input_mean (B, H, da), input_cov
+    (B, H, da, da) and, with an ``InputConstraints``, input_violation (B, H, rows), joint_input_violation (B,))."""
+    dev = inputs.device
+    H, B, P, da = inputs.shape
+    ic = input_constraints
+    out = {"input_mean": _empty(dev, B, H, da), "input_cov": _empty(dev, B, H, da, da)}
+    if ic is not None:
+        out["input_violation"], out["joint_input_violation"] = _empty(dev, B, H, ic.m), _empty(dev, B)
+    with torch.cuda.device(dev):
+        check(lib().gpmpc_particle_input_stats(B, P, H, da, ptr(inputs.contiguous()), ctypes.byref(ic.c) if ic is not None else None,
+                                               ptr(out["input_mean"]), ptr(out["input_cov"]), _vp(out.get("input_violation")),
+                                               _vp(out.get("joint_input_violation")), stream_ptr(dev)), "gpmpc_particle_input_stats")
+    return out
+
+
+def particle_rollout(model_or_dynamics, x0, U, particles=1024, seed=0, call_index=0, constraints=None, return_particles=True, chunk=0,
+                     feedback=None, mean_ref=None, input_constraints=None):
     """Monte-Carlo rollout of B plans with ``particles`` particles each through the GP posterior (every plan sees the same noise).
     x0 (ds,) or (B, ds); U (H, da) or (B, H, da); constraints: a ``StateConstraints`` (its rows a . x <= b are counted; kappa is not used).
     Returns device tensors: ``particles`` (B, P, H+1, ds) (a view), ``mean`` (B, H+1, ds), ``cov`` (B, H+1, ds, ds) (divisor P - 1),
     ``clamped`` (B, H) int32 -- particles whose latent variance came out negative at a step --, and with constraints ``violation``
-    (B, H+1, rows), the fraction of particles with a . x > b, and ``joint_violation`` (B,), the fraction violating any row at any step >= 1."""
+    (B, H+1, rows), the fraction of particles with a . x > b, and ``joint_violation`` (B,), the fraction violating any row at any step >= 1.
+    feedback=K ((da, ds) or (H, da, ds)) with mean_ref (B, H+1, ds) (or (H+1, ds)), and / or input_constraints (an ``InputConstraints``): the
+    particles run under u = U_t + K_t (x - mean_ref_t) (C ABI ``gpmpc_particle_rollout_feedback``; the same noise, no new normals), and the
+    result also holds ``inputs`` (B, P, H, da) (a view), ``input_mean`` (B, H, da), ``input_cov`` (B, H, da, da) and, with input rows,
+    ``input_violation`` (B, H, rows) and ``joint_input_violation`` (B,) over the steps 0 ... H-1."""
     model = _model(model_or_dynamics)
     ds, da, dev = model.ds, model.da, model.device
     U = _dev(U, dev)
@@ -232,6 +285,47 @@ def particle_rollout(model_or_dynamics, x0, U, particles=1024, seed=0, call_inde
     out = {"mean": _empty(dev, B, H + 1, ds), "cov": _empty(dev, B, H + 1, ds, ds), "clamped": _empty(dev, B, H, dtype=torch.int32)}
     viol = _empty(dev, B, H + 1, sc.m) if sc is not None else None
     joint = _empty(dev, B) if sc is not None else None
+    ic = input_constraints
+    if ic is not None and not isinstance(ic, InputConstraints):
+        raise TypeError("input_constraints: an InputConstraints")
+    if ic is not None and ic.da != da:
+        raise ValueError("the input constraint rows have %d coefficients, the model has %d inputs" % (ic.da, da))
+    if feedback is not None or ic is not None or mean_ref is not None:
+        K = kstride = mu = None
+        if feedback is not None:
+            K = _dev(feedback, dev)
+            if tuple(K.shape) not in ((da, ds), (H, da, ds)) or da == 0:
+                raise ValueError("feedback gain: (%d, %d) or (%d, %d, %d), got %s" % (da, ds, H, da, ds, tuple(K.shape)))
+            if mean_ref is None:
+                raise ValueError("a feedback gain needs mean_ref, the mean trajectory it acts around")
+        kstride = da * ds if K is not None and K.dim() == 3 else 0
+        if mean_ref is not None:
+            mu = _dev(mean_ref, dev).reshape(-1, H + 1, ds)
+            if mu.shape[0] == 1 and B > 1:
+                mu = mu.expand(B, H + 1, ds)
+            if mu.shape[0] != B:
+                raise ValueError("mean_ref: (%d, %d) or (%d, %d, %d), got %s" % (H + 1, ds, B, H + 1, ds, tuple(mu.shape)))
+            mu = mu.contiguous()
+        inp = _empty(dev, H, B * P, da)
+        out["input_mean"], out["input_cov"] = _empty(dev, B, H, da), _empty(dev, B, H, da, da)
+        if ic is not None:
+            out["input_violation"], out["joint_input_violation"] = _empty(dev, B, H, ic.m), _empty(dev, B)
+        with torch.cuda.device(dev):
+            nb = lib().gpmpc_particle_rollout_feedback_workspace_bytes(ctypes.byref(model.c), B, P, H, chunk, 1)
+            ws = _workspace(dev, nb)
+            check(lib().gpmpc_particle_rollout_feedback(
+                ctypes.byref(model.c), B, P, H, ptr(x0), _vp(U) if da else None, int(seed) & (2 ** 64 - 1), int(call_index),
+                ctypes.byref(sc.c) if sc is not None else None, ptr(part), ptr(out["mean"]), ptr(out["cov"]), _vp(out["clamped"]), _vp(viol),
+                _vp(joint), _vp(K.contiguous() if K is not None else None), kstride, _vp(mu), ctypes.byref(ic.c) if ic is not None else None,
+                ptr(inp), ptr(out["input_mean"]), ptr(out["input_cov"]), _vp(out.get("input_violation")), _vp(out.get("joint_input_violation")),
+                chunk, _vp(ws), nb, stream_ptr(dev)), "gpmpc_particle_rollout_feedback")
+        out["inputs"] = inp.reshape(H, B, P, da).permute(1, 2, 0, 3)
+        if sc is not None:
+            out["violation"], out["joint_violation"] = viol, joint
+        if return_particles:
+            out["particles"] = part.reshape(H + 1, B, P, ds).permute(1, 2, 0, 3)
+        out["model"] = model
+        return out
     with torch.cuda.device(dev):
         nb = lib().gpmpc_particle_rollout_workspace_bytes(ctypes.byref(model.c), B, P, H, chunk)
         ws = _workspace(dev, nb)

@@ -11,7 +11,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import CostParamsC, StateConstraintsC, check, lib, ptr, require_gpu, stream_ptr, host_doubles
+from ._lib import CostParamsC, InputConstraintsC, StateConstraintsC, check, lib, ptr, require_gpu, stream_ptr, host_doubles
 
 
 def _dev(a, device):
@@ -207,6 +207,32 @@ class StateConstraints:
         if not rows:
             raise ValueError("no finite bound given")
         return cls(np.array(rows), np.array(rhs), kappa=kappa, prob=prob)
+
+
+class InputConstraints:
+    """Linear chance constraints on the COMMANDED input u_t = v_t + K_t (x_t - mu_t) of the full-covariance linearised rollout, held at
+    every step t = 0..H-1 (C ABI ``gpmpc_input_constraints``):
+
+        g_u[t, r] = C[r] . v_t + kappa[r] * sqrt(a^T Sigma_t a) - d[r]  <=  0,      a = K_t^T C[r]
+
+    C: (m_u, da) or (da,); d: (m_u,) or scalar; ``kappa`` / ``prob`` as ``StateConstraints``.  Without a gain the rows bound v_t alone."""
+
+    def __init__(self, C, d, kappa=None, prob=None):
+        s = StateConstraints(C, d, kappa=kappa, prob=prob)                   # the same checks: rows, finiteness, kappa >= 0
+        self.C, self.d, self.kappa = s.A, s.b, s.kappa
+        self.m, self.da = s.m, s.ds
+        c = InputConstraintsC()
+        c.n_rows = self.m
+        c.C[:self.m * self.da] = self.C.reshape(-1).tolist()
+        c.d[:self.m] = self.d.tolist()
+        c.kappa[:self.m] = self.kappa.tolist()
+        self.c = c
+
+    @classmethod
+    def box(cls, lb, ub, da, prob=None, kappa=None):
+        """Rows u_j <= ub[j] and -u_j <= -lb[j] for every finite bound, as ``StateConstraints.box``."""
+        s = StateConstraints.box(lb, ub, da, prob=prob, kappa=kappa)
+        return cls(s.A, s.b, kappa=s.kappa)
 
 
 def noise_arrays(ds, da, init_cov=None, action_var=None, process_var=None):

@@ -1214,8 +1214,9 @@ int gpmpc_mppi_solve_linearised(const gpmpc_gp_model* model_host, int H, const d
  * With the gradient: the O(N D^2) pass and the per-plan close, small at N = 2048, visible at N = 300 and M = 256.  Objective only it is
  * worse than the operation count says, for the reason above (stage A delivers g only with its whole Jacobian).  Not measured: one Kinv for
  * all GPs, other ds / da / H, per-kernel times, hardware counters.
- * Not provided: the input-cost term tr(R K Sigma K^T) and input constraints tightened by K Sigma K^T; a gain per plan of a batch; the
- * device L-BFGS and augmented-Lagrangian solvers on this rule; graph capture; particles under feedback; gains chosen by the optimiser; a
+ * The input-cost term tr(R K Sigma K^T) and input constraints tightened by K Sigma K^T: "the commanded input", below.
+ * Not provided: a gain per plan of a batch; the
+ * device L-BFGS and augmented-Lagrangian solvers on this rule; graph capture; gains chosen by the optimiser; a
  * single-enqueue MPPI solve (the Python layer loops gpmpc_mppi_sample, this rollout, gpmpc_mppi_update).
  * ------------------------------------------------------------------------- */
 /* One step of B plans.  mu_prev dev [B][ds]; cov_prev dev [B][ds][ds]; U_t dev, input j of plan b at U_t[b u_stride + j] (NULL with
@@ -1241,6 +1242,104 @@ int gpmpc_linearised_fc_vjp(int B, int H, int state_dim, int action_dim, const d
  * [B][H][p][p+da] (NULL with out_gjac NULL) -> out_g dev [B][H][n_rows] and, unless NULL, out_gjac dev [B][H n_rows][H da]. */
 int gpmpc_linearised_fc_constraints(int B, int H, int state_dim, int action_dim, const gpmpc_state_constraints* cons_host,
                                     const double* means, const double* covs, const double* jac_dev, double* out_g, double* out_gjac,
+                                    void* stream);
+
+/* ---------------------------------------------------------------------------
+ * Linearised propagation, full covariance: the commanded input (kernels in csrc/linprop_inputs.hip).  With a gain the
+ * controller's input is a random variable.  Commanded input of step t = 0 ... H-1: mean v_t, covariance Su_t = K_t Sigma_t K_t^T (da x da),
+ * K_t through the K_dev / k_step_stride pair of gpmpc_linearised_fc_rollout.  action_var stays what it is, actuator noise added inside
+ * Sz, and is not part of Su_t.  K = NULL means Su_t = 0.
+ *
+ * Input cost.  c_b = sum_{j=0}^{H-1} tr(R K_j Sigma_j K_j^T) = sum_j sum_{a,b,k,l} R_ab K_bk Sigma_j[k][l] K_al, R that of the cost struct,
+ * general and not necessarily symmetric.  It is the expectation of the input term (u - u_ref)^T R (u - u_ref) minus its value at the
+ * mean, so it depends neither on u_ref nor on a cost schedule.  Local derivative in the convention of gpmpc_cost_grad (a general,
+ * possibly non-symmetric Sigma):  d c / d Sigma_j[k][l] = sum_{a,b} K_al R_ab K_bk for j < H, and 0 for j = H.  Step 0 contributes a
+ * constant (Sigma_0 = init_cov).  The steps are summed in ascending order by one workgroup per plan; no atomics.
+ *
+ * Input chance constraints.  Rows c_r . u <= d_r held with the quantile kappa_r: for t = 0 ... H-1 and row r, with a = K_t^T c_r (ds),
+ *     q = a^T Sigma_t a      sd = sqrt(q)      g_u[t][r] = c_r . v_t + kappa_r sd - d_r   <= 0
+ * by the rules of gpmpc_linearised_fc_constraints: q <= 0 gives sd = 0 and no variance part; a NaN in v_t or Sigma_t makes the rows of
+ * step t NaN, and no other step's.  out_gu [B][H][n_u]; out_gujac [B][H n_u][H da], row t n_u + r, column tau da + j, every element
+ * written.  With S_t the sensitivities of the packed state of step t (before the step is taken):
+ *     tau > t :  exactly 0.0
+ *     tau = t :  c_rj
+ *     tau < t :  (kappa_r / (2 sd)) sum_{k<=l} w_kl S_t[Sigma_kl][tau, j],    w_kk = a_k^2,  w_kl = 2 a_k a_l (k < l)
+ * Row t = 0 therefore has only its tau = 0 block.  The sweep is that of gpmpc_linearised_fc_constraints: grid (B, ceil(H da / 64)), one lane
+ * per column, the sensitivities in LDS; values only when out_gujac is NULL.
+ *
+ * gpmpc_linearised_fc_rollout_inputs is gpmpc_linearised_fc_rollout with both: the existing launches, the input-cost kernel between
+ * gpmpc_cost_grad and the adjoint sweep, the input-constraint kernel at the end.  With input_cost = 0 and ucons_host = NULL every output
+ * is bit for bit the old entry's; means, covs, jac, g and g_jac are never affected; out_cost[b] = cost_plain[b] + c_b, one rounding, c_b as
+ * gpmpc_feedback_input_cost returns it; out_grad is bit for bit d_U + gpmpc_linearised_fc_vjp(jac, d_means, d_covs + out_dcovs), the sum
+ * of the two seeds being one rounding per element; out_gu / out_gujac are bit for bit gpmpc_feedback_input_constraints on the returned
+ * arrays; objective only, the values are the same bits.  The workspace is that of gpmpc_linearised_fc_rollout.
+ *
+ * Refusals (GPMPC_E_ARG with a text, before any launch): everything gpmpc_linearised_fc_rollout refuses; action_dim < 1; n_rows outside
+ * 1...GPMPC_MAX_CONS, a negative or NaN kappa; input_cost without a cost; out_gu / out_gujac not given exactly when ucons_host is (the
+ * Jacobian only with GPMPC_WANT_GRAD); k_step_stride other than 0 or da ds.  The size query returns 0 for arguments that would be refused.
+ *
+ * Particles under the same feedback (the Monte-Carlo check of both effects).  u^p = v_b + K_t (x^p - mu_b), summed over k in ascending
+ * order (gpmpc_particle_inputs; K_t = NULL copies v_b); gpmpc_particle_step_inputs is gpmpc_particle_step with an input per particle,
+ * U_p dev [B P][da], in the place of U_t / u_stride (a variant of the assemble kernel; everything downstream is unchanged: action noise
+ * is added to U_p as it is to U_t).  gpmpc_particle_rollout_feedback takes the arguments of gpmpc_particle_rollout plus the gain pair,
+ * mu_ref dev [B][H+1][ds] (the mean trajectory the gain acts around, e.g. out_means of the linearised rollout) and the input rows; its
+ * particles are bit for bit the chain gpmpc_particle_noise -> gpmpc_particle_inputs -> gpmpc_particle_step_inputs, and with K_dev = NULL
+ * bit for bit those of gpmpc_particle_rollout: the same noise addressing, no new normals.  gpmpc_particle_input_stats follows the rules
+ * of gpmpc_particle_stats on inputs [H][B P][da]: fixed-order sums, a two-pass covariance with divisor P - 1, exactly symmetric, a
+ * violation is c_r . u > d_r, the joint figure runs over all rows and all steps 0 ... H-1.  Refused besides what the sibling entries
+ * refuse: action_dim < 1, bad rows, a k_step_stride other than 0 or da ds, a NULL mu_ref together with a gain, out_uviol / out_ujoint not
+ * given exactly when the rows are.
+ *
+ * Measurements, and what has not been measured: DESIGN.md section 3n.
+ * Not provided: the rate term R_delta under feedback (its feedback part needs cross-step covariances: R_delta stays on the nominal
+ * inputs); a gain per plan; gains chosen by the optimiser; the device L-BFGS / augmented-Lagrangian solvers on this rule; the
+ * particle-cost planner under feedback; graph capture.
+ * ------------------------------------------------------------------------- */
+typedef struct gpmpc_input_constraints {
+    int n_rows;                                       /* 1...GPMPC_MAX_CONS */
+    int reserved;
+    double C[GPMPC_MAX_CONS * GPMPC_MAX_D];           /* [n_rows][da] row-major in the leading n_rows*da entries */
+    double d[GPMPC_MAX_CONS];
+    double kappa[GPMPC_MAX_CONS];
+} gpmpc_input_constraints;
+/* Pure function of a trajectory, like gpmpc_linearised_fc_vjp: K_dev dev [da][ds] (k_step_stride 0) or [H][da][ds] (da ds), or NULL;
+ * covs dev [B][H+1][ds][ds] -> out_c dev [B] and, unless NULL, out_dcovs dev [B][H+1][ds][ds], every element written. */
+int gpmpc_feedback_input_cost(int B, int H, int state_dim, int action_dim, const gpmpc_cost_params* cost_host, const double* K_dev,
+                              size_t k_step_stride, const double* covs_dev, double* out_c, double* out_dcovs, void* stream);
+/* Pure function of a trajectory: U dev [B][H][da], covs dev [B][H+1][ds][ds], jac dev [B][H][p][p+da] (NULL with out_gujac NULL)
+ * -> out_gu dev [B][H][n_rows] and, unless NULL, out_gujac dev [B][H n_rows][H da]. */
+int gpmpc_feedback_input_constraints(int B, int H, int state_dim, int action_dim, const gpmpc_input_constraints* ucons_host,
+                                     const double* K_dev, size_t k_step_stride, const double* U_dev, const double* covs_dev,
+                                     const double* jac_dev, double* out_gu, double* out_gujac, void* stream);
+size_t gpmpc_linearised_fc_rollout_inputs_workspace_bytes(const gpmpc_gp_model* model_host, int B, int H, unsigned flags, int chunk,
+                                                          int input_cost, const gpmpc_input_constraints* ucons_host);
+int gpmpc_linearised_fc_rollout_inputs(const gpmpc_gp_model* model_host, int B, int H, const double* x0, const double* U,
+                                       const double* K_dev, size_t k_step_stride, const gpmpc_cost_params* cost_host,
+                                       const gpmpc_state_constraints* cons_host, unsigned flags, double* out_means, double* out_covs,
+                                       double* out_jac, double* out_cost, double* out_grad, double* out_g, double* out_gjac, int input_cost,
+                                       const gpmpc_input_constraints* ucons_host, double* out_gu, double* out_gujac, int chunk,
+                                       void* workspace, size_t workspace_bytes, void* stream);
+
+/* out_u dev [B P][da] from x_prev dev [B P][ds], input j of plan b at U_t[b u_stride + j], K_t dev [da][ds] or NULL, the mean of plan b
+ * at mu_t + b mu_stride (NULL only with K_t NULL). */
+int gpmpc_particle_inputs(int B, int P, int state_dim, int action_dim, const double* x_prev, const double* U_t, size_t u_stride,
+                          const double* K_t, const double* mu_t, size_t mu_stride, double* out_u, void* stream);
+size_t gpmpc_particle_step_inputs_workspace_bytes(const gpmpc_gp_model* model_host, int B, int P, int chunk);
+int gpmpc_particle_step_inputs(const gpmpc_gp_model* model_host, int B, int P, const double* x_prev, const double* U_p, const double* eps,
+                               double* out_next, double* out_mean, double* out_var, int chunk, void* workspace, size_t workspace_bytes,
+                               void* stream);
+/* inputs dev [H][B P][da] -> out_umean dev [B][H][da], out_ucov dev [B][H][da][da] (either may be NULL), and with rows out_uviol dev
+ * [B][H][n_rows], out_ujoint dev [B] (both NULL without). */
+int gpmpc_particle_input_stats(int B, int P, int H, int action_dim, const double* inputs, const gpmpc_input_constraints* ucons_host,
+                               double* out_umean, double* out_ucov, double* out_uviol, double* out_ujoint, void* stream);
+/* want_inputs of the size query: whether out_inputs will be given (without it the inputs of all steps live in the workspace). */
+size_t gpmpc_particle_rollout_feedback_workspace_bytes(const gpmpc_gp_model* model_host, int B, int P, int H, int chunk, int want_inputs);
+int gpmpc_particle_rollout_feedback(const gpmpc_gp_model* model_host, int B, int P, int H, const double* x0, const double* U,
+                                    unsigned long long seed, unsigned call_index, const gpmpc_state_constraints* cons_host,
+                                    double* out_particles, double* out_mean, double* out_cov, int* out_clamped, double* out_viol,
+                                    double* out_joint, const double* K_dev, size_t k_step_stride, const double* mu_ref,
+                                    const gpmpc_input_constraints* ucons_host, double* out_inputs, double* out_umean, double* out_ucov,
+                                    double* out_uviol, double* out_ujoint, int chunk, void* workspace, size_t workspace_bytes,
                                     void* stream);
 
 #ifdef __cplusplus
