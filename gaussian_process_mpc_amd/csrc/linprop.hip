@@ -446,6 +446,8 @@ extern "C" int gpmpc_linearised_rollout(const gpmpc_gp_model* m, int B, int H, c
         if (!gpmpc_roll_tail_fits(H, ds, da, false)) return gpmpc_refuse(who, "H = %d is too long for the cost kernel", H);
         if (int rc = gpmpc_schedule_resolve(cost, ds, da, H, who, &sched)) return rc;
     }
+    // (gpmpc_rollout_constraints would refuse it too, but after the steps are enqueued and without a text)
+    if (cons && da < 1) return gpmpc_refuse(who, "constraints need action_dim >= 1");
     const LpRollLayout R = lp_roll_layout(m, B, H, grad, chunk);
     if (workspace_bytes < R.total) return GPMPC_E_WORKSPACE;
     hipStream_t s = (hipStream_t)stream;

@@ -1079,7 +1079,8 @@ int gpmpc_mppi_solve_particles(const gpmpc_gp_model* model_host, int H, int P, c
  * action_dim or jac_stride < 2ds (2ds+da) with B > 1, outputs of a step that alias its inputs, flags other than GPMPC_WANT_GRAD
  * (GPMPC_USE_GRAPH and the GPMPC_FP32_* modes: not yet / never), out_jac without GPMPC_WANT_GRAD, a cost without out_cost (or without
  * out_grad under GPMPC_WANT_GRAD), constraint rows without out_g (out_gjac), bad constraint rows, a bad cost schedule, a cost with
- * action_dim = 0 or with a horizon beyond the cost kernel's LDS (about 48 KiB / (8 (2 + 2ds + da)) steps); in gpmpc_mppi_solve_linearised
+ * action_dim = 0 or with a horizon beyond the cost kernel's LDS (about 48 KiB / (8 (2 + 2ds + da)) steps), constraint rows with
+ * action_dim = 0; in gpmpc_mppi_solve_linearised
  * also what gpmpc_mppi_solve refuses.  A workspace below *_workspace_bytes (which return 0 for arguments that would be refused):
  * GPMPC_E_WORKSPACE.
  *

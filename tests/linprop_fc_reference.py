@@ -119,8 +119,9 @@ def step(model, mu, cov, U_t, K=None, prec=None, drop_cross_hess=False, feedback
     g, g_abs = base["g"], base["g_abs"]                                              # (B, ds, D)
     W = np.einsum("bdl,bal->bad", Sz, g)                                             # W[b][a][d] = sum_l Sz[d][l] G_a[l]
     W_abs = np.einsum("bdl,bal->bad", Sz_abs, _abs(g)) + np.einsum("bdl,bal->bad", _abs(Sz), g_abs)
-    Pm = g[:, :, :ds] + np.einsum("baj,jk->bak", g[:, :, ds:], Kg)
-    P_abs = g_abs[:, :, :ds] + np.einsum("baj,jk->bak", g_abs[:, :, ds:], _abs(Kg))
+    # (da = 0: no sum at all -- numpy's einsum over an EMPTY axis of a long double slice hands back memory it never wrote)
+    Pm = g[:, :, :ds] + (np.einsum("baj,jk->bak", g[:, :, ds:], Kg) if da else 0)
+    P_abs = g_abs[:, :, :ds] + (np.einsum("baj,jk->bak", g_abs[:, :, ds:], _abs(Kg)) if da else 0)
     s2 = (G.cast(np.asarray(model["sf"], dtype=np.float64), prec) ** 2)[None, :] - base["q"] + pv[None, :]
     s2_mag = (G.cast(np.asarray(model["sf"], dtype=np.float64), prec) ** 2)[None, :] + _abs(base["q"]) + pv[None, :]
     GW = np.einsum("bad,bcd->bac", g, W)                                             # G_a . W_c

@@ -32,10 +32,12 @@ import particle_reference as P
 dims, noise_model = P.dims, P.noise_model
 
 
-def make_model(n, ds, da, kind="pergp", seed=0, sn=0.1, noise=False, nominal=False, pair=False):
+def make_model(n, ds, da, kind="pergp", seed=0, sn=0.1, noise=False, nominal=False, pair=False, groups=None):
     """A GP bundle on random inputs (the generator of tests/test_gpu_particles.py).  kind: pergp (per-GP hyper-parameters and inverses) |
     shared (one hyper-parameter set, ONE inverse: gp_stride = 0) | nonsym (per-GP, every entry of the inverse perturbed by a relative 1e-3:
     visibly not symmetric).  pair: the GPs 0 and 2 share (lambda, sigma_f), GP 1 stands apart (two groups, the first with a gap).
+    groups: a list of index lists, each sharing the (lambda, sigma_f) of its first member; pair is groups=[[0, 2]].  Nothing is drawn for
+    it: with groups=None every array is what it was before the argument existed.
     noise: a non-default init_cov diagonal, action_var and process_var."""
     rng = np.random.default_rng(100 * n + 10 * ds + da + seed)
     D = ds + da
@@ -44,8 +46,10 @@ def make_model(n, ds, da, kind="pergp", seed=0, sn=0.1, noise=False, nominal=Fal
     sf = rng.uniform(0.6, 1.8, ds)
     if kind == "shared":
         lam, sf = np.tile(lam[:1], (ds, 1)), np.tile(sf[:1], ds)
-    elif pair:
-        lam[2], sf[2] = lam[0], sf[0]
+    else:
+        for members in ([[0, 2]] if pair else []) + [list(g) for g in (groups or [])]:
+            for a in members[1:]:
+                lam[a], sf[a] = lam[members[0]], sf[members[0]]
     Y = np.stack([np.sin(X @ rng.standard_normal(D)) for _ in range(ds)], axis=1) + sn * rng.standard_normal((n, ds))
     Ks = []
     for a in range(ds):
